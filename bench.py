@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rasterized Gaussians/s, forward+backward (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|cfg2|cfg5|long]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|cfg2|cfg5|long] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workloads (``--workload auto``: cfg2 at N = 1, cfg5 at N > 1):
@@ -70,6 +70,7 @@ class Scene:
         self.theta, self.rho = T(np.zeros(3), True), T(np.zeros(3), True)
         self.means2D = torch.zeros_like(self.means3D, requires_grad=True)             # the caller's screen-space gradient holder
         self.cams, self.rast = {}, {}
+        self.keep = None            # a dict: fwd_bwd stores the rasterizer's outputs in it (--dump-outputs)
         for k in keyframes:
             R_w, t_w = keyframe_pose(k)
             cam = make_camera(WIDTH, HEIGHT, R=R_w, t=t_w)
@@ -85,6 +86,8 @@ class Scene:
         color, radii, depth, opacity, n_touched = self.rast[k](means3D=self.means3D, means2D=self.means2D, opacities=self.opac, shs=self.shs,
                                                                scales=self.scales, rotations=self.rots, theta=self.theta, rho=self.rho)
         torch.autograd.backward([color, depth], [self.gcol, self.gdep])
+        if self.keep is not None:
+            self.keep.update(color=color.detach(), depth=depth.detach(), opacity=opacity.detach(), radii=radii, n_touched=n_touched)
         return radii
 
     def view_facts(self, k):
@@ -282,15 +285,47 @@ def note(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
-def timed(step, steps, warmup, barrier):
+def timed(step, steps, warmup, barrier, last=None):
+    """seconds for `steps` timed steps; `last`, when given, runs in place of `step` as the final timed step (--dump-outputs)"""
     for _ in range(warmup):
         step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if last else steps):
         step()
+    if last:
+        last()
     barrier()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 60 << 20          # array data: with the .npy headers the files stay under 64 MB (10^6 or 2^20 bytes)
+
+
+def dump_outputs(out_dir, arrays, P, seed=0):
+    """--dump-outputs: writes each tensor of `arrays` (None: skipped) to out_dir/<name>.npy, float64 kept, everything else as float32. If the whole set
+    exceeds DUMP_BUDGET_BYTES, the per-Gaussian arrays (leading dimension P) keep only a fixed, seeded sample of rows, the same rows in
+    every array, whose indices go to gaussian_index.npy. Returns what the result line reports about the dump."""
+    host = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    per_gaussian = [n for n, a in host.items() if a.ndim >= 1 and a.shape[0] == P]
+    total = sum(a.nbytes for a in host.values())
+    rows = P
+    if total > DUMP_BUDGET_BYTES:
+        row_bytes = sum(host[n].nbytes // P for n in per_gaussian) + 8          # + the index's float64
+        rows = max(1, (DUMP_BUDGET_BYTES - (total - sum(host[n].nbytes for n in per_gaussian))) // row_bytes)
+        idx = np.sort(np.random.default_rng(seed).choice(P, size=rows, replace=False))
+        for n in per_gaussian:
+            host[n] = np.ascontiguousarray(host[n][idx])
+        host["gaussian_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": sorted(host), "bytes": sum(a.nbytes for a in host.values()), "gaussian_rows": int(rows), "gaussians": P}
 
 
 def run_cfg2(scene, world, rank, steps, warmup, barrier, k):
@@ -510,7 +545,14 @@ def main():
     ap.add_argument("--graph-replay", action="store_true", help="with --no-secondary: still measure the step captured as one hipGraph (tools/dev_ab.sh)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-timeout", type=float, default=150.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (cfg2 / long: images, radii, n_touched and the gradients; "
+                         "cfg5: the summed parameter gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded sample of Gaussians beyond)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.exchange == "reduce_scatter":
+        ap.error("--dump-outputs needs --exchange all_reduce: after a reduce-scatter no rank holds the whole summed gradient")
     if args.cpu_baseline_child:        # CPU only: no GPU, no product code
         from synthetic_scene import make_camera, make_cotangents, make_gaussians
         cam = make_camera(WIDTH, HEIGHT)
@@ -587,11 +629,22 @@ def main():
         note(f"{workload}: P = {P}, world = {world}")
         # headline: speculative binning (the SLAM loop's steady state); the dominant kernel is timed inside the timed region
         _, _, step = run_cfg2(scene, world, rank, 0, args.warmup, barrier, rank)
+        kept = {}
+
+        def last_step():                        # the final timed step, keeping what the rasterizer returned
+            scene.keep = kept
+            step()
+            scene.keep = None
         _C.profile_reset()
         _C.profile_enable(["render_bwd"])       # 2 event records per step on the launch stream
-        dt = reduce_max(timed(step, args.steps, 0, barrier))
+        dt = reduce_max(timed(step, args.steps, 0, barrier, last=last_step if args.dump_outputs else None))
         _C.profile_enable(False)
         dom_ms, dom_calls = _C.profile_read()["render_bwd"]
+        dumped = None
+        if args.dump_outputs and rank == 0:    # before anything below runs the step again
+            grads = zip(("means3D", "shs", "opacities", "scales", "rotations", "theta", "rho", "means2D"),
+                        scene.params + [scene.theta, scene.rho, scene.means2D])
+            dumped = dump_outputs(args.dump_outputs, dict(kept, **{f"grad_{n}": p.grad for n, p in grads}), P)
         kern = kernel_breakdown(step)
         note(f"timed region done: {dt / args.steps * 1e3:.4f} ms per step")
         nospec = None
@@ -628,6 +681,8 @@ def main():
                                      "reported against the HBM roof because north_star asks for it"},
                 "kernel_us": kern,
             }
+            if dumped is not None:
+                out["dump_outputs"] = dumped
             iss = out["roofline"].get("issue") or {}
             rb = iss.get("render_bwd") or {}
             if rb.get("pairs_per_wave") and rb.get("waves") and dom_s > 0:
@@ -708,6 +763,10 @@ def main():
         dt = reduce_max(timed(step, args.steps, 0, barrier))
         _C.profile_enable(False)
         dom_ms, dom_calls = _C.profile_read()["render_bwd"]
+        dumped = None
+        if args.dump_outputs and rank == 0:    # the iteration's summed gradients (the bucket's views), before anything below steps again
+            names = ("xyz", "f_dc", "opacity", "scaling", "rotation") if multi_view else ("means3D", "shs", "opacities", "scales", "rotations")
+            dumped = dump_outputs(args.dump_outputs, {f"grad_{n}": p.grad for n, p in zip(names, scene.params)}, P)
         # what every rank holds after the timed steps (sum of |parameter|, float64): equal on all ranks if the exchange kept them in step, and --
         # same seeds, same step count -- equal between the all-reduce and the reduce-scatter exchange up to summation order
         param_digests = None
@@ -769,6 +828,8 @@ def main():
                              "whole_step_algorithmic_bytes": b_total * len(sms.keyframes)},
                 "kernel_us": kern,
             }
+            if dumped is not None:
+                out["dump_outputs"] = dumped
         if world > 1 and not args.no_secondary and args.gaussians is None:
             # the round-1 weak-scaling mode as a secondary figure: one 200k-Gaussian view per rank + all-reduce
             sw = Scene(CFG2_P, dev, 0, 0.005, keyframes=(rank,), cot_seed=1 + rank)

@@ -122,9 +122,12 @@ def run_backend(iters, window, all_kfs):
     b.viewpoints = {k: ToyCamera(k) for k in all_kfs}
     b._render = types.MethodType(toy_render, b)
     b._render_many = lambda cams, deltas: [toy_render(b, c, d) for c, d in zip(cams, deltas)]       # (the product's is one multi-view launch chain)
-    be.slam_losses = types.SimpleNamespace(get_loss_mapping=toy_loss)
-    b.map_static(window, iters=iters)
-    b.map_static(window, prune=True)
+    product_losses, be.slam_losses = be.slam_losses, types.SimpleNamespace(get_loss_mapping=toy_loss)
+    try:
+        b.map_static(window, iters=iters)
+        b.map_static(window, prune=True)
+    finally:                                             # run in the test's own process too: later tests get the product loss back
+        be.slam_losses = product_losses
     g = b.gaussians
     return {"params": [p.detach().numpy().copy() for p in (g._xyz, g._shs, g._opacity, g._scaling, g._rotation)],
             "poses": {k: (v.R.numpy().copy(), v.T.numpy().copy(), v.exposure_a.item(), v.exposure_b.item()) for k, v in b.viewpoints.items()},
