@@ -141,25 +141,14 @@ constexpr int VIEW_SLOT_GROUPS = 4;                             // gsr_set_optio
 constexpr int SPEC_SLOTS = 1 + 2 * MAX_VIEWS * VIEW_SLOT_GROUPS;
 static thread_local SpecState t_spec[16][SPEC_SLOTS];   // [device][0 = single-view calls | per group: 1..V views of a batch | MAX_VIEWS+1.. views of a flow batch]
 static thread_local int t_view_slot_group = 0;
-// a flow view's tile rectangle (gsr_view.flow_clip) for a view that goes through the single-view path inside a gsr_forward_views call
-static thread_local const int* t_clip_single = nullptr;
-// gsr_track_step (include/slam_map.h): the loss epilogue of the forward pass's render_fwd launches, and the launch that replaces tau_sum_kernel
-static thread_local const TrackLossArgs* t_track_loss = nullptr;
-struct TrackTail { const float* exposure_partials; float* dL_dexposure; CameraStepArgs step; };
-static thread_local const TrackTail* t_track_tail = nullptr;
-static thread_local SpecState* t_cur = &t_spec[0][0];
-static int select_device_state(int slot = 0)
+static int current_device()
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    t_cur = &t_spec[dev][slot];
     return dev;
 }
-#define t_mailbox (t_cur->mailbox)
-#define t_mailbox_dev (t_cur->mailbox_dev)
-#define t_seq (t_cur->seq)
-#define t_last_R_alloc (t_cur->last_R_alloc)
-#define t_last_max_tile (t_cur->last_max_tile)
+// the capacity estimate and mailbox of view slot `slot` of this thread on the current device
+static SpecState& spec_state(int slot) { return t_spec[current_device()][slot]; }
 static thread_local bool t_use_mailbox = true;
 static thread_local bool t_speculate = true;
 // Lazy mode (gsr_set_option("lazy", 1)): a speculative forward pass returns WITHOUT waiting for the scan kernel's header -- no host
@@ -181,18 +170,13 @@ static inline size_t spec_capacity(size_t last)
 }
 static thread_local bool t_options_read = false;
 static thread_local unsigned t_views_batched = 0;
-static bool t_fuse_sort = getenv("GSR_FUSE_SORT") ? getenv("GSR_FUSE_SORT")[0] != '0' : true;   // sort short tile lists inside render_fwd
+// Process-wide options (gsr_set_option may change them from any thread):
 // render_bwd's work items: full pieces in tile order, then the partial pieces longest first at the end of every XCD's sequence (gs_device.h:
 // item_block_*; one extra block of the scatter launch ranks them). GSR_ORDER_ITEMS=0: tile order, as rounds 2-5 (A/B runs; the results are
 // bit-identical either way)
-static bool t_order_items = getenv("GSR_ORDER_ITEMS") ? getenv("GSR_ORDER_ITEMS")[0] != '0' : true;
+static std::atomic<bool> g_order_items{getenv("GSR_ORDER_ITEMS") ? getenv("GSR_ORDER_ITEMS")[0] != '0' : true};
 // SH coefficient rows move through LDS in preprocess_fwd / geometry_bwd (gs_backward.h); GSR_SH_ROWS=0: per lane (bit-identical results)
-static bool t_sh_rows = getenv("GSR_SH_ROWS") ? getenv("GSR_SH_ROWS")[0] != '0' : true;
-// render_fwd's blocks take the tiles of their XCD band by list length, dealt over the band's CUs (gs_forward.h F3c). GSR_ORDER_TILES=0: band order
-static bool t_order_tiles = getenv("GSR_ORDER_TILES") ? getenv("GSR_ORDER_TILES")[0] != '0' : true;
-static const int t_deal_heavy = getenv("GSR_DEAL_HEAVY") ? atoi(getenv("GSR_DEAL_HEAVY")) : 1;      // lists per CU held back for the CUs with one block less (gs_forward.h)
-// 0: band order; 1 + heavy otherwise (the scatter launch's argument)
-static int order_fwd_tiles(int T, bool lds_hist) { return t_order_items && t_order_tiles && lds_hist && T / 8 >= ORDER_FWD_MIN_BAND ? 1 + std::max(0, std::min(7, t_deal_heavy)) : 0; }
+static std::atomic<bool> g_sh_rows{getenv("GSR_SH_ROWS") ? getenv("GSR_SH_ROWS")[0] != '0' : true};
 // HexPlane plane gradients as fixed-point integer sums (gs_hexplane_binned.h: HexOrd): bitwise the same run to run. 0: float atomics (rounds 1-5)
 static std::atomic<int> g_hex_ordered{getenv("GSR_HEX_ORDERED") ? (getenv("GSR_HEX_ORDERED")[0] != '0' ? 1 : 0) : 1};
 static void read_option_env()
@@ -203,34 +187,77 @@ static void read_option_env()
     if (const char* e = getenv("GSR_SPECULATE")) t_speculate = e[0] != '0';
     if (const char* e = getenv("GSR_LAZY")) t_lazy = e[0] != '0';
 }
-
-static int ensure_mailbox()
+// The options of one rasterizer call, read once at its entry point: every launch of the call sees the same values.
+struct Options { bool speculate, lazy, mailbox, order_items, sh_rows; };
+static Options read_options()
 {
-    if (!t_mailbox) {
-        GSR_HIP_CHECK(hipHostMalloc((void**)&t_mailbox, 8 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
-        memset(t_mailbox, 0, 8 * sizeof(uint32_t));
-        GSR_HIP_CHECK(hipHostGetDevicePointer((void**)&t_mailbox_dev, t_mailbox, 0));
+    read_option_env();
+    return {t_speculate, t_lazy, t_use_mailbox, g_order_items.load(std::memory_order_relaxed), g_sh_rows.load(std::memory_order_relaxed)};
+}
+
+// gsr_track_step (include/slam_map.h): what replaces tau_sum_kernel at the end of the backward pass
+struct TrackTail { const float* exposure_partials; float* dL_dexposure; CameraStepArgs step; };
+// The per-call state of the rasterizer orchestration, built at the extern "C" entry point and handed down.
+struct Call {
+    Options opt;
+    SpecState* spec = nullptr;                    // capacity estimate + mailbox of the (device, view slot) a forward pass renders for
+    const int* flow_clip = nullptr;               // a flow view's tile rectangle (gsr_view.flow_clip); NULL = the whole image
+    const TrackLossArgs* track_loss = nullptr;    // gsr_track_step: the loss epilogue of render_fwd (render_fwd_track_kernel)
+    const TrackTail* track_tail = nullptr;        // gsr_track_step: track_tail_kernel in place of tau_sum_kernel
+};
+
+// small launches are latency-bound: the per-Gaussian kernels then request every row they may need up front (gs_forward.h)
+constexpr int EAGER_MAX_P = 512 * 1024;
+// render_fwd's blocks take the tiles of their XCD band by list length, dealt over the band's CUs (gs_forward.h F3c), DEAL_HEAVY lists per CU
+// held back for the CUs with one block less. Needs the work-item ranking block (order_items) and the LDS histogram. Returns the scatter
+// launch's argument: 0 = band order, 1 + DEAL_HEAVY otherwise.
+constexpr int DEAL_HEAVY = 1;
+static int order_fwd_tiles(bool order_items, int T) { return order_items && T / 8 >= ORDER_FWD_MIN_BAND ? 1 + DEAL_HEAVY : 0; }
+// the same choices as gs_views.h takes them in one word: bit 0 = ordered work items, bit 1 = ordered render_fwd tiles, bits 2.. = DEAL_HEAVY
+static int views_order_word(bool order_items, int T) { return order_items ? 1 | (order_fwd_tiles(true, T) ? 2 | DEAL_HEAVY << 2 : 0) : 0; }
+// Longest tile list the speculative launches are sized for, from the last frame's (plus head room): picks the sort kernels (and the chunk
+// grid of the long-list sort).
+static uint32_t tile_list_capacity(uint32_t last_max_tile)
+{
+    const uint32_t want = last_max_tile + (uint32_t)((unsigned long long)last_max_tile * tile_margin() / 1000ull);
+    return want <= (uint32_t)SORT_SMALL_CAP ? (uint32_t)SORT_SMALL_CAP
+         : want <= (uint32_t)SORT_MID_CAP ? (uint32_t)SORT_MID_CAP
+         : want <= (uint32_t)SORT_LDS_CAP ? (uint32_t)SORT_LDS_CAP
+         : (want + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP * (uint32_t)SORT_LDS_CAP;
+}
+// preprocess_fwd's dynamic LDS at its largest: the tile histogram of a frame of HIST_LDS_TILES tiles, then one SH window per wave
+constexpr size_t PRE_LDS_MAX = (((size_t)HIST_LDS_TILES * sizeof(uint32_t) + 15) & ~size_t(15)) + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float);
+static_assert(PRE_LDS_MAX <= 160 * 1024, "preprocess_fwd's LDS must fit gfx950's 160 KiB per workgroup");
+
+static int ensure_mailbox(SpecState& s)
+{
+    if (!s.mailbox) {
+        GSR_HIP_CHECK(hipHostMalloc((void**)&s.mailbox, 8 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
+        memset(s.mailbox, 0, 8 * sizeof(uint32_t));
+        GSR_HIP_CHECK(hipHostGetDevicePointer((void**)&s.mailbox_dev, s.mailbox, 0));
     }
     return 0;
 }
 
-static int wait_for_header(hipStream_t stream, const uint32_t* device_header, uint32_t seq, uint32_t out[4])
+// the header of the forward pass numbered `seq` of slot `s`; use_mailbox: the call's option, cleared (for this call and the thread) when
+// the mailbox turns out not to work
+static int wait_for_header(hipStream_t stream, const SpecState& s, bool& use_mailbox, const uint32_t* device_header, uint32_t seq, uint32_t out[4])
 {
-    if (t_use_mailbox) {
+    if (use_mailbox) {
         // spin on the mailbox (the scan kernel is a few microseconds away when the GPU is not backed up); after ~1e5 polls the wait is
         // evidently long, so the core is yielded between polls; the stream is checked now and then so that a faulted / finished stream
         // cannot hang us
         for (unsigned long long spins = 0;; spins++) {
-            if (__atomic_load_n(&t_mailbox[4], __ATOMIC_ACQUIRE) == seq) {
-                for (int i = 0; i < 4; i++) out[i] = __atomic_load_n(&t_mailbox[i], __ATOMIC_RELAXED);
+            if (__atomic_load_n(&s.mailbox[4], __ATOMIC_ACQUIRE) == seq) {
+                for (int i = 0; i < 4; i++) out[i] = __atomic_load_n(&s.mailbox[i], __ATOMIC_RELAXED);
                 return 0;
             }
             if (spins > 100000ull) sched_yield();
             if ((spins & 0xFFFFF) == 0xFFFFF) {
                 hipError_t q = hipStreamQuery(stream);
                 if (q == hipSuccess) {   // stream drained: the store must be visible by now, otherwise fall back for good
-                    if (__atomic_load_n(&t_mailbox[4], __ATOMIC_ACQUIRE) == seq) continue;
-                    t_use_mailbox = false;
+                    if (__atomic_load_n(&s.mailbox[4], __ATOMIC_ACQUIRE) == seq) continue;
+                    t_use_mailbox = use_mailbox = false;
                     break;
                 }
                 if (q != hipErrorNotReady) { g_last_error = std::string("stream error while waiting for the header: ") + hipGetErrorString(q); return GSR_ERR_HIP; }
@@ -296,7 +323,13 @@ int gsr_set_option(const char* name, int value)
         if (value >= 0) t_cap_test_shrink_permille = value > 1000 ? 1000 : value;
         return old_shrink;
     }
-    bool* opt = n == "speculate" ? &t_speculate : n == "lazy" ? &t_lazy : n == "mailbox" ? &t_use_mailbox : n == "order_items" ? &t_order_items : n == "sh_rows" ? &t_sh_rows : nullptr;
+    if (n == "order_items" || n == "sh_rows") {               // process-wide
+        std::atomic<bool>& opt = n == "order_items" ? g_order_items : g_sh_rows;
+        const int old = opt.load(std::memory_order_relaxed) ? 1 : 0;
+        if (value >= 0) opt.store(value != 0, std::memory_order_relaxed);
+        return old;
+    }
+    bool* opt = n == "speculate" ? &t_speculate : n == "lazy" ? &t_lazy : n == "mailbox" ? &t_use_mailbox : nullptr;
     if (!opt) { g_last_error = "gsr_set_option: unknown option '" + n + "' (speculate, lazy, mailbox, order_items, sh_rows, cap_margin_permille, cap_tile_margin_permille, cap_floor, view_slot_group)"; return GSR_ERR_INVALID_ARGUMENT; }
     const int old = *opt ? 1 : 0;
     if (value >= 0) *opt = value != 0;
@@ -305,16 +338,15 @@ int gsr_set_option(const char* name, int value)
 
 int gsr_forward_status(unsigned int* overflow_count, unsigned int* last_num_rendered)
 {
-    select_device_state();
-    if (overflow_count) *overflow_count = t_mailbox ? __atomic_load_n(&t_mailbox[5], __ATOMIC_ACQUIRE) : 0u;
-    if (last_num_rendered) *last_num_rendered = t_mailbox ? __atomic_load_n(&t_mailbox[0], __ATOMIC_ACQUIRE) : 0u;
+    const uint32_t* mb = spec_state(0).mailbox;
+    if (overflow_count) *overflow_count = mb ? __atomic_load_n(&mb[5], __ATOMIC_ACQUIRE) : 0u;
+    if (last_num_rendered) *last_num_rendered = mb ? __atomic_load_n(&mb[0], __ATOMIC_ACQUIRE) : 0u;
     return 0;
 }
 
 int gsr_forward_status_views(unsigned int* overflow_count_total)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    const int dev = current_device();
     unsigned int total = 0;
     for (int slot = 0; slot < SPEC_SLOTS; slot++)
         if (const uint32_t* mb = t_spec[dev][slot].mailbox) total += __atomic_load_n(&mb[5], __ATOMIC_ACQUIRE);
@@ -326,8 +358,7 @@ int gsr_forward_status_views(unsigned int* overflow_count_total)
  * last_R_alloc, last_max_tile. out: [slots][8]; returns the number of slots. */
 int gsr_debug_view_slots(unsigned int* out, int max_slots)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    const int dev = current_device();
     const int n = max_slots < SPEC_SLOTS ? max_slots : SPEC_SLOTS;
     for (int slot = 0; slot < n; slot++) {
         const SpecState& s = t_spec[dev][slot];
@@ -368,7 +399,7 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 
 }  // extern "C"
 
-static RawInputs to_device_view(const gsr_raw_inputs* in)
+static RawInputs to_device_view(const gsr_raw_inputs* in, const int* flow_clip)
 {
     RawInputs r{};
     if (in) {
@@ -376,7 +407,7 @@ static RawInputs to_device_view(const gsr_raw_inputs* in)
         r.logit_opacity = in->logit_opacity; r.f_dc = in->features_dc; r.f_rest = in->features_rest;
         r.dyn_slot = in->dyn_slot; r.dx = in->dx; r.ds = in->ds; r.dr = in->dr; r.gather = in->gather;
         r.flow_dx2 = in->flow_dx2; r.flow_proj1 = in->flow_proj1; r.flow_proj2 = in->flow_proj2;
-        r.flow_clip = in->flow_proj1 ? t_clip_single : nullptr;
+        r.flow_clip = in->flow_proj1 ? flow_clip : nullptr;
         r.delta_mode = in->delta_mode; r.delta_stride = in->delta_stride;
     }
     return r;
@@ -391,41 +422,51 @@ static bool raw_inputs_ok(const gsr_raw_inputs* in, int M)
            (flow || (in->features_dc && (M == 1 || in->features_rest))) && ((!in->dx && !in->ds && !in->dr) || in->dyn_slot || in->delta_mode);
 }
 
-static int forward_impl(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_fn binning_alloc, void* binning_user,
-                gsr_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-                const float* means3D, const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
-                float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-                float* out_depth, float* out_opacity, int* radii, int* n_touched, int debug, void* stream_, const gsr_raw_inputs* raw, int slot = 0)
+// forward_impl's inputs: gsr_forward's arrays (raw == NULL), or gsr_forward_raw's descriptor (the arrays are then NULL)
+struct FwdInputs {
+    const float* means3D = nullptr; const float* shs = nullptr; const float* colors_precomp = nullptr; const float* opacities = nullptr;
+    const float* scales = nullptr; const float* rotations = nullptr; const float* cov3D_precomp = nullptr; int prefiltered = 0;
+    const gsr_raw_inputs* raw = nullptr;
+};
+struct FwdCamera { const float* viewmatrix; const float* projmatrix; const float* cam_pos; float tan_fovx, tan_fovy; };
+struct FwdOutputs { float* color; float* depth; float* opacity; int* radii; int* n_touched; };
+struct FwdAllocs { gsr_alloc_fn geometry; void* geometry_user; gsr_alloc_fn binning; void* binning_user; gsr_alloc_fn image; void* image_user; };
+
+static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, const float* background, int width, int height, const FwdInputs& in,
+                        float scale_modifier, const FwdCamera& cam, FwdOutputs out, int debug, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || width <= 0 || height <= 0 || !geometry_alloc || !binning_alloc || !image_alloc) {
+    const gsr_raw_inputs* const raw = in.raw;
+    if (P < 0 || width <= 0 || height <= 0 || !alloc.geometry || !alloc.binning || !alloc.image) {
         g_last_error = "gsr_forward: invalid size or missing allocator"; return GSR_ERR_INVALID_ARGUMENT;
     }
-    if (!background || !out_color || !out_depth || !out_opacity || !n_touched) { g_last_error = "gsr_forward: null output/background"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (!background || !out.color || !out.depth || !out.opacity || !out.n_touched) { g_last_error = "gsr_forward: null output/background"; return GSR_ERR_INVALID_ARGUMENT; }
     if (P > 0 && raw) {
-        if (!viewmatrix || !projmatrix || !cam_pos || M <= 0 || !raw_inputs_ok(raw, M)) { g_last_error = "gsr_forward_raw: null / inconsistent input"; return GSR_ERR_INVALID_ARGUMENT; }
+        if (!cam.viewmatrix || !cam.projmatrix || !cam.cam_pos || M <= 0 || !raw_inputs_ok(raw, M)) { g_last_error = "gsr_forward_raw: null / inconsistent input"; return GSR_ERR_INVALID_ARGUMENT; }
         if (D < 0 || D > 3 || (D + 1) * (D + 1) > M) { g_last_error = "gsr_forward_raw: sh degree out of range for M"; return GSR_ERR_INVALID_ARGUMENT; }
     } else if (P > 0) {
-        if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos) { g_last_error = "gsr_forward: null input"; return GSR_ERR_INVALID_ARGUMENT; }
-        if (!cov3D_precomp && (!scales || !rotations)) { g_last_error = "gsr_forward: need scales+rotations or cov3D_precomp"; return GSR_ERR_INVALID_ARGUMENT; }
+        if (!in.means3D || !in.opacities || !cam.viewmatrix || !cam.projmatrix || !cam.cam_pos) { g_last_error = "gsr_forward: null input"; return GSR_ERR_INVALID_ARGUMENT; }
+        if (!in.cov3D_precomp && (!in.scales || !in.rotations)) { g_last_error = "gsr_forward: need scales+rotations or cov3D_precomp"; return GSR_ERR_INVALID_ARGUMENT; }
         // rasterizer_impl.cu:245-248 analogue: colours must come from somewhere
-        if (!colors_precomp && (!shs || M <= 0)) { g_last_error = "gsr_forward: need shs (M>0) or colors_precomp"; return GSR_ERR_INVALID_ARGUMENT; }
-        if (!colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M)) { g_last_error = "gsr_forward: sh degree out of range for M"; return GSR_ERR_INVALID_ARGUMENT; }
+        if (!in.colors_precomp && (!in.shs || M <= 0)) { g_last_error = "gsr_forward: need shs (M>0) or colors_precomp"; return GSR_ERR_INVALID_ARGUMENT; }
+        if (!in.colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M)) { g_last_error = "gsr_forward: sh degree out of range for M"; return GSR_ERR_INVALID_ARGUMENT; }
     }
     const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y, T = gx * gy;
     const size_t N = (size_t)width * height;
-    select_device_state(slot);
+    SpecState& spec = *c.spec;
+    const int prefiltered = in.prefiltered;
 
-    char* gchunk = geometry_alloc(geometry_user, gsr_geometry_buffer_size(P));
-    char* ichunk = image_alloc(image_user, gsr_image_buffer_size(width, height, P));
+    char* gchunk = alloc.geometry(alloc.geometry_user, gsr_geometry_buffer_size(P));
+    char* ichunk = alloc.image(alloc.image_user, gsr_image_buffer_size(width, height, P));
     if (!gchunk || !ichunk) { g_last_error = "gsr_forward: allocation callback returned NULL"; return GSR_ERR_ALLOC; }
     GeomState geom = GeomState::from(gchunk, (size_t)P);
     ImageState img = ImageState::from(ichunk, N, (size_t)T, (size_t)P);
     const bool lds_hist = use_lds_hist((size_t)T);
     const size_t hist_lds_bytes = lds_hist ? (size_t)T * sizeof(uint32_t) : 0;
-    const bool order_items = t_order_items && lds_hist;        // (the ordering block keeps the tiles' list lengths in the same dynamic LDS)
-    if (!radii) radii = geom.internal_radii;   // rasterizer_impl.cu:232-235
+    const bool order_items = c.opt.order_items && lds_hist;        // (the ordering block keeps the tiles' list lengths in the same dynamic LDS)
+    const int order_fwd = order_fwd_tiles(order_items, T);
+    const int* const flow_clip = raw && raw->flow_proj1 ? c.flow_clip : nullptr;
+    int* const radii = out.radii ? out.radii : geom.internal_radii;   // rasterizer_impl.cu:232-235
 
     // Zero-filled scratch: the flag word only when someone can raise it (prefiltered; the reference's callers never set it), the
     // per-tile counters only when they are accumulated with atomics (the fallback for frames with more tiles than the LDS
@@ -437,42 +478,42 @@ static int forward_impl(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_al
         GSR_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(uint32_t), stream));
 
     const int nblocks = (P + GB - 1) / GB;
-    // small launches are latency-bound: the per-Gaussian kernels then request every row they may need up front (gs_forward.h)
-    static const int eager_max = getenv("GSR_EAGER_MAX") ? atoi(getenv("GSR_EAGER_MAX")) : 512 * 1024;
-    const int eager = P <= eager_max ? 1 : 0;
+    const int eager = P <= EAGER_MAX_P ? 1 : 0;
     if (P > 0) {
         PreprocessArgs a;
         a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.gx = gx; a.gy = gy;
-        a.means3D = means3D; a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations; a.opacities = opacities;
-        a.shs = shs; a.cov3D_precomp = cov3D_precomp; a.colors_precomp = colors_precomp;
-        a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.cam_pos = cam_pos;
-        a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-        a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx);   // rasterizer_impl.cu:225-226
-        a.prefiltered = prefiltered; a.radii = radii; a.n_touched = n_touched;
+        a.means3D = in.means3D; a.scales = in.scales; a.scale_modifier = scale_modifier; a.rotations = in.rotations; a.opacities = in.opacities;
+        a.shs = in.shs; a.cov3D_precomp = in.cov3D_precomp; a.colors_precomp = in.colors_precomp;
+        a.viewmatrix = cam.viewmatrix; a.projmatrix = cam.projmatrix; a.cam_pos = cam.cam_pos;
+        a.tan_fovx = cam.tan_fovx; a.tan_fovy = cam.tan_fovy;
+        a.focal_y = height / (2.0f * cam.tan_fovy); a.focal_x = width / (2.0f * cam.tan_fovx);   // rasterizer_impl.cu:225-226
+        a.prefiltered = prefiltered; a.radii = radii; a.n_touched = out.n_touched;
         a.rec = geom.rec; a.cov3D = geom.cov3D;
         a.clamped = geom.clamped; a.tiles_touched = geom.tiles_touched; a.block_sums = geom.block_sums; a.tile_count = img.tile_count;
         a.flags = flags; a.block_tile_base = lds_hist ? img.block_tile_base : nullptr;
-        a.raw = to_device_view(raw);
+        a.raw = to_device_view(raw, flow_clip);
         {
             ScopedKernelTimer tm(K_PREPROCESS, stream);
             a.eager = eager;
             // SH rows through LDS (gs_device.h: stage_rows): one 6.25 KB window per wave behind the tile histogram, reserved only when coefficients
             // above the DC band are read (the LDS histogram path: the windows sit in the same dynamic allocation)
-            const bool sh_win = t_sh_rows && lds_hist && D > 0 && !colors_precomp && (M == 9 || M == 16) && !(raw && raw->flow_proj1);
+            const bool sh_win = c.opt.sh_rows && lds_hist && D > 0 && !in.colors_precomp && (M == 9 || M == 16) && !(raw && raw->flow_proj1);
             a.sh_win_offset = sh_win ? (int)((hist_lds_bytes + 15) & ~size_t(15)) : 0;
             const size_t pre_lds = sh_win ? (size_t)a.sh_win_offset + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float) : hist_lds_bytes;
             if (sh_win) {
+                // the attribute is a cap set once per (kernel, device): the largest frame's bytes, so that a later frame with more tiles than
+                // the first one still launches (each launch still passes only the bytes it uses)
                 static std::atomic<unsigned long long> attr_set[3];
                 const void* fn = raw && raw->delta_mode ? reinterpret_cast<const void*>(preprocess_fwd_kernel<true, true>)
                                : raw ? reinterpret_cast<const void*>(preprocess_fwd_kernel<true>) : reinterpret_cast<const void*>(preprocess_fwd_kernel<false>);
-                const int rc = ensure_dynamic_lds(fn, (int)pre_lds, attr_set[raw && raw->delta_mode ? 2 : raw ? 1 : 0]);
+                const int rc = ensure_dynamic_lds(fn, (int)PRE_LDS_MAX, attr_set[raw && raw->delta_mode ? 2 : raw ? 1 : 0]);
                 if (rc) return rc;
             }
             if (raw && raw->delta_mode) hipLaunchKernelGGL((preprocess_fwd_kernel<true, true>), dim3(nblocks), dim3(GB), pre_lds, stream, a);
             else if (raw) hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(nblocks), dim3(GB), pre_lds, stream, a);
             else hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3(nblocks), dim3(GB), pre_lds, stream, a);
         }
-        GSR_STAGE("preprocess_fwd");
+        GSR_STAGE("preprocess_fwd");   // (returns the launch's error: hipGetLastError)
         if (lds_hist) {
             ScopedKernelTimer tm(K_SCAN, stream);
             if (nblocks <= TO_SEGS * 16)
@@ -491,159 +532,123 @@ static int forward_impl(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_al
     // the host reads R from the mailbox afterwards, while the GPU is already busy with them. The scan kernel compares the
     // frame's real needs with the speculative capacity and raises FLAG_OVERFLOW if they do not fit: the speculative kernels
     // then exit at once and the host redoes them on an exact-size buffer (also the path of the first call and of debug mode).
-    read_option_env();
-    if (t_lazy && t_mailbox) {
+    if (c.opt.lazy && spec.mailbox) {
         // lazy mode never waits, so the capacity estimate is refreshed from whatever header the GPU published last (a few calls old)
-        const uint32_t s0 = __atomic_load_n(&t_mailbox[4], __ATOMIC_ACQUIRE);
+        const uint32_t s0 = __atomic_load_n(&spec.mailbox[4], __ATOMIC_ACQUIRE);
         if (s0 != 0) {
-            const uint32_t r = __atomic_load_n(&t_mailbox[0], __ATOMIC_RELAXED), ra = __atomic_load_n(&t_mailbox[2], __ATOMIC_RELAXED);
-            const uint32_t mx = __atomic_load_n(&t_mailbox[3], __ATOMIC_RELAXED);
-            if (__atomic_load_n(&t_mailbox[4], __ATOMIC_ACQUIRE) == s0 && r <= 0x7fffffffu && ra <= 0x7fffffffu) {
+            const uint32_t r = __atomic_load_n(&spec.mailbox[0], __ATOMIC_RELAXED), ra = __atomic_load_n(&spec.mailbox[2], __ATOMIC_RELAXED);
+            const uint32_t mx = __atomic_load_n(&spec.mailbox[3], __ATOMIC_RELAXED);
+            if (__atomic_load_n(&spec.mailbox[4], __ATOMIC_ACQUIRE) == s0 && r <= 0x7fffffffu && ra <= 0x7fffffffu) {
                 const size_t need = ra > r ? ra : r;
                 // grow at once, shrink slowly: a view that briefly needs less must not take the slack away from the next one
-                t_last_R_alloc = need > t_last_R_alloc ? need : t_last_R_alloc - (t_last_R_alloc - need) / 16;
-                t_last_max_tile = mx > t_last_max_tile ? mx : t_last_max_tile;
+                spec.last_R_alloc = need > spec.last_R_alloc ? need : spec.last_R_alloc - (spec.last_R_alloc - need) / 16;
+                spec.last_max_tile = mx > spec.last_max_tile ? mx : spec.last_max_tile;
             }
         }
     }
-    const bool speculate = t_speculate && t_last_R_alloc && !debug && P > 0;
-    const size_t cap = speculate ? spec_capacity(t_last_R_alloc) : 0;
-    // longest tile list the speculative launches are sized for: decides which sort kernels run (and the chunk grid of the long-list sort)
-    const uint32_t want_tile = t_last_max_tile + (uint32_t)((unsigned long long)t_last_max_tile * tile_margin() / 1000ull);
-    const uint32_t cap_tile = want_tile <= (uint32_t)SORT_SMALL_CAP ? (uint32_t)SORT_SMALL_CAP
-                            : want_tile <= (uint32_t)SORT_MID_CAP ? (uint32_t)SORT_MID_CAP
-                            : want_tile <= (uint32_t)SORT_LDS_CAP ? (uint32_t)SORT_LDS_CAP
-                            : (want_tile + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP * (uint32_t)SORT_LDS_CAP;
+    const bool speculate = c.opt.speculate && spec.last_R_alloc && !debug && P > 0;
+    const size_t cap = speculate ? spec_capacity(spec.last_R_alloc) : 0;
+    const uint32_t cap_tile = tile_list_capacity(spec.last_max_tile);
     // F2b (gs_forward.h): on a speculative frame of the LDS-histogram path the scatter launch does the scan's work itself -- one launch less
-    // (GSR_SCAN_IN_SCATTER=0: the scan as its own launch, as rounds 1-5)
-    static const bool scan_in_scatter_ok = !(getenv("GSR_SCAN_IN_SCATTER") && getenv("GSR_SCAN_IN_SCATTER")[0] == '0');
-    const bool scan_in_scatter = scan_in_scatter_ok && speculate && lds_hist && nblocks <= GB;
+    const bool scan_in_scatter = speculate && lds_hist && nblocks <= GB;
     {
         ScopedKernelTimer tm(K_SCAN, stream);
-        { const int rc = ensure_mailbox(); if (rc) return rc; }
-        if (++t_seq == 0) t_seq = 1;
+        { const int rc = ensure_mailbox(spec); if (rc) return rc; }
+        if (++spec.seq == 0) spec.seq = 1;
         if (!scan_in_scatter)
             hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, nblocks, geom.block_sums, geom.block_base, T, img.tile_count,
                                img.ranges, img.tile_cursor, prefiltered ? flags : (const uint32_t*)nullptr, (uint32_t)cap, cap_tile, img.chunk_base,
                                geom.header,
-                               t_use_mailbox ? t_mailbox_dev : nullptr, t_seq);
+                               c.opt.mailbox ? spec.mailbox_dev : nullptr, spec.seq);
     }
     GSR_STAGE("scan");
 
+    // render_fwd, or its tracking variant with the loss epilogue (gsr_track_step)
+    auto launch_render_fwd = [&](auto... args) {
+        ScopedKernelTimer tm(K_RENDER_FWD, stream);
+        if (c.track_loss) hipLaunchKernelGGL(render_fwd_track_kernel, dim3(T), dim3(RB), 0, stream, args..., *c.track_loss);
+        else hipLaunchKernelGGL(render_fwd_kernel, dim3(T), dim3(RB), 0, stream, args...);
+    };
     // scatter -> sort -> render on a binning buffer laid out for carve_R instances / cap_sorted sorted entries
-    auto enqueue_binning_and_render = [&](char* chunk, size_t carve_R, size_t cap_sorted, bool spec, bool any_padding,
+    auto enqueue_binning_and_render = [&](char* chunk, size_t carve_R, size_t cap_sorted, bool spec_launch, bool any_padding,
                                           uint32_t longest_list) -> int {
-        const bool long_lists = longest_list > (uint32_t)SORT_SMALL_CAP;
         const BinningPtrs bin = carve_binning(chunk, carve_R, cap_sorted, (size_t)T);
-        uint32_t* const chk = spec ? geom.header : nullptr;
+        uint32_t* const chk = spec_launch ? geom.header : nullptr;
         if (any_padding) GSR_HIP_CHECK(hipMemsetAsync(bin.keys, 0xFF, cap_sorted * sizeof(uint64_t), stream));   // sort padding
         {
             ScopedKernelTimer tm(K_SCATTER, stream);
             ScanInScatter sis{};
-            if (spec && scan_in_scatter) {
+            if (spec_launch && scan_in_scatter) {
                 sis.dense_total = img.tile_cursor; sis.block_sums = geom.block_sums; sis.nblocks = nblocks; sis.ranges = img.ranges; sis.block_base = geom.block_base;
                 sis.chunk_base = img.chunk_base; sis.flags = prefiltered ? flags : (const uint32_t*)nullptr; sis.cap_R = (uint32_t)cap; sis.cap_tile_list = cap_tile;
-                sis.host_mailbox = t_use_mailbox ? t_mailbox_dev : nullptr; sis.seq = t_seq;
+                sis.host_mailbox = c.opt.mailbox ? spec.mailbox_dev : nullptr; sis.seq = spec.seq;
             }
             hipLaunchKernelGGL(scatter_instances_kernel, dim3(nblocks + (order_items || sis.dense_total ? 1 : 0)), dim3(GB), hist_lds_bytes, stream, P, gx, gy, radii, geom.rec,
                                geom.tiles_touched, geom.block_base, geom.point_offsets, img.tile_cursor, img.ranges,
-                               lds_hist ? img.block_tile_base : nullptr, bin.keys, bin.inst_gauss, geom.header, spec ? 1 : 0,
-                               (uint32_t)carve_R, (uint32_t)cap_sorted, eager, (raw && raw->flow_proj1) ? t_clip_single : (const int*)nullptr,
-                               order_items ? img.tile_count : (uint32_t*)nullptr, order_fwd_tiles(T, lds_hist), sis);
+                               lds_hist ? img.block_tile_base : nullptr, bin.keys, bin.inst_gauss, geom.header, spec_launch ? 1 : 0,
+                               (uint32_t)carve_R, (uint32_t)cap_sorted, eager, flow_clip,
+                               order_items ? img.tile_count : (uint32_t*)nullptr, order_fwd, sis);
         }
         GSR_STAGE("scatter_instances");
-        if (!t_fuse_sort || long_lists) {   // lists of up to SORT_SMALL_CAP entries are sorted inside render_fwd (fused); longer ones here
+        if (longest_list > (uint32_t)SORT_SMALL_CAP) {   // lists of up to SORT_SMALL_CAP entries are sorted inside render_fwd; longer ones here
             ScopedKernelTimer tm(K_SORT, stream);
-            if (!t_fuse_sort)
-                hipLaunchKernelGGL((sort_tiles_kernel<SORT_SMALL_CAP, 0>), dim3(T), dim3(256), 0, stream, T, img.ranges, bin.keys,
-                                   bin.inst_gauss, bin.sorted, chk);
-            // dev knobs: GSR_LONG_FROM = list length above which the chunk + rank path is taken (default SORT_LDS_CAP; 1024 drops the
-            // one-block-per-tile LDS sort of the 1024..4096 lists), GSR_LONG_CHUNK = its chunk size (1024 / 2048 / 4096)
-            static const uint32_t long_from = getenv("GSR_LONG_FROM") ? (uint32_t)atoi(getenv("GSR_LONG_FROM")) : (uint32_t)SORT_LDS_CAP;
-            static const int long_chunk = getenv("GSR_LONG_CHUNK") ? atoi(getenv("GSR_LONG_CHUNK")) : SORT_LDS_CAP;
-            if (long_lists && long_from > (uint32_t)SORT_SMALL_CAP) {
-                // one launch: 18 KiB blocks (eight per CU) when no list exceeds 2048 keys, 36 KiB blocks (four per CU) otherwise. Splitting
-                // the tiles between two launches by length was measured: the two tails cost more than the occupancy returns (99 -> 131 us).
-                if (longest_list <= (uint32_t)SORT_MID_CAP)
-                    hipLaunchKernelGGL((sort_tiles_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
-                                       bin.keys, bin.inst_gauss, bin.sorted, chk);
-                else
-                    hipLaunchKernelGGL((sort_tiles_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
-                                       bin.keys, bin.inst_gauss, bin.sorted, chk);
-            }
-            if (longest_list > long_from) {   // chunk-wise LDS sort + rank by counting (gs_forward.h F4b)
-#define GSR_LONG(CK)                                                                                                                   \
-    do {                                                                                                                              \
-        const dim3 g((unsigned)T, (longest_list + (uint32_t)(CK) - 1) / (uint32_t)(CK));                                               \
-        hipLaunchKernelGGL((sort_long_chunks_kernel<CK>), g, dim3(256), 0, stream, img.ranges, bin.keys, chk, long_from);              \
-        hipLaunchKernelGGL((rank_long_chunks_kernel<CK>), g, dim3(256), 0, stream, img.ranges, (const uint64_t*)bin.keys,               \
-                           (const uint32_t*)bin.inst_gauss, bin.sorted, chk, long_from);                                               \
-    } while (0)
-                if (long_chunk == 1024) GSR_LONG(1024); else if (long_chunk == 2048) GSR_LONG(2048); else GSR_LONG(4096);
-#undef GSR_LONG
+            // one launch: 18 KiB blocks (eight per CU) when no list exceeds 2048 keys, 36 KiB blocks (four per CU) otherwise. Splitting
+            // the tiles between two launches by length was measured: the two tails cost more than the occupancy returns (99 -> 131 us).
+            if (longest_list <= (uint32_t)SORT_MID_CAP)
+                hipLaunchKernelGGL((sort_tiles_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
+                                   bin.keys, bin.inst_gauss, bin.sorted, chk);
+            else
+                hipLaunchKernelGGL((sort_tiles_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
+                                   bin.keys, bin.inst_gauss, bin.sorted, chk);
+            if (longest_list > (uint32_t)SORT_LDS_CAP) {   // chunk-wise LDS sort + rank by counting (gs_forward.h F4b)
+                const dim3 g((unsigned)T, (longest_list + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP);
+                hipLaunchKernelGGL((sort_long_chunks_kernel<SORT_LDS_CAP>), g, dim3(256), 0, stream, img.ranges, bin.keys, chk, (uint32_t)SORT_LDS_CAP);
+                hipLaunchKernelGGL((rank_long_chunks_kernel<SORT_LDS_CAP>), g, dim3(256), 0, stream, img.ranges, (const uint64_t*)bin.keys,
+                                   (const uint32_t*)bin.inst_gauss, bin.sorted, chk, (uint32_t)SORT_LDS_CAP);
             }
         }
         GSR_STAGE("sort_tiles");
-        {   // Tiles with an empty range still run and write the background (forward.cu:297-299,382-391; Q21).
-            ScopedKernelTimer tm(K_RENDER_FWD, stream);
-            if (t_track_loss)
-                hipLaunchKernelGGL(render_fwd_track_kernel, dim3(T), dim3(RB), 0, stream, T, gx, img.ranges, bin.sorted, width, height, geom.rec,
-                                   background, img.final_T, img.n_contrib, out_color, out_depth,
-                                   out_opacity, n_touched, img.final_C, bin.ckpt, chk, t_fuse_sort ? (const uint64_t*)bin.keys : nullptr,
-                                   (const uint32_t*)bin.inst_gauss, bin.sorted, (const uint32_t*)img.chunk_base, bin.chunk_info,
-                                   order_items ? (const uint32_t*)img.tile_count : (const uint32_t*)nullptr, order_fwd_tiles(T, lds_hist) ? 1 : 0, *t_track_loss);
-            else
-            hipLaunchKernelGGL(render_fwd_kernel, dim3(T), dim3(RB), 0, stream, T, gx, img.ranges, bin.sorted, width, height, geom.rec,
-                               background, img.final_T, img.n_contrib, out_color, out_depth,
-                               out_opacity, n_touched, img.final_C, bin.ckpt, chk, t_fuse_sort ? (const uint64_t*)bin.keys : nullptr,
-                               (const uint32_t*)bin.inst_gauss, bin.sorted, (const uint32_t*)img.chunk_base, bin.chunk_info,
-                               order_items ? (const uint32_t*)img.tile_count : (const uint32_t*)nullptr, order_fwd_tiles(T, lds_hist) ? 1 : 0);
-        }
+        // Tiles with an empty range still run and write the background (forward.cu:297-299,382-391; Q21).
+        launch_render_fwd(T, gx, img.ranges, bin.sorted, width, height, geom.rec, background, img.final_T, img.n_contrib, out.color, out.depth,
+                          out.opacity, out.n_touched, img.final_C, bin.ckpt, chk, (const uint64_t*)bin.keys, (const uint32_t*)bin.inst_gauss, bin.sorted,
+                          (const uint32_t*)img.chunk_base, bin.chunk_info, order_items ? (const uint32_t*)img.tile_count : (const uint32_t*)nullptr,
+                          order_fwd ? 1 : 0);
         GSR_STAGE("render_fwd");
         return 0;
     };
 
     char* bchunk = nullptr;
     if (speculate) {
-        bchunk = binning_alloc(binning_user, binning_bytes(cap, cap, (size_t)T));
+        bchunk = alloc.binning(alloc.binning_user, binning_bytes(cap, cap, (size_t)T));
         if (!bchunk) { g_last_error = "gsr_forward: binning allocation callback returned NULL"; return GSR_ERR_ALLOC; }
         const int rc = enqueue_binning_and_render(bchunk, cap, cap, true, false, cap_tile);
         if (rc) return rc;
     }
-    if (speculate && t_lazy) return (int)(cap > 0x7fffffffull ? 0x7fffffffull : cap);   // no wait: see t_lazy
+    if (speculate && c.opt.lazy) return (int)(cap > 0x7fffffffull ? 0x7fffffffull : cap);   // no wait: see t_lazy
     // The one host wait of the forward pass (the reference's is the blocking cudaMemcpy at rasterizer_impl.cu:283-284).
     uint32_t hdr[4];
-    { const int rc = wait_for_header(stream, geom.header, t_seq, hdr); if (rc) return rc; }
+    { const int rc = wait_for_header(stream, spec, c.opt.mailbox, geom.header, spec.seq, hdr); if (rc) return rc; }
     const uint32_t R = hdr[HDR_R], flg = hdr[HDR_FLAGS], R_alloc = hdr[HDR_R_ALLOC], max_tile_list = hdr[HDR_MAX_TILE];
     if (flg & FLAG_PREFILTERED) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return GSR_ERR_PREFILTERED; }
     if (R > 0x7fffffffu || R_alloc > 0x7fffffffu) { g_last_error = "gsr_forward: more than 2^31 instances"; return GSR_ERR_INVALID_ARGUMENT; }
-    t_last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);     // (never 0: 0 means "no estimate yet"; a frame may legitimately have no instance)
-    t_last_max_tile = max_tile_list;
+    spec.last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);     // (never 0: 0 means "no estimate yet"; a frame may legitimately have no instance)
+    spec.last_max_tile = max_tile_list;
     if (speculate && !(flg & FLAG_OVERFLOW)) return (int)R;
 
     if (R > 0) {
-        bchunk = binning_alloc(binning_user, binning_bytes((size_t)R, (size_t)R_alloc, (size_t)T));
+        bchunk = alloc.binning(alloc.binning_user, binning_bytes((size_t)R, (size_t)R_alloc, (size_t)T));
         if (!bchunk) { g_last_error = "gsr_forward: binning allocation callback returned NULL"; return GSR_ERR_ALLOC; }
         const int rc = enqueue_binning_and_render(bchunk, (size_t)R, (size_t)R_alloc, false, R_alloc != R, max_tile_list);
         if (rc) return rc;
     } else {
-        if (!bchunk) bchunk = binning_alloc(binning_user, binning_bytes(0, 0, (size_t)T));
+        if (!bchunk) bchunk = alloc.binning(alloc.binning_user, binning_bytes(0, 0, (size_t)T));
         if (!bchunk) { g_last_error = "gsr_forward: binning allocation callback returned NULL"; return GSR_ERR_ALLOC; }
         // keep point_offsets defined for debug readers / backward even when nothing is visible
         if (P > 0) GSR_HIP_CHECK(hipMemsetAsync(geom.point_offsets, 0, (size_t)P * sizeof(uint32_t), stream));
-        ScopedKernelTimer tm(K_RENDER_FWD, stream);
-        if (t_track_loss)
-            hipLaunchKernelGGL(render_fwd_track_kernel, dim3(T), dim3(RB), 0, stream, T, gx, img.ranges, (const uint2*)nullptr, width, height,
-                               geom.rec, background, img.final_T, img.n_contrib, out_color,
-                               out_depth, out_opacity, n_touched, img.final_C, (float*)nullptr, (const uint32_t*)nullptr,
-                               (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint2*)nullptr, (const uint32_t*)nullptr, (uint4*)nullptr,
-                               (const uint32_t*)nullptr, 0, *t_track_loss);
-        else
-        hipLaunchKernelGGL(render_fwd_kernel, dim3(T), dim3(RB), 0, stream, T, gx, img.ranges, (const uint2*)nullptr, width, height,
-                           geom.rec, background, img.final_T, img.n_contrib, out_color,
-                           out_depth, out_opacity, n_touched, img.final_C, (float*)nullptr, (const uint32_t*)nullptr,
-                           (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint2*)nullptr, (const uint32_t*)nullptr, (uint4*)nullptr,
-                           (const uint32_t*)nullptr, 0);
+        launch_render_fwd(T, gx, img.ranges, (const uint2*)nullptr, width, height, geom.rec, background, img.final_T, img.n_contrib, out.color,
+                          out.depth, out.opacity, out.n_touched, img.final_C, (float*)nullptr, (const uint32_t*)nullptr,
+                          (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint2*)nullptr, (const uint32_t*)nullptr, (uint4*)nullptr,
+                          (const uint32_t*)nullptr, 0);
     }
     GSR_STAGE("render_fwd");
     return (int)R;
@@ -658,9 +663,11 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_fn b
                 const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                 float* out_depth, float* out_opacity, int* radii, int* n_touched, int debug, void* stream)
 {
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                        cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_opacity, radii, n_touched, debug, stream, nullptr);
+    Call c{read_options(), &spec_state(0)};
+    const FwdInputs in{means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, prefiltered, nullptr};
+    return forward_impl(c, {geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user}, P, D, M, background, width, height,
+                        in, scale_modifier, {viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy}, {out_color, out_depth, out_opacity, radii, n_touched},
+                        debug, stream);
 }
 
 int gsr_forward_raw(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_fn binning_alloc, void* binning_user,
@@ -670,9 +677,12 @@ int gsr_forward_raw(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_
                     int debug, void* stream)
 {
     if (!in) { g_last_error = "gsr_forward_raw: null input descriptor"; return GSR_ERR_INVALID_ARGUMENT; }
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width, height,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, 0, out_color, out_depth, out_opacity, radii, n_touched, debug, stream, in);
+    Call c{read_options(), &spec_state(0)};
+    FwdInputs fin;
+    fin.raw = in;
+    return forward_impl(c, {geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user}, P, D, M, background, width, height,
+                        fin, scale_modifier, {viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy}, {out_color, out_depth, out_opacity, radii, n_touched},
+                        debug, stream);
 }
 
 }  // extern "C"
@@ -686,6 +696,11 @@ char* captured_alloc(void* u, size_t bytes)
     c->got = c->fn(c->user, bytes);
     return c->got;
 }
+// the three allocations of one forward pass, remembered for the caller
+struct CapturedAllocs {
+    CapturedAlloc g, b, i;
+    FwdAllocs fns() { return {captured_alloc, &g, captured_alloc, &b, captured_alloc, &i}; }
+};
 ViewDims view_dims(int P, int width, int height)
 {
     ViewDims d;
@@ -695,19 +710,22 @@ ViewDims view_dims(int P, int width, int height)
 }
 }  // namespace
 
-static int forward_one_view(gsr_view& vw, int slot, gsr_alloc_fn geometry_alloc, gsr_alloc_fn binning_alloc, gsr_alloc_fn image_alloc, int P, int D, int M,
-                            const float* background, int width, int height, const gsr_raw_inputs* in, float scale_modifier, float tan_fovx, float tan_fovy,
-                            int debug, void* stream)
+// view `vw` of a gsr_forward_views call through the single-view path, on view slot `slot`
+static int forward_one_view(const Options& opt, gsr_view& vw, int slot, gsr_alloc_fn geometry_alloc, gsr_alloc_fn binning_alloc, gsr_alloc_fn image_alloc,
+                            int P, int D, int M, const float* background, int width, int height, const gsr_raw_inputs* in, float scale_modifier,
+                            float tan_fovx, float tan_fovy, int debug, void* stream)
 {
     gsr_raw_inputs one = *in;
     one.dx = vw.dx; one.ds = vw.ds; one.dr = vw.dr;
     one.flow_dx2 = vw.flow_dx2; one.flow_proj1 = vw.flow_proj1; one.flow_proj2 = vw.flow_proj2;
-    CapturedAlloc g{geometry_alloc, vw.geometry_user, nullptr}, b{binning_alloc, vw.binning_user, nullptr}, i{image_alloc, vw.image_user, nullptr};
-    const int rc = forward_impl(captured_alloc, &g, captured_alloc, &b, captured_alloc, &i, P, D, M, background, width, height, nullptr, nullptr, nullptr, nullptr,
-                                nullptr, scale_modifier, nullptr, nullptr, vw.viewmatrix, vw.projmatrix, vw.cam_pos, tan_fovx, tan_fovy, 0, vw.out_color,
-                                vw.out_depth, vw.out_opacity, vw.radii, vw.n_touched, debug, stream, &one, slot);
+    Call c{opt, &spec_state(slot), vw.flow_clip};
+    FwdInputs fin;
+    fin.raw = &one;
+    CapturedAllocs al{{geometry_alloc, vw.geometry_user, nullptr}, {binning_alloc, vw.binning_user, nullptr}, {image_alloc, vw.image_user, nullptr}};
+    const int rc = forward_impl(c, al.fns(), P, D, M, background, width, height, fin, scale_modifier, {vw.viewmatrix, vw.projmatrix, vw.cam_pos, tan_fovx, tan_fovy},
+                                {vw.out_color, vw.out_depth, vw.out_opacity, vw.radii, vw.n_touched}, debug, stream);
     if (rc < 0) return rc;
-    vw.geom_buffer = g.got; vw.binning_buffer = b.got; vw.image_buffer = i.got; vw.num_rendered = rc;
+    vw.geom_buffer = al.g.got; vw.binning_buffer = al.b.got; vw.image_buffer = al.i.got; vw.num_rendered = rc;
     return 0;
 }
 
@@ -734,41 +752,31 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     // several (view_slot_group): a slot shared by two calls per iteration sees its estimate flip between two cameras -- eager calls then redo
     // the view through the single-view path every time, captured ones overflow at every replay
     const int slot0 = 1 + t_view_slot_group * 2 * MAX_VIEWS + (flow ? MAX_VIEWS : 0);
-    const int* clips[MAX_VIEWS];                             // a flow view's tile rectangle: gsr_view.flow_clip
-    for (int v = 0; v < MAX_VIEWS; v++) clips[v] = (flow && v < V) ? views[v].flow_clip : nullptr;
     const ViewDims d = view_dims(P, width, height);
-    read_option_env();
+    Options opt = read_options();
     // the batched path needs a capacity estimate for every slot (the first iteration of a window goes view by view and leaves one)
-    const int dev = select_device_state(0);
-    bool batched = !debug && t_speculate && use_lds_hist((size_t)d.T) && V > 1;
-    for (int v = 0; v < V && batched; v++) batched = t_spec[dev][slot0 + v].last_R_alloc != 0;
+    bool batched = !debug && opt.speculate && use_lds_hist((size_t)d.T) && V > 1;
+    for (int v = 0; v < V && batched; v++) batched = spec_state(slot0 + v).last_R_alloc != 0;
     if (!batched) {
         for (int v = 0; v < V; v++) {
-            t_clip_single = clips[v];
-            const int rc = forward_one_view(views[v], slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier,
-                                            tan_fovx, tan_fovy, debug, stream_);
-            t_clip_single = nullptr;
+            const int rc = forward_one_view(opt, views[v], slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in,
+                                            scale_modifier, tan_fovx, tan_fovy, debug, stream_);
             if (rc) return rc;
         }
         return 0;
     }
-    static const int eager_max = getenv("GSR_EAGER_MAX") ? atoi(getenv("GSR_EAGER_MAX")) : 512 * 1024;
     t_views_batched++;
     ViewTable t;
     memset(&t, 0, sizeof(t));
-    uint32_t want_tile = 0;
-    for (int v = 0; v < V; v++) want_tile = std::max(want_tile, t_spec[dev][slot0 + v].last_max_tile);
-    want_tile += (uint32_t)((unsigned long long)want_tile * tile_margin() / 1000ull);
-    const uint32_t cap_tile = want_tile <= (uint32_t)SORT_SMALL_CAP ? (uint32_t)SORT_SMALL_CAP
-                            : want_tile <= (uint32_t)SORT_MID_CAP ? (uint32_t)SORT_MID_CAP
-                            : want_tile <= (uint32_t)SORT_LDS_CAP ? (uint32_t)SORT_LDS_CAP
-                            : (want_tile + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP * (uint32_t)SORT_LDS_CAP;
+    uint32_t last_max_tile = 0;
+    for (int v = 0; v < V; v++) last_max_tile = std::max(last_max_tile, spec_state(slot0 + v).last_max_tile);
+    const uint32_t cap_tile = tile_list_capacity(last_max_tile);
     for (int v = 0; v < V; v++) {
         gsr_view& w = views[v];
-        select_device_state(slot0 + v);
-        { const int rc = ensure_mailbox(); if (rc) return rc; }
-        if (++t_seq == 0) t_seq = 1;
-        const size_t cap = spec_capacity(t_last_R_alloc);
+        SpecState& spec = spec_state(slot0 + v);
+        { const int rc = ensure_mailbox(spec); if (rc) return rc; }
+        if (++spec.seq == 0) spec.seq = 1;
+        const size_t cap = spec_capacity(spec.last_R_alloc);
         w.geom_buffer = geometry_alloc(w.geometry_user, gsr_geometry_buffer_size(P));
         w.image_buffer = image_alloc(w.image_user, gsr_image_buffer_size(width, height, P));
         w.binning_buffer = binning_alloc(w.binning_user, binning_bytes(cap, cap, (size_t)d.T));
@@ -776,20 +784,21 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
         ViewSlot& s = t.v[v];
         s.viewmatrix = w.viewmatrix; s.projmatrix = w.projmatrix; s.projmatrix_raw = w.projmatrix_raw; s.cam_pos = w.cam_pos;
         s.dx = w.dx; s.ds = w.ds; s.dr = w.dr;
-        s.flow_dx2 = w.flow_dx2; s.flow_proj1 = w.flow_proj1; s.flow_proj2 = w.flow_proj2; s.flow_clip = clips[v];
+        s.flow_dx2 = w.flow_dx2; s.flow_proj1 = w.flow_proj1; s.flow_proj2 = w.flow_proj2; s.flow_clip = flow ? w.flow_clip : nullptr;
         s.geom = w.geom_buffer; s.image = w.image_buffer; s.binning = w.binning_buffer;
         s.out_color = w.out_color; s.out_depth = w.out_depth; s.out_opacity = w.out_opacity; s.radii = w.radii; s.n_touched = w.n_touched;
-        s.mailbox = t_use_mailbox ? t_mailbox_dev : nullptr; s.cap = (uint32_t)std::min<size_t>(cap, 0x7fffffffu); s.cap_tile = cap_tile; s.seq = t_seq;
+        s.mailbox = opt.mailbox ? spec.mailbox_dev : nullptr; s.cap = (uint32_t)std::min<size_t>(cap, 0x7fffffffu); s.cap_tile = cap_tile; s.seq = spec.seq;
     }
     PreprocessArgs a;
     memset(&a, 0, sizeof(a));
     a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.gx = d.gx; a.gy = d.gy;
     a.scale_modifier = scale_modifier; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
     a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx);
-    a.prefiltered = 0; a.eager = P <= eager_max ? 1 : 0;
-    a.raw = to_device_view(in);
+    a.prefiltered = 0; a.eager = P <= EAGER_MAX_P ? 1 : 0;
+    a.raw = to_device_view(in, nullptr);
     const dim3 gv((unsigned)d.nblocks, (unsigned)V), tv((unsigned)d.T, (unsigned)V);
     const size_t hist_lds_bytes = (size_t)d.T * sizeof(uint32_t);
+    const int order = views_order_word(opt.order_items, d.T);
     {
         ScopedKernelTimer tm(K_PREPROCESS, stream);
         if (in->delta_mode) hipLaunchKernelGGL((preprocess_views_kernel<true, true>), gv, dim3(GB), hist_lds_bytes, stream, a, t, d);
@@ -804,16 +813,13 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     }
     {
         ScopedKernelTimer tm(K_SCATTER, stream);
-        hipLaunchKernelGGL(scatter_views_kernel, dim3((unsigned)d.nblocks + (t_order_items ? 1u : 0u), (unsigned)V), dim3(GB), hist_lds_bytes, stream, t, d, a.eager,
-                           t_order_items ? (order_fwd_tiles(d.T, true) ? 3 + 4 * (order_fwd_tiles(d.T, true) - 1) : 1) : 0);
+        hipLaunchKernelGGL(scatter_views_kernel, dim3((unsigned)d.nblocks + (opt.order_items ? 1u : 0u), (unsigned)V), dim3(GB), hist_lds_bytes, stream, t, d, a.eager,
+                           order);
     }
-    if (!t_fuse_sort || cap_tile > (uint32_t)SORT_SMALL_CAP) {
+    if (cap_tile > (uint32_t)SORT_SMALL_CAP) {   // lists of up to SORT_SMALL_CAP entries are sorted inside render_fwd
         ScopedKernelTimer tm(K_SORT, stream);
-        if (!t_fuse_sort) hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_SMALL_CAP, 0>), tv, dim3(256), 0, stream, t, d);
-        if (cap_tile > (uint32_t)SORT_SMALL_CAP) {
-            if (cap_tile <= (uint32_t)SORT_MID_CAP) hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
-            else hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
-        }
+        if (cap_tile <= (uint32_t)SORT_MID_CAP) hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
+        else hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
         if (cap_tile > (uint32_t)SORT_LDS_CAP) {
             const dim3 gl((unsigned)d.T, (cap_tile + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP, (unsigned)V);
             hipLaunchKernelGGL((sort_long_chunks_views_kernel<SORT_LDS_CAP>), gl, dim3(256), 0, stream, t, d, (uint32_t)SORT_LDS_CAP);
@@ -822,29 +828,27 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     }
     {
         ScopedKernelTimer tm(K_RENDER_FWD, stream);
-        hipLaunchKernelGGL(render_fwd_views_kernel, tv, dim3(RB), 0, stream, t, d, background, t_fuse_sort ? 1 : 0, t_order_items ? (order_fwd_tiles(d.T, true) ? 3 + 4 * (order_fwd_tiles(d.T, true) - 1) : 1) : 0);
+        hipLaunchKernelGGL(render_fwd_views_kernel, tv, dim3(RB), 0, stream, t, d, background, 1, order);
     }
     GSR_HIP_CHECK(hipGetLastError());
     // one wait per view (they are all long done by the time the host has enqueued the tile kernels); a view that outgrew its capacity is
     // redone through the single-view path, which allocates exactly
     for (int v = 0; v < V; v++) {
         gsr_view& w = views[v];
-        select_device_state(slot0 + v);
-        if (t_lazy) { w.num_rendered = (int)t.v[v].cap; continue; }
+        SpecState& spec = spec_state(slot0 + v);
+        if (opt.lazy) { w.num_rendered = (int)t.v[v].cap; continue; }
         uint32_t hdr[4];
         char* gp = w.geom_buffer;
         const GeomState geom = GeomState::from(gp, (size_t)P);
-        { const int rc = wait_for_header(stream, geom.header, t.v[v].seq, hdr); if (rc) return rc; }
+        { const int rc = wait_for_header(stream, spec, opt.mailbox, geom.header, t.v[v].seq, hdr); if (rc) return rc; }
         const uint32_t R = hdr[HDR_R], flg = hdr[HDR_FLAGS], R_alloc = hdr[HDR_R_ALLOC];
         if (R > 0x7fffffffu || R_alloc > 0x7fffffffu) { g_last_error = "gsr_forward_views: more than 2^31 instances"; return GSR_ERR_INVALID_ARGUMENT; }
-        t_last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);
-        t_last_max_tile = hdr[HDR_MAX_TILE];
+        spec.last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);
+        spec.last_max_tile = hdr[HDR_MAX_TILE];
         w.num_rendered = (int)R;
         if (flg & FLAG_OVERFLOW) {
-            t_clip_single = clips[v];
-            const int rc = forward_one_view(w, slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier, tan_fovx,
-                                            tan_fovy, debug, stream_);
-            t_clip_single = nullptr;
+            const int rc = forward_one_view(opt, w, slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier,
+                                            tan_fovx, tan_fovy, debug, stream_);
             if (rc) return rc;
         }
     }
@@ -867,6 +871,7 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
                         (!flow && (!out->log_scales || !out->raw_rotations || !out->logit_opacity || !out->features_dc || (M > 1 && !out->features_rest)))))) {
         g_last_error = "gsr_backward_views: invalid argument"; return GSR_ERR_INVALID_ARGUMENT;
     }
+    const Options opt = read_options();
     const ViewDims d = view_dims(P, width, height);
     ViewTable t;
     memset(&t, 0, sizeof(t));
@@ -901,8 +906,8 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
     a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.scale_modifier = scale_modifier;
     a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx); a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
     a.pose_only = pose_only ? 1 : 0;
-    a.sh_rows = t_sh_rows ? 1 : 0;
-    a.raw = to_device_view(in);
+    a.sh_rows = opt.sh_rows ? 1 : 0;
+    a.raw = to_device_view(in, nullptr);
     a.rawg = RawGrads{};
     a.rawg.scale_dim = in->scale_dim;
     {
@@ -919,7 +924,7 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
     return 0;
 }
 
-static int backward_impl(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D, const float* shs,
+static int backward_impl(const Call& c, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D, const float* shs,
                  const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* projmatrix_raw,
                  const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer,
@@ -967,9 +972,9 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
     a.dL_dmean3D = dL_dmean3D; a.dL_dcov3D = dL_dcov3D; a.dL_dsh = dL_dsh; a.dL_dscale = dL_dscale; a.dL_drot = dL_drot; a.dL_dtau = dL_dtau;
     a.accumulate = accumulate ? 1 : 0;
     a.pose_only = pose_only ? 1 : 0;
-    a.sh_rows = t_sh_rows ? 1 : 0;
+    a.sh_rows = c.opt.sh_rows ? 1 : 0;
     a.tau_partials = dL_dtau_sum ? geom.tau_partials : nullptr;
-    a.raw = to_device_view(raw);
+    a.raw = to_device_view(raw, nullptr);
     a.rawg = RawGrads{};
     if (raw) { a.rawg.f_dc = rawg->features_dc; a.rawg.f_rest = rawg->features_rest; a.rawg.ddx = rawg->dx; a.rawg.dds = rawg->ds; a.rawg.ddr = rawg->dr; a.rawg.scale_dim = raw->scale_dim; a.rawg.ddx2 = rawg->dx2; }
     {
@@ -977,9 +982,9 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
         if (raw && raw->delta_mode) hipLaunchKernelGGL((geometry_bwd_kernel<true, true>), dim3((P + 255) / 256), dim3(256), 0, stream, a);
         else if (raw) hipLaunchKernelGGL(geometry_bwd_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(geometry_bwd_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, a);
-        if (dL_dtau_sum && t_track_tail)     // gsr_track_step: pose-gradient sum + exposure-gradient sum + camera step in one launch
+        if (dL_dtau_sum && c.track_tail)     // gsr_track_step: pose-gradient sum + exposure-gradient sum + camera step in one launch
             hipLaunchKernelGGL(track_tail_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, (const float*)geom.tau_partials, dL_dtau_sum, T,
-                               t_track_tail->exposure_partials, t_track_tail->dL_dexposure, t_track_tail->step);
+                               c.track_tail->exposure_partials, c.track_tail->dL_dexposure, c.track_tail->step);
         else if (dL_dtau_sum)
             hipLaunchKernelGGL(tau_sum_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, geom.tau_partials, dL_dtau_sum);
     }
@@ -1044,7 +1049,7 @@ int gsr_backward_fused(int P, int D, int M, int R, const float* background, int 
                  float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscale, float* dL_drot, float* dL_dtau, float* dL_dtau_sum, int debug, void* stream)
 {
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+    return backward_impl(Call{read_options()}, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
                          viewmatrix, projmatrix, projmatrix_raw, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer,
                          dL_dpix, dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
                          dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, debug, stream, nullptr, nullptr);
@@ -1057,7 +1062,7 @@ int gsr_backward_raw(int P, int D, int M, int R, const float* background, int wi
                      float* dL_dtau_sum, int debug, void* stream)
 {
     if (!in || !out) { g_last_error = "gsr_backward_raw: null descriptor"; return GSR_ERR_INVALID_ARGUMENT; }
-    return backward_impl(P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
+    return backward_impl(Call{read_options()}, P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
                          projmatrix, projmatrix_raw, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
                          dL_dpix_depth, dL_dmean2D, nullptr, out->logit_opacity, nullptr, nullptr, out->xyz, nullptr, nullptr,
                          out->log_scales, out->raw_rotations, nullptr, dL_dtau_sum, debug, stream, in, out);
@@ -1760,7 +1765,6 @@ int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, cons
     hipLaunchKernelGGL(hexsort_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, n);
     const int C = f.feat_dim, ppb = HEX_BLOCK / C;
     const dim3 g1((unsigned)((n + ppb - 1) / ppb));
-    const int dbg = getenv("GSR_HEXV_DEBUG") ? atoi(getenv("GSR_HEXV_DEBUG")) : 0;   // development: 1 = skip the spatial streams, 2 = skip the time streams
     const int gpw = C >= 64 ? 1 : 64 / C;                        // groups per wave (hexsort_phase2_views_kernel)
     const int64_t chunks2 = (n + HEXSORT_CHUNK - 1) / HEXSORT_CHUNK;
     const int64_t groups = (int64_t)3 * ((chunks2 + gpw - 1) / gpw) * gpw;
@@ -1776,11 +1780,11 @@ int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, cons
 #define GSR_HEXVB_PHASE2(CC, LM, when)                                                                                                  \
         if (when) {                                                                                                                     \
             if (ordered) {                                                                                                              \
-                if (!(dbg & 1)) hipLaunchKernelGGL((hexsort_phase2_views_kernel<CC, LM, true>), g2, dim3(256), 0, stream, f, ws, vw, n, ord);        \
-                if (!(dbg & 2)) hipLaunchKernelGGL((hexsort_phase2_time_kernel<CC, LM, true>), g3, dim3(256), 0, stream, f, ws, vw, tv, n, ord);     \
+                hipLaunchKernelGGL((hexsort_phase2_views_kernel<CC, LM, true>), g2, dim3(256), 0, stream, f, ws, vw, n, ord);                        \
+                hipLaunchKernelGGL((hexsort_phase2_time_kernel<CC, LM, true>), g3, dim3(256), 0, stream, f, ws, vw, tv, n, ord);                     \
             } else {                                                                                                                    \
-                if (!(dbg & 1)) hipLaunchKernelGGL((hexsort_phase2_views_kernel<CC, LM, false>), g2, dim3(256), 0, stream, f, ws, vw, n, ord);       \
-                if (!(dbg & 2)) hipLaunchKernelGGL((hexsort_phase2_time_kernel<CC, LM, false>), g3, dim3(256), 0, stream, f, ws, vw, tv, n, ord);    \
+                hipLaunchKernelGGL((hexsort_phase2_views_kernel<CC, LM, false>), g2, dim3(256), 0, stream, f, ws, vw, n, ord);                       \
+                hipLaunchKernelGGL((hexsort_phase2_time_kernel<CC, LM, false>), g3, dim3(256), 0, stream, f, ws, vw, tv, n, ord);                    \
             }                                                                                                                           \
         }
     switch (C) { GSR_HEXVB_CASE(8) GSR_HEXVB_CASE(16) GSR_HEXVB_CASE(32) GSR_HEXVB_CASE(64) }
@@ -1878,22 +1882,20 @@ int gsr_deform_mlp_forward(const gsr_deform_mlp* mlp, int64_t n, const float* fe
     if (n < 0 || (n > 0 && (!features || !out))) { g_last_error = "gsr_deform_mlp_forward: null / invalid argument"; return GSR_ERR_INVALID_ARGUMENT; }
     if (n == 0) return 0;
     // round 6: the bf16-split kernel (gs_mlp.h: three terms per operand, six products, weights stationary in registers) for the widths the
-    // shipped networks use; GSR_MLP_FP32=1: the fp32-MFMA kernel of rounds 1-5 (also every other width)
-    static const bool fp32_only = getenv("GSR_MLP_FP32") && getenv("GSR_MLP_FP32")[0] == '1';
-    static const int rt = getenv("GSR_MLP_RT") ? atoi(getenv("GSR_MLP_RT")) : 2;      // row tiles per block: 2 (two blocks per CU: 1.37 ms at 4 M rows) or 4 (one: 1.65)
+    // shipped networks use, two row tiles per block (two blocks per CU: 1.37 ms at 4 M rows; four row tiles, one block per CU: 1.65); every
+    // other width: the fp32-MFMA kernel of rounds 1-5
     const int nt = w.in_dim / 16;
-    if (!fp32_only && (nt == 2 || nt == 4 || nt == 8)) {
-        static std::atomic<unsigned long long> attr_set[6];
-#define GSR_MLP3_LAUNCH(NT, RT, SLOT)                                                                                                             \
+    if (nt == 2 || nt == 4 || nt == 8) {
+        static std::atomic<unsigned long long> attr_set[3];
+#define GSR_MLP3_LAUNCH(NT, SLOT)                                                                                                                 \
         do {                                                                                                                                      \
-            using L = Mlp3Layout<NT, RT>;                                                                                                         \
-            { const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_fwd3_kernel<NT, RT>), L::BYTES, attr_set[SLOT]); if (rc) return rc; } \
+            using L = Mlp3Layout<NT, 2>;                                                                                                          \
+            { const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_fwd3_kernel<NT, 2>), L::BYTES, attr_set[SLOT]); if (rc) return rc; } \
             const int64_t tiles = (n + L::R - 1) / L::R;                                                                                          \
-            hipLaunchKernelGGL((deform_mlp_fwd3_kernel<NT, RT>), dim3((unsigned)std::min<int64_t>(tiles, 256 * (RT >= 4 ? 1 : 2))), dim3(MLP3_THREADS), L::BYTES, \
+            hipLaunchKernelGGL((deform_mlp_fwd3_kernel<NT, 2>), dim3((unsigned)std::min<int64_t>(tiles, 256 * 2)), dim3(MLP3_THREADS), L::BYTES,  \
                                (hipStream_t)stream_, n, features, w, out);                                                                        \
         } while (0)
-        if (rt == 2) { if (nt == 2) GSR_MLP3_LAUNCH(2, 2, 0); else if (nt == 4) GSR_MLP3_LAUNCH(4, 2, 1); else GSR_MLP3_LAUNCH(8, 2, 2); }
-        else { if (nt == 2) GSR_MLP3_LAUNCH(2, 4, 3); else if (nt == 4) GSR_MLP3_LAUNCH(4, 4, 4); else GSR_MLP3_LAUNCH(8, 4, 5); }
+        if (nt == 2) GSR_MLP3_LAUNCH(2, 0); else if (nt == 4) GSR_MLP3_LAUNCH(4, 1); else GSR_MLP3_LAUNCH(8, 2);
 #undef GSR_MLP3_LAUNCH
         GSR_HIP_CHECK(hipGetLastError());
         return 0;
@@ -2010,13 +2012,11 @@ static int dense_forward_launch(const char* who, int M, int N, int K, const floa
     if (colsum_out && (!vec_out || !workspace || (reinterpret_cast<uintptr_t>(workspace) % 16))) {
         g_last_error = std::string(who) + ": the column sums need N % 4 == 0, 16-byte aligned rows of Y / mask and a 16-byte aligned workspace"; return GSR_ERR_INVALID_ARGUMENT;
     }
-    static const int forced_bt = getenv("GSR_DENSE_ROW_TILES") ? atoi(getenv("GSR_DENSE_ROW_TILES")) : 0;      // (development: 2 .. 10)
     float* partial = colsum_out ? reinterpret_cast<float*>(workspace) : nullptr;
-    // full-width outputs (the network's layers): one block of eight waves per CU, two LDS stages (dense_fwd8_kernel); GSR_DENSE_WIDE=0: the
+    // full-width outputs (the network's layers): one block of eight waves per CU, two LDS stages (dense_fwd8_kernel); otherwise the
     // 128-column kernel
-    static const bool wide_ok = !(getenv("GSR_DENSE_WIDE") && getenv("GSR_DENSE_WIDE")[0] == '0');
-    if (wide_ok && vec_out && N % DENSE8_BN == 0) {
-        const int bt8 = forced_bt >= 2 && forced_bt <= DENSE_MAX_BT ? forced_bt : dense8_row_tiles(M, N / DENSE8_BN);
+    if (vec_out && N % DENSE8_BN == 0) {
+        const int bt8 = dense8_row_tiles(M, N / DENSE8_BN);
         const dim3 grid8((unsigned)((M + 16 * bt8 - 1) / (16 * bt8)), (unsigned)(N / DENSE8_BN));
         Dense8Layer L;
         L.X = X; L.gate = gate; L.planes = reinterpret_cast<const unsigned short*>(planes); L.bias = bias; L.Y = Y; L.mask = mask; L.colsum = partial;
@@ -2036,7 +2036,7 @@ static int dense_forward_launch(const char* who, int M, int N, int K, const floa
         GSR_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    const int bt = forced_bt >= 2 && forced_bt <= DENSE_MAX_BT ? forced_bt : dense_row_tiles(M, Npad / DENSE_BN);
+    const int bt = dense_row_tiles(M, Npad / DENSE_BN);
     const dim3 grid((unsigned)((M + 16 * bt - 1) / (16 * bt)), (unsigned)(Npad / DENSE_BN));
     hipLaunchKernelGGL(dense_fwd_kernel, grid, dim3(DENSE_THREADS), 0, stream, M, N, K, X, ldx, gate, ldgate,
                        reinterpret_cast<const unsigned short*>(planes), Npad, Kpad, bias, relu ? 1 : 0, Y, ldy, vec ? 1 : 0, vec_out ? 1 : 0, bt, mask, ldmask, partial);
@@ -2090,8 +2090,7 @@ int gsr_dense_chain(int M, int N, int count, const gsr_dense_chain_op* ops, char
         for (int l = 0; l < count; l++) if (ops[l].dbias) GSR_HIP_CHECK(hipMemsetAsync(ops[l].dbias, 0, (size_t)N * sizeof(float), stream));
         return 0;
     }
-    static const int forced_bt = getenv("GSR_DENSE_ROW_TILES") ? atoi(getenv("GSR_DENSE_ROW_TILES")) : 0;
-    const int bt = forced_bt >= 2 && forced_bt <= DENSE_MAX_BT ? forced_bt : dense8_row_tiles(M, 1);
+    const int bt = dense8_row_tiles(M, 1);
     const unsigned blocks = (unsigned)((M + 16 * bt - 1) / (16 * bt));
     const size_t per_op = ((size_t)((M + 31) / 32) * (size_t)N * sizeof(float) + 255) & ~size_t(255);
     Dense8Chain c;
@@ -2196,9 +2195,8 @@ static int dense_wgrad_many_plan(int M, int count, const gsr_dense_wgrad_item* i
         tiles += ((q.N + DENSE_BM - 1) / DENSE_BM) * ((q.K + DENSE_BN - 1) / DENSE_BN);
     }
     if (out) { out->count = count; out->total_tiles = tiles; }
-    // every block resident at once (two per CU), at least four 32-row steps per slice; GSR_WGM_BLOCKS: dev knob
-    static const int blocks = getenv("GSR_WGM_BLOCKS") ? std::max(1, atoi(getenv("GSR_WGM_BLOCKS"))) : 512;
-    int s = std::max(1, blocks / std::max(1, tiles));
+    // every block resident at once (512 blocks: two per CU), at least four 32-row steps per slice
+    int s = std::max(1, 512 / std::max(1, tiles));
     s = std::min(s, std::max(1, (M + 4 * DENSE_WG_ROWS - 1) / (4 * DENSE_WG_ROWS)));
     const int rps = std::max(DENSE_WG_ROWS, round_up_int((std::max(M, 1) + s - 1) / s, DENSE_WG_ROWS));
     *rows_per_slice = rps;
@@ -2407,8 +2405,7 @@ int gsr_index_csr(int S, int E, int Nv, const int64_t* idx, char* workspace, voi
     int *order, *seg, *cursor;
     index_csr_carve(workspace, S, E, Nv, order, seg, cursor);
     GSR_HIP_CHECK(hipMemsetAsync(cursor, 0, (size_t)S * sizeof(int), stream));
-    static const bool reg_ok = !(getenv("GSR_CSR_REGISTERS") && getenv("GSR_CSR_REGISTERS")[0] == '0');
-    if (reg_ok && E >= 1 && E <= 20 * CSR_REG_TRIP && Nv < 65535) {          // small sets: packed to 16 bits, a wave holds the whole set in registers
+    if (E >= 1 && E <= 20 * CSR_REG_TRIP && Nv < 65535) {          // small sets: packed to 16 bits, a wave holds the whole set in registers
         const int Epad = index_csr_epad(E);
         unsigned short* packed = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(cursor) + index_csr_ints(S, E, Nv));
         hipLaunchKernelGGL(index_csr_pack_kernel, dim3((unsigned)((Epad + 255) / 256), (unsigned)S), dim3(256), 0, stream, E, Epad, idx, packed);
@@ -2523,9 +2520,8 @@ int gsr_node_blend_backward_batch(const gsr_node_blend* a, int B, const float* n
     const bool use_lds = a->m <= NODE_LDS_MAX;
     const size_t stride = node_ws_floats(a->n, a->m);
     // K <= 4 (every shipped call): the ordered route -- contributions written per (Gaussian, k), summed per node in the order of the Gaussians
-    // (index_csr_kernel + segment_sum_kernel above): bit-reproducible. GSR_NODE_ATOMICS=1 keeps round 3's LDS-atomic accumulation.
-    static const bool force_atomics = getenv("GSR_NODE_ATOMICS") && getenv("GSR_NODE_ATOMICS")[0] == '1';
-    const bool ordered = a->K <= NODE_DET_MAX_K && a->n > 0 && !force_atomics;
+    // (index_csr_kernel + segment_sum_kernel above): bit-reproducible. K > 4: round 3's LDS-atomic accumulation.
+    const bool ordered = a->K <= NODE_DET_MAX_K && a->n > 0;
     float* summed;
     if (ordered) {
         const int E = (int)(a->n * a->K);
@@ -2698,21 +2694,21 @@ int gsr_track_step(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_f
     tl.opacity_thr = loss->opacity_depth_threshold; tl.use_opacity = loss->opacity_weights ? 1 : 0;
     tl.c_rgb = loss->alpha / (3.0f * (float)N); tl.c_depth = (1.0f - loss->alpha) / (float)N;          // (make_loss_args)
     tl.dL_dimage = g_image; tl.dL_ddepth = g_depth; tl.partials = partials;
-    CapturedAlloc g{geometry_alloc, geometry_user, nullptr}, b{binning_alloc, binning_user, nullptr}, i{image_alloc, image_user, nullptr};
-    t_track_loss = &tl;
-    const int R = forward_impl(captured_alloc, &g, captured_alloc, &b, captured_alloc, &i, P, D, M, background, width, height, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, scale_modifier, nullptr, nullptr, step->viewmatrix, step->full_proj, step->campos, tan_fovx, tan_fovy, 0,
-                               out_color, out_depth, out_opacity, radii, n_touched, 0, stream, in);
-    t_track_loss = nullptr;
+    Call c{read_options(), &spec_state(0)};
+    c.track_loss = &tl;
+    c.track_tail = &tail;
+    FwdInputs fin;
+    fin.raw = in;
+    CapturedAllocs al{{geometry_alloc, geometry_user, nullptr}, {binning_alloc, binning_user, nullptr}, {image_alloc, image_user, nullptr}};
+    const int R = forward_impl(c, al.fns(), P, D, M, background, width, height, fin, scale_modifier, {step->viewmatrix, step->full_proj, step->campos, tan_fovx, tan_fovy},
+                               {out_color, out_depth, out_opacity, radii, n_touched}, 0, stream);
     if (R < 0) return R;
     gsr_raw_grads none;
     memset(&none, 0, sizeof(none));
-    t_track_tail = &tail;
-    const int rc = backward_impl(P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, step->viewmatrix,
-                                 step->full_proj, projmatrix_raw, step->campos, tan_fovx, tan_fovy, radii, g.got, b.got, i.got, g_image, g_depth, dL_dmean2D,
+    const int rc = backward_impl(c, P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, step->viewmatrix,
+                                 step->full_proj, projmatrix_raw, step->campos, tan_fovx, tan_fovy, radii, al.g.got, al.b.got, al.i.got, g_image, g_depth, dL_dmean2D,
                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tau6, GSR_BACKWARD_POSE_ONLY, stream,
                                  in, &none);
-    t_track_tail = nullptr;
     if (rc < 0) return rc;
     GSR_HIP_CHECK(hipGetLastError());
     return R;

@@ -255,7 +255,9 @@ int gsr_debug_wave_reduce10(const float* in, float* out, void* stream);
  * onto [0, n_items); block b runs on XCD b % 8 in the order of b / 8 (csrc/gs_device.h: item_block_*). Negative: argument out of range. */
 int gsr_debug_item_block(unsigned int n_items, unsigned int n_partial, unsigned int rank, int partial);
 
-/* Per-host-thread options of the forward pass; returns the previous value (value < 0: query only) or a negative error code.
+/* Options of the rasterizer; returns the previous value (value < 0: query only) or a negative error code. "order_items", "sh_rows" and
+ * "hex_ordered" are PROCESS-wide (an autograd backward runs on another thread than its forward); every other option is per host thread.
+ * A forward or backward call reads the options once, when it starts.
  *   "speculate" (default 1): scatter / sort / render are enqueued on a binning buffer sized from the previous frame before the host
  *                knows num_rendered; 0 = wait for it first, like the reference's blocking copy (rasterizer_impl.cu:283-284).
  *   "lazy"      (default 0): a speculative gsr_forward returns without ANY host wait; its return value is then an upper bound of
@@ -286,7 +288,7 @@ int gsr_debug_item_block(unsigned int n_items, unsigned int n_partial, unsigned 
  *                pass (which writes the work-item table).
  *   "sh_rows" (default 1): the SH coefficients of a wave's 64 Gaussians move as whole rows through LDS (one DMA instruction / one store per
  *                row) instead of one strided access per coefficient and lane; same arithmetic, bit-identical results. 0 = per lane.
- *   "hex_ordered" (default 1; PROCESS-wide, value < 0 only reads): the HexPlane field's sorted backward passes (deformation_field.h) sum the plane
+ *   "hex_ordered" (default 1; value < 0 only reads): the HexPlane field's sorted backward passes (deformation_field.h) sum the plane
  *                gradients as fixed-point integers -- bitwise reproducible; 0 = float atomics. Environment: GSR_HEX_ORDERED.
  *   "cap_test_shrink_permille" (default 0 = off): TEST facility -- lay speculative buffers out for this fraction of the previous
  *                frame's count, so that overflows (and the callers' recovery paths) can be provoked deliberately.

@@ -62,6 +62,21 @@ def test_forward_backward_parity(P, W, H, deg, maxdeg, sm, kw):
     _check(m)
 
 
+def test_sh_window_frame_grows_within_process():
+    """preprocess_fwd's dynamic LDS (tile histogram + SH windows) grows with the tile count; its launch attribute is set once per process,
+    so a frame with many more tiles than the process's first SH-degree-3 frame must still launch and match the oracle."""
+    for (W, H) in ((64, 48), (960, 720)):      # 12 tiles, then 2700 (<= HIST_LDS_TILES)
+        cam = make_camera(W, H)
+        g = make_gaussians(4000, cam, seed=3, sh_degree=3, scale_mean=0.01)
+        gc, gd = make_cotangents(cam)
+        bg = np.array([1.0, 0.5, 0.2], np.float32)
+        oo, _, go = oracle_run(g, cam, bg, gc, gd)
+        oh, gh = hip_run(g, cam, bg, gc, gd)
+        m = compare(oh, gh, oo, go)
+        m["P"] = 4000
+        _check(m)
+
+
 def test_intermediate_state_parity():
     """Stage-by-stage: geometry state, scan, per-tile ranges and the depth-sorted lists must match the reference pipeline
     (preprocess / InclusiveSum / duplicateWithKeys + SortPairs / identifyTileRanges)."""

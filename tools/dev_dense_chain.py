@@ -50,5 +50,5 @@ def replayed(f, n=20):
     with torch.cuda.graph(g):
         f()
     return timed(g.replay, n)
-print(json.dumps({"rows": R, "between": between, "wide": os.environ.get("GSR_DENSE_WIDE", "1"), "chain_replayed_us": round(replayed(chain), 1),
+print(json.dumps({"rows": R, "between": between, "chain_replayed_us": round(replayed(chain), 1),
                   "chain_eager_us": round(timed(chain), 1), "library_replayed_us": round(replayed(lib_chain), 1)}))

@@ -2,13 +2,14 @@
 blocks round robin over 32 CUs (k = b / 8 -> CU k % 32), how many blocks share a CU. One line of JSON.
     GSR_GLUE=ctypes GSR_LIB=.../timeline.so python tools/dev_dispatch_census.py"""
 import ctypes, json, os, sys
+# band order: tile index <-> block index by xcd_tile_of_block (render_fwd orders its tiles only together with render_bwd's work items)
+os.environ.setdefault("GSR_ORDER_ITEMS", "0")
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "4dgs-slam_amd")]
 import torch
 import bench
 from diff_gaussian_rasterization import _C
-os.environ.setdefault("GSR_ORDER_TILES", "0")          # band order: tile index <-> block index by xcd_tile_of_block
 scene = bench.Scene(200_000, torch.device("cuda", 0), 0, 0.005, keyframes=(0,))
 lib = _C.load_library()
 lib.gsr_debug_spans.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]

@@ -31,4 +31,4 @@ def run():
     return e0.elapsed_time(e1)
 for _ in range(2):
     run()
-print(json.dumps({"P": a.P, "views": a.views, "dbg": os.environ.get("GSR_HEXV_DEBUG", "0"), "backward_ms": round(min(run() for _ in range(4)), 3)}))
+print(json.dumps({"P": a.P, "views": a.views, "backward_ms": round(min(run() for _ in range(4)), 3)}))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """dev: the fused deformation MLP alone (gsr_deform_mlp_forward / _backward) at config #3's batch: time per launch and the error against fp64,
-with the fp32 library's error beside it. GSR_MLP_FP32=1 / GSR_MLP_RT=2 select the other kernels (read once per process)."""
+with the fp32 library's error beside it. in_dim 32 / 64 / 128 take the bf16-split kernel, other multiples of 16 the fp32-MFMA one."""
 import json, os, sys, time
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,8 +34,7 @@ def ref(dtype):
     return torch.cat(outs, 1)
 r64, r32 = ref(torch.float64), ref(torch.float32)
 err = lambda a: float((a.double() - r64).abs().max() / r64.abs().max())
-res = {"n": n, "in_dim": in_dim, "env": {k: os.environ.get(k) for k in ("GSR_MLP_FP32", "GSR_MLP_RT")},
-       "fwd_err_vs_fp64": err(out[:200_000].detach()), "library_fp32_err_vs_fp64": err(r32)}
+res = {"n": n, "in_dim": in_dim, "fwd_err_vs_fp64": err(out[:200_000].detach()), "library_fp32_err_vs_fp64": err(r32)}
 def timed(fn, it=10):
     for _ in range(3): fn()
     torch.cuda.synchronize(); t0 = time.perf_counter()
