@@ -38,6 +38,8 @@
 #include "../../include/slam_losses.h"
 #include "../../include/slam_map.h"
 #include "gs_map.h"
+#include "../../include/frame_io.h"
+#include "gs_frame.h"
 
 namespace gsr {
 
@@ -80,9 +82,9 @@ static size_t required(F&& f)
 }
 
 // ---- per-kernel timing with events on the launch stream ---------------------------------------------------------
-enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_COUNT };
+enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"preprocess_fwd", "scan", "scatter_instances", "sort_tiles",
-                                                  "render_fwd", "render_bwd", "geometry_bwd", "knn_total"};
+                                                  "render_fwd", "render_bwd", "geometry_bwd", "knn_total", "frame_prepare"};
 struct Profiler {
     unsigned mask = 0;   // bit i set => kernel id i is timed
     struct Rec { hipEvent_t a, b; int id; };
@@ -2848,6 +2850,24 @@ int gsr_kabsch_rotations(int n, const float* S, float* R, void* stream_)
     if (n < 0 || (n > 0 && (!S || !R))) { g_last_error = "gsr_kabsch_rotations: null argument"; return GSR_ERR_INVALID_ARGUMENT; }
     if (n == 0) return 0;
     hipLaunchKernelGGL(kabsch_rotation_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream_, n, S, R);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_frame_prepare(int width, int height, const unsigned char* rgb, const float* map_xy, const float* lut, const unsigned char* mask_l,
+                      float mask_threshold, float* image, unsigned char* motion, void* stream_)
+{
+    if (!rgb || !lut || !image) { g_last_error = "gsr_frame_prepare: rgb, lut and image must not be NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (width <= 0 || height <= 0 || (long long)width * height * 3 > 0x7fffffffLL) {
+        g_last_error = "gsr_frame_prepare: width and height must be positive and width * height * 3 below 2^31";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (mask_l && !motion) { g_last_error = "gsr_frame_prepare: mask_l given without a motion output"; return GSR_ERR_INVALID_ARGUMENT; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n = width * height;
+    ScopedKernelTimer tm(K_FRAME_PREPARE, stream);
+    hipLaunchKernelGGL(frame_prepare_kernel, dim3((unsigned)((n + FRAME_BLOCK - 1) / FRAME_BLOCK)), dim3(FRAME_BLOCK), 0, stream, width, height, rgb,
+                       reinterpret_cast<const float2*>(map_xy), lut, mask_l, mask_threshold, image, motion);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

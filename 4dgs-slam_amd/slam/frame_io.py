@@ -1,0 +1,45 @@
+"""ctypes binding of include/frame_io.h (gsr_frame_prepare) on libgs_rasterizer_hip.so. No CPU path."""
+import ctypes as C
+
+import torch
+
+from diff_gaussian_rasterization import _C
+
+_vp, _f, _i = C.c_void_p, C.c_float, C.c_int
+_declared = False
+
+
+def lib():
+    global _declared
+    L = _C.load_library()
+    if not _declared:
+        L.gsr_frame_prepare.restype = _i
+        L.gsr_frame_prepare.argtypes = [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]
+        _declared = True
+    return L
+
+
+def _dev(t, name, dtype, shape):
+    if t is None:
+        return None
+    _C._require_device(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be a contiguous {dtype} device tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def frame_prepare(rgb, map_xy, lut, mask_l, mask_threshold, image, motion, stream=None):
+    """One launch: image [3,H,W] = lut[remap(rgb)] (map_xy None = no undistortion), motion [H,W] = !(mask_l / 255 > threshold) (all
+    True without mask_l). rgb uint8 [H,W,3]; map_xy float32 [H,W,2] or None; lut float32 [256]; mask_l uint8 [H,W] or None; motion
+    bool / uint8 [H,W] or None. stream: a torch stream (default: the current stream of rgb's device)."""
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise RuntimeError(f"rgb must be [H, W, 3], got {tuple(rgb.shape)}")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    args = (_dev(rgb, "rgb", torch.uint8, (H, W, 3)), _dev(map_xy, "map_xy", torch.float32, (H, W, 2)), _dev(lut, "lut", torch.float32, (256,)),
+            _dev(mask_l, "mask_l", torch.uint8, (H, W)), float(mask_threshold), _dev(image, "image", torch.float32, (3, H, W)),
+            None if motion is None else _dev(motion, "motion", torch.uint8 if motion.dtype == torch.uint8 else torch.bool, (H, W)))
+    s = (stream if stream is not None else torch.cuda.current_stream(rgb.device)).cuda_stream
+    L = lib()
+    rc = L.gsr_frame_prepare(W, H, *args, s)
+    if rc < 0:
+        _C._err(L, rc, "gsr_frame_prepare")

@@ -1,0 +1,406 @@
+"""Recorded RGB-D sequences: the TUM / Bonn and CoFusion loaders of the reference (utils/dataset.py:85-181, 490-660, 677-696, 962-976)
+with the interface of slam/dataset.py:
+
+    dataset[idx] -> (image [3,H,W] float32 device, depth [H,W] float32 numpy, pose [4,4] float32 W2C device, motion_mask [H,W] bool device)
+
+Path parsing (``parse_tum`` / ``parse_cofusion``) is separate from decoding and runs without a GPU. PNG decoding stays on the host (PIL,
+slam/frame_decode.py) in a background thread that reads ahead of the SLAM loop; the frame is staged in pinned memory, and its upload,
+lens undistortion, byte -> float conversion, CHW transpose and motion-mask threshold are one HIP launch on a side stream
+(gsr_frame_prepare, include/frame_io.h) that the caller's stream waits for. There is no ``gt_flow``: the backend skips its flow term without one, as it does for any dataset that lacks it.
+
+What the reference does and this does not: YOLO masks (motion masks come only from mask files), EXR depth (CoFusion's depth_noise/*.exr
+raises), and its TUM mask list is not sliced by Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
+import collections
+import concurrent.futures
+import glob
+import math
+import os
+import re
+import time
+import weakref
+
+import numpy as np
+
+from . import frame_decode
+from .camera import fov_from_focal
+
+MASK_THRESHOLD = 0.01          # utils/dataset.py:346: ToTensor(mask_L) > 0.01 is a moving pixel
+
+
+# ---- path parsing (host only) ------------------------------------------------------------------------------------------------------
+class FrameList:
+    """What a sequence is on disk: per kept frame its colour, depth and (optional) mask file and its W2C pose (float64)."""
+
+    def __init__(self, color_paths, depth_paths, poses, mask_paths=None, depth_float32=False):
+        self.color_paths, self.depth_paths = list(color_paths), list(depth_paths)
+        self.poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        self.mask_paths = list(mask_paths) if mask_paths else None
+        self.depth_float32 = depth_float32       # CoFusion divides in float32, TUM in float64 (then casts)
+
+    def __len__(self):
+        return len(self.color_paths)
+
+    def sliced(self, start, end):
+        """Calibration start / end (end -1 = to the last frame), applied to every per-frame list."""
+        n = len(self)
+        end = n if end == -1 else end
+        return FrameList(self.color_paths[start:end], self.depth_paths[start:end], self.poses[start:end],
+                         self.mask_paths[start:end] if self.mask_paths else None, self.depth_float32)
+
+
+def read_list(path, skiprows=0):
+    """np.loadtxt(path, delimiter=" ", dtype=str, skiprows=skiprows): the first skiprows lines are dropped, '#' starts a comment."""
+    rows = []
+    with open(path, "r") as f:
+        for k, line in enumerate(f):
+            if k < skiprows:
+                continue
+            line = line.split("#", 1)[0].strip()
+            if line:
+                rows.append(line.split())
+    return rows
+
+
+def extract_number(path):
+    """The trailing number of a '<...><digits>.png' name (utils/dataset.py:114-122); 0 without one."""
+    m = re.search(r"(\d+)(?=\.png$)", path)
+    return float(m.group(1)) if m else 0
+
+
+def quaternion_matrix(q_wxyz):
+    """Homogeneous rotation of a (w, x, y, z) quaternion, normalised first (trimesh.transformations.quaternion_matrix)."""
+    q = np.asarray(q_wxyz, dtype=np.float64)
+    n = float(np.dot(q, q))
+    if n < np.finfo(float).eps * 4.0:
+        return np.identity(4)
+    w, x, y, z = q * math.sqrt(2.0 / n)
+    return np.array([[1.0 - y * y - z * z, x * y - z * w, x * z + y * w, 0.0],
+                     [x * y + z * w, 1.0 - x * x - z * z, y * z - x * w, 0.0],
+                     [x * z - y * w, y * z + x * w, 1.0 - x * x - y * y, 0.0],
+                     [0.0, 0.0, 0.0, 1.0]])
+
+
+def pose_from_tum(vec):
+    """W2C from a TUM line's (timestamp tx ty tz qx qy qz qw): inv(T), T = [R(q) | t] with the quaternion rolled to w-first."""
+    vec = np.asarray(vec, dtype=np.float64)
+    T = quaternion_matrix(np.roll(vec[4:8], 1))
+    T[:3, 3] = vec[1:4]
+    return np.linalg.inv(T)
+
+
+def associate_frames(tstamp_image, tstamp_depth, tstamp_pose, max_dt=0.08):
+    """TUMParser.associate_frames: per colour frame the nearest depth and pose stamps, both within max_dt."""
+    out = []
+    for i, t in enumerate(tstamp_image):
+        j = int(np.argmin(np.abs(tstamp_depth - t)))
+        k = int(np.argmin(np.abs(tstamp_pose - t)))
+        if abs(tstamp_depth[j] - t) < max_dt and abs(tstamp_pose[k] - t) < max_dt:
+            out.append((i, j, k))
+    return out
+
+
+def parse_tum(datapath, frame_rate=32, max_dt=0.08):
+    """TUMParser (utils/dataset.py:85-181): rgb.txt / depth.txt / groundtruth.txt (else pose.txt, first line skipped), association,
+    frame-rate subsampling, W2C poses, and per kept frame the render_mask/*.png at its rgb.txt row (masks sorted by trailing number)."""
+    pose_list = None
+    for name in ("groundtruth.txt", "pose.txt"):
+        if os.path.isfile(os.path.join(datapath, name)):
+            pose_list = os.path.join(datapath, name)
+            break
+    if pose_list is None:
+        raise FileNotFoundError(f"{datapath}: neither groundtruth.txt nor pose.txt")
+    mask_dir = os.path.join(datapath, "render_mask")
+    mask_all = sorted(glob.glob(os.path.join(mask_dir, "*.png")), key=extract_number) if os.path.isdir(mask_dir) else None
+    image_data = read_list(os.path.join(datapath, "rgb.txt"))
+    depth_data = read_list(os.path.join(datapath, "depth.txt"))
+    pose_vecs = np.array([[float(x) for x in r] for r in read_list(pose_list, skiprows=1)], dtype=np.float64)
+    if not image_data or not depth_data or not len(pose_vecs):
+        raise ValueError(f"{datapath}: rgb.txt, depth.txt and the pose file must each list at least one entry")
+    tstamp_image = np.array([float(r[0]) for r in image_data])
+    tstamp_depth = np.array([float(r[0]) for r in depth_data])
+    assoc = associate_frames(tstamp_image, tstamp_depth, pose_vecs[:, 0], max_dt)
+    if not assoc:
+        raise ValueError(f"{datapath}: no colour frame has a depth frame and a pose within {max_dt} s")
+    keep = [0]
+    for ix in range(1, len(assoc)):
+        if tstamp_image[assoc[ix][0]] - tstamp_image[assoc[keep[-1]][0]] > 1.0 / frame_rate:
+            keep.append(ix)
+    colors, depths, poses, masks = [], [], [], []
+    for ix in keep:
+        i, j, k = assoc[ix]
+        colors.append(os.path.join(datapath, image_data[i][1]))
+        depths.append(os.path.join(datapath, depth_data[j][1]))
+        poses.append(pose_from_tum(pose_vecs[k]))
+        if mask_all is not None:
+            if i >= len(mask_all):
+                raise ValueError(f"{mask_dir}: {len(mask_all)} masks, but rgb.txt row {i} is a kept frame")
+            masks.append(mask_all[i])
+    return FrameList(colors, depths, poses, masks if mask_all is not None else None)
+
+
+def parse_cofusion(datapath):
+    """CoFusion (utils/dataset.py:490-575): colour/*.png, depth/*.png, mask_colour/*.png, trajectories/gt-cam-0.txt (identity poses
+    without it). EXR depth (depth_noise/*.exr) needs an OpenEXR reader this project does not have."""
+    colors = sorted(glob.glob(os.path.join(datapath, "colour", "*.png")))
+    exr = sorted(glob.glob(os.path.join(datapath, "depth_noise", "*.exr")))
+    if exr:
+        raise NotImplementedError(f"{os.path.join(datapath, 'depth_noise')}: EXR depth is not supported (no OpenEXR reader); "
+                                  "provide depth/*.png instead")
+    depths = sorted(glob.glob(os.path.join(datapath, "depth", "*.png")))
+    masks = sorted(glob.glob(os.path.join(datapath, "mask_colour", "*.png")))
+    n = len(colors)
+    if n == 0 or len(depths) < n:
+        raise ValueError(f"{datapath}: {n} colour/*.png and {len(depths)} depth/*.png (need at least one frame and a depth per frame)")
+    traj = os.path.join(datapath, "trajectories", "gt-cam-0.txt")
+    if os.path.isfile(traj):
+        rows = read_list(traj)
+        if len(rows) < n:
+            raise ValueError(f"{traj}: {len(rows)} poses for {n} frames")
+        poses = [pose_from_tum([float(x) for x in r]) for r in rows[:n]]
+    else:
+        poses = [np.eye(4) for _ in range(n)]
+    return FrameList(colors, depths[:n], poses, masks or None, depth_float32=True)
+
+
+def undistort_map(width, height, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+    """cv2.initUndistortRectifyMap(K, (k1, k2, p1, p2, k3), R = I, newK = K, (width, height), CV_32FC1) restated in float64, stored as
+    float32 [H,W,2] = (map_x, map_y): where the undistorted pixel (u, v) samples the distorted frame."""
+    v, u = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    x, y = (u - cx) / fx, (v - cy) / fy
+    r2 = x * x + y * y
+    kr = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+    mx = fx * (x * kr + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)) + cx
+    my = fy * (y * kr + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y) + cy
+    return np.stack([mx, my], -1).astype(np.float32)
+
+
+def byte_lut():
+    """float32(b / 255.0) in double for every byte b: the reference's torch.from_numpy(image / 255.0).to(float32)."""
+    return (np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)
+
+
+# ---- decoding (host) ---------------------------------------------------------------------------------------------------------------
+def decode_frame(frames, idx, width, height, depth_scale):
+    """PIL decode of frame idx of a FrameList (frame_decode.decode_frame)."""
+    return frame_decode.decode_frame(frames.color_paths[idx], frames.depth_paths[idx], frames.mask_paths[idx] if frames.mask_paths else None,
+                                     width, height, depth_scale, frames.depth_float32)
+
+
+class _Reader:
+    """Decoding ahead of the consumer in one thread, and a small bounded cache; holds no reference to the dataset object."""
+
+    def __init__(self, tasks, depth, cache):
+        self.tasks, self.n, self.depth = tasks, len(tasks), depth
+        # a thread that runs PIL and numpy only: it never touches the device, so it cannot disturb a graph capture on the caller's thread
+        # (a decoding process measured no faster)
+        self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="frame-decode") if depth > 0 else None
+        self.pending = {}
+        self.cache = collections.OrderedDict()
+        self.cache_size = max(1, cache)
+        self.stats = {"decode_ms": [], "wait_ms": 0.0, "prefetched": 0, "on_demand": 0, "cached": 0}
+
+    def _decode(self, idx):
+        return frame_decode.decode_frame(*self.tasks[idx])
+
+    def _done(self, f):
+        self.stats["decode_ms"].append(f.decode_ms)
+        return f
+
+    def schedule(self, first):
+        if self.pool is None:
+            return
+        for k in range(first, min(first + self.depth, self.n)):
+            if k not in self.pending and k not in self.cache:
+                self.pending[k] = self.pool.submit(frame_decode.decode_frame, *self.tasks[k])
+
+    def get(self, idx):
+        t0 = time.perf_counter()
+        fut = self.pending.pop(idx, None)
+        if idx in self.cache:
+            f = self.cache.pop(idx)
+            self.stats["cached"] += 1
+        elif fut is not None:
+            f = self._done(fut.result())
+            self.stats["prefetched"] += 1
+        else:
+            f = self._done(self._decode(idx))
+            self.stats["on_demand"] += 1
+        self.stats["wait_ms"] += (time.perf_counter() - t0) * 1e3
+        self.cache[idx] = f
+        while len(self.cache) > self.cache_size:
+            self.cache.popitem(last=False)
+        for k in [k for k in self.pending if k < idx or k > idx + self.depth]:     # a jump (eval re-reads): drop what is now stale
+            if self.pending[k].cancel():
+                del self.pending[k]
+        self.schedule(idx + 1)
+        return f
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+            self.pool = None
+        self.pending.clear()
+
+
+# ---- datasets ----------------------------------------------------------------------------------------------------------------------
+class RecordedRGBDDataset:
+    """A recorded sequence with the interface of slam/dataset.py's SyntheticRGBDDataset (no gt_flow)."""
+
+    def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None):
+        import torch
+        from .camera import getProjectionMatrix2
+        if max_frames is not None:
+            frames = frames.sliced(0, min(int(max_frames), len(frames)))
+        if len(frames) == 0:
+            raise ValueError("the sequence has no frames (after Calibration start / end)")
+        self.frames = frames
+        self.device = torch.device(device)
+        c = calibration
+        self.fx, self.fy, self.cx, self.cy = float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"])
+        self.width, self.height = int(c["width"]), int(c["height"])
+        self.fovx, self.fovy = fov_from_focal(self.fx, self.width), fov_from_focal(self.fy, self.height)
+        self.depth_scale = float(c["depth_scale"])
+        self.num_imgs = len(frames)
+        self.dynamic_objects = 0
+        self.projection_matrix = getProjectionMatrix2(0.01, 100.0, self.cx, self.cy, self.fx, self.fy, self.width,
+                                                      self.height).transpose(0, 1).to(self.device)
+        self.poses = torch.tensor(frames.poses, dtype=torch.float32, device=self.device)
+        self._lut = torch.tensor(byte_lut(), device=self.device)
+        self._map = None
+        if distorted:
+            m = undistort_map(self.width, self.height, self.fx, self.fy, self.cx, self.cy,
+                              *(float(c.get(k, 0.0)) for k in ("k1", "k2", "p1", "p2", "k3")))
+            self._map = torch.tensor(m, device=self.device)
+        torch.cuda.synchronize(self.device)             # the tables exist before the side stream reads them
+        self._side = torch.cuda.Stream(self.device)
+        tasks = [(frames.color_paths[i], frames.depth_paths[i], frames.mask_paths[i] if frames.mask_paths else None, self.width, self.height,
+                  self.depth_scale, frames.depth_float32) for i in range(self.num_imgs)]
+        self._reader = _Reader(tasks, int(prefetch), cache=int(prefetch) + 4)
+        self._finalizer = weakref.finalize(self, self._reader.close)
+        self._reader.schedule(0)
+        self._reader.get(0)                             # the reader is up and frame 0 is decoded before the dataset is handed out
+        self._reader.stats.update(wait_ms=0.0, prefetched=0, on_demand=0)
+
+    def __len__(self):
+        return self.num_imgs
+
+    def close(self):
+        """Stop the reader thread (also done when the dataset is dropped and at interpreter exit)."""
+        self._finalizer()
+
+    @property
+    def ingest_stats(self):
+        s = self._reader.stats
+        d = np.asarray(s["decode_ms"], dtype=np.float64)
+        return {"decode_ms_mean": float(d.mean()) if len(d) else None, "decode_ms_p95": float(np.percentile(d, 95)) if len(d) else None,
+                "decoded": int(len(d)), "wait_ms_total": s["wait_ms"], "prefetched": s["prefetched"], "on_demand": s["on_demand"],
+                "cached": s["cached"], "prefetch_depth": self._reader.depth}
+
+    def __getitem__(self, idx):
+        import torch
+        from . import frame_io
+        if not 0 <= idx < self.num_imgs:
+            raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
+        hf = self._reader.get(idx)
+        H, W, dev = self.height, self.width, self.device
+        main = torch.cuda.current_stream(dev)
+        # pinned staging on this thread (the decoding thread never touches the device); the host allocator keeps a block until the
+        # copy that reads it has completed
+        rgb_h = torch.from_numpy(hf.rgb).pin_memory()
+        mask_h = None if hf.mask is None else torch.from_numpy(hf.mask).pin_memory()
+        with torch.cuda.stream(self._side):
+            rgb = rgb_h.to(dev, non_blocking=True)
+            mask = None if mask_h is None else mask_h.to(dev, non_blocking=True)
+            image = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+            motion = torch.empty((H, W), dtype=torch.bool, device=dev)
+            frame_io.frame_prepare(rgb, self._map, self._lut, mask, MASK_THRESHOLD, image, motion, self._side)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        main.wait_event(ready)
+        image.record_stream(main)                       # allocated on the side stream, used (and freed) on the caller's
+        motion.record_stream(main)
+        return image, hf.depth, self.poses[idx].clone(), motion
+
+
+class TUMDataset(RecordedRGBDDataset):
+    """TUM RGB-D and Bonn (utils/dataset.py:677-696): Dataset.type 'tum'; Bonn calibrations are distorted."""
+
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None):
+        c = config["Dataset"]["Calibration"]
+        frames = parse_tum(config["Dataset"]["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+        super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames)
+
+
+class CoFusionDataset(RecordedRGBDDataset):
+    """CoFusion (utils/dataset.py:490-660): Dataset.type 'CoFusion'; never undistorted, depth divided in float32."""
+
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None):
+        c, d = config["Dataset"]["Calibration"], config["Dataset"]
+        frames = parse_cofusion(d["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+        if d.get("seg_teddy", False) or d.get("seg_clock", False):           # :545-547, after the slicing
+            frames.color_paths = sorted(frames.color_paths, key=extract_number)
+            frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
+        super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames)
+
+
+SUPPORTED_TYPES = ("tum", "CoFusion")
+
+
+def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None):
+    """utils/dataset.py:962-976 for the recorded RGB-D types this project reads: 'tum' (TUM, Bonn) and 'CoFusion'."""
+    kind = config["Dataset"].get("type")
+    if kind == "tum":
+        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames)
+    if kind == "CoFusion":
+        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames)
+    raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn) and 'CoFusion'")
+
+
+# ---- writing a sequence (tests, measurements, exporting the synthetic generator) --------------------------------------------------
+def rotation_to_quaternion(R):
+    """(qx, qy, qz, qw) of a rotation matrix (Shepperd's method, float64)."""
+    R = np.asarray(R, dtype=np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = 2.0 * math.sqrt(tr + 1.0)
+        w, x, y, z = 0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = 2.0 * math.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
+        w, x, y, z = (R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s
+    elif R[1, 1] > R[2, 2]:
+        s = 2.0 * math.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
+        w, x, y, z = (R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s
+    else:
+        s = 2.0 * math.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
+        w, x, y, z = (R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s
+    return np.array([x, y, z, w])
+
+
+def write_tum_sequence(dataset, root, masks=False, t0=1000.0, hz=30.0):
+    """Write the frames of an in-memory dataset (slam/dataset.py interface) in the TUM layout: rgb/*.png = round(colour * 255),
+    depth/*.png = round(depth * 5000) as 16-bit, groundtruth.txt (C2W as tx ty tz qx qy qz qw) and, with masks=True, render_mask/*.png
+    (255 on moving pixels). Returns the Calibration block of a config for it."""
+    from PIL import Image
+    for d in ("rgb", "depth") + (("render_mask",) if masks else ()):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    rgb_lines, depth_lines, pose_lines = [], [], []
+    for i in range(len(dataset)):
+        color, depth, pose, motion = dataset[i]
+        t = t0 + i / hz
+        c = np.rint(color.clamp(0, 1).permute(1, 2, 0).cpu().numpy().astype(np.float64) * 255).astype(np.uint8)
+        Image.fromarray(c).save(os.path.join(root, "rgb", f"{t:.6f}.png"))
+        Image.fromarray(np.rint(np.asarray(depth, np.float64) * 5000).astype(np.uint16)).save(os.path.join(root, "depth", f"{t:.6f}.png"))
+        if masks:
+            Image.fromarray(np.where(motion.cpu().numpy(), 0, 255).astype(np.uint8)).save(os.path.join(root, "render_mask", f"mask_{i}.png"))
+        c2w = np.linalg.inv(pose.double().cpu().numpy())
+        rgb_lines.append(f"{t:.6f} rgb/{t:.6f}.png")
+        depth_lines.append(f"{t:.6f} depth/{t:.6f}.png")
+        pose_lines.append(f"{t:.6f} " + " ".join(f"{v:.12f}" for v in (*c2w[:3, 3], *rotation_to_quaternion(c2w[:3, :3]))))
+    for name, header, lines in (("rgb.txt", "# color images\n# file: written from an in-memory dataset\n# timestamp filename\n", rgb_lines),
+                                ("depth.txt", "# depth maps\n# file: written from an in-memory dataset\n# timestamp filename\n", depth_lines),
+                                ("groundtruth.txt", "# ground truth trajectory\n# file: written from an in-memory dataset\n"
+                                                    "# timestamp tx ty tz qx qy qz qw\n", pose_lines)):
+        with open(os.path.join(root, name), "w") as f:
+            f.write(header + "\n".join(lines) + "\n")
+    return {"fx": float(dataset.fx), "fy": float(dataset.fy), "cx": float(dataset.cx), "cy": float(dataset.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
+            "p2": 0.0, "k3": 0.0, "distorted": False, "width": int(dataset.width), "height": int(dataset.height), "depth_scale": 5000.0}

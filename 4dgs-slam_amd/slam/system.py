@@ -1,7 +1,7 @@
 """The SLAM system -- the counterpart of the reference's ``slam.py`` SLAM class (:39-230) in one process: builds the Gaussian model,
 front-end and back-end from a configuration with the reference's YAML structure (configs/rgbd/tum/base_config.yaml), runs the
-sequence, evaluates ATE / PSNR (utils/eval_utils.py). GUI, wandb, multiprocessing queues and the dataset loaders are out of scope;
-any object with the interface of slam/dataset.py can be passed as the dataset."""
+sequence, evaluates ATE / PSNR (utils/eval_utils.py). GUI, wandb and multiprocessing queues are out of scope; any object with the
+interface of slam/dataset.py can be passed as the dataset (recorded TUM / Bonn / CoFusion sequences: slam/recorded.py, slam/config.py)."""
 import copy
 import time
 import types

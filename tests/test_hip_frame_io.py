@@ -1,0 +1,170 @@
+"""gsr_frame_prepare (include/frame_io.h, csrc/gs_frame.h) on the device against a numpy integer restatement of cv2.remap's INTER_LINEAR
+fixed-point path for 8-bit images (BORDER_CONSTANT 0), the reference's byte -> float conversion and its mask threshold.
+
+OpenCV is not a dependency of this project, so agreement with cv2 itself is not checked here: the map is slam/recorded.py's float64
+restatement of cv2.initUndistortRectifyMap (tests/test_recorded_dataset_host.py pins it to the closed form) and the kernel is pinned,
+bit for bit, to the restatement below."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "4dgs-slam_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+pytestmark = pytest.mark.gpu
+
+BONN = dict(fx=542.822841, fy=542.576870, cx=315.593520, cy=237.756098, k1=0.039903, k2=-0.099343, p1=-0.00073, p2=-0.000144, k3=0.0)
+
+
+def remap_ref(src, m):
+    """cv2.remap(src, m[..., 0], m[..., 1], INTER_LINEAR, BORDER_CONSTANT, 0) for uint8 src [H,W,3], integer arithmetic throughout."""
+    H, W = src.shape[:2]
+    X = np.rint(m[..., 0].astype(np.float64) * 32).astype(np.int64)           # m * 32 is exact in float32; rint = half to even
+    Y = np.rint(m[..., 1].astype(np.float64) * 32).astype(np.int64)
+    x0, y0, ax, ay = X >> 5, Y >> 5, X & 31, Y & 31
+    acc = np.full(m.shape[:2] + (3,), 16384, np.int64)
+    for dx, dy, w in ((0, 0, (32 - ax) * (32 - ay) * 32), (1, 0, ax * (32 - ay) * 32), (0, 1, (32 - ax) * ay * 32), (1, 1, ax * ay * 32)):
+        xs, ys = x0 + dx, y0 + dy
+        ok = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        p = src[np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)].astype(np.int64) * ok[..., None]
+        acc += w[..., None] * p
+    return (acc >> 15).astype(np.uint8)
+
+
+def _to_float_chw(u8):
+    return np.ascontiguousarray((u8 / 255.0).astype(np.float32).transpose(2, 0, 1))
+
+
+def _run(rgb_np, map_np=None, mask_np=None, thr=0.01):
+    from slam import frame_io, recorded
+    dev = torch.device("cuda:0")
+    H, W = rgb_np.shape[:2]
+    rgb = torch.tensor(rgb_np, device=dev)
+    mp = None if map_np is None else torch.tensor(map_np, device=dev)
+    mask = None if mask_np is None else torch.tensor(mask_np, device=dev)
+    lut = torch.tensor(recorded.byte_lut(), device=dev)
+    image = torch.full((3, H, W), float("nan"), device=dev)
+    motion = torch.zeros((H, W), dtype=torch.bool, device=dev)
+    frame_io.frame_prepare(rgb, mp, lut, mask, thr, image, motion)
+    torch.cuda.synchronize()
+    return image.cpu().numpy(), motion.cpu().numpy()
+
+
+def _frame(W, H, seed):
+    rng = np.random.default_rng(seed)
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    flat = img.reshape(-1)
+    flat[:256] = np.arange(256, dtype=np.uint8)                 # every byte value appears
+    return img
+
+
+@pytest.mark.parametrize("W,H", [(640, 480), (960, 540), (37, 23)])
+def test_undistorted_is_the_byte_table(W, H):
+    img = _frame(W, H, W)
+    out, motion = _run(img)
+    assert np.array_equal(out.view(np.uint32), _to_float_chw(img).view(np.uint32))
+    assert motion.all()                                         # no mask file: every pixel static
+
+
+def _scaled(cal, W, H):
+    s, t = W / 640.0, H / 480.0
+    return dict(cal, fx=cal["fx"] * s, fy=cal["fy"] * t, cx=cal["cx"] * s, cy=cal["cy"] * t)
+
+
+@pytest.mark.parametrize("W,H", [(640, 480), (37, 23)])
+@pytest.mark.parametrize("name,cal", [("bonn", BONN), ("barrel", dict(BONN, k1=-0.35, k2=0.0)), ("pincushion", dict(BONN, k1=0.35, k2=0.1))])
+def test_distorted_matches_the_integer_remap(W, H, name, cal):
+    from slam import recorded
+    c = _scaled(cal, W, H)
+    m = recorded.undistort_map(W, H, c["fx"], c["fy"], c["cx"], c["cy"], c["k1"], c["k2"], c["p1"], c["p2"], c["k3"])
+    img = _frame(W, H, 7)
+    out, _ = _run(img, m)
+    want = remap_ref(img, m)
+    assert np.array_equal(out.view(np.uint32), _to_float_chw(want).view(np.uint32))
+    if name == "pincushion":       # with newK = K a barrel samples inward; a pincushion sends taps across the border, partly and wholly
+        X, Y = np.rint(m[..., 0] * 32).astype(np.int64) >> 5, np.rint(m[..., 1] * 32).astype(np.int64) >> 5
+        outside = (X + 1 < 0) | (X >= W) | (Y + 1 < 0) | (Y >= H)
+        partial = ~outside & ((X < 0) | (X + 1 >= W) | (Y < 0) | (Y + 1 >= H))
+        assert outside.any() and partial.any()
+        assert (want[outside] == 0).all() and (out[:, outside] == 0).all()
+
+
+def test_undistortion_semantics_on_an_analytic_pattern():
+    """The distorted frame holds a smooth pattern g sampled at the distorted pixel grid; the output at (u, v) is g at the map's point
+    (where the undistorted pixel looks in the distorted frame), within bilinear + byte quantisation error."""
+    from slam import recorded
+    W, H = 640, 480
+    c = BONN
+    m = recorded.undistort_map(W, H, c["fx"], c["fy"], c["cx"], c["cy"], c["k1"], c["k2"], c["p1"], c["p2"], c["k3"])
+    g = lambda x, y: np.stack([0.5 + 0.4 * np.sin(x / 37.0) * np.cos(y / 29.0), 0.5 + 0.4 * np.cos((x + y) / 41.0), 0.2 + 0.6 * x / W], -1)
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    dist = np.round(g(u, v) * 255).astype(np.uint8)
+    out, _ = _run(dist, m)
+    inside = (m[..., 0] >= 0) & (m[..., 0] <= W - 1) & (m[..., 1] >= 0) & (m[..., 1] <= H - 1)
+    want = g(m[..., 0].astype(np.float64), m[..., 1].astype(np.float64)).transpose(2, 0, 1)
+    err = np.abs(out - want)[:, inside]
+    assert inside.mean() > 0.95 and err.max() < 3.0 / 255, err.max()
+    # and it is not the identity: the distortion moves samples by more than that somewhere
+    assert np.abs(_to_float_chw(dist) - out)[:, inside].max() > 6.0 / 255
+
+
+def test_mask_threshold():
+    W, H = 16, 16
+    L = np.arange(256, dtype=np.uint8).reshape(H, W)
+    img = _frame(W, H, 1)
+    _, motion = _run(img, mask_np=L, thr=0.01)
+    assert motion[0, 2] and not motion[0, 3]                  # 2/255 = 0.0078 is static, 3/255 = 0.0118 is moving
+    assert np.array_equal(motion.reshape(-1), ~(L.reshape(-1).astype(np.float32) / np.float32(255.0) > np.float32(0.01)))
+    for k in (0, 1, 2, 3, 77, 128, 254):                       # the threshold exactly at float32(k / 255): L <= k is static
+        _, motion = _run(img, mask_np=L, thr=float(np.float32(k) / np.float32(255.0)))
+        assert np.array_equal(motion.reshape(-1), np.arange(256) <= k), k
+
+
+def test_bad_arguments_are_errors():
+    from slam import frame_io, recorded
+    L = frame_io.lib()
+    dev = torch.device("cuda:0")
+    rgb = torch.zeros((4, 5, 3), dtype=torch.uint8, device=dev)
+    lut = torch.tensor(recorded.byte_lut(), device=dev)
+    img = torch.zeros((3, 4, 5), device=dev)
+    mask = torch.zeros((4, 5), dtype=torch.uint8, device=dev)
+    s = torch.cuda.current_stream().cuda_stream
+    assert L.gsr_frame_prepare(5, 4, None, None, lut.data_ptr(), None, 0.01, img.data_ptr(), None, s) < 0
+    assert b"NULL" in L.gsr_last_error()
+    assert L.gsr_frame_prepare(0, 4, rgb.data_ptr(), None, lut.data_ptr(), None, 0.01, img.data_ptr(), None, s) < 0
+    assert L.gsr_frame_prepare(5, -1, rgb.data_ptr(), None, lut.data_ptr(), None, 0.01, img.data_ptr(), None, s) < 0
+    assert L.gsr_frame_prepare(5, 4, rgb.data_ptr(), None, lut.data_ptr(), mask.data_ptr(), 0.01, img.data_ptr(), None, s) < 0
+    assert L.gsr_frame_prepare(5, 4, rgb.data_ptr(), None, None, None, 0.01, img.data_ptr(), None, s) < 0
+    assert L.gsr_frame_prepare(5, 4, rgb.data_ptr(), None, lut.data_ptr(), None, 0.01, img.data_ptr(), None, s) == 0
+    with pytest.raises(RuntimeError, match="shape"):
+        frame_io.frame_prepare(rgb, None, lut, None, 0.01, torch.zeros((3, 5, 4), device=dev), None)
+    with pytest.raises(RuntimeError, match="HIP device"):
+        frame_io.frame_prepare(rgb.cpu(), None, lut, None, 0.01, img, None)
+    torch.cuda.synchronize()
+
+
+def test_one_launch_per_frame():
+    from diff_gaussian_rasterization import _C
+    from slam import recorded
+    W, H = 640, 480
+    c = BONN
+    m = recorded.undistort_map(W, H, c["fx"], c["fy"], c["cx"], c["cy"], c["k1"], c["k2"], c["p1"], c["p2"], c["k3"])
+    img = _frame(W, H, 3)
+    _run(img, m)                                               # warm
+    _C.profile_reset()
+    _C.profile_enable(["frame_prepare"])
+    try:
+        for _ in range(3):
+            _run(img, m, mask_np=img[..., 0].copy())
+        stats = _C.profile_read()
+    finally:
+        _C.profile_enable(False)
+        _C.profile_reset()
+    ms, calls = stats["frame_prepare"]
+    assert calls == 3 and ms > 0
+    print(f"gsr_frame_prepare 640x480 distorted + mask: {ms / calls * 1e3:.1f} us per frame (event-timed)")

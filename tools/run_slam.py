@@ -1,0 +1,62 @@
+#!/usr/bin/env python
+"""The SLAM system on a recorded sequence, as the reference's `slam.py --config X.yaml [--eval] [--dynamic]` (slam.py:250-276): the config
+(with its inherit_from chain, slam/config.py) names a TUM / Bonn or CoFusion sequence on disk (slam/recorded.py). Prints the JSON document
+of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the time the loop waited for a frame, and how many frames
+came from the read-ahead thread vs were decoded on demand."""
+import argparse
+import json
+import os
+import sys
+from datetime import datetime
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "4dgs-slam_amd")):
+    sys.path.insert(0, p)
+from slam.config import apply_cli_overrides, load_config  # noqa: E402
+from slam.recorded import load_dataset  # noqa: E402
+from slam.system import SLAM  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--dynamic", action="store_true", default=False)
+    ap.add_argument("--dataset-path", default=None, help="overrides Dataset.dataset_path")
+    ap.add_argument("--frames", type=int, default=None, help="use the first N frames (after Calibration start / end)")
+    ap.add_argument("--save-dir", default=None, help="where results go (default: slam.py's Results.save_dir/<scene>/<name>_<time>)")
+    ap.add_argument("--prefetch", type=int, default=4, help="frames decoded ahead of the loop")
+    args = ap.parse_args(argv)
+
+    config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
+    if args.dataset_path:
+        config["Dataset"]["dataset_path"] = args.dataset_path
+    save_dir = args.save_dir
+    if save_dir is None and config["Results"]["save_results"]:          # slam.py:278-285
+        path = config["Dataset"]["dataset_path"].rstrip("/").split("/")
+        stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
+        save_dir = os.path.join(config["Results"]["save_dir"], "_".join(path[-3:-1]), path[-1] + "_" + stamp)
+    if save_dir:
+        os.makedirs(save_dir, exist_ok=True)
+        with open(os.path.join(save_dir, "config.json"), "w") as f:
+            json.dump(config, f, indent=1, default=str)
+    torch.manual_seed(0)
+    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames)
+    slam = SLAM(config, ds, save_dir=save_dir)
+    res = slam.run()
+    res["graph_stats"] = slam.frontend.graph_stats
+    res["mapping_graph_stats"] = {"static": dict(getattr(slam.backend, "graph_stats", {}) or {}),
+                                  "dynamic": dict(getattr(slam.backend, "dynamic_graph_stats", {}) or {}),
+                                  "initialize_map": dict(getattr(slam.backend, "init_graph_stats", {}) or {}),
+                                  "initialize_network": dict(getattr(slam.backend, "network_init_graph_stats", {}) or {})}
+    res["resolution"] = [ds.width, ds.height]
+    res["ingest"] = ds.ingest_stats
+    ds.close()
+    name = os.path.splitext(os.path.basename(args.config))[0] + ("_dynamic" if args.dynamic else "")
+    print(json.dumps({name: res}, indent=1, default=str))
+
+
+if __name__ == "__main__":
+    main()
