@@ -40,6 +40,8 @@
 #include "gs_map.h"
 #include "../../include/frame_io.h"
 #include "gs_frame.h"
+#include "../../include/optical_flow.h"
+#include "gs_raft.h"
 
 namespace gsr {
 
@@ -2868,6 +2870,77 @@ int gsr_frame_prepare(int width, int height, const unsigned char* rgb, const flo
     ScopedKernelTimer tm(K_FRAME_PREPARE, stream);
     hipLaunchKernelGGL(frame_prepare_kernel, dim3((unsigned)((n + FRAME_BLOCK - 1) / FRAME_BLOCK)), dim3(FRAME_BLOCK), 0, stream, width, height, rgb,
                        reinterpret_cast<const float2*>(map_xy), lut, mask_l, mask_threshold, image, motion);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// min_side: the smallest side a pyramid level may have (the pyramid: 1; the lookup divides by (side - 1): 2)
+static bool raft_size_ok(const char* who, int h, int w, int min_side)
+{
+    if (h <= 0 || w <= 0 || (h >> 3) < min_side || (w >> 3) < min_side || (long long)h * w > 65536) {
+        g_last_error = std::string(who) + ": every pyramid level must have sides of at least " + std::to_string(min_side) +
+                       " and the low-res grid at most 65536 pixels";
+        return false;
+    }
+    return true;
+}
+
+int gsr_raft_corr_pyramid(int dim, int h, int w, const float* f1, const float* f2, float* const* pyr12, float* const* pyr21, void* stream_)
+{
+    if (!raft_size_ok("gsr_raft_corr_pyramid", h, w, 1)) return GSR_ERR_INVALID_ARGUMENT;
+    if (dim <= 0 || !f1 || !f2 || !pyr12) { g_last_error = "gsr_raft_corr_pyramid: dim must be positive and f1, f2, pyr12 given"; return GSR_ERR_INVALID_ARGUMENT; }
+    for (int l = 0; l < RAFT_LEVELS; ++l)
+        if (!pyr12[l] || (pyr21 && !pyr21[l])) { g_last_error = "gsr_raft_corr_pyramid: a level pointer is NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N = h * w;
+    const unsigned tiles = (unsigned)((N + CORR_TILE - 1) / CORR_TILE);
+    hipLaunchKernelGGL(raft_corr_kernel, dim3(tiles, tiles), dim3(CORR_BLOCK), 0, stream, dim, N, f1, f2, pyr12[0], pyr21 ? pyr21[0] : nullptr);
+    GSR_HIP_CHECK(hipGetLastError());
+    int hp = h, wp = w;
+    for (int l = 1; l < RAFT_LEVELS; ++l) {
+        const size_t cells = (size_t)N * (hp >> 1) * (wp >> 1);
+        hipLaunchKernelGGL(raft_pool_kernel, dim3((unsigned)((cells + 255) / 256), pyr21 ? 2u : 1u), dim3(256), 0, stream, N, hp, wp,
+                           pyr12[l - 1], pyr12[l], pyr21 ? pyr21[l - 1] : nullptr, pyr21 ? pyr21[l] : nullptr);
+        GSR_HIP_CHECK(hipGetLastError());
+        hp >>= 1;
+        wp >>= 1;
+    }
+    return 0;
+}
+
+int gsr_raft_corr_lookup(int batch, int h, int w, const float* const* pyr, const float* coords, float* out, void* stream_)
+{
+    if (!raft_size_ok("gsr_raft_corr_lookup", h, w, 2)) return GSR_ERR_INVALID_ARGUMENT;
+    if (batch < 1 || batch > RAFT_MAX_BATCH || !pyr || !coords || !out) {
+        g_last_error = "gsr_raft_corr_lookup: batch must be 1 or 2 and pyr, coords, out given";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    RaftPyramids p{};
+    for (int b = 0; b < batch; ++b)
+        for (int l = 0; l < RAFT_LEVELS; ++l) {
+            p.level[b][l] = pyr[b * RAFT_LEVELS + l];
+            if (!p.level[b][l]) { g_last_error = "gsr_raft_corr_lookup: a level pointer is NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(raft_lookup_kernel, dim3((unsigned)((h * w + 255) / 256), RAFT_LEVELS, batch), dim3(256), 0, stream, h, w, p, coords, out);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_raft_upsample(int batch, int h, int w, const float* flow, const float* mask, int pad_left, int pad_top, int out_w, int out_h, int ndc,
+                      float* out, void* stream_)
+{
+    if (batch < 1 || batch > 65535 || h <= 0 || w <= 0 || !flow || !mask || !out) {
+        g_last_error = "gsr_raft_upsample: batch, h and w must be positive and flow, mask, out given";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (pad_left < 0 || pad_top < 0 || out_w <= 0 || out_h <= 0 || out_h > 65535 || pad_left + out_w > 8 * w || pad_top + out_h > 8 * h) {
+        g_last_error = "gsr_raft_upsample: the crop window must lie inside the 8h x 8w upsampled flow";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(raft_upsample_kernel, dim3((unsigned)((out_w + 255) / 256), out_h, batch), dim3(256), 0, stream, h, w, flow, mask, pad_left,
+                       pad_top, out_w, out_h, ndc, out);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

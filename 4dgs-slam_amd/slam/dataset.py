@@ -6,9 +6,9 @@ repository's rasterizer. It has the interface the reference's loops expect from 
     dataset.fx / fy / cx / cy / fovx / fovy / width / height / num_imgs / device / dynamic_objects / dystart
 
 ``motion_mask`` follows the reference's convention: True = static pixel (``~motion_mask`` selects the moving object,
-utils/slam_backend.py:486-488). Recorded TUM / Bonn / CoFusion sequences are read by slam/recorded.py; YOLO masks and RAFT flow of the
-reference are out of scope (external weights); the ground-truth flow this generator can produce stands in for RAFT where the dynamic
-branch wants one."""
+utils/slam_backend.py:486-488). Recorded TUM / Bonn / CoFusion sequences are read by slam/recorded.py, which gets its flow from RAFT
+(slam/optical_flow.py) when given weights; YOLO masks are out of scope (external weights); the ground-truth flow this generator can
+produce stands in for RAFT where the dynamic branch wants one."""
 import math
 
 import numpy as np

@@ -1,0 +1,373 @@
+"""Optical flow for the dynamic mapping's flow term: RAFT (Teed & Deng, ECCV 2020) in the configuration the reference calls
+(utils/camera_utils.py:368-417 generate_flow: RAFT-basic, 20 iterations, test mode, 'sintel' padding), in inference only.
+
+The RAFT-specific hot path is HIP (include/optical_flow.h, csrc/gs_raft.h): the all-pairs correlation pyramid of both directions from
+one product on the matrix cores, the 9x9 window lookup of every iteration, and the convex upsampling with the unpad crop and the NDC
+scaling. The convolutions of the two encoders and of the update block are torch.nn.functional.conv2d (MIOpen) in fp32.
+
+The network is written here as functions over a flat parameter table whose names and shapes are those of the reference's RAFT
+state_dict (179 entries), so the published raft-things.pth loads unchanged. ``RaftFlow.pair`` computes both directions of a pair with
+one correlation product and the two directions batched through the update block; each image's encoder outputs are cached (bounded,
+by the caller's key), so a keyframe that appears in two pairs is encoded once."""
+import collections
+import ctypes as C
+import math
+import os
+import zlib
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from diff_gaussian_rasterization import _C
+
+LEVELS, RADIUS, HDIM, CDIM, ITERS = 4, 4, 128, 128, 20
+CORR_CHANNELS = LEVELS * (2 * RADIUS + 1) ** 2          # 324
+MASK_CHANNELS = 9 * 64                                  # 576
+NORM_EPS = 1e-5                                         # nn.InstanceNorm2d / nn.BatchNorm2d defaults
+
+
+# ---- the parameter table -------------------------------------------------------------------------------------------------------------
+def _norm_entries(name, ch, norm):
+    if norm == "batch":
+        return [(f"{name}.weight", (ch,)), (f"{name}.bias", (ch,)), (f"{name}.running_mean", (ch,)), (f"{name}.running_var", (ch,)),
+                (f"{name}.num_batches_tracked", ())]
+    return []                                           # instance norm without affine parameters or running statistics
+
+
+def _conv_entries(name, cout, cin, kh, kw=None):
+    return [(f"{name}.weight", (cout, cin, kh, kh if kw is None else kw)), (f"{name}.bias", (cout,))]
+
+
+def _encoder_entries(prefix, norm, out_dim):
+    """BasicEncoder: 7x7/2 stem (64), three stages of two residual blocks (64, 96/2, 128/2), 1x1 head; in state_dict order (the stem's
+    norm before its convolution; a block's convolutions, its norms, then its projection shortcut, whose norm is registered both as norm3
+    and as downsample.1)."""
+    e = _norm_entries(f"{prefix}.norm1", 64, norm) + _conv_entries(f"{prefix}.conv1", 64, 3, 7)
+    cin = 64
+    for s, (ch, stride) in enumerate(((64, 1), (96, 2), (128, 2)), start=1):
+        for b in range(2):
+            blk = f"{prefix}.layer{s}.{b}"
+            st = stride if b == 0 else 1
+            e += _conv_entries(f"{blk}.conv1", ch, cin, 3) + _conv_entries(f"{blk}.conv2", ch, ch, 3)
+            e += _norm_entries(f"{blk}.norm1", ch, norm) + _norm_entries(f"{blk}.norm2", ch, norm)
+            if st != 1:
+                e += _norm_entries(f"{blk}.norm3", ch, norm)
+                e += _conv_entries(f"{blk}.downsample.0", ch, cin, 1) + _norm_entries(f"{blk}.downsample.1", ch, norm)
+            cin = ch
+    return e + _conv_entries(f"{prefix}.conv2", out_dim, 128, 1)
+
+
+def param_shapes():
+    """name -> shape of every entry of RAFT-basic's state_dict, in its order."""
+    u = "update_block"
+    e = _encoder_entries("fnet", "instance", 256) + _encoder_entries("cnet", "batch", HDIM + CDIM)
+    e += (_conv_entries(f"{u}.encoder.convc1", 256, CORR_CHANNELS, 1) + _conv_entries(f"{u}.encoder.convc2", 192, 256, 3)
+          + _conv_entries(f"{u}.encoder.convf1", 128, 2, 7) + _conv_entries(f"{u}.encoder.convf2", 64, 128, 3)
+          + _conv_entries(f"{u}.encoder.conv", 128 - 2, 64 + 192, 3))
+    for d, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
+        for g in "zrq":
+            e += _conv_entries(f"{u}.gru.conv{g}{d}", HDIM, HDIM + 128 + HDIM, kh, kw)
+    e += _conv_entries(f"{u}.flow_head.conv1", 256, HDIM, 3) + _conv_entries(f"{u}.flow_head.conv2", 2, 256, 3)
+    e += _conv_entries(f"{u}.mask.0", 256, 128, 3) + _conv_entries(f"{u}.mask.2", MASK_CHANNELS, 256, 1)
+    return collections.OrderedDict(e)
+
+
+def recipe_state_dict(seed=0):
+    """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator np.random.default_rng([seed, crc32(name)]);
+    conv weights U(+-sqrt(1 / fan_in)), norm weights U(0.8, 1.2), other vectors U(+-0.05), running_mean U(+-0.1), running_var
+    U(0.5, 1.5), num_batches_tracked 0. Flows from them are finite and mostly inside the image, but carry no meaning."""
+    out = collections.OrderedDict()
+    for name, shape in param_shapes().items():
+        rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+        if name.endswith("num_batches_tracked"):
+            out[name] = torch.tensor(0, dtype=torch.int64)
+            continue
+        if len(shape) == 4:
+            b = math.sqrt(1.0 / (shape[1] * shape[2] * shape[3]))
+            v = rng.uniform(-b, b, shape)
+        elif name.endswith("running_mean"):
+            v = rng.uniform(-0.1, 0.1, shape)
+        elif name.endswith("running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        elif name.endswith(".weight"):
+            v = rng.uniform(0.8, 1.2, shape)
+        else:
+            v = rng.uniform(-0.05, 0.05, shape)
+        out[name] = torch.from_numpy(v.astype(np.float32))
+    return out
+
+
+def check_state_dict(sd):
+    """Strip DataParallel's `module.` prefix and check the entries against param_shapes(): a missing, extra or misshapen entry raises
+    and names it. Returns the stripped dict."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    if any(".conv3." in k for k in sd) or tuple(getattr(sd.get("update_block.encoder.convc1.weight"), "shape", ())) == (96, 196, 1, 1):
+        raise ValueError("this is a RAFT-small checkpoint; only RAFT-basic (raft-things.pth and its kind) is supported")
+    want = param_shapes()
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise KeyError(f"RAFT checkpoint lacks {missing[0]!r} ({len(missing)} missing entries)")
+    extra = [k for k in sd if k not in want]
+    if extra:
+        raise KeyError(f"RAFT checkpoint has an unexpected entry {extra[0]!r} ({len(extra)} extra entries)")
+    for k, shape in want.items():
+        got = tuple(sd[k].shape)
+        if got != shape:
+            raise ValueError(f"RAFT checkpoint entry {k!r} has shape {got}, expected {shape}")
+    return sd
+
+
+# ---- sizes ---------------------------------------------------------------------------------------------------------------------------
+def pad_amounts(height, width):
+    """InputPadder 'sintel' mode (RAFT/utils/utils.py): replicate padding to a multiple of 8, split evenly with the odd pixel after.
+    Returns (left, right, top, bottom)."""
+    ph = ((height // 8 + 1) * 8 - height) % 8
+    pw = ((width // 8 + 1) * 8 - width) % 8
+    return pw // 2, pw - pw // 2, ph // 2, ph - ph // 2
+
+
+def check_size(height, width):
+    """Every pyramid level needs at least 2 x 2 cells: bilinear_sampler divides by (H - 1) and (W - 1) of each level, so a level of
+    height or width 1 yields NaN in the reference. Raises ValueError below that (padded size under 128 in either direction)."""
+    l, r, t, b = pad_amounts(height, width)
+    hp, wp = height + t + b, width + l + r
+    if hp // 64 < 2 or wp // 64 < 2:
+        raise ValueError(f"a {width}x{height} image pads to {wp}x{hp}: RAFT needs a padded size of at least 128x128 "
+                         f"(the coarsest correlation level would have a side of 1)")
+    return hp, wp
+
+
+# ---- kernels (ctypes binding of include/optical_flow.h) -------------------------------------------------------------------------------
+_vp, _i = C.c_void_p, C.c_int
+_declared = False
+
+
+def lib():
+    global _declared
+    L = _C.load_library()
+    if not _declared:
+        L.gsr_raft_corr_pyramid.restype = _i
+        L.gsr_raft_corr_pyramid.argtypes = [_i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp]
+        L.gsr_raft_corr_lookup.restype = _i
+        L.gsr_raft_corr_lookup.argtypes = [_i, _i, _i, C.POINTER(_vp), _vp, _vp, _vp]
+        L.gsr_raft_upsample.restype = _i
+        L.gsr_raft_upsample.argtypes = [_i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]
+        _declared = True
+    return L
+
+
+def _f32(t, name, shape=None):
+    _C._require_device(t, name)
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
+                           f", got {t.dtype} {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def level_sizes(h, w):
+    out = []
+    for _ in range(LEVELS):
+        out.append((h, w))
+        h, w = h // 2, w // 2
+    return out
+
+
+def corr_pyramid(fmap1, fmap2, both=True):
+    """The correlation pyramid of fmaps [D, h, w]: a list of LEVELS tensors [2 (or 1), h*w, h_l, w_l]; index 0 is 1->2 (row: a pixel of
+    image 1, grid: image 2), index 1 is 2->1. One launch of the product for both directions, one per pooled level."""
+    D, h, w = (int(s) for s in fmap1.shape)
+    _f32(fmap1, "fmap1", (D, h, w))
+    _f32(fmap2, "fmap2", (D, h, w))
+    nd = 2 if both else 1
+    levels = [torch.empty((nd, h * w, hl, wl), dtype=torch.float32, device=fmap1.device) for hl, wl in level_sizes(h, w)]
+    p12 = (_vp * LEVELS)(*[t[0].data_ptr() for t in levels])
+    p21 = (_vp * LEVELS)(*[t[1].data_ptr() for t in levels]) if both else None
+    L = lib()
+    rc = L.gsr_raft_corr_pyramid(D, h, w, fmap1.data_ptr(), fmap2.data_ptr(), p12, p21, torch.cuda.current_stream(fmap1.device).cuda_stream)
+    if rc < 0:
+        _C._err(L, rc, "gsr_raft_corr_pyramid")
+    return levels
+
+
+def corr_lookup(levels, coords, out=None):
+    """CorrBlock.__call__: coords [B, 2, h, w] (B = the pyramid's direction count) -> [B, 324, h, w]."""
+    B, _, h, w = (int(s) for s in coords.shape)
+    if B != int(levels[0].shape[0]) or tuple(levels[0].shape[1:]) != (h * w, h, w):
+        raise RuntimeError(f"coords {tuple(coords.shape)} do not match the pyramid {tuple(levels[0].shape)}")
+    _f32(coords, "coords", (B, 2, h, w))
+    for t in levels:
+        _f32(t, "pyramid level")
+    if out is None:
+        out = torch.empty((B, CORR_CHANNELS, h, w), dtype=torch.float32, device=coords.device)
+    _f32(out, "out", (B, CORR_CHANNELS, h, w))
+    ptrs = (_vp * (B * LEVELS))(*[levels[l][b].data_ptr() for b in range(B) for l in range(LEVELS)])
+    L = lib()
+    rc = L.gsr_raft_corr_lookup(B, h, w, ptrs, coords.data_ptr(), out.data_ptr(), torch.cuda.current_stream(coords.device).cuda_stream)
+    if rc < 0:
+        _C._err(L, rc, "gsr_raft_corr_lookup")
+    return out
+
+
+def upsample(flow, mask, pad, out_hw, ndc=True):
+    """RAFT.upsample_flow + InputPadder.unpad (+ flow / (W, H) * 2 with ndc): flow [B, 2, h, w], mask [B, 576, h, w], pad = (left, right,
+    top, bottom), out_hw = (H, W) unpadded -> [B, H, W, 2]."""
+    B, _, h, w = (int(s) for s in flow.shape)
+    H, W = (int(s) for s in out_hw)
+    _f32(flow, "flow", (B, 2, h, w))
+    _f32(mask, "mask", (B, MASK_CHANNELS, h, w))
+    out = torch.empty((B, H, W, 2), dtype=torch.float32, device=flow.device)
+    L = lib()
+    rc = L.gsr_raft_upsample(B, h, w, flow.data_ptr(), mask.data_ptr(), int(pad[0]), int(pad[2]), W, H, int(bool(ndc)), out.data_ptr(),
+                             torch.cuda.current_stream(flow.device).cuda_stream)
+    if rc < 0:
+        _C._err(L, rc, "gsr_raft_upsample")
+    return out
+
+
+# ---- the network ---------------------------------------------------------------------------------------------------------------------
+class RaftFlow:
+    """RAFT-basic inference (hidden = context = 128, 4 levels, radius 4, 20 iterations) on one device."""
+
+    _loaded = {}                  # (checkpoint path, mtime, device) -> estimator: a checkpoint is read once per process
+
+    def __init__(self, state_dict, device="cuda:0", cache_frames=8):
+        sd = check_state_dict(state_dict)
+        self.device = torch.device(device)
+        # the projection shortcut's norm is one module under two names; loading a state_dict leaves it with downsample.1's values
+        self.p = {k: v.detach().to(self.device, torch.float32 if v.is_floating_point() else v.dtype).contiguous() for k, v in sd.items()}
+        self.cache_frames = max(2, int(cache_frames))
+        self._enc = collections.OrderedDict()     # key -> (fmap [256,h,w], net [128,h,w], inp [128,h,w]) of one padded image
+        self.encoder_runs = 0
+        self.pairs = 0
+
+    @classmethod
+    def from_checkpoint(cls, path, device="cuda:0", **kw):
+        path = os.path.realpath(path)
+        key = (path, os.path.getmtime(path), str(torch.device(device)))
+        hit = cls._loaded.get(key)
+        if hit is None:
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+            if not isinstance(sd, dict):
+                raise ValueError(f"{path}: expected a state_dict, got {type(sd).__name__}")
+            hit = cls._loaded[key] = cls(sd, device, **kw)
+        return hit
+
+    # -- encoders
+    def _norm(self, x, name, kind):
+        if kind == "instance":
+            return F.instance_norm(x, eps=NORM_EPS)
+        p = self.p
+        return F.batch_norm(x, p[name + ".running_mean"], p[name + ".running_var"], p[name + ".weight"], p[name + ".bias"], False, 0.0, NORM_EPS)
+
+    def _conv(self, x, name, stride=1, padding=0):
+        return F.conv2d(x, self.p[name + ".weight"], self.p[name + ".bias"], stride, padding)
+
+    def _encoder(self, x, prefix, kind):
+        x = F.relu(self._norm(self._conv(x, f"{prefix}.conv1", 2, 3), f"{prefix}.norm1", kind))
+        for s, stride in ((1, 1), (2, 2), (3, 2)):
+            for b in range(2):
+                blk = f"{prefix}.layer{s}.{b}"
+                st = stride if b == 0 else 1
+                y = F.relu(self._norm(self._conv(x, f"{blk}.conv1", st, 1), f"{blk}.norm1", kind))
+                y = F.relu(self._norm(self._conv(y, f"{blk}.conv2", 1, 1), f"{blk}.norm2", kind))
+                if st != 1:
+                    x = self._norm(self._conv(x, f"{blk}.downsample.0", st, 0), f"{blk}.downsample.1", kind)
+                x = F.relu(x + y)
+        return self._conv(x, f"{prefix}.conv2")
+
+    def _prepare(self, image):
+        """generate_flow's input: image * 255 (the float keyframe image), replicate-padded ('sintel'), then RAFT's 2 (x / 255) - 1."""
+        if image.dim() != 3 or image.shape[0] != 3:
+            raise ValueError(f"expected a [3, H, W] image, got {tuple(image.shape)}")
+        H, W = int(image.shape[1]), int(image.shape[2])
+        check_size(H, W)
+        x = image.to(self.device, torch.float32)[None] * 255
+        x = F.pad(x, list(pad_amounts(H, W)), mode="replicate")
+        return 2 * (x / 255.0) - 1.0
+
+    def encode(self, image, key=None):
+        """(fmap, net, inp, (H, W)) of one image, from the cache when `key` was encoded before (then `image` may be None)."""
+        if key is not None and key in self._enc:
+            self._enc.move_to_end(key)
+            return self._enc[key]
+        if image is None:
+            raise KeyError(f"no image given and {key!r} is not in the encoder cache")
+        x = self._prepare(image)
+        fmap = self._encoder(x, "fnet", "instance")[0].contiguous()
+        net, inp = torch.split(self._encoder(x, "cnet", "batch")[0], [HDIM, CDIM], dim=0)
+        hit = (fmap, torch.tanh(net).contiguous(), torch.relu(inp).contiguous(), (int(image.shape[1]), int(image.shape[2])))
+        self.encoder_runs += 1
+        if key is not None:
+            self._enc[key] = hit
+            while len(self._enc) > self.cache_frames:
+                self._enc.popitem(last=False)
+        return hit
+
+    def forget(self, key):
+        self._enc.pop(key, None)
+
+    # -- update block
+    def _update(self, net, inp, corr, flow, with_mask):
+        u = "update_block"
+        c = F.relu(self._conv(corr, f"{u}.encoder.convc1"))
+        c = F.relu(self._conv(c, f"{u}.encoder.convc2", 1, 1))
+        f = F.relu(self._conv(flow, f"{u}.encoder.convf1", 1, 3))
+        f = F.relu(self._conv(f, f"{u}.encoder.convf2", 1, 1))
+        motion = torch.cat([F.relu(self._conv(torch.cat([c, f], 1), f"{u}.encoder.conv", 1, 1)), flow], 1)
+        x = torch.cat([inp, motion], 1)
+        h = net
+        for d, pad in (("1", (0, 2)), ("2", (2, 0))):          # the separable GRU: a 1x5 pass, then a 5x1 pass
+            hx = torch.cat([h, x], 1)
+            z = torch.sigmoid(self._conv(hx, f"{u}.gru.convz{d}", 1, pad))
+            r = torch.sigmoid(self._conv(hx, f"{u}.gru.convr{d}", 1, pad))
+            q = torch.tanh(self._conv(torch.cat([r * h, x], 1), f"{u}.gru.convq{d}", 1, pad))
+            h = (1 - z) * h + z * q
+        delta = self._conv(F.relu(self._conv(h, f"{u}.flow_head.conv1", 1, 1)), f"{u}.flow_head.conv2", 1, 1)
+        mask = .25 * self._conv(F.relu(self._conv(h, f"{u}.mask.0", 1, 1)), f"{u}.mask.2") if with_mask else None
+        return h, mask, delta
+
+    # -- a pair
+    @torch.no_grad()
+    def pair(self, image_i, image_j, key_i=None, key_j=None, iters=ITERS, ndc=True, trace=None):
+        """RAFT(image1 = image_i, image2 = image_j) and RAFT(image1 = image_j, image2 = image_i): (flow_ij, flow_ji), each [H, W, 2] float32
+        on the device, in NDC units (flow / (W, H) * 2, utils/camera_utils.py:412-413) or pixels with ndc=False. Images: [3, H, W] float
+        in [0, 1]; an image may be None when its key is in the encoder cache. key_i / key_j name the images for that cache (None: not
+        cached). `trace`, a dict, receives the intermediates."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("RaftFlow.pair was called while the current stream is capturing a graph: flows must be estimated before "
+                               "capture (dynamic_graph fills its flow planes during table setup)")
+        # deterministic convolution algorithms: the same pair gives the same bits on every call (the flow targets are cached by pair)
+        with torch.backends.cudnn.flags(enabled=torch.backends.cudnn.enabled, benchmark=False, deterministic=True):
+            return self._pair(image_i, image_j, key_i, key_j, iters, ndc, trace)
+
+    def _pair(self, image_i, image_j, key_i, key_j, iters, ndc, trace):
+        f_i, net_i, inp_i, (H, W) = self.encode(image_i, key_i)
+        f_j, net_j, inp_j, hw_j = self.encode(image_j, key_j)
+        if hw_j != (H, W):
+            raise ValueError(f"the two images differ in size: {W}x{H} vs {hw_j[1]}x{hw_j[0]}")
+        pad = pad_amounts(H, W)
+        _, h, w = (int(s) for s in f_i.shape)
+        levels = corr_pyramid(f_i, f_j, both=True)             # [0]: i -> j, [1]: j -> i
+        net = torch.stack([net_i, net_j])
+        inp = torch.stack([inp_i, inp_j])
+        ys, xs = torch.meshgrid(torch.arange(h, device=self.device), torch.arange(w, device=self.device), indexing="ij")
+        coords0 = torch.stack([xs, ys]).float()[None].expand(2, 2, h, w).contiguous()
+        coords1 = coords0.clone()
+        corr = torch.empty((2, CORR_CHANNELS, h, w), dtype=torch.float32, device=self.device)
+        if trace is not None:
+            trace.update(fmap_i=f_i, fmap_j=f_j, net_i=net_i, inp_i=inp_i, net_j=net_j, inp_j=inp_j, pyramid=levels)
+        mask = None
+        for it in range(iters):
+            corr_lookup(levels, coords1, corr)
+            flow = coords1 - coords0
+            net, mask, delta = self._update(net, inp, corr, flow, with_mask=it == iters - 1)
+            coords1 = coords1 + delta
+            if trace is not None and it == 0:
+                trace.update(corr1=corr.clone(), flow1=(coords1 - coords0).clone())
+        flow = (coords1 - coords0).contiguous()
+        if trace is not None:
+            trace["flow_low"] = flow
+        up = upsample(flow, mask.contiguous(), pad, (H, W), ndc=ndc)
+        self.pairs += 1
+        return up[0], up[1]

@@ -6,7 +6,9 @@ with the interface of slam/dataset.py:
 Path parsing (``parse_tum`` / ``parse_cofusion``) is separate from decoding and runs without a GPU. PNG decoding stays on the host (PIL,
 slam/frame_decode.py) in a background thread that reads ahead of the SLAM loop; the frame is staged in pinned memory, and its upload,
 lens undistortion, byte -> float conversion, CHW transpose and motion-mask threshold are one HIP launch on a side stream
-(gsr_frame_prepare, include/frame_io.h) that the caller's stream waits for. There is no ``gt_flow``: the backend skips its flow term without one, as it does for any dataset that lacks it.
+(gsr_frame_prepare, include/frame_io.h) that the caller's stream waits for. Given an optical-flow estimator (``flow=``, slam/optical_flow.py
+RaftFlow), the dataset has ``gt_flow`` -- RAFT's flow between two frames, as the reference's generate_flow asks it for; without one it has no
+``gt_flow`` and the backend skips its flow term, as it does for any dataset that lacks it.
 
 What the reference does and this does not: YOLO masks (motion masks come only from mask files), EXR depth (CoFusion's depth_noise/*.exr
 raises), and its TUM mask list is not sliced by Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
@@ -244,9 +246,11 @@ class _Reader:
 
 # ---- datasets ----------------------------------------------------------------------------------------------------------------------
 class RecordedRGBDDataset:
-    """A recorded sequence with the interface of slam/dataset.py's SyntheticRGBDDataset (no gt_flow)."""
+    """A recorded sequence with the interface of slam/dataset.py's SyntheticRGBDDataset; ``gt_flow`` only with a flow estimator."""
 
-    def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None):
+    FLOW_CACHE_PAIRS = 16          # estimated pairs kept (both directions each; 4.9 MB per pair at 640x480)
+
+    def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None, flow=None):
         import torch
         from .camera import getProjectionMatrix2
         if max_frames is not None:
@@ -280,6 +284,12 @@ class RecordedRGBDDataset:
         self._reader.schedule(0)
         self._reader.get(0)                             # the reader is up and frame 0 is decoded before the dataset is handed out
         self._reader.stats.update(wait_ms=0.0, prefetched=0, on_demand=0)
+        self._flow = flow
+        if flow is not None:
+            self._flow_token = object()                 # names this dataset's frames in the estimator's encoder cache
+            self._flow_cache = collections.OrderedDict()
+            self._flow_events = []
+            self.gt_flow = self._gt_flow
 
     def __len__(self):
         return self.num_imgs
@@ -296,12 +306,59 @@ class RecordedRGBDDataset:
                 "decoded": int(len(d)), "wait_ms_total": s["wait_ms"], "prefetched": s["prefetched"], "on_demand": s["on_demand"],
                 "cached": s["cached"], "prefetch_depth": self._reader.depth}
 
-    def __getitem__(self, idx):
+    def _gt_flow(self, idx_from, idx_to):
+        """(flow [H,W,2] float32 NDC on the device, valid [H,W] bool): RAFT with image1 = frame idx_from, image2 = frame idx_to, divided by
+        (W, H) and times 2 (utils/camera_utils.py:386-417). Both directions of a pair come from one estimator call, in frame order, and are
+        kept. `valid` is all true: the reference's forward-backward consistency masks never enter its loss."""
         import torch
-        from . import frame_io
+        hit = self._flow_cache.get((idx_from, idx_to))
+        if hit is None:
+            a, b = sorted((int(idx_from), int(idx_to)))
+            est = self._flow
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            image = lambda i: None if (self._flow_token, i) in est._enc else self._frame_image(i)
+            fab, fba = est.pair(image(a), image(b), key_i=(self._flow_token, a), key_j=(self._flow_token, b))
+            end.record()
+            self._flow_events.append((start, end))
+            valid = torch.ones((self.height, self.width), dtype=torch.bool, device=self.device)
+            while len(self._flow_cache) >= 2 * self.FLOW_CACHE_PAIRS:
+                self._flow_cache.popitem(last=False)
+            self._flow_cache[(a, b)] = (fab, valid)
+            self._flow_cache[(b, a)] = (fba, valid)
+            hit = self._flow_cache[(idx_from, idx_to)]
+        return hit
+
+    @property
+    def flow_stats(self):
+        """Pairs estimated and the device ms per pair (None without an estimator)."""
+        if self._flow is None:
+            return None
+        ms = [s.elapsed_time(e) for s, e in self._flow_events] if self._flow_events else []
+        if ms:
+            self._flow_events[-1][1].synchronize()
+        return {"pairs": len(ms), "ms_per_pair": float(np.mean(ms)) if ms else None, "ms_first": ms[0] if ms else None,
+                "ms_rest_mean": float(np.mean(ms[1:])) if len(ms) > 1 else None}
+
+    def _frame_image(self, idx):
+        """Frame idx's image [3,H,W] without moving the read-ahead window (a keyframe the flow term needs again)."""
+        if not 0 <= idx < self.num_imgs:
+            raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
+        hf = self._reader.cache.get(idx)
+        if hf is None:
+            hf = self._reader._decode(idx)
+        return self._prepare(hf)[0]
+
+    def __getitem__(self, idx):
         if not 0 <= idx < self.num_imgs:
             raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
         hf = self._reader.get(idx)
+        image, motion = self._prepare(hf)
+        return image, hf.depth, self.poses[idx].clone(), motion
+
+    def _prepare(self, hf):
+        import torch
+        from . import frame_io
         H, W, dev = self.height, self.width, self.device
         main = torch.cuda.current_stream(dev)
         # pinned staging on this thread (the decoding thread never touches the device); the host allocator keeps a block until the
@@ -319,40 +376,41 @@ class RecordedRGBDDataset:
         main.wait_event(ready)
         image.record_stream(main)                       # allocated on the side stream, used (and freed) on the caller's
         motion.record_stream(main)
-        return image, hf.depth, self.poses[idx].clone(), motion
+        return image, motion
 
 
 class TUMDataset(RecordedRGBDDataset):
     """TUM RGB-D and Bonn (utils/dataset.py:677-696): Dataset.type 'tum'; Bonn calibrations are distorted."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
         c = config["Dataset"]["Calibration"]
         frames = parse_tum(config["Dataset"]["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
-        super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames)
+        super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames, flow=flow)
 
 
 class CoFusionDataset(RecordedRGBDDataset):
     """CoFusion (utils/dataset.py:490-660): Dataset.type 'CoFusion'; never undistorted, depth divided in float32."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
         c, d = config["Dataset"]["Calibration"], config["Dataset"]
         frames = parse_cofusion(d["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
         if d.get("seg_teddy", False) or d.get("seg_clock", False):           # :545-547, after the slicing
             frames.color_paths = sorted(frames.color_paths, key=extract_number)
             frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
-        super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames)
+        super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow)
 
 
 SUPPORTED_TYPES = ("tum", "CoFusion")
 
 
-def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None):
-    """utils/dataset.py:962-976 for the recorded RGB-D types this project reads: 'tum' (TUM, Bonn) and 'CoFusion'."""
+def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
+    """utils/dataset.py:962-976 for the recorded RGB-D types this project reads: 'tum' (TUM, Bonn) and 'CoFusion'. flow: an optical-flow
+    estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None."""
     kind = config["Dataset"].get("type")
     if kind == "tum":
-        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames)
+        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow)
     if kind == "CoFusion":
-        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames)
+        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow)
     raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn) and 'CoFusion'")
 
 

@@ -2,11 +2,14 @@
 """The SLAM system on a recorded sequence, as the reference's `slam.py --config X.yaml [--eval] [--dynamic]` (slam.py:250-276): the config
 (with its inherit_from chain, slam/config.py) names a TUM / Bonn or CoFusion sequence on disk (slam/recorded.py). Prints the JSON document
 of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the time the loop waited for a frame, and how many frames
-came from the read-ahead thread vs were decoded on demand."""
+came from the read-ahead thread vs were decoded on demand. With --dynamic --raft-weights PATH (the reference's pretrained/raft-things.pth) the
+dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py), and a `flow` block reports the pairs estimated and the
+device ms per pair."""
 import argparse
 import json
 import os
 import sys
+import warnings
 from datetime import datetime
 
 import torch
@@ -28,7 +31,11 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=None, help="use the first N frames (after Calibration start / end)")
     ap.add_argument("--save-dir", default=None, help="where results go (default: slam.py's Results.save_dir/<scene>/<name>_<time>)")
     ap.add_argument("--prefetch", type=int, default=4, help="frames decoded ahead of the loop")
+    ap.add_argument("--raft-weights", default=None, help="RAFT-basic checkpoint (raft-things.pth): the flow term of --dynamic runs")
     args = ap.parse_args(argv)
+    if args.raft_weights and not args.dynamic:
+        warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
+        args.raft_weights = None
 
     config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
     if args.dataset_path:
@@ -43,7 +50,11 @@ def main(argv=None):
         with open(os.path.join(save_dir, "config.json"), "w") as f:
             json.dump(config, f, indent=1, default=str)
     torch.manual_seed(0)
-    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames)
+    flow = None
+    if args.raft_weights:
+        from slam.optical_flow import RaftFlow
+        flow = RaftFlow.from_checkpoint(args.raft_weights, "cuda:0")
+    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow)
     slam = SLAM(config, ds, save_dir=save_dir)
     res = slam.run()
     res["graph_stats"] = slam.frontend.graph_stats
@@ -53,6 +64,8 @@ def main(argv=None):
                                   "initialize_network": dict(getattr(slam.backend, "network_init_graph_stats", {}) or {})}
     res["resolution"] = [ds.width, ds.height]
     res["ingest"] = ds.ingest_stats
+    if flow is not None:
+        res["flow"] = ds.flow_stats
     ds.close()
     name = os.path.splitext(os.path.basename(args.config))[0] + ("_dynamic" if args.dynamic else "")
     print(json.dumps({name: res}, indent=1, default=str))
