@@ -42,6 +42,8 @@
 #include "gs_frame.h"
 #include "../../include/optical_flow.h"
 #include "gs_raft.h"
+#include "../../include/segmentation.h"
+#include "gs_yolo.h"
 
 namespace gsr {
 
@@ -2941,6 +2943,96 @@ int gsr_raft_upsample(int batch, int h, int w, const float* flow, const float* m
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(raft_upsample_kernel, dim3((unsigned)((out_w + 255) / 256), out_h, batch), dim3(256), 0, stream, h, w, flow, mask, pad_left,
                        pad_top, out_w, out_h, ndc, out);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static size_t yolo_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// workspace: score [A] | cls [A] | box float4 [A] | order [A] | obox float4 [A] | n | mask u64 [A, words]
+size_t gsr_yolo_workspace_size(int anchors)
+{
+    if (anchors <= 0 || anchors > YOLO_MAX_ANCHORS) return 0;
+    const size_t A = (size_t)anchors, words = (A + 63) / 64;
+    return yolo_align(A * 4) * 2 + yolo_align(A * 16) * 2 + yolo_align(A * 4) + yolo_align(4) + A * words * 8;
+}
+
+int gsr_yolo_detect(int levels, const int* level_hw, const float* level_stride, const float* const* head, const float* const* coef, int nc,
+                    int nm, const int* classes, int n_classes, float conf, float iou, int max_det, void* workspace, float* dets, int max_dets,
+                    int* counts, void* stream_)
+{
+    if (levels < 1 || levels > YOLO_MAX_LEVELS || !level_hw || !level_stride || !head || !coef || !classes || !workspace || !dets || !counts) {
+        g_last_error = "gsr_yolo_detect: 1 to 4 levels, and level_hw, level_stride, head, coef, classes, workspace, dets, counts given";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (nc < 1 || nc > YOLO_MAX_CLASSES || nm < 1 || nm > YOLO_MAX_NM || n_classes < 1 || max_det < 1 || max_dets < 1 || !(conf >= 0.f) ||
+        !(iou >= 0.f)) {
+        g_last_error = "gsr_yolo_detect: needs 1 <= nc <= 256, 1 <= nm <= 64, at least one class, max_det, max_dets >= 1, conf, iou >= 0";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    YoloLevels L{};
+    L.levels = levels;
+    long long A = 0;
+    for (int l = 0; l < levels; ++l) {
+        L.h[l] = level_hw[2 * l];
+        L.w[l] = level_hw[2 * l + 1];
+        L.head[l] = head[l];
+        L.coef[l] = coef[l];
+        L.stride[l] = level_stride[l];
+        L.first[l] = (int)A;
+        if (L.h[l] < 1 || L.w[l] < 1 || !head[l] || !coef[l] || !(level_stride[l] > 0.f)) {
+            g_last_error = "gsr_yolo_detect: a level has an empty grid, a NULL tensor or a stride that is not positive";
+            return GSR_ERR_INVALID_ARGUMENT;
+        }
+        A += (long long)L.h[l] * L.w[l];
+        if (A > YOLO_MAX_ANCHORS) {
+            g_last_error = "gsr_yolo_detect: more than " + std::to_string(YOLO_MAX_ANCHORS) + " anchors (the sort's LDS capacity)";
+            return GSR_ERR_INVALID_ARGUMENT;
+        }
+    }
+    L.first[levels] = (int)A;
+    YoloClassSet cs{};
+    for (int k = 0; k < n_classes; ++k) {
+        if (classes[k] < 0 || classes[k] >= nc) { g_last_error = "gsr_yolo_detect: a class id is outside [0, nc)"; return GSR_ERR_INVALID_ARGUMENT; }
+        cs.bits[classes[k] >> 5] |= 1u << (classes[k] & 31);
+    }
+    const int words = (int)((A + 63) / 64);
+    char* ws = (char*)workspace;
+    float* score = (float*)ws;                     ws += yolo_align(A * 4);
+    int* cls = (int*)ws;                           ws += yolo_align(A * 4);
+    float4* box = (float4*)ws;                     ws += yolo_align(A * 16);
+    int* order = (int*)ws;                         ws += yolo_align(A * 4);
+    float4* obox = (float4*)ws;                    ws += yolo_align(A * 16);
+    int* n = (int*)ws;                             ws += yolo_align(4);
+    unsigned long long* mask = (unsigned long long*)ws;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(yolo_decode_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, stream, L, (int)A, nc, cs, conf, score, cls, box);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(yolo_sort_kernel, dim3(1), dim3(YOLO_SORT_BLOCK), 0, stream, (int)A, score, cls, box, order, obox, n);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(yolo_iou_kernel, dim3((unsigned)words, (unsigned)words), dim3(64), 0, stream, n, obox, iou, words, mask);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(yolo_select_kernel, dim3(1), dim3(64), 0, stream, L, n, order, score, cls, box, mask, words, nc, nm, max_det, max_dets,
+                       dets, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_yolo_masks(int max_dets, const float* dets, const int* counts, int nm, const float* proto, int proto_h, int proto_w, int height, int width,
+                   unsigned char* yolo_mask, unsigned char* motion, void* stream_)
+{
+    if (max_dets < 0 || !dets || !counts || !proto || nm < 1 || nm > YOLO_MAX_NM || (!yolo_mask && !motion)) {
+        g_last_error = "gsr_yolo_masks: dets, counts, proto and an output given, 1 <= nm <= 64";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (height <= 0 || width <= 0 || height % YOLO_TILE || width % YOLO_TILE || proto_h * 4 != height || proto_w * 4 != width ||
+        (long long)height * width > 0x7fffffffLL) {
+        g_last_error = "gsr_yolo_masks: height and width must be positive multiples of 32 and the proto exactly a quarter of them";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(yolo_mask_kernel, dim3((unsigned)(width / YOLO_TILE), (unsigned)(height / YOLO_TILE)), dim3(256), 0, stream, counts,
+                       max_dets, dets, nm, proto, proto_h, proto_w, height, width, yolo_mask, motion);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -8,10 +8,14 @@ slam/frame_decode.py) in a background thread that reads ahead of the SLAM loop; 
 lens undistortion, byte -> float conversion, CHW transpose and motion-mask threshold are one HIP launch on a side stream
 (gsr_frame_prepare, include/frame_io.h) that the caller's stream waits for. Given an optical-flow estimator (``flow=``, slam/optical_flow.py
 RaftFlow), the dataset has ``gt_flow`` -- RAFT's flow between two frames, as the reference's generate_flow asks it for; without one it has no
-``gt_flow`` and the backend skips its flow term, as it does for any dataset that lacks it.
+``gt_flow`` and the backend skips its flow term, as it does for any dataset that lacks it. Given a segmenter (``segmenter=``,
+slam/segmentation.py YoloSeg), every frame runs YOLO on the side stream right after its preparation and the instance masks of the loader's
+COCO classes are cleared from its motion mask (slam/segmentation.py dataset_classes: TUM / Bonn person, plus chair with seg_chair, ORed
+with the file masks; CoFusion person / clock / teddy bear, and no YOLO when mask files exist); without one, motion masks come only from
+mask files.
 
-What the reference does and this does not: YOLO masks (motion masks come only from mask files), EXR depth (CoFusion's depth_noise/*.exr
-raises), and its TUM mask list is not sliced by Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
+What the reference does and this does not: EXR depth (CoFusion's depth_noise/*.exr raises), and its TUM mask list is not sliced by
+Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
 import collections
 import concurrent.futures
 import glob
@@ -249,8 +253,10 @@ class RecordedRGBDDataset:
     """A recorded sequence with the interface of slam/dataset.py's SyntheticRGBDDataset; ``gt_flow`` only with a flow estimator."""
 
     FLOW_CACHE_PAIRS = 16          # estimated pairs kept (both directions each; 4.9 MB per pair at 640x480)
+    SEG_CACHE_FRAMES = 32          # segmented motion masks kept (0.3 MB each at 640x480): evaluation reads the frames again
 
-    def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None, flow=None):
+    def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None, flow=None, segmenter=None,
+                 seg_classes=None):
         import torch
         from .camera import getProjectionMatrix2
         if max_frames is not None:
@@ -290,6 +296,10 @@ class RecordedRGBDDataset:
             self._flow_cache = collections.OrderedDict()
             self._flow_events = []
             self.gt_flow = self._gt_flow
+        self._segmenter = segmenter if seg_classes else None
+        self.seg_classes = list(seg_classes) if self._segmenter is not None else None
+        self._seg_cache = collections.OrderedDict()   # frame -> its motion mask with the instance masks cleared
+        self._seg_events = []
 
     def __len__(self):
         return self.num_imgs
@@ -340,8 +350,19 @@ class RecordedRGBDDataset:
         return {"pairs": len(ms), "ms_per_pair": float(np.mean(ms)) if ms else None, "ms_first": ms[0] if ms else None,
                 "ms_rest_mean": float(np.mean(ms[1:])) if len(ms) > 1 else None}
 
+    @property
+    def segmentation_stats(self):
+        """Frames segmented and the device ms per frame (network + post-processing; None without a segmenter)."""
+        if self._segmenter is None:
+            return None
+        if self._seg_events:
+            self._seg_events[-1][1].synchronize()
+        ms = [s.elapsed_time(e) for s, e in self._seg_events]
+        return {"frames": len(ms), "classes": self.seg_classes, "ms_per_frame": float(np.mean(ms)) if ms else None,
+                "ms_first": ms[0] if ms else None, "ms_rest_mean": float(np.mean(ms[1:])) if len(ms) > 1 else None}
+
     def _frame_image(self, idx):
-        """Frame idx's image [3,H,W] without moving the read-ahead window (a keyframe the flow term needs again)."""
+        """Frame idx's image [3,H,W] without moving the read-ahead window (a keyframe the flow term needs again); never segmented."""
         if not 0 <= idx < self.num_imgs:
             raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
         hf = self._reader.cache.get(idx)
@@ -353,10 +374,21 @@ class RecordedRGBDDataset:
         if not 0 <= idx < self.num_imgs:
             raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
         hf = self._reader.get(idx)
-        image, motion = self._prepare(hf)
-        return image, hf.depth, self.poses[idx].clone(), motion
+        if self._segmenter is None:
+            image, motion = self._prepare(hf)
+            return image, hf.depth, self.poses[idx].clone(), motion
+        hit = self._seg_cache.get(idx)
+        image, motion = self._prepare(hf, segment=hit is None)
+        if hit is None:
+            self._seg_cache[idx] = motion
+            while len(self._seg_cache) > self.SEG_CACHE_FRAMES:
+                self._seg_cache.popitem(last=False)
+        else:
+            self._seg_cache.move_to_end(idx)
+            motion = hit
+        return image, hf.depth, self.poses[idx].clone(), motion.clone()
 
-    def _prepare(self, hf):
+    def _prepare(self, hf, segment=False):
         import torch
         from . import frame_io
         H, W, dev = self.height, self.width, self.device
@@ -371,6 +403,12 @@ class RecordedRGBDDataset:
             image = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             motion = torch.empty((H, W), dtype=torch.bool, device=dev)
             frame_io.frame_prepare(rgb, self._map, self._lut, mask, MASK_THRESHOLD, image, motion, self._side)
+            if segment:                                 # YOLO on the prepared frame; motion &= ~(instance masks), in place
+                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record(self._side)
+                self._segmenter(image, self.seg_classes, motion=motion)
+                end.record(self._side)
+                self._seg_events.append((start, end))
             ready = torch.cuda.Event()
             ready.record(self._side)
         main.wait_event(ready)
@@ -382,35 +420,40 @@ class RecordedRGBDDataset:
 class TUMDataset(RecordedRGBDDataset):
     """TUM RGB-D and Bonn (utils/dataset.py:677-696): Dataset.type 'tum'; Bonn calibrations are distorted."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+        from .segmentation import dataset_classes
         c = config["Dataset"]["Calibration"]
         frames = parse_tum(config["Dataset"]["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
-        super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames, flow=flow)
+        super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames, flow=flow,
+                         segmenter=segmenter, seg_classes=dataset_classes("tum", config["Dataset"], bool(frames.mask_paths)))
 
 
 class CoFusionDataset(RecordedRGBDDataset):
     """CoFusion (utils/dataset.py:490-660): Dataset.type 'CoFusion'; never undistorted, depth divided in float32."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+        from .segmentation import dataset_classes
         c, d = config["Dataset"]["Calibration"], config["Dataset"]
         frames = parse_cofusion(d["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
         if d.get("seg_teddy", False) or d.get("seg_clock", False):           # :545-547, after the slicing
             frames.color_paths = sorted(frames.color_paths, key=extract_number)
             frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
-        super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow)
+        super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter,
+                         seg_classes=dataset_classes("CoFusion", d, bool(frames.mask_paths)))
 
 
 SUPPORTED_TYPES = ("tum", "CoFusion")
 
 
-def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None):
+def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
     """utils/dataset.py:962-976 for the recorded RGB-D types this project reads: 'tum' (TUM, Bonn) and 'CoFusion'. flow: an optical-flow
-    estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None."""
+    estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None. segmenter: a YOLO instance segmenter
+    (slam/segmentation.py YoloSeg) whose masks of the loader's classes are cleared from the motion masks, or None."""
     kind = config["Dataset"].get("type")
     if kind == "tum":
-        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow)
+        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
     if kind == "CoFusion":
-        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow)
+        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
     raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn) and 'CoFusion'")
 
 

@@ -4,7 +4,8 @@
 of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the time the loop waited for a frame, and how many frames
 came from the read-ahead thread vs were decoded on demand. With --dynamic --raft-weights PATH (the reference's pretrained/raft-things.pth) the
 dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py), and a `flow` block reports the pairs estimated and the
-device ms per pair."""
+device ms per pair. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
+(slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame."""
 import argparse
 import json
 import os
@@ -22,7 +23,7 @@ from slam.recorded import load_dataset  # noqa: E402
 from slam.system import SLAM  # noqa: E402
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", required=True)
     ap.add_argument("--eval", action="store_true")
@@ -32,10 +33,19 @@ def main(argv=None):
     ap.add_argument("--save-dir", default=None, help="where results go (default: slam.py's Results.save_dir/<scene>/<name>_<time>)")
     ap.add_argument("--prefetch", type=int, default=4, help="frames decoded ahead of the loop")
     ap.add_argument("--raft-weights", default=None, help="RAFT-basic checkpoint (raft-things.pth): the flow term of --dynamic runs")
+    ap.add_argument("--yolo-weights", default=None, help="YOLO-seg checkpoint (yolov9e-seg.pt): motion masks of people and the "
+                                                         "loader's object classes")
     args = ap.parse_args(argv)
     if args.raft_weights and not args.dynamic:
         warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
         args.raft_weights = None
+    if args.yolo_weights and not os.path.isfile(args.yolo_weights):
+        ap.error(f"--yolo-weights {args.yolo_weights}: no such file")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
     if args.dataset_path:
@@ -54,7 +64,11 @@ def main(argv=None):
     if args.raft_weights:
         from slam.optical_flow import RaftFlow
         flow = RaftFlow.from_checkpoint(args.raft_weights, "cuda:0")
-    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow)
+    segmenter = None
+    if args.yolo_weights:
+        from slam.segmentation import YoloSeg
+        segmenter = YoloSeg.from_checkpoint(args.yolo_weights, "cuda:0")
+    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow, segmenter=segmenter)
     slam = SLAM(config, ds, save_dir=save_dir)
     res = slam.run()
     res["graph_stats"] = slam.frontend.graph_stats
@@ -66,6 +80,8 @@ def main(argv=None):
     res["ingest"] = ds.ingest_stats
     if flow is not None:
         res["flow"] = ds.flow_stats
+    if segmenter is not None:
+        res["segmentation"] = ds.segmentation_stats
     ds.close()
     name = os.path.splitext(os.path.basename(args.config))[0] + ("_dynamic" if args.dynamic else "")
     print(json.dumps({name: res}, indent=1, default=str))
