@@ -16,7 +16,6 @@ floats each). The view-independent terms (isotropic-scale regulariser, ARAP / el
 must be seeded alike: they take the same random draws (extra keyframes, time samples, split noise)."""
 import os
 import random
-import time
 
 import torch
 
@@ -166,7 +165,7 @@ class BackEnd:
     # ---- map initialisation (:237-296) -----------------------------------------------------------------------------------
     def initialize_map(self, cur_frame_idx, viewpoint):
         """:237-296. Runs of plain iterations -- between the densifications (every init_gaussian_update iterations) and the opacity resets --
-        are replayed as hipGraphs (slam/mapping_graph.InitGraph: the same arithmetic, one replay per iteration)."""
+        are replayed as hipGraphs (slam/mapping_graph.InitGraph through slam/graph_run.py: the same arithmetic, one replay per iteration)."""
         pkg = None
         rm_dynamic = not (self.dystart == cur_frame_idx)
         mapping_iteration = 0
@@ -208,50 +207,19 @@ class BackEnd:
         return n
 
     def _initialize_map_graph_run(self, viewpoint, rm_dynamic, run):
-        """`run` plain iterations of initialize_map as warm-up + capture + replays; returns the last render package, or None when nothing was
-        executed (the caller goes on eagerly)."""
-        from .mapping_graph import InitGraph
-        from diff_gaussian_rasterization import _C
+        """`run` plain iterations of initialize_map as warm-up + capture + replays (slam/graph_run.py); returns the last render package, or
+        None when nothing was executed (the caller goes on eagerly)."""
+        from .mapping_graph import InitGraph, INIT_CAPTURE_OPTIONS
+        from . import graph_run
         g = self.gaussians
-        stats = self.__dict__.setdefault("init_graph_stats", {"runs": 0, "replays": 0, "direct": 0, "redone": 0, "failed": 0})
-        if getattr(self, "_init_graph_broken", False) or g.optimizer.scheduled_segments() is None:
+        if graph_run.broken(self, "init_graph") or g.optimizer.scheduled_segments() is None:
             return None
         try:
             ig = InitGraph(self, viewpoint, rm_dynamic, run)
         except RuntimeError as e:
-            self._graph_note(stats, e)
+            graph_run.note_failure(self, "init_graph", e)
             return None
-        warm = min(self.graph_warmup, run)
-        ig.warm_up(warm)
-        done = warm
-        if run > warm:
-            overflow0 = _C.forward_status()[0]
-            ig.snapshot()
-            before = _C.debug_view_slots(1)[0]
-            try:
-                ig.capture()
-                ig.replay(run - warm)
-                torch.cuda.current_stream(ig.device).synchronize()
-                ok = _C.forward_status()[0] == overflow0
-                if not ok:      # what outgrew what (kept in the statistics: the capture margins of slam/mapping_graph.py are sized from these)
-                    after = _C.debug_view_slots(1)[0]
-                    stats.setdefault("overflow_causes", []).append({"iteration": int(self.iteration_count), "run": int(run), "gaussians": int(g.get_xyz.shape[0]),
-                                                                    "estimate_R": before["estimate_R_alloc"], "estimate_longest_tile": before["estimate_longest_tile"],
-                                                                    "overflowing_R_alloc": after["R_alloc"], "overflowing_longest_tile": after["longest_tile"]})
-            except Exception as e:        # a failed capture leaves the warm-up valid: the rest of the run goes on eagerly, no more captures
-                self._init_graph_broken = True
-                torch.cuda.synchronize(ig.device)
-                self._graph_note(stats, e)
-                ok = False
-            if ok:
-                done = run
-                stats["replays"] += run - warm
-                stats["runs"] += 1
-            else:                          # a replayed frame outgrew its binning buffer (or the capture failed): undo, let the eager loop repeat
-                ig.restore()
-                g.optimizer.zero_grad(set_to_none=True)
-                stats["redone"] += run - warm
-        stats["direct"] += warm
+        done = graph_run.replay_run(self, ig, run, min(self.graph_warmup, run), kind="init_graph", options=INIT_CAPTURE_OPTIONS)
         self.iteration_count += done
         g.optimizer.advance_steps(ig.todo, done)
         pkg = ig.pkg if done == run else None
@@ -529,63 +497,33 @@ class BackEnd:
         return self._kf_operands
 
     def _map_static_graph_run(self, current_window, viewpoint_stack, random_viewpoint_stack, run, last):
-        """`run` plain iterations: draws up front, `graph_warmup` iterations executed directly, one capture, run - warm-up replays. Returns
-        the number of iterations done (0: nothing was executed, the caller goes on eagerly)."""
-        from .mapping_graph import MappingGraph
-        from diff_gaussian_rasterization import _C
+        """`run` plain iterations: draws up front, `graph_warmup` iterations executed directly, one capture, run - warm-up replays
+        (slam/graph_run.py); what the graph did not do runs eagerly with the same draws. Returns the number of iterations done (0: nothing
+        was executed, the caller goes on eagerly)."""
+        from .mapping_graph import MappingGraph, CAPTURE_OPTIONS
+        from . import graph_run
         g = self.gaussians
-        stats = self.__dict__.setdefault("graph_stats", {"runs": 0, "replays": 0, "direct": 0, "redone": 0, "failed": 0})
         if g.optimizer.scheduled_segments() is None:         # (no gradient buffers / moments yet: the eager iteration creates them)
             return 0
         rng_state = torch.get_rng_state()
         draws = [self._draw_extras(len(random_viewpoint_stack)) for _ in range(run)]
-        count0 = self.iteration_count
         try:
-            mg = MappingGraph(self, current_window, viewpoint_stack, random_viewpoint_stack, draws, count0)
+            mg = MappingGraph(self, current_window, viewpoint_stack, random_viewpoint_stack, draws, self.iteration_count)
         except RuntimeError as e:
             torch.set_rng_state(rng_state)
-            self._graph_note(stats, e)
+            graph_run.note_failure(self, "graph", e)
             return 0
-        warm = min(self.graph_warmup, run)
-        mg.warm_up(warm)
-        overflow0 = _C.forward_status_views()     # (the directly executed iterations waited for their headers and redid what overflowed themselves)
-        if run > warm:
-            mg.snapshot()
-            try:
-                t_cap = time.perf_counter()
-                mg.capture()
-                stats["capture_ms"] = stats.get("capture_ms", 0.0) + (time.perf_counter() - t_cap) * 1e3
-                stats["last_capture_parts_ms"] = [round(v, 3) for v in getattr(mg, "capture_parts_ms", ())]     # begin, host pass, end + instantiate, hipMallocs
-            except Exception as e:        # a capture that fails leaves the iterations done so far valid: finish the run eagerly, stop capturing
-                self._graph_broken = True
-                torch.cuda.synchronize(mg.device)
-                mg.restore()
-                g.optimizer.zero_grad(set_to_none=True)
-                self._clear_camera_grads(list(viewpoint_stack) + mg.slots)
-                self._graph_note(stats, e)
-                self._finish_run(mg, draws, mg.executed)
-                self._run_eagerly(current_window, viewpoint_stack, random_viewpoint_stack, draws[mg.executed:], last)
-                return run
-            mg.replay(run - warm)
-            torch.cuda.current_stream(mg.device).synchronize()
-            if _C.forward_status_views() != overflow0:          # a replayed view outgrew its binning buffer: undo the replays, redo them eagerly
-                mg.restore()
-                stats["redone"] += run - warm
-                self._finish_run(mg, draws, warm)
-                self._run_eagerly(current_window, viewpoint_stack, random_viewpoint_stack, draws[warm:], last)
-                mg.release()
-                return run
-        stats["runs"] += 1
-        stats["direct"] += warm
-        stats["replays"] += run - warm
-        self._finish_run(mg, draws, run)
-        if last:
+        done = graph_run.replay_run(self, mg, run, min(self.graph_warmup, run), kind="graph", options=CAPTURE_OPTIONS)
+        self._finish_run(mg, done)
+        if done < run:
+            for j, extras_idx in enumerate(draws[done:], done):
+                self._map_static_iteration(current_window, viewpoint_stack, random_viewpoint_stack, False, last and j == run - 1, extras_idx=extras_idx)
+        elif last:
             with torch.no_grad():
                 self._publish_visibility(current_window, {k: mg.pkgs[k]["n_touched"] for k in range(len(viewpoint_stack))})
-        mg.release()
         return run
 
-    def _finish_run(self, mg, draws, n):
+    def _finish_run(self, mg, n):
         """Host-side state after `n` graph iterations: what n eager iterations would have left (counters, Adam's step counts, learning rate)."""
         g = self.gaussians
         self.iteration_count += n
@@ -593,16 +531,6 @@ class BackEnd:
         g.optimizer.advance_steps(mg.todo, n)
         if n:
             g.update_learning_rate(self.iteration_count)
-
-    def _run_eagerly(self, current_window, viewpoint_stack, random_viewpoint_stack, draws, last):
-        for j, extras_idx in enumerate(draws):
-            self._map_static_iteration(current_window, viewpoint_stack, random_viewpoint_stack, False, last and j == len(draws) - 1, extras_idx=extras_idx)
-
-    def _graph_note(self, stats, error):
-        stats["failed"] += 1
-        stats["last_error"] = f"{type(error).__name__}: {error}"
-        if self.config["Training"].get("mapping_graph") == "strict":
-            raise error
 
     def _clear_camera_grads(self, cams):
         for v in cams:

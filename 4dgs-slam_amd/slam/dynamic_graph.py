@@ -26,11 +26,11 @@ recorded once and replayed:
 run, the iterations that densify or reset opacities (those replace the model's tensors: they end a run) -- or captured once and replayed.
 Direct and replayed iterations are bit-identical (tests/test_hip_slam.py). The call's two halves (:350-355: the loss weights double on the
 moving pixels in the first half; :337-338,:765-770: the Gaussians only step in the second) are different graphs: a run never crosses the
-boundary. A replayed forward pass that outgrows its binning buffer is detected after the run (sticky overflow counters); the run is then
-undone from a snapshot and repeated directly."""
+boundary. Warm-up, capture, replays and undo are slam/graph_run.py's: a replayed forward pass that outgrows its binning buffer is detected
+after the run (sticky overflow counters), the run is then undone from a snapshot (``state_tensors()``) and repeated directly; so is the rest
+of a run whose capture fails."""
 import ctypes as C
 import os
-import time
 
 import numpy as np
 import torch
@@ -40,6 +40,7 @@ from diff_gaussian_rasterization._abi import gsr_keyframe_entry
 import control_nodes
 import slam_losses
 
+from . import graph_run
 from .camera import Camera
 from .deform_model import draw_loss_times, time_key
 from .mapping_graph import N_INDEX_WORDS
@@ -52,6 +53,8 @@ CAPTURE_MARGIN_PERMILLE, CAPTURE_TILE_MARGIN_PERMILLE = (int(v) for v in os.envi
 # capture says little about the next draw (flow slot: 7 042 at capture, > 25 000 later = the 3x margin overrun, 99 iterations redone in the
 # config #4 stand-in, 39 of 400 in the census) -- a floor in instances (~70 B each: 9 MB per view) instead of a ratio alone
 CAPTURE_FLOOR_INSTANCES = int(os.environ.get("GSR_DYN_CAP_FLOOR", "131072"))
+CAPTURE_OPTIONS = {"cap_margin_permille": CAPTURE_MARGIN_PERMILLE, "cap_tile_margin_permille": CAPTURE_TILE_MARGIN_PERMILLE,
+                   "cap_floor": CAPTURE_FLOOR_INSTANCES}
 FLOW_CLIPS = os.environ.get("GSR_FLOW_CLIPS", "1") != "0"      # render the flow images only where the flow loss reads them (gsr_view.flow_clip)
 FLOW_TARGET_BUDGET_FRACTION = 0.03  # ... and at most this share of the device memory free when the first target is formed
 FLOW_TARGET_CACHE_MAX = 512       # keyframe pairs whose flow targets are kept (~7 MB each at 640x480); dropped ones are formed again on demand
@@ -111,8 +114,9 @@ class DynamicMapping:
         self.slot_clips = torch.zeros((max(1, self.n_slots), 8), dtype=torch.int32, device=dev)       # per slot: its rectangle, its partner's
         self._layouts, self._tables, self._window_ops = {}, {}, {}
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.run, self.graph, self.pkgs = None, None, None
-        self.stats = be.__dict__.setdefault("dynamic_graph_stats", {"runs": 0, "replays": 0, "direct": 0, "special": 0, "redone": 0, "failed": 0})
+        self.run, self.pkgs = None, None
+        self.stats = graph_run.stats(be, "dynamic_graph")
+        self.stats.setdefault("special", 0)
 
     @staticmethod
     def _entries(pairs):
@@ -282,7 +286,7 @@ class DynamicMapping:
         r.table = torch.from_numpy(table.view(np.int32)).pin_memory().to(self.device, non_blocking=True)
         r.current = torch.zeros(r.row_words, dtype=torch.int32, device=self.device)
         self.counter.zero_()
-        self.run, self.graph = r, None
+        self.run = r
         return r
 
     # ---- the iteration (one code path: run directly, or captured and replayed) ---------------------------------------------------------------
@@ -456,46 +460,8 @@ class DynamicMapping:
             self.iteration()
         self.stats["direct"] += n
 
-    def warm_up(self, n):
-        """`n` iterations executed directly on a side stream (torch's capture protocol: autograd's stream bookkeeping must have seen the
-        stream family the capture will use)."""
-        dev = self.device
-        s = self.be.graph_streams(dev)[0]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(n):
-                self.iteration()
-        torch.cuda.current_stream(dev).wait_stream(s)
-
-    def capture(self):
-        """(raw capture API on a persistent side stream and ONE private memory pool per back-end: see MappingGraph.capture)"""
-        be, dev = self.be, self.device
-        lazy_before = _C.set_option("lazy", 1)
-        margin_before = _C.set_option("cap_margin_permille", CAPTURE_MARGIN_PERMILLE)
-        tile_before = _C.set_option("cap_tile_margin_permille", CAPTURE_TILE_MARGIN_PERMILLE)
-        floor_before = _C.set_option("cap_floor", CAPTURE_FLOOR_INSTANCES)
-        # TEST facility (Training.graph_test_shrink_permille): lay the captured buffers out too small, so that replays overflow
-        shrink_before = _C.set_option("cap_test_shrink_permille", int(be.config["Training"].get("graph_test_shrink_permille", 0)))
-        s = be.graph_streams(dev)[1]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        self.graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.stream(s):
-                self.graph.capture_begin(pool=be.graph_pool(dev))
-                try:
-                    self.iteration()
-                finally:
-                    self.graph.capture_end()
-        finally:
-            _C.set_option("lazy", lazy_before)       # the flags only matter while host code runs: replays never consult them
-            _C.set_option("cap_margin_permille", margin_before)
-            _C.set_option("cap_tile_margin_permille", tile_before)
-            _C.set_option("cap_floor", floor_before)
-            _C.set_option("cap_test_shrink_permille", shrink_before)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        be._graph_keepalive = self.graph             # (drops the previous run's graph: the pool now belongs to this one)
-
-    def snapshot(self):
+    # ---- for slam/graph_run.py -------------------------------------------------------------------------------------------------------
+    def state_tensors(self):
         g, r = self.g, self.run
         tensors = [p for grp in g.optimizer.param_groups for p in grp["params"]]
         if r.todo:
@@ -508,67 +474,26 @@ class DynamicMapping:
         tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D, self.counter]
         for v in self.views:
             tensors += [v._R, v._T, v._adam, v._converged, v.exposure_a, v.exposure_b, v.cam_rot_delta, v.cam_trans_delta]
-        with torch.no_grad():
-            self._snap = [(t, t.detach().clone()) for t in tensors]
+        return tensors
 
-    def restore(self):
-        with torch.no_grad():
-            for t, c in self._snap:
-                t.detach().copy_(c)
-            for v in self.views:
-                v.refresh_matrices()
+    def discard(self):
+        for v in self.views:
+            v.refresh_matrices()
+        self.g.optimizer.zero_grad(set_to_none=True)
+        self.g.deform.optimizer.zero_grad(set_to_none=True)
+        self.be._clear_camera_grads(self.views + self.slots + self.partner_slots)
 
     def plain_run(self, rows):
-        """A run of plain iterations: replays of one captured iteration when the run is long enough and graphs are on, else direct."""
+        """A run of plain iterations: replays of one captured iteration when the run is long enough and graphs are on; directly executed,
+        what the graph did not do."""
         be, r = self.be, self.run
-        use_graph = (be._graphs_enabled() and rows >= be.graph_min_run and not getattr(be, "_dynamic_graph_broken", False)
-                     and (not r.stepping or r.todo is not None))
-        if not use_graph:
-            self.direct(rows)
-            self.finish(rows)
-            return
-        warm = min(be.dynamic_graph_warmup, rows)
-        self.warm_up(warm)
-        self.stats["direct"] += warm
-        overflow0 = _C.forward_status_views()
-        slots_before = _C.debug_view_slots(100)
-        self.snapshot()
-        try:
-            t0 = time.perf_counter()
-            self.capture()
-            self.stats["capture_ms"] = self.stats.get("capture_ms", 0.0) + (time.perf_counter() - t0) * 1e3
-        except Exception as e:        # a capture that fails leaves the iterations done so far valid: finish the run directly, stop capturing
-            be._dynamic_graph_broken = True
-            torch.cuda.synchronize(self.device)
-            self.restore()
-            self.g.optimizer.zero_grad(set_to_none=True)
-            self.g.deform.optimizer.zero_grad(set_to_none=True)
-            be._clear_camera_grads(self.views + self.slots + self.partner_slots)
-            self.stats["failed"] += 1
-            self.stats["last_error"] = f"{type(e).__name__}: {e}"
-            if be.config["Training"].get("mapping_graph") == "strict":
-                raise
-            self.graph = None
-            self.direct(rows - warm)
-            self.finish(rows)
-            return
-        for _ in range(rows - warm):
-            self.graph.replay()
-        torch.cuda.current_stream(self.device).synchronize()
-        if _C.forward_status_views() != overflow0:          # a replayed view outgrew its binning buffer: undo the replays, redo them directly
-            # (which slot outgrew what, kept in the statistics: slots whose overflow counter moved, with the estimates the layout started from)
-            slots_after = _C.debug_view_slots(100)
-            moved = [dict(slot=k, **{n: a[n] for n in ("R_alloc", "longest_tile", "estimate_R_alloc", "estimate_longest_tile")},
-                          captured_estimate_R=b["estimate_R_alloc"], captured_estimate_tile=b["estimate_longest_tile"])
-                     for k, (a, b) in enumerate(zip(slots_after, slots_before)) if a["overflows"] != b["overflows"]]
-            self.stats.setdefault("overflow_causes", []).append({"rows": int(rows - warm), "gaussians": int(self.g.get_xyz.shape[0]), "slots": moved[:6]})
-            self.restore()
-            self.stats["redone"] += rows - warm
-            self.graph = None
-            self.direct(rows - warm)
-        else:
-            self.stats["replays"] += rows - warm
-            self.stats["runs"] += 1
+        done = 0
+        if (be._graphs_enabled() and rows >= be.graph_min_run and not graph_run.broken(be, "dynamic_graph")
+                and (not r.stepping or r.todo is not None)):
+            # (TEST facility, Training.graph_test_shrink_permille: lay the captured buffers out too small, so that replays overflow)
+            options = dict(CAPTURE_OPTIONS, cap_test_shrink_permille=int(be.config["Training"].get("graph_test_shrink_permille", 0)))
+            done = graph_run.replay_run(be, self, rows, min(be.dynamic_graph_warmup, rows), kind="dynamic_graph", options=options)
+        self.direct(rows - done)
         self.finish(rows)
 
     def execute(self):
@@ -604,14 +529,15 @@ class DynamicMapping:
             if i == self.iters:
                 with torch.no_grad():
                     be._publish_visibility(self.current_window, {k: self.pkgs[k]["n_touched"] for k in range(nv)}, n_views=nv)
-        self.run, self.graph, self.pkgs, self._snap = None, None, None, None
+        self.run, self.pkgs = None, None
         return split
 
 
 class NetworkInit:
     """BackEnd.initialize_network's loop (utils/slam_backend.py:160-234: the node network fitted on ONE view -- network, blend, render, the
     mapping loss without exposure, backward, Adam on the network) in the indexed layout (one time sample, every head), its iterations after the
-    first -- which may densify -- as hipGraph replays. ``iteration()`` is one code path, executed directly or captured and replayed."""
+    first -- which may densify -- as hipGraph replays (slam/graph_run.py). ``iteration()`` is one code path, executed directly or captured and
+    replayed."""
 
     def __init__(self, backend, viewpoint):
         be = self.be = backend
@@ -620,8 +546,8 @@ class NetworkInit:
         dev = self.device = viewpoint.device
         self.ops = be.keyframe_operands.get(be.config, viewpoint, dev, rm_dynamic=False, dynamic=False)
         self.time = torch.tensor([time_key(viewpoint.time)], dtype=torch.float32).to(dev)
-        self.graph, self.pkg = None, None
-        self.stats = be.__dict__.setdefault("network_init_graph_stats", {"runs": 0, "replays": 0, "direct": 0, "redone": 0, "failed": 0})
+        self.pkg = None
+        self.stats = graph_run.stats(be, "network_init_graph")
 
     @staticmethod
     def eligible(be, viewpoint, update_gaussians):
@@ -650,7 +576,7 @@ class NetworkInit:
         self.pkg = pkg
         return pkg
 
-    def _snapshot(self):
+    def state_tensors(self):
         g, v = self.g, self.viewpoint
         net = g.deform.optimizer
         tensors = []
@@ -660,12 +586,16 @@ class NetworkInit:
                 tensors += [s for s in net.state.get(p, {}).values() if torch.is_tensor(s)]
         tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D]
         tensors += [p.grad for p in (v.cam_rot_delta, v.cam_trans_delta, v.exposure_a, v.exposure_b) if p is not None and p.grad is not None]
-        with torch.no_grad():
-            return [(t, t.detach().clone()) for t in tensors]
+        return tensors
+
+    def discard(self):
+        """(the view's camera gradients are part of the snapshot: they accumulate across the loop on purpose, see iteration())"""
+        self.g.optimizer.zero_grad(set_to_none=True)
+        self.g.deform.optimizer.zero_grad(set_to_none=True)
 
     def run(self, iterations):
         """All iterations of the loop; returns the last render package."""
-        be, dev = self.be, self.device
+        be = self.be
         i = 0
         while i < iterations:
             if i % be.init_gaussian_update == 0:
@@ -676,69 +606,12 @@ class NetworkInit:
             rows = 0
             while i + rows < iterations and (i + rows) % be.init_gaussian_update != 0:
                 rows += 1
-            if not (be._graphs_enabled() and rows >= be.graph_min_run and not getattr(be, "_network_init_graph_broken", False)):
-                for _ in range(rows):
-                    self.iteration()
+            done = 0
+            if be._graphs_enabled() and rows >= be.graph_min_run and not graph_run.broken(be, "network_init_graph"):
+                done = graph_run.replay_run(be, self, rows, min(be.dynamic_graph_warmup, rows), kind="network_init_graph", options=CAPTURE_OPTIONS)
+            else:
                 self.stats["direct"] += rows
-                i += rows
-                continue
-            warm = min(be.dynamic_graph_warmup, rows)
-            s0, s1 = be.graph_streams(dev)
-            s0.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s0):
-                for _ in range(warm):
-                    self.iteration()
-            torch.cuda.current_stream(dev).wait_stream(s0)
-            self.stats["direct"] += warm
-            overflow0 = _C.forward_status()[0]
-            snap = self._snapshot()
-            ok = True
-            lazy_before = _C.set_option("lazy", 1)
-            margin_before = _C.set_option("cap_margin_permille", CAPTURE_MARGIN_PERMILLE)
-            tile_before = _C.set_option("cap_tile_margin_permille", CAPTURE_TILE_MARGIN_PERMILLE)
-            floor_before = _C.set_option("cap_floor", CAPTURE_FLOOR_INSTANCES)
-            try:
-                s1.wait_stream(torch.cuda.current_stream(dev))
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(s1):
-                    self.graph.capture_begin(pool=be.graph_pool(dev))
-                    try:
-                        self.iteration()
-                    finally:
-                        self.graph.capture_end()
-                torch.cuda.current_stream(dev).wait_stream(s1)
-                be._graph_keepalive = self.graph
-            except Exception as e:
-                be._network_init_graph_broken = True
-                torch.cuda.synchronize(dev)
-                self.stats["failed"] += 1
-                self.stats["last_error"] = f"{type(e).__name__}: {e}"
-                if be.config["Training"].get("mapping_graph") == "strict":
-                    raise
-                ok = False
-            finally:
-                _C.set_option("lazy", lazy_before)
-                _C.set_option("cap_margin_permille", margin_before)
-                _C.set_option("cap_tile_margin_permille", tile_before)
-                _C.set_option("cap_floor", floor_before)
-            if ok:
-                for _ in range(rows - warm):
-                    self.graph.replay()
-                torch.cuda.current_stream(dev).synchronize()
-                ok = _C.forward_status()[0] == overflow0
-            if ok:
-                self.stats["replays"] += rows - warm
-                self.stats["runs"] += 1
-            else:                               # undo whatever the capture / the replays did, repeat directly
-                with torch.no_grad():
-                    for t, c in snap:
-                        t.detach().copy_(c)
-                self.g.optimizer.zero_grad(set_to_none=True)
-                self.g.deform.optimizer.zero_grad(set_to_none=True)
-                self.graph = None
-                self.stats["redone"] += rows - warm
-                for _ in range(rows - warm):
-                    self.iteration()
+            for _ in range(rows - done):
+                self.iteration()
             i += rows
-        pkg, self.graph = self.pkg, None
-        return pkg
+        return self.pkg

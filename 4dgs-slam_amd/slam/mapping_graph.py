@@ -18,8 +18,9 @@ rasterizer's lazy mode, cameras in persistent device buffers, a camera step with
 
 The host draws the random keyframes for the whole run up front -- the same ``torch.randperm`` calls in the same order as the eager loop -- and
 ``iteration()`` is ONE code path: executed directly for the warm-up iterations of a run, captured once, then replayed. Results are
-bit-identical to the eager loop (tests/test_hip_slam.py). A replayed forward pass that outgrows its (generously sized) binning buffer is
-detected after the run through the sticky overflow counters; the run is then undone from a snapshot and repeated eagerly."""
+bit-identical to the eager loop (tests/test_hip_slam.py). Warm-up, capture, replays and undo are slam/graph_run.py's: a replayed forward pass
+that outgrows its (generously sized) binning buffer is detected after the run through the sticky overflow counters, the run is then undone
+from a snapshot (``state_tensors()``) and repeated eagerly; so is the rest of a run whose capture fails."""
 import ctypes as C
 
 import numpy as np
@@ -32,11 +33,12 @@ import slam_losses
 from .camera import Camera
 
 N_INDEX_WORDS = 2            # random keyframes per iteration (utils/slam_backend.py:1031-1037)
-CAPTURE_MARGIN_PERMILLE = 500
-CAPTURE_TILE_MARGIN_PERMILLE = 3000     # the longest tile list may grow 4x during the replays (see include/gs_rasterizer.h)
+# head room of the binning buffers a captured iteration lays out (gsr_set_option, see include/gs_rasterizer.h): the longest tile list may
+# grow 4x during the replays
+CAPTURE_OPTIONS = {"cap_margin_permille": 500, "cap_tile_margin_permille": 3000}
 # initialize_map's runs: the instance count of the ONE view being fitted grew 1.82x inside a 99-iteration run right after the opacity reset
 # (104 438 -> 190 427 instances at iteration 501 of the config #4 stand-in; 1.5x was the margin, 97 iterations were redone): 3x here
-INIT_CAPTURE_MARGIN_PERMILLE = 2000
+INIT_CAPTURE_OPTIONS = dict(CAPTURE_OPTIONS, cap_margin_permille=2000)
 
 
 def device_store_budget(device, fraction, floor_bytes=256 << 20):
@@ -175,7 +177,7 @@ class MappingGraph:
         self.table = torch.from_numpy(table.view(np.int32)).pin_memory().to(dev, non_blocking=True)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.current = torch.zeros(self.row_words, dtype=torch.int32, device=dev)
-        self.graph, self.pkgs, self.executed = None, None, 0
+        self.pkgs = None
 
     # ---- the iteration (one code path: run directly, or captured and replayed) ---------------------------------------------------------------
     def iteration(self):
@@ -207,78 +209,20 @@ class MappingGraph:
         self.pkgs = rendered
         return rendered
 
-    def warm_up(self, n):
-        """`n` iterations executed directly, on a side stream (torch's capture protocol: autograd's stream bookkeeping must have seen the
-        stream family the capture will use). They are iterations like any other: rows 0..n-1 of the schedule."""
-        dev = self.device
-        s = self.backend.graph_streams(dev)[0]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(n):
-                self.iteration()
-                self.executed += 1
-        torch.cuda.current_stream(dev).wait_stream(s)
-
-    def capture(self):
-        """Capture one iteration. Not through ``torch.cuda.graph``: its __enter__ runs gc.collect() and empties the allocator's cache -- tens of
-        milliseconds per capture at SLAM sizes, and every mapping call captures anew (the map's tensors change with every keyframe). All
-        captures of a back-end share ONE private memory pool; the previous graph is kept alive until this capture has begun, so the pool
-        (and its blocks) survive from capture to capture."""
-        be, dev = self.backend, self.device
-        lazy_before = _C.set_option("lazy", 1)
-        margin_before = _C.set_option("cap_margin_permille", CAPTURE_MARGIN_PERMILLE)
-        tile_before = _C.set_option("cap_tile_margin_permille", CAPTURE_TILE_MARGIN_PERMILLE)
-        s = be.graph_streams(dev)[1]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        self.graph = torch.cuda.CUDAGraph()
-        import time
-        t0 = time.perf_counter()
-        a0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
-        try:
-            with torch.cuda.stream(s):
-                self.graph.capture_begin(pool=be.graph_pool(dev))
-                t1 = time.perf_counter()
-                try:
-                    self.iteration()
-                finally:
-                    t2 = time.perf_counter()
-                    self.graph.capture_end()
-            t3 = time.perf_counter()
-            self.capture_parts_ms = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - a0)
-        finally:
-            _C.set_option("lazy", lazy_before)       # the flags only matter while host code runs: replays never consult them
-            _C.set_option("cap_margin_permille", margin_before)
-            _C.set_option("cap_tile_margin_permille", tile_before)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        be._graph_keepalive = self.graph             # (drops the previous run's graph: the pool now belongs to this one)
-        return self
-
-    def replay(self, n):
-        for _ in range(n):
-            self.graph.replay()
-        self.executed += n
-
-    # ---- undo (a replayed frame outgrew its buffers) -----------------------------------------------------------------------------------
-    def snapshot(self):
+    # ---- for slam/graph_run.py -------------------------------------------------------------------------------------------------------
+    def state_tensors(self):
         g = self.backend.gaussians
         tensors = [p for _, p in self.todo] + [g.optimizer.state[p][k] for _, p in self.todo for k in ("exp_avg", "exp_avg_sq")]
         tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D, self.counter]
         for v in self.window:
             tensors += [v._R, v._T, v._adam, v._converged, v.exposure_a, v.exposure_b, v.cam_rot_delta, v.cam_trans_delta]
-        with torch.no_grad():
-            self._snap = [(t, t.detach().clone()) for t in tensors]
-        self._snap_executed = self.executed
+        return tensors
 
-    def restore(self):
-        with torch.no_grad():
-            for t, c in self._snap:
-                t.detach().copy_(c)
-            for v in self.window:
-                v.refresh_matrices()
-        self.executed = self._snap_executed
-
-    def release(self):
-        self.graph, self.pkgs, self._snap = None, None, None
+    def discard(self):
+        for v in self.window:
+            v.refresh_matrices()
+        self.backend.gaussians.optimizer.zero_grad(set_to_none=True)
+        self.backend._clear_camera_grads(self.window + self.slots)
 
 
 class InitGraph:
@@ -305,7 +249,7 @@ class InitGraph:
         self.table = torch.from_numpy(table.view(np.int32)).pin_memory().to(dev, non_blocking=True)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.current = torch.zeros(self.row_words, dtype=torch.int32, device=dev)
-        self.graph, self.pkg, self.executed = None, None, 0
+        self.pkg = None
 
     def iteration(self):
         be, g, dev, v = self.backend, self.backend.gaussians, self.device, self.viewpoint
@@ -326,57 +270,14 @@ class InitGraph:
         self.pkg = pkg
         return pkg
 
-    def warm_up(self, n):
-        dev = self.device
-        s = self.backend.graph_streams(dev)[0]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(n):
-                self.iteration()
-                self.executed += 1
-        torch.cuda.current_stream(dev).wait_stream(s)
-
-    def capture(self):
-        """(see MappingGraph.capture)"""
-        be, dev = self.backend, self.device
-        lazy_before = _C.set_option("lazy", 1)
-        margin_before = _C.set_option("cap_margin_permille", INIT_CAPTURE_MARGIN_PERMILLE)
-        tile_before = _C.set_option("cap_tile_margin_permille", CAPTURE_TILE_MARGIN_PERMILLE)
-        s = be.graph_streams(dev)[1]
-        s.wait_stream(torch.cuda.current_stream(dev))
-        self.graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.stream(s):
-                self.graph.capture_begin(pool=be.graph_pool(dev))
-                try:
-                    self.iteration()
-                finally:
-                    self.graph.capture_end()
-        finally:
-            _C.set_option("lazy", lazy_before)
-            _C.set_option("cap_margin_permille", margin_before)
-            _C.set_option("cap_tile_margin_permille", tile_before)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        be._graph_keepalive = self.graph
-        return self
-
-    def replay(self, n):
-        for _ in range(n):
-            self.graph.replay()
-        self.executed += n
-
-    def snapshot(self):
+    def state_tensors(self):
         g = self.backend.gaussians
         tensors = [p for _, p in self.todo] + [g.optimizer.state[p][k] for _, p in self.todo for k in ("exp_avg", "exp_avg_sq")]
         tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D, self.counter]
         v = self.viewpoint
         tensors += [p.grad for p in (v.cam_rot_delta, v.cam_trans_delta, v.exposure_a, v.exposure_b) if p is not None and p.grad is not None]
-        with torch.no_grad():
-            self._snap = [(t, t.detach().clone()) for t in tensors]
-        self._snap_executed = self.executed
+        return tensors
 
-    def restore(self):
-        with torch.no_grad():
-            for t, c in self._snap:
-                t.detach().copy_(c)
-        self.executed = self._snap_executed
+    def discard(self):
+        """(the view's camera gradients are part of the snapshot: they accumulate across the loop on purpose, see iteration())"""
+        self.backend.gaussians.optimizer.zero_grad(set_to_none=True)

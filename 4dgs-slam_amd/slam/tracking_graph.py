@@ -26,6 +26,7 @@ from gaussian_renderer import render
 import slam_losses
 
 from .camera import Camera
+from .graph_run import capture_options
 
 # GSR_TRACK_STEP=0: the iteration through autograd (render -> weighted_l1_loss -> backward -> pose_step: ten launches), as rounds 2-5 ran it
 FUSED_STEP = os.environ.get("GSR_TRACK_STEP", "1") not in ("", "0")
@@ -154,18 +155,17 @@ class TrackingGraph:
         capture() does not move the camera."""
         c = self.cam
         keep = [t.detach().clone() for t in (c._R, c._T, c._adam, c.exposure_a, c.exposure_b)]
-        self._lazy_before = _C.set_option("lazy", 1)
-        s = torch.cuda.Stream(device=c.device)
-        s.wait_stream(torch.cuda.current_stream(c.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.iteration()
-        torch.cuda.current_stream(c.device).wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.pkg = self.iteration()          # static outputs: after a replay they hold that iteration's render (depth / opacity of the
-                                                 # last tracking iteration feed get_median_depth, utils/slam_frontend.py:461)
-        _C.set_option("lazy", self._lazy_before)      # the flag only matters while host code runs: replays never consult it
+        with capture_options(lazy=1):
+            s = torch.cuda.Stream(device=c.device)
+            s.wait_stream(torch.cuda.current_stream(c.device))
+            with torch.cuda.stream(s):
+                for _ in range(warmup):
+                    self.iteration()
+            torch.cuda.current_stream(c.device).wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.pkg = self.iteration()          # static outputs: after a replay they hold that iteration's render (depth / opacity of the
+                                                     # last tracking iteration feed get_median_depth, utils/slam_frontend.py:461)
         with torch.no_grad():
             for dst, src in zip((c._R, c._T, c._adam, c.exposure_a, c.exposure_b), keep):
                 dst.copy_(src)

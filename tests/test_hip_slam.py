@@ -547,9 +547,10 @@ def _map_static_state(be):
             "graph_stats": dict(getattr(be, "graph_stats", None) or {}) or None}
 
 
-def _map_static_outcome(graph, calls=(50,)):
-    """States after consecutive map_static calls of the given lengths (+ the pruning call after the last)."""
-    slam, window = _mapping_state(n_kf=7, gaussian_update_every=30, gaussian_update_offset=12, mapping_graph="strict" if graph else False)
+def _map_static_outcome(graph, calls=(50,), mode="strict"):
+    """States after consecutive map_static calls of the given lengths (+ the pruning call after the last); `mode`: Training.mapping_graph
+    when `graph` is on."""
+    slam, window = _mapping_state(n_kf=7, gaussian_update_every=30, gaussian_update_offset=12, mapping_graph=mode if graph else False)
     be = slam.backend
     # perturb the window poses a little so that the pose steps have something to do
     for k, idx in enumerate(window):
@@ -815,6 +816,83 @@ def test_dynamic_mapping_iterations_as_hip_graphs_are_bit_identical_to_direct_ex
         for i, (x, y) in enumerate(zip(xs, ys)):
             assert x.shape == y.shape and torch.equal(x, y), (name, i, float((x - y).abs().max()))
     assert a[0]["ate_rmse"] == b[0]["ate_rmse"] and a[0]["before_opt"]["mean_psnr"] == b[0]["before_opt"]["mean_psnr"]
+
+
+def _failing_capture(monkeypatch, runner_class):
+    """Make the graph captures of `runner_class`'s runs raise a RuntimeError before capture_begin (slam/graph_run.capture): nothing reaches
+    the HIP runtime; the other kinds of run capture as usual."""
+    from slam import graph_run
+    capture = graph_run.capture
+
+    def failing(backend, runner, options):
+        if isinstance(runner, runner_class):
+            raise RuntimeError(f"test: no capture for {runner_class.__name__}")
+        return capture(backend, runner, options)
+    monkeypatch.setattr(graph_run, "capture", failing)
+
+
+def test_static_mapping_graph_run_whose_capture_fails_is_finished_eagerly(monkeypatch):
+    """slam/graph_run.replay_run's capture-failure path for map_static: the run is undone to what its warm-up left and finished eagerly, no
+    later run captures (a failed static capture switches every kind off), and the outcome is bit-identical to the eager loop."""
+    from slam.mapping_graph import MappingGraph
+    _failing_capture(monkeypatch, MappingGraph)
+    calls = (10, 20, 20)
+    eager, window = _map_static_outcome(False, calls)
+    graph, _ = _map_static_outcome(True, calls, mode=True)
+    st = graph[-1]["graph_stats"]
+    assert st is not None and st["failed"] >= 1 and st["replays"] == 0, st
+    diffs = [_first_difference(e, g, window) for e, g in zip(eager, graph)]
+    assert diffs == [None] * len(diffs), diffs
+
+
+def test_initialize_map_graph_run_whose_capture_fails_is_finished_eagerly(monkeypatch):
+    """The capture-failure path for initialize_map's runs (mapping_graph.InitGraph): undone to the warm-up, finished by the eager loop; the
+    view's accumulated camera gradients survive the undo. Bit-identical to the eager loop."""
+    from slam.mapping_graph import InitGraph
+    _failing_capture(monkeypatch, InitGraph)
+    a, steps_a, count_a, stats = _initialisation_outcome(True, tracking_graph=False)
+    assert stats["failed"] >= 1 and stats["replays"] == 0, stats
+    b, steps_b, count_b, _ = _initialisation_outcome(False, tracking_graph=False)
+    assert steps_a == steps_b and count_a == count_b and len(a) == len(b)
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert x.shape == y.shape and torch.equal(x, y), (i, tuple(x.shape), tuple(y.shape))
+
+
+@pytest.mark.parametrize("runner, kind", [("DynamicMapping", "dynamic_graph"), ("NetworkInit", "network_init_graph")])
+def test_dynamic_graph_run_whose_capture_fails_is_finished_directly(monkeypatch, runner, kind):
+    """The capture-failure path for the dynamic mapping call's runs and initialize_network's: undone to the warm-up, finished by direct
+    execution; the SLAM run ends exactly where the directly executed one ends."""
+    from slam import dynamic_graph
+    _failing_capture(monkeypatch, getattr(dynamic_graph, runner))
+    a = _short_dynamic_run(mapping_graph=True, tracking_graph=False)
+    stats = dict(getattr(a[3].backend, f"{kind}_stats"))
+    assert stats["failed"] >= 1 and stats["replays"] == 0, stats
+    b = _directly_executed_dynamic_run()
+    assert a[0]["gaussians"] == b[0]["gaussians"] and a[0]["keyframes"] == b[0]["keyframes"]
+    for name, xs, ys in (("gaussians", a[1], b[1]), ("network", a[2], b[2])):
+        for i, (x, y) in enumerate(zip(xs, ys)):
+            assert x.shape == y.shape and torch.equal(x, y), (name, i, float((x - y).abs().max()))
+    assert a[0]["ate_rmse"] == b[0]["ate_rmse"] and a[0]["before_opt"]["mean_psnr"] == b[0]["before_opt"]["mean_psnr"]
+
+
+def test_graph_run_whose_capture_fails_raises_in_strict_mode(monkeypatch):
+    """Training.mapping_graph = "strict": a failed capture propagates (once, after the capture options and the snapshot are restored) and is
+    counted. capture_options puts the previous option values back however its block is left."""
+    from diff_gaussian_rasterization import _C
+    from slam import graph_run
+    from slam.mapping_graph import MappingGraph
+    before = _C.set_option("cap_margin_permille", -1)
+    with pytest.raises(ValueError):
+        with graph_run.capture_options(cap_margin_permille=before + 7):
+            assert _C.set_option("cap_margin_permille", -1) == before + 7
+            raise ValueError
+    assert _C.set_option("cap_margin_permille", -1) == before
+    _failing_capture(monkeypatch, MappingGraph)
+    slam, window = _mapping_state(n_kf=7, gaussian_update_every=30, gaussian_update_offset=12, mapping_graph="strict")
+    be = slam.backend
+    with pytest.raises(RuntimeError, match="no capture for MappingGraph"):
+        be.map_static(window, iters=10)
+    assert be.graph_stats["failed"] == 1 and be.graph_stats["replays"] == 0 and not be._graphs_enabled(), be.graph_stats
 
 
 def _dynamic_shard_worker(rank, world, port, ret):
