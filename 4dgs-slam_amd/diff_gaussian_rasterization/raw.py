@@ -36,9 +36,11 @@ def _f32(t, name, keep):
     return tc.data_ptr()
 
 
-def _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, keep, gather=None):
+def _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, keep, gather=None, flow=None):
+    """The gsr_raw_inputs descriptor. A flow render (render_flow) has no colours: f_dc and f_rest are None, and flow = (d_xyz2, proj1,
+    proj2) puts the second camera on the descriptor of a single-view call (the multi-view call keeps it on each gsr_view)."""
     for t, name in ((xyz, "_xyz"), (log_scales, "_scaling"), (raw_rot, "_rotation"), (logit_opacity, "_opacity"), (f_dc, "_features_dc")):
-        if t.dtype != torch.float32:
+        if t is not None and t.dtype != torch.float32:
             raise RuntimeError(f"{name} must be float32, got {t.dtype}")
     if dyn_slot is not None and dyn_slot.dtype != torch.int32:
         raise RuntimeError("dyn_slot must be int32")
@@ -50,6 +52,9 @@ def _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, d
     if gather is not None and gather.dtype != torch.int32:
         raise RuntimeError("gather must be int32")
     d.gather = _f32(gather, "gather", keep)
+    if flow is not None:
+        dx2, proj1, proj2 = flow
+        d.flow_dx2, d.flow_proj1, d.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
     return d
 
 
@@ -86,6 +91,40 @@ def _targets(ps, M):
     return out
 
 
+def _forward_raw(rs, desc, keep, P, D, M, dev):
+    """gsr_forward_raw: the five outputs (color, radii, depth, opacity, n_touched), num_rendered and the geometry, binning and image
+    buffers the backward pass reads."""
+    H, W = int(rs.image_height), int(rs.image_width)
+    img = torch.empty((_C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
+    color, depth, opacity = img[:_C.NUM_CHANNELS], img[_C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[_C.NUM_CHANNELS + 1:]
+    ints = torch.empty((2, P), dtype=torch.int32, device=dev)
+    radii, n_touched = ints[0], ints[1]
+    geom, binning, imgbuf = _C._Arena(dev), _C._Arena(dev), _C._Arena(dev)
+    lib = _C.load_library()
+    with torch.cuda.device(dev):
+        rc = lib.gsr_forward_raw(
+            geom.cb, None, binning.cb, None, imgbuf.cb, None, P, D, M, _f32(rs.bg, "bg", keep), W, H, C.byref(desc), float(rs.scale_modifier),
+            _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep), _f32(rs.campos, "campos", keep),
+            float(rs.tanfovx), float(rs.tanfovy), color.data_ptr(), depth.data_ptr(), opacity.data_ptr(), radii.data_ptr(),
+            n_touched.data_ptr(), int(bool(rs.debug)), _C._stream(dev))
+    return (color, radii, depth, opacity, n_touched), rc, (geom.tensor, binning.tensor, imgbuf.tensor)
+
+
+def _backward_raw(ctx, desc, keep, P, D, M, radii, state, g_color, g_depth, g_m2d, out, tau, flags):
+    """gsr_backward_raw of the forward call ctx recorded (ctx.rs, ctx.num_rendered; state: its geometry, binning and image buffers).
+    The gradients go to g_m2d, tau and the pointers of out."""
+    rs, dev = ctx.rs, radii.device
+    H, W = int(rs.image_height), int(rs.image_width)
+    lib = _C.load_library()
+    with torch.cuda.device(dev):
+        lib.gsr_backward_raw(
+            P, D, M, int(ctx.num_rendered), _f32(rs.bg, "bg", keep), W, H, C.byref(desc), float(rs.scale_modifier),
+            _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep), _f32(rs.projmatrix_raw, "projmatrix_raw", keep),
+            _f32(rs.campos, "campos", keep), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(), *(t.data_ptr() for t in state),
+            _f32(g_color.to(torch.float32), "dL_dcolor", keep), _f32(g_depth.to(torch.float32), "dL_ddepth", keep), g_m2d.data_ptr(),
+            C.byref(out), tau.data_ptr(), int(bool(rs.debug)) | flags, _C._stream(dev))
+
+
 class _RasterizeGaussiansRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, theta, rho, rs, gather=None):
@@ -118,28 +157,15 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, radii, geom_t, bin_t, img_t)
             ctx.mark_non_differentiable(radii, n_touched)
             return color, radii, depth, opacity, n_touched
-        lib = _C.load_library()
-        P, H, W = int(xyz.shape[0] if gather is None else gather.shape[0]), int(rs.image_height), int(rs.image_width)
+        P = int(xyz.shape[0] if gather is None else gather.shape[0])
         M = 1 + (int(f_rest.shape[1]) if f_rest is not None and f_rest.numel() else 0)
-        img = torch.empty((_C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
-        color, depth, opacity = img[:_C.NUM_CHANNELS], img[_C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[_C.NUM_CHANNELS + 1:]
-        ints = torch.empty((2, P), dtype=torch.int32, device=dev)
-        radii, n_touched = ints[0], ints[1]
-        geom, binning, imgbuf = _C._Arena(dev), _C._Arena(dev), _C._Arena(dev)
         keep = []
         desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, keep, gather)
-        with torch.cuda.device(dev):
-            rc = lib.gsr_forward_raw(
-                geom.cb, None, binning.cb, None, imgbuf.cb, None, P, int(rs.sh_degree), M, _f32(rs.bg, "bg", keep), W, H,
-                C.byref(desc), float(rs.scale_modifier), _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep),
-                _f32(rs.campos, "campos", keep), float(rs.tanfovx), float(rs.tanfovy),
-                color.data_ptr(), depth.data_ptr(), opacity.data_ptr(), radii.data_ptr(), n_touched.data_ptr(),
-                int(bool(rs.debug)), _C._stream(dev))
-        ctx.num_rendered, ctx.M = rc, M
-        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, radii,
-                              geom.tensor, binning.tensor, imgbuf.tensor)
-        ctx.mark_non_differentiable(radii, n_touched)
-        return color, radii, depth, opacity, n_touched
+        outs, ctx.num_rendered, state = _forward_raw(rs, desc, keep, P, int(rs.sh_degree), M, dev)
+        ctx.M = M
+        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, dx, ds, dr, outs[1], *state)
+        ctx.mark_non_differentiable(outs[1], outs[4])
+        return outs
 
     @staticmethod
     def backward(ctx, g_color, _g_radii, g_depth, _g_opacity, _g_touched):
@@ -186,9 +212,6 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                     opt(g_dx, dx) if g_dx is not None else None, opt(g_ds, ds) if g_ds is not None else None, opt(g_dr, dr) if g_dr is not None else None,
                     _pose_grad(tau[3:], th_shape) if th_shape is not None else None,
                     _pose_grad(tau[:3], rho_shape) if rho_shape is not None else None, None, None)
-        lib = _C.load_library()
-        g_color = g_color if g_color.dtype == torch.float32 else g_color.to(torch.float32)
-        g_depth = g_depth if g_depth.dtype == torch.float32 else g_depth.to(torch.float32)
         # one allocation; parameter order of the optimizer (gaussian_model.py:404-434), then the screen-space gradient
         widths = [3, 3, 3 * (M - 1), 1, S, 4, 3]
         if targets is not None or pose_only:
@@ -215,14 +238,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             out.features_dc, out.features_rest = g_fdc.data_ptr(), (g_frest.data_ptr() if M > 1 else None)
             out.dx, out.ds, out.dr = (g_dx.data_ptr() if g_dx is not None else None, g_ds.data_ptr() if g_ds is not None else None,
                                       g_dr.data_ptr() if g_dr is not None else None)
-        with torch.cuda.device(dev):
-            lib.gsr_backward_raw(
-                P if gather is None else int(gather.shape[0]), int(rs.sh_degree), M, int(ctx.num_rendered), _f32(rs.bg, "bg", keep), W, H, C.byref(desc), float(rs.scale_modifier),
-                _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep), _f32(rs.projmatrix_raw, "projmatrix_raw", keep),
-                _f32(rs.campos, "campos", keep), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(),
-                geom.data_ptr(), binning.data_ptr(), imgbuf.data_ptr(), _f32(g_color, "dL_dcolor", keep), _f32(g_depth, "dL_ddepth", keep),
-                g_m2d.data_ptr(), C.byref(out), tau.data_ptr(), int(bool(rs.debug)) | (2 if targets is not None else 0) | (4 if pose_only else 0),
-                _C._stream(dev))
+        _backward_raw(ctx, desc, keep, P if gather is None else int(gather.shape[0]), int(rs.sh_degree), M, radii, (geom, binning, imgbuf),
+                      g_color, g_depth, g_m2d, out, tau, (2 if targets is not None else 0) | (4 if pose_only else 0))
         if targets is not None or pose_only:
             g_xyz = g_ls = g_rot = g_logit = g_fdc = g_frest = None
         if pose_only:
@@ -296,39 +313,23 @@ class _RasterizeFlowRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, rs):
         _C._require_device(xyz, "_xyz")
-        dev = xyz.device
-        lib = _C.load_library()
-        P, H, W = int(xyz.shape[0]), int(rs.image_height), int(rs.image_width)
-        img = torch.empty((_C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
-        color, depth, opacity = img[:_C.NUM_CHANNELS], img[_C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[_C.NUM_CHANNELS + 1:]
-        ints = torch.empty((2, P), dtype=torch.int32, device=dev)
-        radii, n_touched = ints[0], ints[1]
-        geom, binning, imgbuf = _C._Arena(dev), _C._Arena(dev), _C._Arena(dev)
         keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, xyz, None, dyn_slot, dx1, ds, dr, keep)
-        desc.features_dc = None
-        desc.flow_dx2, desc.flow_proj1, desc.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
-        with torch.cuda.device(dev):
-            rc = lib.gsr_forward_raw(
-                geom.cb, None, binning.cb, None, imgbuf.cb, None, P, 0, 1, _f32(rs.bg, "bg", keep), W, H, C.byref(desc), float(rs.scale_modifier),
-                _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep), _f32(rs.campos, "campos", keep),
-                float(rs.tanfovx), float(rs.tanfovy), color.data_ptr(), depth.data_ptr(), opacity.data_ptr(), radii.data_ptr(),
-                n_touched.data_ptr(), int(bool(rs.debug)), _C._stream(dev))
+        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, dx1, ds, dr, keep, flow=(dx2, proj1, proj2))
+        outs, rc, state = _forward_raw(rs, desc, keep, int(xyz.shape[0]), 0, 1, xyz.device)
         ctx.rs, ctx.num_rendered = rs, rc
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, radii, geom.tensor, binning.tensor, imgbuf.tensor)
-        ctx.mark_non_differentiable(radii, n_touched)
-        return color, radii, depth, opacity, n_touched
+        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, outs[1], *state)
+        ctx.mark_non_differentiable(outs[1], outs[4])
+        return outs
 
     @staticmethod
     def backward(ctx, g_color, _g_radii, g_depth, _g_opacity, _g_touched):
         rs = ctx.rs
-        (xyz, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, radii, geom, binning, imgbuf) = ctx.saved_tensors
+        (xyz, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, radii, *state) = ctx.saved_tensors
         dev = xyz.device
-        lib = _C.load_library()
         P, H, W, S = int(xyz.shape[0]), int(rs.image_height), int(rs.image_width), int(log_scales.shape[-1])
-        g_color = _zero_cotangent(3, H, W, dev) if g_color is None else g_color.to(torch.float32)
-        g_depth = _zero_cotangent(1, H, W, dev) if g_depth is None else g_depth.to(torch.float32)
+        g_color = _zero_cotangent(3, H, W, dev) if g_color is None else g_color
+        g_depth = _zero_cotangent(1, H, W, dev) if g_depth is None else g_depth
         # xyz | scratch for the constants' gradients the kernel writes anyway (log-scale, rotation, opacity) | means2D | tau
         flat = torch.empty((P * (3 + S + 4 + 1 + 3) + 6,), dtype=torch.float32, device=dev)
         o = 0
@@ -341,20 +342,12 @@ class _RasterizeFlowRaw(torch.autograd.Function):
         tau = flat[o:o + 6]
         g_dx1, g_dx2, g_ds, g_dr = _zero_grads_like(dx1, dx2, ds, dr)
         keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, xyz, None, dyn_slot, dx1, ds, dr, keep)
-        desc.features_dc = None
-        desc.flow_dx2, desc.flow_proj1, desc.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
+        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, dx1, ds, dr, keep, flow=(dx2, proj1, proj2))
         out = gsr_raw_grads()
         out.xyz, out.log_scales, out.raw_rotations, out.logit_opacity = g_xyz.data_ptr(), g_ls.data_ptr(), g_rot.data_ptr(), g_logit.data_ptr()
         p = lambda t: None if t is None else t.data_ptr()
         out.dx, out.ds, out.dr, out.dx2 = p(g_dx1), p(g_ds), p(g_dr), p(g_dx2)
-        with torch.cuda.device(dev):
-            lib.gsr_backward_raw(
-                P, 0, 1, int(ctx.num_rendered), _f32(rs.bg, "bg", keep), W, H, C.byref(desc), float(rs.scale_modifier),
-                _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep), _f32(rs.projmatrix_raw, "projmatrix_raw", keep),
-                _f32(rs.campos, "campos", keep), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(), geom.data_ptr(), binning.data_ptr(),
-                imgbuf.data_ptr(), _f32(g_color, "dL_dcolor", keep), _f32(g_depth, "dL_ddepth", keep), g_m2d.data_ptr(), C.byref(out),
-                tau.data_ptr(), int(bool(rs.debug)), _C._stream(dev))
+        _backward_raw(ctx, desc, keep, P, 0, 1, radii, state, g_color, g_depth, g_m2d, out, tau, 0)
         # inputs: xyz, means2D, log_scales, raw_rot, logit_opacity, dyn_slot, dx1, dx2, ds, dr, proj1, proj2, rs
         return (g_xyz, g_m2d, None, None, None, None, g_dx1, g_dx2, g_ds, g_dr, None, None, None)
 

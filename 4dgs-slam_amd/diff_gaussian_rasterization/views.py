@@ -44,6 +44,116 @@ def _camera_lists(settings):
     return ([rs.viewmatrix for rs in settings], [rs.projmatrix for rs in settings], [rs.projmatrix_raw for rs in settings], [rs.campos for rs in settings])
 
 
+def _forward_views(ctx, settings, xyz, D, M, desc, keep, per_view):
+    """gsr_forward_views: fills every gsr_view's camera, output and allocation-id fields; per_view(v, w) adds view v's delta (and flow)
+    fields. Returns (img [V, C+2, H, W], ints [V, 2, P], num_rendered per view, state: geometry, binning, image buffer per view)."""
+    dev, V, rs0 = xyz.device, len(settings), settings[0]
+    P, H, W = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width)
+    img = torch.empty((V, _C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
+    ints = torch.empty((V, 2, P), dtype=torch.int32, device=dev)
+    views = (gsr_view * V)()
+    base = id(ctx) & 0x3FFFFFFFFFFF
+    holders = []
+    lib = _C.load_library()
+    for v in range(V):
+        rs, w = settings[v], views[v]
+        w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
+        w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
+        per_view(v, w)
+        w.out_color, w.out_depth = img[v, :_C.NUM_CHANNELS].data_ptr(), img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1].data_ptr()
+        w.out_opacity, w.radii, w.n_touched = img[v, _C.NUM_CHANNELS + 1:].data_ptr(), ints[v, 0].data_ptr(), ints[v, 1].data_ptr()
+        for k in range(3):
+            holders.append({"dev": dev, "t": None})
+            _arenas[base + 3 * v + k] = holders[-1]
+        w.geometry_user, w.binning_user, w.image_user = base + 3 * v, base + 3 * v + 1, base + 3 * v + 2
+    try:
+        with torch.cuda.device(dev):
+            lib.gsr_forward_views(V, views, _alloc_cb, _alloc_cb, _alloc_cb, P, D, M, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc),
+                                  float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(bool(rs0.debug)), _C._stream(dev))
+    finally:
+        for u in range(base, base + 3 * V):
+            _arenas.pop(u, None)
+    return img, ints, [int(w.num_rendered) for w in views], [h["t"] for h in holders]
+
+
+def _outputs(ctx, img, ints):
+    """The five outputs per view: color, radii, depth, opacity, n_touched."""
+    outs = []
+    for v in range(ctx.V):
+        outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
+    ctx.mark_non_differentiable(*outs[1::5], *outs[4::5])      # every view's radii and n_touched, in ONE call (a call replaces the set)
+    return tuple(outs)
+
+
+def _cotangents(grads, H, W, dev):
+    """dL/dcolor and dL/ddepth per view, a shared zero image where the loss did not use that output."""
+    return ([_zero_cotangent(3, H, W, dev) if g is None else g for g in grads[0::5]],
+            [_zero_cotangent(1, H, W, dev) if g is None else g for g in grads[2::5]])
+
+
+def _backward_views(ctx, grads, xyz, S, D, M, desc, keep, out, ints, state, flags, per_view):
+    """gsr_backward_views of the forward call ctx recorded: fills every gsr_view's camera, state, cotangent and per-view output fields;
+    per_view(v, w) adds view v's delta (and flow) fields and their gradients. The parameter gradients go to the pointers of out (none
+    with GSR_BACKWARD_POSE_ONLY, flags & 4). Returns per_view_out [V, P*3+6]: the screen-space gradient and the pose sum of every view."""
+    V, settings, rs0 = ctx.V, ctx.settings, ctx.settings[0]
+    dev, P, H, W = xyz.device, int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width)
+    lib = _C.load_library()
+    per_view_out = torch.empty((V, P * 3 + 6), dtype=torch.float32, device=dev)
+    views = (gsr_view * V)()
+    for v, (g_color, g_depth) in enumerate(zip(*_cotangents(grads, H, W, dev))):
+        rs, w = settings[v], views[v]
+        w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
+        w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
+        per_view(v, w)
+        w.radii = ints[v, 0].data_ptr()
+        w.geom_buffer, w.binning_buffer, w.image_buffer = state[3 * v].data_ptr(), state[3 * v + 1].data_ptr(), state[3 * v + 2].data_ptr()
+        w.num_rendered = ctx.num_rendered[v]
+        w.dL_dcolor, w.dL_ddepth = _f32(g_color.to(torch.float32), "dL_dcolor", keep), _f32(g_depth.to(torch.float32), "dL_ddepth", keep)
+        w.dL_dmean2D, w.dL_dtau_sum = per_view_out[v, :P * 3].data_ptr(), per_view_out[v, P * 3:].data_ptr()
+    scratch = None if flags & 4 else torch.empty((int(lib.gsr_views_scratch_size(V, P, M, S)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib.gsr_backward_views(V, views, P, D, M, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc), float(rs0.scale_modifier),
+                               float(rs0.tanfovx), float(rs0.tanfovy), C.byref(out), None if scratch is None else scratch.data_ptr(),
+                               int(bool(rs0.debug)) | flags, _C._stream(dev))
+    return per_view_out
+
+
+def _param_grads(out, targets, P, M, S, dev):
+    """Points out's six parameter gradients at the accumulation targets, or else at views of one new allocation, which are returned
+    (optimizer order: xyz, f_dc, f_rest, opacity, scaling, rotation)."""
+    own = None
+    if targets is not None:
+        g = [t_.view(-1) for t_ in targets]
+    else:
+        widths = [3, 3, 3 * (M - 1), 1, S, 4]
+        g = own = torch.empty((P * sum(widths),), dtype=torch.float32, device=dev).split([P * w_ for w_ in widths])
+    out.xyz, out.features_dc, out.features_rest = g[0].data_ptr(), g[1].data_ptr(), (g[2].data_ptr() if M > 1 else None)
+    out.logit_opacity, out.log_scales, out.raw_rotations = g[3].data_ptr(), g[4].data_ptr(), g[5].data_ptr()
+    return own
+
+
+def _param_results(g, P, M, S, logit_shape):
+    """The parameter gradients g (optimizer order) as the backward pass returns them: xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest."""
+    return [g[0].view(P, 3), g[4].view(P, S), g[5].view(P, 4), g[3].view(logit_shape), g[1].view(P, 1, 3), g[2].view(P, M - 1, 3) if M > 1 else None]
+
+
+def _pose_shapes(thetas, rhos):
+    """Per view the shapes of theta and rho, None for a view without one."""
+    return [(tuple(th.shape) if isinstance(th, torch.Tensor) else None, tuple(rh.shape) if isinstance(rh, torch.Tensor) else None)
+            for th, rh in zip(thetas, rhos)]
+
+
+def _view_grads(per_view_out, P, pose_shapes, delta_grads):
+    """The gradients of every view's inputs: screen-space gradient, the view's delta gradients (delta_grads[v]), then theta and rho
+    from the view's pose sum (None where the view has no such input)."""
+    res = []
+    for v, ((th_shape, rho_shape), gd) in enumerate(zip(pose_shapes, delta_grads)):
+        tau = per_view_out[v, P * 3:]
+        res += [per_view_out[v, :P * 3].view(P, 3), *gd, _pose_grad(tau[3:], th_shape) if th_shape is not None else None,
+                _pose_grad(tau[:3], rho_shape) if rho_shape is not None else None]
+    return res
+
+
 class _RasterizeViewsRaw(torch.autograd.Function):
     """inputs: xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, settings (list), then six per view:
     means2D, dx, ds, dr, theta, rho. outputs: five per view: color, radii, depth, opacity, n_touched."""
@@ -51,76 +161,37 @@ class _RasterizeViewsRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, settings, *per_view):
         _C._require_device(xyz, "_xyz")
-        lib = _C.load_library()
         dev, V = xyz.device, len(settings)
         rs0 = settings[0]
-        P, H, W = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width)
         M = 1 + (int(f_rest.shape[1]) if f_rest is not None and f_rest.numel() else 0)
         ctx.settings, ctx.V, ctx.M = settings, V, M
         ctx.set_materialize_grads(False)
         ctx.acc_params = _acc_params(xyz, f_dc, f_rest, logit_opacity, log_scales, raw_rot)
-        ctx.pose_shapes = [(tuple(per_view[6 * v + 4].shape) if isinstance(per_view[6 * v + 4], torch.Tensor) else None,
-                            tuple(per_view[6 * v + 5].shape) if isinstance(per_view[6 * v + 5], torch.Tensor) else None) for v in range(V)]
+        ctx.pose_shapes = _pose_shapes(per_view[4::6], per_view[5::6])
         glue = _glue()
         if glue is not None:
-            cams = _camera_lists(settings)
             with torch.cuda.device(dev):
                 img, ints, rendered, state = glue.rasterize_views_forward(
-                    rs0.bg, xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest if (f_rest is not None and f_rest.numel()) else None, dyn_slot, *cams,
-                    [per_view[6 * v + 1] for v in range(V)], [per_view[6 * v + 2] for v in range(V)], [per_view[6 * v + 3] for v in range(V)], [], [], [],
-                    float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), H, W, int(rs0.sh_degree), bool(rs0.debug), _C._stream(dev), [])
-            ctx.num_rendered = [int(r) for r in rendered]
-            deltas = [per_view[6 * v + k] for v in range(V) for k in (1, 2, 3)]
-            ctx.n_state = len(state)
-            ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, ints, *state, *deltas)
-            outs = []
-            for v in range(V):
-                outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
-            ctx.mark_non_differentiable(*[outs[5 * v + k] for v in range(V) for k in (1, 4)])      # every view's radii and n_touched, in ONE call (a call replaces the set)
-            return tuple(outs)
-        img = torch.empty((V, _C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
-        ints = torch.empty((V, 2, P), dtype=torch.int32, device=dev)
-        keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, None, None, None, keep)
-        views = (gsr_view * V)()
-        base = id(ctx) & 0x3FFFFFFFFFFF
-        holders = []
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            _, dx, ds, dr = per_view[6 * v: 6 * v + 4]
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
-            w.dx, w.ds, w.dr = _f32(dx, "dx", keep), _f32(ds, "ds", keep), _f32(dr, "dr", keep)
-            w.out_color, w.out_depth = img[v, :_C.NUM_CHANNELS].data_ptr(), img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1].data_ptr()
-            w.out_opacity, w.radii, w.n_touched = img[v, _C.NUM_CHANNELS + 1:].data_ptr(), ints[v, 0].data_ptr(), ints[v, 1].data_ptr()
-            hs = [{"dev": dev, "t": None} for _ in range(3)]
-            holders.append(hs)
-            for k, h in enumerate(hs):
-                _arenas[base + 3 * v + k] = h
-            w.geometry_user, w.binning_user, w.image_user = base + 3 * v, base + 3 * v + 1, base + 3 * v + 2
-        try:
-            with torch.cuda.device(dev):
-                lib.gsr_forward_views(V, views, _alloc_cb, _alloc_cb, _alloc_cb, P, int(rs0.sh_degree), M, _f32(rs0.bg, "bg", keep), W, H,
-                                      C.byref(desc), float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(bool(rs0.debug)),
-                                      _C._stream(dev))
-        finally:
-            for v in range(V):
-                for k in range(3):
-                    _arenas.pop(base + 3 * v + k, None)
-        ctx.num_rendered = [int(views[v].num_rendered) for v in range(V)]
-        state = [holders[v][k]["t"] for v in range(V) for k in range(3)]          # geometry, binning, image per view
-        deltas = [per_view[6 * v + k] for v in range(V) for k in (1, 2, 3)]
+                    rs0.bg, xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest if (f_rest is not None and f_rest.numel()) else None, dyn_slot,
+                    *_camera_lists(settings), list(per_view[1::6]), list(per_view[2::6]), list(per_view[3::6]), [], [], [],
+                    float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(rs0.image_height), int(rs0.image_width),
+                    int(rs0.sh_degree), bool(rs0.debug), _C._stream(dev), [])
+        else:
+            keep = []
+            desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, None, None, None, keep)
+
+            def deltas(v, w):
+                _, dx, ds, dr = per_view[6 * v: 6 * v + 4]
+                w.dx, w.ds, w.dr = _f32(dx, "dx", keep), _f32(ds, "ds", keep), _f32(dr, "dr", keep)
+            img, ints, rendered, state = _forward_views(ctx, settings, xyz, int(rs0.sh_degree), M, desc, keep, deltas)
+        ctx.num_rendered = [int(r) for r in rendered]
         ctx.n_state = len(state)
-        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, ints, *state, *deltas)
-        outs = []
-        for v in range(V):
-            outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
-        ctx.mark_non_differentiable(*[outs[5 * v + k] for v in range(V) for k in (1, 4)])
-        return tuple(outs)
+        ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, ints, *state,
+                              *[per_view[6 * v + k] for v in range(V) for k in (1, 2, 3)])
+        return _outputs(ctx, img, ints)
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _C.load_library()
         V, M, settings = ctx.V, ctx.M, ctx.settings
         saved = ctx.saved_tensors
         xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, ints = saved[:8]
@@ -130,92 +201,35 @@ class _RasterizeViewsRaw(torch.autograd.Function):
         rs0 = settings[0]
         P, H, W, S = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width), int(log_scales.shape[-1])
         targets = _targets(ctx.acc_params, M) if ctx.acc_params is not None else None
-        param_idx = (0, 1, 2, 3, 4, 5)
         delta_needed = any(ctx.needs_input_grad[8 + 6 * v + k] for v in range(V) for k in (1, 2, 3))
-        pose_only = not any(ctx.needs_input_grad[k] for k in param_idx) and not delta_needed
+        pose_only = not any(ctx.needs_input_grad[k] for k in range(6)) and not delta_needed
         if pose_only:
             targets = None
         glue = _glue()
         if glue is not None:
-            cot = lambda g_, c: _zero_cotangent(c, H, W, dev) if g_ is None else g_
             with torch.cuda.device(dev):
                 pg, per_view_out, dl = glue.rasterize_views_backward(
                     rs0.bg, xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest if (f_rest is not None and f_rest.numel()) else None, dyn_slot,
-                    *_camera_lists(settings), [deltas[3 * v] for v in range(V)], [deltas[3 * v + 1] for v in range(V)], [deltas[3 * v + 2] for v in range(V)],
-                    [], [], [], float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), H, W, int(rs0.sh_degree), ints, list(state),
-                    ctx.num_rendered, [cot(grads[5 * v], 3) for v in range(V)], [cot(grads[5 * v + 2], 1) for v in range(V)],
-                    [t_.view(-1) for t_ in targets] if targets is not None else [], targets is not None, pose_only, bool(rs0.debug), _C._stream(dev))
-            if targets is not None or pose_only:
-                res = [None] * 8
-            else:
-                res = [pg[0].view(P, 3), pg[4].view(P, S), pg[5].view(P, 4), pg[3].view(logit_opacity.shape), pg[1].view(P, 1, 3),
-                       pg[2].view(P, M - 1, 3) if M > 1 else None, None, None]
-            for v in range(V):
-                th_shape, rho_shape = ctx.pose_shapes[v]
-                tau = per_view_out[v, P * 3:]
-                res += [per_view_out[v, :P * 3].view(P, 3), dl[4 * v], dl[4 * v + 2], dl[4 * v + 3],
-                        _pose_grad(tau[3:], th_shape) if th_shape is not None else None, _pose_grad(tau[:3], rho_shape) if rho_shape is not None else None]
-            return tuple(res)
-        keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, None, None, None, keep)
-        widths = [3, 3, 3 * (M - 1), 1, S, 4]
-        if targets is not None or pose_only:
-            own = None
-            gviews = [t_.view(-1) for t_ in targets] if targets is not None else [None] * 6
+                    *_camera_lists(settings), list(deltas[0::3]), list(deltas[1::3]), list(deltas[2::3]), [], [], [],
+                    float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), H, W, int(rs0.sh_degree), ints, list(state),
+                    ctx.num_rendered, *_cotangents(grads, H, W, dev), [t_.view(-1) for t_ in targets] if targets is not None else [],
+                    targets is not None, pose_only, bool(rs0.debug), _C._stream(dev))
+            delta_grads = zip(dl[0::4], dl[2::4], dl[3::4])
         else:
-            own = torch.empty((P * sum(widths),), dtype=torch.float32, device=dev)
-            gviews, o = [], 0
-            for w_ in widths:
-                gviews.append(own[o:o + P * w_])
-                o += P * w_
-        out = gsr_raw_grads()
-        if not pose_only:
-            out.xyz, out.features_dc, out.features_rest = gviews[0].data_ptr(), gviews[1].data_ptr(), (gviews[2].data_ptr() if M > 1 else None)
-            out.logit_opacity, out.log_scales, out.raw_rotations = gviews[3].data_ptr(), gviews[4].data_ptr(), gviews[5].data_ptr()
-        per_view_out = torch.empty((V, P * 3 + 6), dtype=torch.float32, device=dev)      # screen-space gradient + pose sum per view
-        views = (gsr_view * V)()
-        delta_grads = []
-        zero_deltas = [None] * (3 * V) if pose_only else _zero_grads_like(*deltas[:3 * V])      # one allocation, one fill for all views
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            g_color, g_depth = grads[5 * v], grads[5 * v + 2]
-            if g_color is None:
-                g_color = _zero_cotangent(3, H, W, dev)
-            if g_depth is None:
-                g_depth = _zero_cotangent(1, H, W, dev)
-            dx, ds, dr = deltas[3 * v: 3 * v + 3]
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
-            w.dx, w.ds, w.dr = _f32(dx, "dx", keep), _f32(ds, "ds", keep), _f32(dr, "dr", keep)
-            w.radii = ints[v, 0].data_ptr()
-            w.geom_buffer, w.binning_buffer, w.image_buffer = state[3 * v].data_ptr(), state[3 * v + 1].data_ptr(), state[3 * v + 2].data_ptr()
-            w.num_rendered = ctx.num_rendered[v]
-            w.dL_dcolor, w.dL_ddepth = _f32(g_color.to(torch.float32), "dL_dcolor", keep), _f32(g_depth.to(torch.float32), "dL_ddepth", keep)
-            w.dL_dmean2D, w.dL_dtau_sum = per_view_out[v, :P * 3].data_ptr(), per_view_out[v, P * 3:].data_ptr()
-            gd = tuple(zero_deltas[3 * v: 3 * v + 3])
-            delta_grads.append(gd)
-            w.ddx, w.dds, w.ddr = (None if g is None else g.data_ptr() for g in gd)
-        scratch = None
-        if not pose_only:
-            scratch = torch.empty((int(lib.gsr_views_scratch_size(V, P, M, S)),), dtype=torch.uint8, device=dev)
-        flags = int(bool(rs0.debug)) | (2 if targets is not None else 0) | (4 if pose_only else 0)
-        with torch.cuda.device(dev):
-            lib.gsr_backward_views(V, views, P, int(rs0.sh_degree), M, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc), float(rs0.scale_modifier),
-                                   float(rs0.tanfovx), float(rs0.tanfovy), C.byref(out), None if scratch is None else scratch.data_ptr(), flags,
-                                   _C._stream(dev))
-        if own is not None:
-            g_xyz, g_fdc, g_frest = gviews[0].view(P, 3), gviews[1].view(P, 1, 3), (gviews[2].view(P, M - 1, 3) if M > 1 else None)
-            g_logit, g_ls, g_rot = gviews[3].view(logit_opacity.shape), gviews[4].view(P, S), gviews[5].view(P, 4)
-        else:
-            g_xyz = g_fdc = g_frest = g_logit = g_ls = g_rot = None
-        res = [g_xyz, g_ls, g_rot, g_logit, g_fdc, g_frest, None, None]
-        for v in range(V):
-            th_shape, rho_shape = ctx.pose_shapes[v]
-            tau = per_view_out[v, P * 3:]
-            gdx, gds, gdr = delta_grads[v]
-            res += [per_view_out[v, :P * 3].view(P, 3), gdx, gds, gdr,
-                    _pose_grad(tau[3:], th_shape) if th_shape is not None else None, _pose_grad(tau[:3], rho_shape) if rho_shape is not None else None]
-        return tuple(res)
+            keep = []
+            desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, dyn_slot, None, None, None, keep)
+            out = gsr_raw_grads()
+            pg = None if pose_only else _param_grads(out, targets, P, M, S, dev)
+            zero_deltas = [None] * (3 * V) if pose_only else _zero_grads_like(*deltas)      # one allocation, one fill for all views
+
+            def fill(v, w):
+                w.dx, w.ds, w.dr = _f32(deltas[3 * v], "dx", keep), _f32(deltas[3 * v + 1], "ds", keep), _f32(deltas[3 * v + 2], "dr", keep)
+                w.ddx, w.dds, w.ddr = (None if g is None else g.data_ptr() for g in zero_deltas[3 * v: 3 * v + 3])
+            per_view_out = _backward_views(ctx, grads, xyz, S, int(rs0.sh_degree), M, desc, keep, out, ints, state,
+                                           (2 if targets is not None else 0) | (4 if pose_only else 0), fill)
+            delta_grads = zip(zero_deltas[0::3], zero_deltas[1::3], zero_deltas[2::3])
+        res = [None] * 6 if targets is not None or pose_only else _param_results(pg, P, M, S, logit_opacity.shape)
+        return tuple(res + [None, None] + _view_grads(per_view_out, P, ctx.pose_shapes, delta_grads))
 
 
 class _RasterizeViewsNet(torch.autograd.Function):
@@ -229,10 +243,7 @@ class _RasterizeViewsNet(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, net_out, settings, *per_view):
         _C._require_device(xyz, "_xyz")
-        lib = _C.load_library()
-        dev, V = xyz.device, len(settings)
-        rs0 = settings[0]
-        P, H, W = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width)
+        V, P = len(settings), int(xyz.shape[0])
         if net_out.dtype != torch.float32 or tuple(net_out.shape) != (V, P, 10):
             raise RuntimeError(f"net_out must be float32 [{V}, {P}, 10], got {net_out.dtype} {tuple(net_out.shape)}")
         _C._require_device(net_out, "net_out")
@@ -241,114 +252,44 @@ class _RasterizeViewsNet(torch.autograd.Function):
         ctx.settings, ctx.V, ctx.M = settings, V, M
         ctx.set_materialize_grads(False)
         ctx.acc_params = _acc_params(xyz, f_dc, f_rest, logit_opacity, log_scales, raw_rot)
-        ctx.pose_shapes = [(tuple(per_view[3 * v + 1].shape) if isinstance(per_view[3 * v + 1], torch.Tensor) else None,
-                            tuple(per_view[3 * v + 2].shape) if isinstance(per_view[3 * v + 2], torch.Tensor) else None) for v in range(V)]
-        img = torch.empty((V, _C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
-        ints = torch.empty((V, 2, P), dtype=torch.int32, device=dev)
+        ctx.pose_shapes = _pose_shapes(per_view[1::3], per_view[2::3])
         keep = []
         desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, None, None, None, None, keep)
         desc.delta_mode, desc.delta_stride = 1, 10
-        views = (gsr_view * V)()
-        base = id(ctx) & 0x3FFFFFFFFFFF
-        holders = []
         net_ptr = net_out.data_ptr()
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
+
+        def rows(v, w):
             row0 = net_ptr + 4 * 10 * P * v
             w.dx, w.ds, w.dr = row0, row0 + 12, row0 + 24
-            w.out_color, w.out_depth = img[v, :_C.NUM_CHANNELS].data_ptr(), img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1].data_ptr()
-            w.out_opacity, w.radii, w.n_touched = img[v, _C.NUM_CHANNELS + 1:].data_ptr(), ints[v, 0].data_ptr(), ints[v, 1].data_ptr()
-            hs = [{"dev": dev, "t": None} for _ in range(3)]
-            holders.append(hs)
-            for k, h in enumerate(hs):
-                _arenas[base + 3 * v + k] = h
-            w.geometry_user, w.binning_user, w.image_user = base + 3 * v, base + 3 * v + 1, base + 3 * v + 2
-        try:
-            with torch.cuda.device(dev):
-                lib.gsr_forward_views(V, views, _alloc_cb, _alloc_cb, _alloc_cb, P, int(rs0.sh_degree), M, _f32(rs0.bg, "bg", keep), W, H,
-                                      C.byref(desc), float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(bool(rs0.debug)),
-                                      _C._stream(dev))
-        finally:
-            for v in range(V):
-                for k in range(3):
-                    _arenas.pop(base + 3 * v + k, None)
-        ctx.num_rendered = [int(views[v].num_rendered) for v in range(V)]
-        state = [holders[v][k]["t"] for v in range(V) for k in range(3)]
+        img, ints, ctx.num_rendered, state = _forward_views(ctx, settings, xyz, int(settings[0].sh_degree), M, desc, keep, rows)
         ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, net_out, ints, *state)
-        outs = []
-        for v in range(V):
-            outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
-        ctx.mark_non_differentiable(*[outs[5 * v + k] for v in range(V) for k in (1, 4)])
-        return tuple(outs)
+        return _outputs(ctx, img, ints)
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _C.load_library()
-        V, M, settings = ctx.V, ctx.M, ctx.settings
+        V, M = ctx.V, ctx.M
         saved = ctx.saved_tensors
         xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, net_out, ints = saved[:8]
         state = saved[8:]
         dev = xyz.device
-        rs0 = settings[0]
-        P, H, W, S = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width), int(log_scales.shape[-1])
+        P, S = int(xyz.shape[0]), int(log_scales.shape[-1])
         targets = _targets(ctx.acc_params, M) if ctx.acc_params is not None else None
         keep = []
         desc = _describe(xyz, log_scales, raw_rot, logit_opacity, f_dc, f_rest, None, None, None, None, keep)
         desc.delta_mode, desc.delta_stride = 1, 10
-        widths = [3, 3, 3 * (M - 1), 1, S, 4]
-        if targets is not None:
-            own = None
-            gviews = [t_.view(-1) for t_ in targets]
-        else:
-            own = torch.empty((P * sum(widths),), dtype=torch.float32, device=dev)
-            gviews, o = [], 0
-            for w_ in widths:
-                gviews.append(own[o:o + P * w_])
-                o += P * w_
         out = gsr_raw_grads()
-        out.xyz, out.features_dc, out.features_rest = gviews[0].data_ptr(), gviews[1].data_ptr(), (gviews[2].data_ptr() if M > 1 else None)
-        out.logit_opacity, out.log_scales, out.raw_rotations = gviews[3].data_ptr(), gviews[4].data_ptr(), gviews[5].data_ptr()
-        per_view_out = torch.empty((V, P * 3 + 6), dtype=torch.float32, device=dev)      # screen-space gradient + pose sum per view
+        own = _param_grads(out, targets, P, M, S, dev)
         g_net = torch.empty_like(net_out)             # every row is written: geometry_bwd stores zeros for the Gaussians a view does not see
-        views = (gsr_view * V)()
         net_ptr, gnet_ptr = net_out.data_ptr(), g_net.data_ptr()
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            g_color, g_depth = grads[5 * v], grads[5 * v + 2]
-            if g_color is None:
-                g_color = _zero_cotangent(3, H, W, dev)
-            if g_depth is None:
-                g_depth = _zero_cotangent(1, H, W, dev)
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
+
+        def rows(v, w):
             row0, grow0 = net_ptr + 4 * 10 * P * v, gnet_ptr + 4 * 10 * P * v
             w.dx, w.ds, w.dr = row0, row0 + 12, row0 + 24
             w.ddx, w.dds, w.ddr = grow0, grow0 + 12, grow0 + 24
-            w.radii = ints[v, 0].data_ptr()
-            w.geom_buffer, w.binning_buffer, w.image_buffer = state[3 * v].data_ptr(), state[3 * v + 1].data_ptr(), state[3 * v + 2].data_ptr()
-            w.num_rendered = ctx.num_rendered[v]
-            w.dL_dcolor, w.dL_ddepth = _f32(g_color.to(torch.float32), "dL_dcolor", keep), _f32(g_depth.to(torch.float32), "dL_ddepth", keep)
-            w.dL_dmean2D, w.dL_dtau_sum = per_view_out[v, :P * 3].data_ptr(), per_view_out[v, P * 3:].data_ptr()
-        scratch = torch.empty((int(lib.gsr_views_scratch_size(V, P, M, S)),), dtype=torch.uint8, device=dev)
-        flags = int(bool(rs0.debug)) | (2 if targets is not None else 0)
-        with torch.cuda.device(dev):
-            lib.gsr_backward_views(V, views, P, int(rs0.sh_degree), M, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc), float(rs0.scale_modifier),
-                                   float(rs0.tanfovx), float(rs0.tanfovy), C.byref(out), scratch.data_ptr(), flags, _C._stream(dev))
-        if os.environ.get("GSR_DEBUG_ZERO_ROWS"):            # development: how many (view, Gaussian) pairs receive no gradient at all
-            print("zero rows of the network cotangent:", float((g_net.abs().amax(dim=-1) == 0).float().mean()), flush=True)
-        if own is not None:
-            res = [gviews[0].view(P, 3), gviews[4].view(P, S), gviews[5].view(P, 4), gviews[3].view(logit_opacity.shape), gviews[1].view(P, 1, 3),
-                   gviews[2].view(P, M - 1, 3) if M > 1 else None, g_net, None]
-        else:
-            res = [None, None, None, None, None, None, g_net, None]
-        for v in range(V):
-            th_shape, rho_shape = ctx.pose_shapes[v]
-            tau = per_view_out[v, P * 3:]
-            res += [per_view_out[v, :P * 3].view(P, 3), _pose_grad(tau[3:], th_shape) if th_shape is not None else None,
-                    _pose_grad(tau[:3], rho_shape) if rho_shape is not None else None]
-        return tuple(res)
+        per_view_out = _backward_views(ctx, grads, xyz, S, int(ctx.settings[0].sh_degree), M, desc, keep, out, ints, state,
+                                       2 if targets is not None else 0, rows)
+        res = [None] * 6 if own is None else _param_results(own, P, M, S, logit_opacity.shape)
+        return tuple(res + [g_net, None] + _view_grads(per_view_out, P, ctx.pose_shapes, [()] * V))
 
 
 def rasterize_views_net(settings, xyz, means2D, log_scales, raw_rotations, logit_opacity, features_dc, features_rest, net_out, poses=None):
@@ -378,10 +319,8 @@ class _RasterizeFlowViewsRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, log_scales, raw_rot, logit_opacity, dyn_slot, settings, clips, *per_view):
         _C._require_device(xyz, "_xyz")
-        lib = _C.load_library()
         dev, V = xyz.device, len(settings)
         rs0 = settings[0]
-        P, H, W = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width)
         ctx.settings, ctx.V = settings, V
         clips = list(clips) if clips is not None else [None] * V      # per view: int32 [4] device tensor (gsr_view.flow_clip) or None
         for c in clips:
@@ -391,63 +330,27 @@ class _RasterizeFlowViewsRaw(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         glue = _glue()
         if glue is not None:
-            col = lambda k: [per_view[7 * v + k] for v in range(V)]
+            col = lambda k: list(per_view[k::7])
             with torch.cuda.device(dev):
                 img, ints, rendered, state = glue.rasterize_views_forward(
                     rs0.bg, xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, *_camera_lists(settings), col(1), col(3), col(4), col(2), col(5), col(6),
-                    float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), H, W, 0, bool(rs0.debug), _C._stream(dev), clips)
-            ctx.num_rendered = [int(r) for r in rendered]
-            ctx.n_state = len(state)
-            ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, dyn_slot, ints, *state, *[per_view[7 * v + k] for v in range(V) for k in range(1, 7)])
-            outs = []
-            for v in range(V):
-                outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
-            ctx.mark_non_differentiable(*[outs[5 * v + k] for v in range(V) for k in (1, 4)])      # every view's radii and n_touched, in ONE call (a call replaces the set)
-            return tuple(outs)
-        img = torch.empty((V, _C.NUM_CHANNELS + 2, H, W), dtype=torch.float32, device=dev)
-        ints = torch.empty((V, 2, P), dtype=torch.int32, device=dev)
-        keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, xyz, None, dyn_slot, None, None, None, keep)
-        desc.features_dc = None
-        views = (gsr_view * V)()
-        base = id(ctx) & 0x3FFFFFFFFFFF
-        holders = []
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            _, dx1, dx2, ds, dr, proj1, proj2 = per_view[7 * v: 7 * v + 7]
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
-            w.dx, w.ds, w.dr = _f32(dx1, "d_xyz1", keep), _f32(ds, "d_scaling1", keep), _f32(dr, "d_rotation1", keep)
-            w.flow_dx2, w.flow_proj1, w.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
-            w.flow_clip = clips[v].data_ptr() if clips[v] is not None else None
-            w.out_color, w.out_depth = img[v, :_C.NUM_CHANNELS].data_ptr(), img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1].data_ptr()
-            w.out_opacity, w.radii, w.n_touched = img[v, _C.NUM_CHANNELS + 1:].data_ptr(), ints[v, 0].data_ptr(), ints[v, 1].data_ptr()
-            hs = [{"dev": dev, "t": None} for _ in range(3)]
-            holders.append(hs)
-            for k, h in enumerate(hs):
-                _arenas[base + 3 * v + k] = h
-            w.geometry_user, w.binning_user, w.image_user = base + 3 * v, base + 3 * v + 1, base + 3 * v + 2
-        try:
-            with torch.cuda.device(dev):
-                lib.gsr_forward_views(V, views, _alloc_cb, _alloc_cb, _alloc_cb, P, 0, 1, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc),
-                                      float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(bool(rs0.debug)), _C._stream(dev))
-        finally:
-            for v in range(V):
-                for k in range(3):
-                    _arenas.pop(base + 3 * v + k, None)
-        ctx.num_rendered = [int(views[v].num_rendered) for v in range(V)]
-        state = [holders[v][k]["t"] for v in range(V) for k in range(3)]
+                    float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), int(rs0.image_height), int(rs0.image_width), 0,
+                    bool(rs0.debug), _C._stream(dev), clips)
+        else:
+            keep = []
+            desc = _describe(xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, None, None, None, keep)
+
+            def flows(v, w):
+                _flow_fields(w, keep, *per_view[7 * v + 1: 7 * v + 7])
+                w.flow_clip = clips[v].data_ptr() if clips[v] is not None else None
+            img, ints, rendered, state = _forward_views(ctx, settings, xyz, 0, 1, desc, keep, flows)
+        ctx.num_rendered = [int(r) for r in rendered]
         ctx.n_state = len(state)
         ctx.save_for_backward(xyz, log_scales, raw_rot, logit_opacity, dyn_slot, ints, *state, *[per_view[7 * v + k] for v in range(V) for k in range(1, 7)])
-        outs = []
-        for v in range(V):
-            outs += [img[v, :_C.NUM_CHANNELS], ints[v, 0], img[v, _C.NUM_CHANNELS:_C.NUM_CHANNELS + 1], img[v, _C.NUM_CHANNELS + 1:], ints[v, 1]]
-        ctx.mark_non_differentiable(*[outs[5 * v + k] for v in range(V) for k in (1, 4)])
-        return tuple(outs)
+        return _outputs(ctx, img, ints)
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _C.load_library()
         V, settings = ctx.V, ctx.settings
         saved = ctx.saved_tensors
         xyz, log_scales, raw_rot, logit_opacity, dyn_slot, ints = saved[:6]
@@ -458,52 +361,33 @@ class _RasterizeFlowViewsRaw(torch.autograd.Function):
         P, H, W, S = int(xyz.shape[0]), int(rs0.image_height), int(rs0.image_width), int(log_scales.shape[-1])
         glue = _glue()
         if glue is not None:
-            col = lambda k: [rest[6 * v + k] for v in range(V)]          # per view: dx1, dx2, ds, dr, proj1, proj2
-            cot = lambda g_, c: _zero_cotangent(c, H, W, dev) if g_ is None else g_
+            col = lambda k: list(rest[k::6])
             with torch.cuda.device(dev):
                 pg, per_view_out, dl = glue.rasterize_views_backward(
                     rs0.bg, xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, *_camera_lists(settings), col(0), col(2), col(3), col(1), col(4), col(5),
                     float(rs0.scale_modifier), float(rs0.tanfovx), float(rs0.tanfovy), H, W, 0, ints, list(state), ctx.num_rendered,
-                    [cot(grads[5 * v], 3) for v in range(V)], [cot(grads[5 * v + 2], 1) for v in range(V)], [], False, False, bool(rs0.debug), _C._stream(dev))
-            res = [pg[0], None, None, None, None, None, None]
-            for v in range(V):
-                res += [per_view_out[v, :P * 3].view(P, 3), dl[4 * v], dl[4 * v + 1], dl[4 * v + 2], dl[4 * v + 3], None, None]
-            return tuple(res)
-        keep = []
-        desc = _describe(xyz, log_scales, raw_rot, logit_opacity, xyz, None, dyn_slot, None, None, None, keep)
-        desc.features_dc = None
-        g_xyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        out = gsr_raw_grads()
-        out.xyz = g_xyz.data_ptr()
-        per_view_out = torch.empty((V, P * 3 + 6), dtype=torch.float32, device=dev)      # screen-space gradient + (unused) pose sum per view
-        zero = _zero_grads_like(*[rest[6 * v + k] for v in range(V) for k in range(4)])   # one fill for every view's delta gradients
-        views = (gsr_view * V)()
-        for v in range(V):
-            rs, w = settings[v], views[v]
-            g_color, g_depth = grads[5 * v], grads[5 * v + 2]
-            g_color = _zero_cotangent(3, H, W, dev) if g_color is None else g_color
-            g_depth = _zero_cotangent(1, H, W, dev) if g_depth is None else g_depth
-            dx1, dx2, ds, dr, proj1, proj2 = rest[6 * v: 6 * v + 6]
-            w.viewmatrix, w.projmatrix = _f32(rs.viewmatrix, "viewmatrix", keep), _f32(rs.projmatrix, "projmatrix", keep)
-            w.projmatrix_raw, w.cam_pos = _f32(rs.projmatrix_raw, "projmatrix_raw", keep), _f32(rs.campos, "campos", keep)
-            w.dx, w.ds, w.dr = _f32(dx1, "d_xyz1", keep), _f32(ds, "d_scaling1", keep), _f32(dr, "d_rotation1", keep)
-            w.flow_dx2, w.flow_proj1, w.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
-            w.radii = ints[v, 0].data_ptr()
-            w.geom_buffer, w.binning_buffer, w.image_buffer = state[3 * v].data_ptr(), state[3 * v + 1].data_ptr(), state[3 * v + 2].data_ptr()
-            w.num_rendered = ctx.num_rendered[v]
-            w.dL_dcolor, w.dL_ddepth = _f32(g_color.to(torch.float32), "dL_dcolor", keep), _f32(g_depth.to(torch.float32), "dL_ddepth", keep)
-            w.dL_dmean2D, w.dL_dtau_sum = per_view_out[v, :P * 3].data_ptr(), per_view_out[v, P * 3:].data_ptr()
-            gd1, gd2, gds, gdr = zero[4 * v: 4 * v + 4]
-            w.ddx, w.ddx2, w.dds, w.ddr = (None if g is None else g.data_ptr() for g in (gd1, gd2, gds, gdr))
-        scratch = torch.empty((int(lib.gsr_views_scratch_size(V, P, 1, S)),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            lib.gsr_backward_views(V, views, P, 0, 1, _f32(rs0.bg, "bg", keep), W, H, C.byref(desc), float(rs0.scale_modifier),
-                                   float(rs0.tanfovx), float(rs0.tanfovy), C.byref(out), scratch.data_ptr(), int(bool(rs0.debug)), _C._stream(dev))
-        res = [g_xyz, None, None, None, None, None, None]
-        for v in range(V):
-            gd1, gd2, gds, gdr = zero[4 * v: 4 * v + 4]
-            res += [per_view_out[v, :P * 3].view(P, 3), gd1, gd2, gds, gdr, None, None]
-        return tuple(res)
+                    *_cotangents(grads, H, W, dev), [], False, False, bool(rs0.debug), _C._stream(dev))
+            g_xyz, delta_grads = pg[0], zip(dl[0::4], dl[1::4], dl[2::4], dl[3::4])
+        else:
+            keep = []
+            desc = _describe(xyz, log_scales, raw_rot, logit_opacity, None, None, dyn_slot, None, None, None, keep)
+            g_xyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            out = gsr_raw_grads()
+            out.xyz = g_xyz.data_ptr()
+            zero = _zero_grads_like(*[rest[6 * v + k] for v in range(V) for k in range(4)])   # one fill for every view's delta gradients
+
+            def flows(v, w):
+                _flow_fields(w, keep, *rest[6 * v: 6 * v + 6])
+                w.ddx, w.ddx2, w.dds, w.ddr = (None if g is None else g.data_ptr() for g in zero[4 * v: 4 * v + 4])
+            per_view_out = _backward_views(ctx, grads, xyz, S, 0, 1, desc, keep, out, ints, state, 0, flows)
+            delta_grads = zip(zero[0::4], zero[1::4], zero[2::4], zero[3::4])
+        return tuple([g_xyz, None, None, None, None, None, None] + _view_grads(per_view_out, P, [(None, None)] * V, delta_grads))
+
+
+def _flow_fields(w, keep, dx1, dx2, ds, dr, proj1, proj2):
+    """A flow view's deltas and the projections of its two cameras."""
+    w.dx, w.ds, w.dr = _f32(dx1, "d_xyz1", keep), _f32(ds, "d_scaling1", keep), _f32(dr, "d_rotation1", keep)
+    w.flow_dx2, w.flow_proj1, w.flow_proj2 = _f32(dx2, "d_xyz2", keep), _f32(proj1, "proj1", keep), _f32(proj2, "proj2", keep)
 
 
 def rasterize_flow_views_raw(settings, xyz, means2D, log_scales, raw_rotations, logit_opacity, dyn_slot, flows, clips=None):

@@ -206,8 +206,11 @@ def test_flow_views_equal_single_flow_calls(V):
 
 def test_native_and_ctypes_marshalling_of_the_views_calls_agree_bitwise():
     """The two calls are marshalled twice: by the native glue (torch_glue.cpp rasterize_views_forward / _backward, the default when the glue
-    is built) and by ctypes in views.py. Same kernels underneath: outputs and every gradient bit for bit, plain views and flow views."""
+    is built) and by ctypes in views.py. Same kernels underneath: outputs and every gradient bit for bit, plain views and flow views, and
+    the pose-only (detached Gaussians) and fused-accumulation (attached gradient bucket) branches of the backward pass."""
     from diff_gaussian_rasterization import _C, views
+    from diff_gaussian_rasterization.autograd import ACCUMULATE_ATTR
+    from mapping_shard import GradBucket
     if views._glue() is None:
         pytest.skip("native glue not built")
     par, settings, cots, slot, deltas, poses = _scene(P=9000, V=6, W=256, H=192, M=4, seed=3)
@@ -220,6 +223,10 @@ def test_native_and_ctypes_marshalling_of_the_views_calls_agree_bitwise():
     fsettings = [rs._replace(bg=zero_bg, sh_degree=0) for rs in settings]
     flows = [(deltas[v][0], dx2[v], deltas[v][1], deltas[v][2], fsettings[v].projmatrix, fsettings[(v + 1) % len(settings)].projmatrix) for v in range(len(settings))]
     leaves = list(par.values()) + [t for d in deltas for t in d] + dx2 + [t for p_ in poses for t in p_]
+    others = leaves[len(par):]
+    detached = {k: t.detach() for k, t in par.items()}
+    detached_deltas = [tuple(t.detach() for t in d) for d in deltas]
+    plist = [par["xyz"], par["f_dc"], par["f_rest"], par["logit"], par["log_scales"], par["rot"]]
 
     def run(native):
         views._NATIVE_MARSHALLING = native
@@ -235,6 +242,22 @@ def test_native_and_ctypes_marshalling_of_the_views_calls_agree_bitwise():
             fo = views.rasterize_flow_views_raw(fsettings, par["xyz"], pts, par["log_scales"].detach(), par["rot"].detach(), par["logit"].detach(), slot, flows)
             torch.autograd.backward([o[0] for o in fo], [c[0] for c in cots])
             got += [t for o in fo for t in o] + [m.grad for m in pts] + [t.grad for t in [par["xyz"]] + [d[0] for d in deltas] + dx2]
+            for t in leaves:
+                t.grad = None
+            outs, m2d = _multi(detached, settings, cots, slot, detached_deltas, poses)          # pose-only backward
+            got += [t for o in outs for t in o] + [m.grad for m in m2d] + [t.grad for p_ in poses for t in p_]
+        bucket = GradBucket(plist).attach()
+        try:
+            for rep in range(2):
+                bucket.zero_grads()
+                for t in others:
+                    t.grad = None
+                outs, m2d = _multi(par, settings, cots, slot, deltas, poses)                  # accumulation into the bucket
+                got += [t for o in outs for t in o] + [m.grad for m in m2d] + [bucket.flat.clone()] + [t.grad for t in others if t.grad is not None]
+        finally:
+            for p_ in plist:
+                p_.grad = None
+                setattr(p_, ACCUMULATE_ATTR, False)
         return got
 
     try:
