@@ -44,6 +44,8 @@
 #include "gs_raft.h"
 #include "../../include/segmentation.h"
 #include "gs_yolo.h"
+#include "../../include/perceptual.h"
+#include "gs_lpips.h"
 
 namespace gsr {
 
@@ -3033,6 +3035,77 @@ int gsr_yolo_masks(int max_dets, const float* dets, const int* counts, int nm, c
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(yolo_mask_kernel, dim3((unsigned)(width / YOLO_TILE), (unsigned)(height / YOLO_TILE)), dim3(256), 0, stream, counts,
                        max_dets, dets, nm, proto, proto_h, proto_w, height, width, yolo_mask, motion);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// levels, shapes and the block layout of a distance call; false (with the error text set) when an argument is out of range
+static bool lpips_levels(const char* who, int batch, int levels, const int* level_chw, LpipsLevels& L)
+{
+    if (batch < 1 || batch > 65535 || levels < 1 || levels > LPIPS_MAX_LEVELS || !level_chw) {
+        g_last_error = std::string(who) + ": 1 <= batch <= 65535, 1 to " + std::to_string(LPIPS_MAX_LEVELS) + " levels and level_chw given";
+        return false;
+    }
+    L.levels = levels;
+    long long blocks = 0;
+    for (int l = 0; l < levels; ++l) {
+        const long long c = level_chw[3 * l], h = level_chw[3 * l + 1], w = level_chw[3 * l + 2];
+        if (c < 1 || h < 1 || w < 1 || h * w > 0x7fffffffLL - LPIPS_BLOCK || c > 65536) {
+            g_last_error = std::string(who) + ": a level has no channels or pixels, more than 65536 channels or 2^31 pixels";
+            return false;
+        }
+        L.c[l] = (int)c;
+        L.hw[l] = (int)(h * w);
+        L.blocks[l] = (int)((h * w + LPIPS_BLOCK - 1) / LPIPS_BLOCK);
+        L.first[l] = (int)blocks;
+        blocks += (long long)batch * L.blocks[l];
+        if (blocks > 0x7fffffffLL) { g_last_error = std::string(who) + ": more than 2^31 blocks"; return false; }
+    }
+    L.first[levels] = (int)blocks;
+    return true;
+}
+
+int gsr_lpips_prepare(int batch, int height, int width, const float* x, const float* y, float* out, void* stream_)
+{
+    if (!x || !y || !out) { g_last_error = "gsr_lpips_prepare: x, y and out must not be NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (batch < 1 || height < 1 || width < 1 || (long long)batch * 6 * height * width > 0x7fffffffLL) {
+        g_last_error = "gsr_lpips_prepare: batch, height and width must be positive and 2 * batch * 3 * height * width below 2^31";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    const int hw = height * width, n = batch * 3 * hw;
+    hipLaunchKernelGGL(lpips_prepare_kernel, dim3((unsigned)((n + LPIPS_PREPARE_BLOCK - 1) / LPIPS_PREPARE_BLOCK)), dim3(LPIPS_PREPARE_BLOCK), 0,
+                       (hipStream_t)stream_, n, hw, x, y, out);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace: one float per block of the distance launch
+size_t gsr_lpips_workspace_size(int batch, int levels, const int* level_chw)
+{
+    LpipsLevels L{};
+    if (!lpips_levels("gsr_lpips_workspace_size", batch, levels, level_chw, L)) return 0;
+    return (size_t)L.first[levels] * sizeof(float);
+}
+
+int gsr_lpips_distance(int batch, int levels, const int* level_chw, const float* const* feat, const float* const* lin, int norm,
+                       void* workspace, float* taps, float* scores, void* stream_)
+{
+    LpipsLevels L{};
+    if (!lpips_levels("gsr_lpips_distance", batch, levels, level_chw, L)) return GSR_ERR_INVALID_ARGUMENT;
+    if (!feat || !lin || !workspace || !scores || (norm != LPIPS_NORM_TORCHMETRICS && norm != LPIPS_NORM_LPIPS)) {
+        g_last_error = "gsr_lpips_distance: feat, lin, workspace and scores given, norm one of GSR_LPIPS_NORM_*";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    for (int l = 0; l < levels; ++l) {
+        if (!feat[l] || !lin[l]) { g_last_error = "gsr_lpips_distance: a level's feat or lin pointer is NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+        L.feat[l] = feat[l];
+        L.lin[l] = lin[l];
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    float* partial = (float*)workspace;
+    hipLaunchKernelGGL(lpips_distance_kernel, dim3((unsigned)L.first[levels]), dim3(LPIPS_BLOCK), 0, stream, L, batch, norm, partial);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)batch), dim3(64), 0, stream, L, partial, taps, scores);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -19,6 +19,7 @@ GSR_HEXPLANE_MAX_VIEWS = 12
 GSR_KNN_MAX_K, GSR_KNN_MAX_DIM, GSR_BLEND_MAX_K = 32, 32, 8                       # control_nodes.h
 GSR_NODE_RADIUS_IS_LOG, GSR_NODE_WEIGHT_IS_LOGIT = 1, 2
 GSR_YOLO_MAX_LEVELS, GSR_YOLO_MAX_ANCHORS, GSR_YOLO_REG_MAX, GSR_YOLO_DET_HEAD = 4, 8192, 16, 7  # segmentation.h
+GSR_LPIPS_MAX_LEVELS, GSR_LPIPS_NORM_TORCHMETRICS, GSR_LPIPS_NORM_LPIPS = 8, 0, 1  # perceptual.h
 
 # ---- types (field names and order as in the headers; every pointer field is a plain address) -----------------------------------
 gsr_alloc_fn = C.CFUNCTYPE(vp, vp, sz)
@@ -236,6 +237,10 @@ FUNCTIONS = {
     "gsr_yolo_workspace_size": (sz, [i]),
     "gsr_yolo_detect": (i, [i, P(i), P(f), P(vp), P(vp), i, i, P(i), i, f, f, i, vp, vp, i, vp, vp]),
     "gsr_yolo_masks": (i, [i, vp, vp, i, vp, i, i, i, i, vp, vp, vp]),
+    # perceptual.h
+    "gsr_lpips_prepare": (i, [i, i, i, vp, vp, vp, vp]),
+    "gsr_lpips_workspace_size": (sz, [i, i, P(i)]),
+    "gsr_lpips_distance": (i, [i, i, P(i), P(vp), P(vp), i, vp, vp, vp, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

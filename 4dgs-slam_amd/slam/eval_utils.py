@@ -1,6 +1,6 @@
 """Trajectory and rendering evaluation -- the counterpart of the reference's ``utils/eval_utils.py``: Horn alignment + ATE
 (align :160-200, evaluate_ate :203-219, the evo APE-RMSE of evaluate_evo :106-150), eval_ate (:221-297), eval_rendering (:300-428:
-masked PSNR, SSIM, depth L1; LPIPS needs the AlexNet weights and is left out), save_gaussians (:431-440). No evo / wandb / cv2."""
+masked PSNR, SSIM, depth L1, and LPIPS when a slam.perceptual.Lpips is given), save_gaussians (:431-440). No evo / wandb / cv2."""
 import json
 import os
 
@@ -78,11 +78,15 @@ def psnr(img1, img2):
 
 
 @torch.no_grad()
-def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_indices=(), iteration="final", deltas_for=None, interval=1):
+def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_indices=(), iteration="final", deltas_for=None, interval=1,
+                   lpips=None):
     """utils/eval_utils.py:300-428: render every frame at its estimated pose and compare with the sensor image: PSNR over the valid
-    pixels (:371-381), SSIM, depth L1 (:383-388). `deltas_for(frame)` -> (dx, ds, dr) supplies the dynamic subset's deformation."""
+    pixels (:371-381), SSIM, depth L1 (:383-388). `deltas_for(frame)` -> (dx, ds, dr) supplies the dynamic subset's deformation.
+    `lpips` (a slam.perceptual.Lpips): the clamped render against the whole sensor image (:352, :378), scores kept on the device and
+    read once after the loop; the result and final_result.json gain `mean_lpips`."""
     psnrs, ssims, depths = [], [], []
     end_idx = len(frames) - 1 if len(frames) > 1 else 1
+    lpips_scores = None if lpips is None else torch.empty(len(range(0, end_idx, interval)), dtype=torch.float32, device=lpips.device)
     for idx in range(0, end_idx, interval):
         frame = frames[idx]
         gt_image, gt_depth, _, motion_mask = dataset[idx]
@@ -100,7 +104,13 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_in
         ssims.append(float(slam_losses.ssim(image, gt_image)))
         l1 = torch.abs(torch.as_tensor(gt_depth, device=image.device)[None] - pkg["depth"]) * valid_depth[None]
         depths.append(float(l1.sum() / (valid_depth.sum() + 1e-7)))
+        if lpips is not None:
+            lpips_scores[len(depths) - 1:len(depths)] = lpips(image[None], gt_image[None])
     out = {"mean_psnr": float(np.mean(psnrs)), "mean_ssim": float(np.mean(ssims)), "l1_depth": float(np.mean(depths)), "frames": len(psnrs)}
+    if lpips is not None:
+        mean_lpips = float(np.mean(lpips_scores.cpu().numpy().astype(np.float64)))
+        out = {"mean_psnr": out["mean_psnr"], "mean_ssim": out["mean_ssim"], "mean_lpips": mean_lpips, "l1_depth": out["l1_depth"],
+               "frames": out["frames"]}
     if save_dir:
         d = os.path.join(save_dir, "psnr", str(iteration))
         os.makedirs(d, exist_ok=True)

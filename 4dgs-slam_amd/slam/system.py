@@ -49,8 +49,9 @@ def merge_config(base, override):
 
 
 class SLAM:
-    def __init__(self, config, dataset, save_dir=None):
+    def __init__(self, config, dataset, save_dir=None, lpips=None):
         self.config = config
+        self.lpips = lpips                                              # slam.perceptual.Lpips or None: mean_lpips in the rendering evaluation
         self.dataset = dataset
         self.save_dir = save_dir
         ns = lambda d: types.SimpleNamespace(**d)
@@ -100,11 +101,13 @@ class SLAM:
             if self.gaussians.deform_init:
                 deltas_for = lambda frame: self.backend._deltas(frame, train=False)
             self.result["before_opt"] = eval_rendering(self._eval_frames(), self.gaussians, self.dataset, self.save_dir, self.pipeline_params,
-                                                       self.background, fe.kf_indices, iteration="before_opt", deltas_for=deltas_for)
+                                                       self.background, fe.kf_indices, iteration="before_opt", deltas_for=deltas_for,
+                                                       lpips=self.lpips)
             if color_refinement_iters:
                 self.backend.color_refinement(iteration_total=color_refinement_iters)
                 self.result["after_opt"] = eval_rendering(self._eval_frames(), self.gaussians, self.dataset, self.save_dir, self.pipeline_params,
-                                                          self.background, fe.kf_indices, iteration="after_opt", deltas_for=deltas_for)
+                                                          self.background, fe.kf_indices, iteration="after_opt", deltas_for=deltas_for,
+                                                          lpips=self.lpips)
         if self.save_dir:
             save_gaussians(self.gaussians, self.save_dir, "final", final=True)
         return self.result

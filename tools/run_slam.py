@@ -5,7 +5,9 @@ of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the 
 came from the read-ahead thread vs were decoded on demand. With --dynamic --raft-weights PATH (the reference's pretrained/raft-things.pth) the
 dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py), and a `flow` block reports the pairs estimated and the
 device ms per pair. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
-(slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame."""
+(slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame.
+With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and the LPIPS v0.1 linear layers) the rendering evaluation
+reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair."""
 import argparse
 import json
 import os
@@ -35,12 +37,17 @@ def parse_args(argv=None):
     ap.add_argument("--raft-weights", default=None, help="RAFT-basic checkpoint (raft-things.pth): the flow term of --dynamic runs")
     ap.add_argument("--yolo-weights", default=None, help="YOLO-seg checkpoint (yolov9e-seg.pt): motion masks of people and the "
                                                          "loader's object classes")
+    ap.add_argument("--lpips-weights", nargs=2, default=None, metavar=("ALEXNET", "LIN"),
+                    help="torchvision AlexNet state_dict and LPIPS v0.1 linear layers: mean_lpips in the rendering evaluation")
     args = ap.parse_args(argv)
     if args.raft_weights and not args.dynamic:
         warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
         args.raft_weights = None
     if args.yolo_weights and not os.path.isfile(args.yolo_weights):
         ap.error(f"--yolo-weights {args.yolo_weights}: no such file")
+    for path in args.lpips_weights or ():
+        if not os.path.isfile(path):
+            ap.error(f"--lpips-weights {path}: no such file")
     return args
 
 
@@ -68,8 +75,14 @@ def main(argv=None):
     if args.yolo_weights:
         from slam.segmentation import YoloSeg
         segmenter = YoloSeg.from_checkpoint(args.yolo_weights, "cuda:0")
+    lpips = None
+    if args.lpips_weights and not config["Results"].get("eval_rendering", True):
+        warnings.warn("--lpips-weights only serves the rendering evaluation (Results.eval_rendering, or --eval); ignored")
+    elif args.lpips_weights:
+        from slam.perceptual import Lpips
+        lpips = Lpips.from_checkpoints(*args.lpips_weights, device="cuda:0")
     ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow, segmenter=segmenter)
-    slam = SLAM(config, ds, save_dir=save_dir)
+    slam = SLAM(config, ds, save_dir=save_dir, lpips=lpips)
     res = slam.run()
     res["graph_stats"] = slam.frontend.graph_stats
     res["mapping_graph_stats"] = {"static": dict(getattr(slam.backend, "graph_stats", {}) or {}),
@@ -82,6 +95,8 @@ def main(argv=None):
         res["flow"] = ds.flow_stats
     if segmenter is not None:
         res["segmentation"] = ds.segmentation_stats
+    if lpips is not None:
+        res["lpips"] = lpips.stats
     ds.close()
     name = os.path.splitext(os.path.basename(args.config))[0] + ("_dynamic" if args.dynamic else "")
     print(json.dumps({name: res}, indent=1, default=str))
