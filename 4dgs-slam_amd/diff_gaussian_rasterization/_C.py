@@ -107,11 +107,12 @@ def _require_device(t: torch.Tensor, name: str):
         )
 
 
-def dev_f32(t, name):
-    """Device pointer of a contiguous float32 device tensor (no copy: anything else is rejected)."""
+def dev_f32(t, name, shape=None):
+    """Device pointer of a contiguous float32 device tensor, of the given shape if any (no copy: anything else is rejected)."""
     _require_device(t, name)
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise RuntimeError(f"{name} must be a contiguous float32 device tensor")
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
+                           f", got {t.dtype} {tuple(t.shape)}")
     return t.data_ptr()
 
 

@@ -12,14 +12,13 @@ by the caller's key), so a keyframe that appears in two pairs is encoded once.""
 import collections
 import ctypes as C
 import math
-import os
-import zlib
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from diff_gaussian_rasterization import _C
+from . import pretrained
 
 LEVELS, RADIUS, HDIM, CDIM, ITERS = 4, 4, 128, 128, 20
 CORR_CHANNELS = LEVELS * (2 * RADIUS + 1) ** 2          # 324
@@ -74,12 +73,12 @@ def param_shapes():
 
 
 def recipe_state_dict(seed=0):
-    """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator np.random.default_rng([seed, crc32(name)]);
+    """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator pretrained.entry_rng(seed, name);
     conv weights U(+-sqrt(1 / fan_in)), norm weights U(0.8, 1.2), other vectors U(+-0.05), running_mean U(+-0.1), running_var
     U(0.5, 1.5), num_batches_tracked 0. Flows from them are finite and mostly inside the image, but carry no meaning."""
     out = collections.OrderedDict()
     for name, shape in param_shapes().items():
-        rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+        rng = pretrained.entry_rng(seed, name)
         if name.endswith("num_batches_tracked"):
             out[name] = torch.tensor(0, dtype=torch.int64)
             continue
@@ -101,20 +100,10 @@ def recipe_state_dict(seed=0):
 def check_state_dict(sd):
     """Strip DataParallel's `module.` prefix and check the entries against param_shapes(): a missing, extra or misshapen entry raises
     and names it. Returns the stripped dict."""
-    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    sd = pretrained.strip_module_prefix(sd, "RAFT checkpoint")
     if any(".conv3." in k for k in sd) or tuple(getattr(sd.get("update_block.encoder.convc1.weight"), "shape", ())) == (96, 196, 1, 1):
         raise ValueError("this is a RAFT-small checkpoint; only RAFT-basic (raft-things.pth and its kind) is supported")
-    want = param_shapes()
-    missing = [k for k in want if k not in sd]
-    if missing:
-        raise KeyError(f"RAFT checkpoint lacks {missing[0]!r} ({len(missing)} missing entries)")
-    extra = [k for k in sd if k not in want]
-    if extra:
-        raise KeyError(f"RAFT checkpoint has an unexpected entry {extra[0]!r} ({len(extra)} extra entries)")
-    for k, shape in want.items():
-        got = tuple(sd[k].shape)
-        if got != shape:
-            raise ValueError(f"RAFT checkpoint entry {k!r} has shape {got}, expected {shape}")
+    pretrained.check_entries(sd, param_shapes(), "RAFT checkpoint")
     return sd
 
 
@@ -139,14 +128,6 @@ def check_size(height, width):
 
 
 # ---- kernels (ctypes binding of include/optical_flow.h) -------------------------------------------------------------------------------
-def _f32(t, name, shape=None):
-    _C._require_device(t, name)
-    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
-                           f", got {t.dtype} {tuple(t.shape)}")
-    return t.data_ptr()
-
-
 def level_sizes(h, w):
     out = []
     for _ in range(LEVELS):
@@ -159,14 +140,14 @@ def corr_pyramid(fmap1, fmap2, both=True):
     """The correlation pyramid of fmaps [D, h, w]: a list of LEVELS tensors [2 (or 1), h*w, h_l, w_l]; index 0 is 1->2 (row: a pixel of
     image 1, grid: image 2), index 1 is 2->1. One launch of the product for both directions, one per pooled level."""
     D, h, w = (int(s) for s in fmap1.shape)
-    _f32(fmap1, "fmap1", (D, h, w))
-    _f32(fmap2, "fmap2", (D, h, w))
+    _C.dev_f32(fmap1, "fmap1", (D, h, w))
+    _C.dev_f32(fmap2, "fmap2", (D, h, w))
     nd = 2 if both else 1
     levels = [torch.empty((nd, h * w, hl, wl), dtype=torch.float32, device=fmap1.device) for hl, wl in level_sizes(h, w)]
     p12 = (C.c_void_p * LEVELS)(*[t[0].data_ptr() for t in levels])
     p21 = (C.c_void_p * LEVELS)(*[t[1].data_ptr() for t in levels]) if both else None
-    L = _C.load_library()
-    L.gsr_raft_corr_pyramid(D, h, w, fmap1.data_ptr(), fmap2.data_ptr(), p12, p21, torch.cuda.current_stream(fmap1.device).cuda_stream)
+    with torch.cuda.device(fmap1.device):
+        _C.load_library().gsr_raft_corr_pyramid(D, h, w, fmap1.data_ptr(), fmap2.data_ptr(), p12, p21, _C._stream(fmap1.device))
     return levels
 
 
@@ -175,15 +156,15 @@ def corr_lookup(levels, coords, out=None):
     B, _, h, w = (int(s) for s in coords.shape)
     if B != int(levels[0].shape[0]) or tuple(levels[0].shape[1:]) != (h * w, h, w):
         raise RuntimeError(f"coords {tuple(coords.shape)} do not match the pyramid {tuple(levels[0].shape)}")
-    _f32(coords, "coords", (B, 2, h, w))
+    _C.dev_f32(coords, "coords", (B, 2, h, w))
     for t in levels:
-        _f32(t, "pyramid level")
+        _C.dev_f32(t, "pyramid level")
     if out is None:
         out = torch.empty((B, CORR_CHANNELS, h, w), dtype=torch.float32, device=coords.device)
-    _f32(out, "out", (B, CORR_CHANNELS, h, w))
+    _C.dev_f32(out, "out", (B, CORR_CHANNELS, h, w))
     ptrs = (C.c_void_p * (B * LEVELS))(*[levels[l][b].data_ptr() for b in range(B) for l in range(LEVELS)])
-    L = _C.load_library()
-    L.gsr_raft_corr_lookup(B, h, w, ptrs, coords.data_ptr(), out.data_ptr(), torch.cuda.current_stream(coords.device).cuda_stream)
+    with torch.cuda.device(coords.device):
+        _C.load_library().gsr_raft_corr_lookup(B, h, w, ptrs, coords.data_ptr(), out.data_ptr(), _C._stream(coords.device))
     return out
 
 
@@ -192,12 +173,12 @@ def upsample(flow, mask, pad, out_hw, ndc=True):
     top, bottom), out_hw = (H, W) unpadded -> [B, H, W, 2]."""
     B, _, h, w = (int(s) for s in flow.shape)
     H, W = (int(s) for s in out_hw)
-    _f32(flow, "flow", (B, 2, h, w))
-    _f32(mask, "mask", (B, MASK_CHANNELS, h, w))
+    _C.dev_f32(flow, "flow", (B, 2, h, w))
+    _C.dev_f32(mask, "mask", (B, MASK_CHANNELS, h, w))
     out = torch.empty((B, H, W, 2), dtype=torch.float32, device=flow.device)
-    L = _C.load_library()
-    L.gsr_raft_upsample(B, h, w, flow.data_ptr(), mask.data_ptr(), int(pad[0]), int(pad[2]), W, H, int(bool(ndc)), out.data_ptr(),
-                        torch.cuda.current_stream(flow.device).cuda_stream)
+    with torch.cuda.device(flow.device):
+        _C.load_library().gsr_raft_upsample(B, h, w, flow.data_ptr(), mask.data_ptr(), int(pad[0]), int(pad[2]), W, H, int(bool(ndc)),
+                                            out.data_ptr(), _C._stream(flow.device))
     return out
 
 
@@ -205,7 +186,7 @@ def upsample(flow, mask, pad, out_hw, ndc=True):
 class RaftFlow:
     """RAFT-basic inference (hidden = context = 128, 4 levels, radius 4, 20 iterations) on one device."""
 
-    _loaded = {}                  # (checkpoint path, mtime, device) -> estimator: a checkpoint is read once per process
+    _loaded = {}                  # pretrained.load_once: a checkpoint is read once per process
 
     def __init__(self, state_dict, device="cuda:0", cache_frames=8):
         sd = check_state_dict(state_dict)
@@ -219,15 +200,10 @@ class RaftFlow:
 
     @classmethod
     def from_checkpoint(cls, path, device="cuda:0", **kw):
-        path = os.path.realpath(path)
-        key = (path, os.path.getmtime(path), str(torch.device(device)))
-        hit = cls._loaded.get(key)
-        if hit is None:
+        def build(path):
             sd = torch.load(path, map_location="cpu", weights_only=True)
-            if not isinstance(sd, dict):
-                raise ValueError(f"{path}: expected a state_dict, got {type(sd).__name__}")
-            hit = cls._loaded[key] = cls(sd, device, **kw)
-        return hit
+            return cls(pretrained.strip_module_prefix(sd, path), device, **kw)
+        return pretrained.load_once(cls._loaded, [path], device, None, build)
 
     # -- encoders
     def _norm(self, x, name, kind):
@@ -310,11 +286,8 @@ class RaftFlow:
         on the device, in NDC units (flow / (W, H) * 2, utils/camera_utils.py:412-413) or pixels with ndc=False. Images: [3, H, W] float
         in [0, 1]; an image may be None when its key is in the encoder cache. key_i / key_j name the images for that cache (None: not
         cached). `trace`, a dict, receives the intermediates."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("RaftFlow.pair was called while the current stream is capturing a graph: flows must be estimated before "
-                               "capture (dynamic_graph fills its flow planes during table setup)")
-        # deterministic convolution algorithms: the same pair gives the same bits on every call (the flow targets are cached by pair)
-        with torch.backends.cudnn.flags(enabled=torch.backends.cudnn.enabled, benchmark=False, deterministic=True):
+        pretrained.refuse_capture("RaftFlow.pair", "estimate flows before capture (dynamic_graph fills its flow planes during table setup)")
+        with pretrained.deterministic_convolutions():          # the flow targets are cached by pair
             return self._pair(image_i, image_j, key_i, key_j, iters, ndc, trace)
 
     def _pair(self, image_i, image_j, key_i, key_j, iters, ndc, trace):

@@ -16,8 +16,6 @@ seeded stand-ins of the same shapes for building and testing without the publish
 import collections
 import ctypes as C
 import math
-import os
-import zlib
 
 import numpy as np
 import torch
@@ -25,6 +23,7 @@ import torch.nn.functional as F
 
 from diff_gaussian_rasterization import _C
 from diff_gaussian_rasterization._abi import GSR_LPIPS_NORM_LPIPS, GSR_LPIPS_NORM_TORCHMETRICS
+from . import pretrained
 
 SHIFT = (-.030, -.088, -.188)                           # LPIPS' ScalingLayer
 SCALE = (.458, .448, .450)
@@ -49,48 +48,30 @@ def param_shapes():
 
 
 def recipe_state_dicts(seed=0):
-    """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator np.random.default_rng([seed, crc32(name)]);
+    """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator pretrained.entry_rng(seed, name);
     He-scaled convolutions N(0, 2 / fan_in), biases N(0, 0.1^2), linear weights U[0, 0.5). Scores from them are well-behaved distances
     but carry no perceptual meaning."""
     alex_shapes, lin_shapes = param_shapes()
     alex, lin = collections.OrderedDict(), collections.OrderedDict()
     for name, shape in alex_shapes.items():
-        rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+        rng = pretrained.entry_rng(seed, name)
         v = rng.standard_normal(shape) * (math.sqrt(2.0 / (shape[1] * shape[2] * shape[3])) if len(shape) == 4 else 0.1)
         alex[name] = torch.from_numpy(v.astype(np.float32))
     for name, shape in lin_shapes.items():
-        rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
-        lin[name] = torch.from_numpy(rng.uniform(0.0, 0.5, shape).astype(np.float32))
+        lin[name] = torch.from_numpy(pretrained.entry_rng(seed, name).uniform(0.0, 0.5, shape).astype(np.float32))
     return alex, lin
-
-
-def _strip(sd, what):
-    if not isinstance(sd, dict):
-        raise ValueError(f"{what}: expected a state_dict, got {type(sd).__name__}")
-    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-
-
-def _check(sd, want, what):
-    missing = [k for k in want if k not in sd]
-    if missing:
-        raise KeyError(f"{what} lacks {missing[0]!r} ({len(missing)} missing entries)")
-    extra = [k for k in sd if k not in want]
-    if extra:
-        raise KeyError(f"{what} has an unexpected entry {extra[0]!r} ({len(extra)} extra entries)")
-    for k, shape in want.items():
-        if not isinstance(sd[k], torch.Tensor) or tuple(sd[k].shape) != shape:
-            raise ValueError(f"{what} entry {k!r} has shape {tuple(getattr(sd[k], 'shape', ()))}, expected {shape}")
 
 
 def check_state_dicts(alexnet_sd, lin_sd):
     """Strip DataParallel's `module.` prefix, drop AlexNet's `classifier.*`, and check both dictionaries against param_shapes(): a missing,
     extra or misshapen entry raises and names it, and so does a negative linear weight (the metric is not a distance then). Returns the
     stripped pair."""
-    alex = {k: v for k, v in _strip(alexnet_sd, "AlexNet checkpoint").items() if not k.startswith("classifier.")}
-    lin = _strip(lin_sd, "LPIPS linear-layer checkpoint")
+    alex = pretrained.strip_module_prefix(alexnet_sd, "AlexNet checkpoint")
+    alex = {k: v for k, v in alex.items() if not k.startswith("classifier.")}
+    lin = pretrained.strip_module_prefix(lin_sd, "LPIPS linear-layer checkpoint")
     alex_shapes, lin_shapes = param_shapes()
-    _check(alex, alex_shapes, "AlexNet checkpoint")
-    _check(lin, lin_shapes, "LPIPS linear-layer checkpoint")
+    pretrained.check_entries(alex, alex_shapes, "AlexNet checkpoint")
+    pretrained.check_entries(lin, lin_shapes, "LPIPS linear-layer checkpoint")
     for k in lin_shapes:
         if not bool((lin[k] >= 0).all()):
             raise ValueError(f"LPIPS linear-layer checkpoint entry {k!r} has a negative weight (min {float(lin[k].min()):g})")
@@ -116,21 +97,14 @@ def check_size(height, width):
 
 
 # ---- kernels (ctypes binding of include/perceptual.h) ---------------------------------------------------------------------------------
-def _f32(t, name, shape=None):
-    _C._require_device(t, name)
-    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
-                           f", got {t.dtype} {tuple(t.shape)}")
-    return t.data_ptr()
-
-
 def prepare(x, y):
     """gsr_lpips_prepare: x, y [B, 3, H, W] in [0, 1] -> the network batch [2B, 3, H, W] (x's rows, then y's), scaled. One launch."""
     B, _, H, W = (int(s) for s in x.shape)
-    _f32(x, "x", (B, 3, H, W))
-    _f32(y, "y", (B, 3, H, W))
+    _C.dev_f32(x, "x", (B, 3, H, W))
+    _C.dev_f32(y, "y", (B, 3, H, W))
     out = torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=x.device)
-    _C.load_library().gsr_lpips_prepare(B, H, W, x.data_ptr(), y.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
+    with torch.cuda.device(x.device):
+        _C.load_library().gsr_lpips_prepare(B, H, W, x.data_ptr(), y.data_ptr(), out.data_ptr(), _C._stream(x.device))
     return out
 
 
@@ -145,22 +119,18 @@ def distance(feats, lins, norm="torchmetrics", workspaces=None):
     chw = []
     for l, (f, w) in enumerate(zip(feats, lins)):
         n, c, h, wd = (int(s) for s in f.shape)
-        _f32(f, f"feats[{l}]", (2 * B, c, h, wd))
-        _f32(w, f"lins[{l}]", (c,))
+        _C.dev_f32(f, f"feats[{l}]", (2 * B, c, h, wd))
+        _C.dev_f32(w, f"lins[{l}]", (c,))
         chw += [c, h, wd]
     nl, dev = len(feats), feats[0].device
     L = _C.load_library()
     chw_c = (C.c_int * len(chw))(*chw)
-    key = (B, tuple(chw), dev)
-    ws = None if workspaces is None else workspaces.get(key)
-    if ws is None:
-        ws = torch.empty(L.gsr_lpips_workspace_size(B, nl, chw_c), dtype=torch.uint8, device=dev)
-        if workspaces is not None:
-            workspaces[key] = ws
+    ws = pretrained.workspace(workspaces, (B, tuple(chw), dev), L.gsr_lpips_workspace_size(B, nl, chw_c), dev)
     taps = torch.empty((B, nl), dtype=torch.float32, device=dev)
     scores = torch.empty(B, dtype=torch.float32, device=dev)
-    L.gsr_lpips_distance(B, nl, chw_c, (C.c_void_p * nl)(*[f.data_ptr() for f in feats]), (C.c_void_p * nl)(*[w.data_ptr() for w in lins]),
-                         NORMS[norm], ws.data_ptr(), taps.data_ptr(), scores.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        L.gsr_lpips_distance(B, nl, chw_c, (C.c_void_p * nl)(*[f.data_ptr() for f in feats]), (C.c_void_p * nl)(*[w.data_ptr() for w in lins]),
+                             NORMS[norm], ws.data_ptr(), taps.data_ptr(), scores.data_ptr(), _C._stream(dev))
     return taps, scores
 
 
@@ -186,7 +156,7 @@ def distance_torch(feats, lins, norm="torchmetrics"):
 class Lpips:
     """LPIPS (AlexNet) on one device: ``lpips(x, y)`` scores image pairs [B, 3, H, W] in [0, 1] and returns [B] on the device."""
 
-    _loaded = {}                  # (both paths and mtimes, device, norm) -> metric: the checkpoints are read once per process
+    _loaded = {}                  # pretrained.load_once: the checkpoints are read once per process
 
     def __init__(self, alexnet_state_dict, lin_state_dict, device="cuda:0", norm="torchmetrics"):
         if norm not in NORMS:
@@ -198,18 +168,13 @@ class Lpips:
                       for idx, _, _, _, stride, pad, pool in CONVS]
         self.lins = [to(lin[f"lin{l}.model.1.weight"]).reshape(-1) for l in range(len(CHANNELS))]
         self._ws = {}
-        self._events = []
+        self._log = pretrained.EventLog(self.device)
         self.pairs = 0
 
     @classmethod
     def from_checkpoints(cls, alexnet_path, lin_path, device="cuda:0", norm="torchmetrics"):
-        paths = tuple(os.path.realpath(p) for p in (alexnet_path, lin_path))
-        key = (paths, tuple(os.path.getmtime(p) for p in paths), str(torch.device(device)), norm)
-        hit = cls._loaded.get(key)
-        if hit is None:
-            alex, lin = (torch.load(p, map_location="cpu", weights_only=True) for p in paths)
-            hit = cls._loaded[key] = cls(alex, lin, device, norm)
-        return hit
+        build = lambda *paths: cls(*(torch.load(p, map_location="cpu", weights_only=True) for p in paths), device, norm)
+        return pretrained.load_once(cls._loaded, (alexnet_path, lin_path), device, norm, build)
 
     def features(self, batch):
         """The five taps of the scaled network batch [N, 3, H, W]."""
@@ -232,16 +197,11 @@ class Lpips:
         if self.device.type == "cpu":
             means, scores = distance_torch(self.features(prepare_torch(x, y)), self.lins, self.norm)
         else:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("Lpips.forward was called while the current stream is capturing a graph: score images outside capture")
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record()
-            # deterministic convolution algorithms: the same pair gives the same bits on every call
-            with torch.backends.cudnn.flags(enabled=torch.backends.cudnn.enabled, benchmark=False, deterministic=True):
-                feats = [f.contiguous() for f in self.features(prepare(x, y))]
-            means, scores = distance(feats, self.lins, self.norm, self._ws)
-            end.record()
-            self._events.append((start, end, int(x.shape[0])))
+            pretrained.refuse_capture("Lpips.forward", "score images outside capture")
+            with self._log.timed(count=int(x.shape[0])):
+                with pretrained.deterministic_convolutions():
+                    feats = [f.contiguous() for f in self.features(prepare(x, y))]
+                means, scores = distance(feats, self.lins, self.norm, self._ws)
         self.pairs += int(x.shape[0])
         return (scores, means) if taps else scores
 
@@ -250,9 +210,6 @@ class Lpips:
     @property
     def stats(self):
         """Pairs scored and the device ms per pair (network + kernels), from device events around every call. Waits for the last call."""
-        if self._events:
-            self._events[-1][1].synchronize()
-        ms = [s.elapsed_time(e) for s, e, _ in self._events]
-        n = sum(b for _, _, b in self._events)
-        return {"pairs": self.pairs, "calls": len(ms), "norm": self.norm, "ms_per_pair": float(sum(ms) / n) if n else None,
-                "ms_first_call": ms[0] if ms else None, "ms_per_pair_rest": float(sum(ms[1:]) / (n - self._events[0][2])) if len(ms) > 1 else None}
+        t = self._log.summary()
+        return {"pairs": self.pairs, "calls": t["calls"], "norm": self.norm, "ms_per_pair": t["ms_per_item"],
+                "ms_first_call": t["ms_first"], "ms_per_pair_rest": t["ms_per_item_rest"]}

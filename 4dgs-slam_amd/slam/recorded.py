@@ -259,6 +259,7 @@ class RecordedRGBDDataset:
                  seg_classes=None):
         import torch
         from .camera import getProjectionMatrix2
+        from .pretrained import EventLog
         if max_frames is not None:
             frames = frames.sliced(0, min(int(max_frames), len(frames)))
         if len(frames) == 0:
@@ -294,12 +295,12 @@ class RecordedRGBDDataset:
         if flow is not None:
             self._flow_token = object()                 # names this dataset's frames in the estimator's encoder cache
             self._flow_cache = collections.OrderedDict()
-            self._flow_events = []
+            self._flow_log = EventLog(self.device)
             self.gt_flow = self._gt_flow
         self._segmenter = segmenter if seg_classes else None
         self.seg_classes = list(seg_classes) if self._segmenter is not None else None
         self._seg_cache = collections.OrderedDict()   # frame -> its motion mask with the instance masks cleared
-        self._seg_events = []
+        self._seg_log = EventLog(self.device)
 
     def __len__(self):
         return self.num_imgs
@@ -325,12 +326,9 @@ class RecordedRGBDDataset:
         if hit is None:
             a, b = sorted((int(idx_from), int(idx_to)))
             est = self._flow
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record()
             image = lambda i: None if (self._flow_token, i) in est._enc else self._frame_image(i)
-            fab, fba = est.pair(image(a), image(b), key_i=(self._flow_token, a), key_j=(self._flow_token, b))
-            end.record()
-            self._flow_events.append((start, end))
+            with self._flow_log.timed():
+                fab, fba = est.pair(image(a), image(b), key_i=(self._flow_token, a), key_j=(self._flow_token, b))
             valid = torch.ones((self.height, self.width), dtype=torch.bool, device=self.device)
             while len(self._flow_cache) >= 2 * self.FLOW_CACHE_PAIRS:
                 self._flow_cache.popitem(last=False)
@@ -344,22 +342,17 @@ class RecordedRGBDDataset:
         """Pairs estimated and the device ms per pair (None without an estimator)."""
         if self._flow is None:
             return None
-        ms = [s.elapsed_time(e) for s, e in self._flow_events] if self._flow_events else []
-        if ms:
-            self._flow_events[-1][1].synchronize()
-        return {"pairs": len(ms), "ms_per_pair": float(np.mean(ms)) if ms else None, "ms_first": ms[0] if ms else None,
-                "ms_rest_mean": float(np.mean(ms[1:])) if len(ms) > 1 else None}
+        t = self._flow_log.summary()
+        return {"pairs": t["calls"], "ms_per_pair": t["ms_per_item"], "ms_first": t["ms_first"], "ms_rest_mean": t["ms_per_item_rest"]}
 
     @property
     def segmentation_stats(self):
         """Frames segmented and the device ms per frame (network + post-processing; None without a segmenter)."""
         if self._segmenter is None:
             return None
-        if self._seg_events:
-            self._seg_events[-1][1].synchronize()
-        ms = [s.elapsed_time(e) for s, e in self._seg_events]
-        return {"frames": len(ms), "classes": self.seg_classes, "ms_per_frame": float(np.mean(ms)) if ms else None,
-                "ms_first": ms[0] if ms else None, "ms_rest_mean": float(np.mean(ms[1:])) if len(ms) > 1 else None}
+        t = self._seg_log.summary()
+        return {"frames": t["calls"], "classes": self.seg_classes, "ms_per_frame": t["ms_per_item"], "ms_first": t["ms_first"],
+                "ms_rest_mean": t["ms_per_item_rest"]}
 
     def _frame_image(self, idx):
         """Frame idx's image [3,H,W] without moving the read-ahead window (a keyframe the flow term needs again); never segmented."""
@@ -404,11 +397,8 @@ class RecordedRGBDDataset:
             motion = torch.empty((H, W), dtype=torch.bool, device=dev)
             frame_io.frame_prepare(rgb, self._map, self._lut, mask, MASK_THRESHOLD, image, motion, self._side)
             if segment:                                 # YOLO on the prepared frame; motion &= ~(instance masks), in place
-                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                start.record(self._side)
-                self._segmenter(image, self.seg_classes, motion=motion)
-                end.record(self._side)
-                self._seg_events.append((start, end))
+                with self._seg_log.timed(self._side):
+                    self._segmenter(image, self.seg_classes, motion=motion)
             ready = torch.cuda.Event()
             ready.record(self._side)
         main.wait_event(ready)

@@ -11,7 +11,6 @@ The post-processing is HIP (include/segmentation.h, csrc/gs_yolo.h): DFL decode,
 masks' crop, bilinear upsampling and threshold, folded into the motion mask in place, in five launches with no host round trip."""
 import ctypes as C
 import io
-import os
 import pickle
 from typing import NamedTuple
 
@@ -20,6 +19,7 @@ import torch.nn.functional as F
 
 from diff_gaussian_rasterization import _C
 from diff_gaussian_rasterization._abi import GSR_YOLO_DET_HEAD, GSR_YOLO_MAX_ANCHORS, GSR_YOLO_MAX_LEVELS, GSR_YOLO_REG_MAX
+from . import pretrained
 
 CONF, IOU, MAX_DET = 0.25, 0.7, 300          # ultralytics predictor defaults
 PERSON, CHAIR, CLOCK, TEDDY_BEAR = 0, 56, 74, 77
@@ -284,14 +284,6 @@ class Segmentation(NamedTuple):
     counts: torch.Tensor          # int32 [3]: detections, candidates, NMS survivors before max_det
 
 
-def _dev_f32(t, name, shape=None):
-    _C._require_device(t, name)
-    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
-                           f", got {t.dtype} {tuple(t.shape)}")
-    return t.data_ptr()
-
-
 def check_size(height, width):
     if height % 32 or width % 32 or height <= 0 or width <= 0:
         raise ValueError(f"a {width}x{height} image: YOLO takes a tensor source as it is, so both sides must be multiples of 32 "
@@ -302,7 +294,7 @@ class YoloSeg:
     """A YOLO instance-segmentation model on one device: ``seg(image, classes, motion)`` runs the network on a [3, H, W] image in [0, 1]
     and folds the union of the instance masks of the requested COCO classes into ``motion`` (motion &= ~yolo)."""
 
-    _loaded = {}                  # (checkpoint path, mtime, device) -> model: a checkpoint is read once per process
+    _loaded = {}                  # pretrained.load_once: a checkpoint is read once per process
 
     def __init__(self, model, device="cuda:0", conf=CONF, iou=IOU, max_det=MAX_DET):
         self.device = torch.device(device)
@@ -330,33 +322,26 @@ class YoloSeg:
 
     @classmethod
     def from_checkpoint(cls, path, device="cuda:0", **kw):
-        path = os.path.realpath(path)
-        key = (path, os.path.getmtime(path), str(torch.device(device)))
-        hit = cls._loaded.get(key)
-        if hit is None:
+        def build(path):
             ckpt = load_checkpoint(path)
             if not isinstance(ckpt, dict):
                 raise ValueError(f"{path}: expected an ultralytics checkpoint dict, got {type(ckpt).__name__}")
             model = ckpt.get("ema") or ckpt.get("model")
             if model is None:
                 raise ValueError(f"{path}: the checkpoint has neither 'ema' nor 'model'")
-            hit = cls._loaded[key] = cls(model, device, **kw)
-        return hit
-
-    def _check_call(self, who):
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"YoloSeg.{who} was called while the current stream is capturing a graph: segment frames before capture")
+            return cls(model, device, **kw)
+        return pretrained.load_once(cls._loaded, [path], device, None, build)
 
     @torch.no_grad()
     def forward(self, image):
         """The network on one image [3, H, W] float in [0, 1]: (per level (head [64 + nc, h, w], coef [nm, h, w]), proto [nm, H/4, W/4])."""
-        self._check_call("forward")
+        pretrained.refuse_capture("YoloSeg.forward", "segment frames before capture")
         if image.dim() != 3 or image.shape[0] != 3:
             raise ValueError(f"expected a [3, H, W] image, got {tuple(image.shape)}")
         check_size(int(image.shape[1]), int(image.shape[2]))
         x = image.to(self.device, torch.float32)[None]
         y = []
-        with torch.backends.cudnn.flags(enabled=torch.backends.cudnn.enabled, benchmark=False, deterministic=True):
+        with pretrained.deterministic_convolutions():
             for f, i, fn in self.layers:
                 if f != -1:
                     x = y[f] if isinstance(f, int) else [x if j == -1 else y[j] for j in f]
@@ -368,7 +353,6 @@ class YoloSeg:
     def postprocess(self, head_outputs, proto, classes, motion=None):
         """The HIP post-processing of given head tensors: per level (head [64 + nc, h, w], coef [nm, h, w]) and proto [nm, H/4, W/4].
         classes: COCO ids. motion: [H, W] bool on the device, cleared where the union is set (in place), or None."""
-        self._check_call("postprocess")
         return postprocess(head_outputs, proto, classes, self.stride, motion, self.conf, self.iou, self.max_det, self._ws)
 
     def __call__(self, image, classes, motion=None):
@@ -380,8 +364,7 @@ class YoloSeg:
 
 def postprocess(head_outputs, proto, classes, strides, motion=None, conf=CONF, iou=IOU, max_det=MAX_DET, workspaces=None):
     """The functional form of YoloSeg.postprocess (strides: the level strides in pixels)."""
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("yolo postprocess was called while the current stream is capturing a graph")
+    pretrained.refuse_capture("yolo postprocess", "segment frames before capture")
     classes = sorted({int(c) for c in classes})
     nl = len(head_outputs)
     if not classes or nl != len(strides) or not 1 <= nl <= GSR_YOLO_MAX_LEVELS:
@@ -389,24 +372,20 @@ def postprocess(head_outputs, proto, classes, strides, motion=None, conf=CONF, i
     nm, ph, pw = (int(s) for s in proto.shape)
     H, W = 4 * ph, 4 * pw
     check_size(H, W)
-    _dev_f32(proto, "proto")
+    _C.dev_f32(proto, "proto")
     nc = int(head_outputs[0][0].shape[0]) - 4 * GSR_YOLO_REG_MAX
     hw, heads, coefs = [], [], []
     for l, (h, c) in enumerate(head_outputs):
         _, lh, lw = (int(s) for s in h.shape)
-        heads.append(_dev_f32(h, f"head[{l}]", (4 * GSR_YOLO_REG_MAX + nc, lh, lw)))
-        coefs.append(_dev_f32(c, f"coef[{l}]", (nm, lh, lw)))
+        heads.append(_C.dev_f32(h, f"head[{l}]", (4 * GSR_YOLO_REG_MAX + nc, lh, lw)))
+        coefs.append(_C.dev_f32(c, f"coef[{l}]", (nm, lh, lw)))
         hw += [lh, lw]
     anchors = sum(hw[2 * l] * hw[2 * l + 1] for l in range(nl))
     if anchors > GSR_YOLO_MAX_ANCHORS:
         raise ValueError(f"{anchors} anchors: at most {GSR_YOLO_MAX_ANCHORS} are supported")
     dev = proto.device
     L = _C.load_library()
-    ws = None if workspaces is None else workspaces.get((anchors, dev))
-    if ws is None:
-        ws = torch.empty(L.gsr_yolo_workspace_size(anchors), dtype=torch.uint8, device=dev)
-        if workspaces is not None:
-            workspaces[(anchors, dev)] = ws
+    ws = pretrained.workspace(workspaces, (anchors, dev), L.gsr_yolo_workspace_size(anchors), dev)
     max_dets = max_det * len(classes)
     dets = torch.empty((max_dets, GSR_YOLO_DET_HEAD + nm), dtype=torch.float32, device=dev)
     counts = torch.empty(3, dtype=torch.int32, device=dev)
@@ -415,12 +394,13 @@ def postprocess(head_outputs, proto, classes, strides, motion=None, conf=CONF, i
         _C._require_device(motion, "motion")
         if motion.dtype not in (torch.bool, torch.uint8) or not motion.is_contiguous() or tuple(motion.shape) != (H, W):
             raise RuntimeError(f"motion must be a contiguous bool [{H}, {W}] device tensor, got {motion.dtype} {tuple(motion.shape)}")
-    s = torch.cuda.current_stream(dev).cuda_stream
-    L.gsr_yolo_detect(nl, (C.c_int * (2 * nl))(*hw), (C.c_float * nl)(*[float(x) for x in strides]), (C.c_void_p * nl)(*heads),
-                      (C.c_void_p * nl)(*coefs), nc, nm, (C.c_int * len(classes))(*classes), len(classes), float(conf), float(iou),
-                      int(max_det), ws.data_ptr(), dets.data_ptr(), max_dets, counts.data_ptr(), s)
-    L.gsr_yolo_masks(max_dets, dets.data_ptr(), counts.data_ptr(), nm, proto.data_ptr(), ph, pw, H, W, mask.data_ptr(),
-                     None if motion is None else motion.data_ptr(), s)
+    with torch.cuda.device(dev):
+        s = _C._stream(dev)
+        L.gsr_yolo_detect(nl, (C.c_int * (2 * nl))(*hw), (C.c_float * nl)(*[float(x) for x in strides]), (C.c_void_p * nl)(*heads),
+                          (C.c_void_p * nl)(*coefs), nc, nm, (C.c_int * len(classes))(*classes), len(classes), float(conf), float(iou),
+                          int(max_det), ws.data_ptr(), dets.data_ptr(), max_dets, counts.data_ptr(), s)
+        L.gsr_yolo_masks(max_dets, dets.data_ptr(), counts.data_ptr(), nm, proto.data_ptr(), ph, pw, H, W, mask.data_ptr(),
+                         None if motion is None else motion.data_ptr(), s)
     return Segmentation(mask, dets, counts)
 
 
@@ -429,12 +409,12 @@ def masks_from_dets(dets, counts, proto, motion=None):
     nm, ph, pw = (int(s) for s in proto.shape)
     H, W = 4 * ph, 4 * pw
     check_size(H, W)
-    _dev_f32(proto, "proto")
-    _dev_f32(dets, "dets", (int(dets.shape[0]), GSR_YOLO_DET_HEAD + nm))
+    _C.dev_f32(proto, "proto")
+    _C.dev_f32(dets, "dets", (int(dets.shape[0]), GSR_YOLO_DET_HEAD + nm))
     mask = torch.empty((H, W), dtype=torch.uint8, device=proto.device)
-    _C.load_library().gsr_yolo_masks(int(dets.shape[0]), dets.data_ptr(), counts.data_ptr(), nm, proto.data_ptr(), ph, pw, H, W,
-                                      mask.data_ptr(), None if motion is None else motion.data_ptr(),
-                                      torch.cuda.current_stream(proto.device).cuda_stream)
+    with torch.cuda.device(proto.device):
+        _C.load_library().gsr_yolo_masks(int(dets.shape[0]), dets.data_ptr(), counts.data_ptr(), nm, proto.data_ptr(), ph, pw, H, W,
+                                          mask.data_ptr(), None if motion is None else motion.data_ptr(), _C._stream(proto.device))
     return mask
 
 

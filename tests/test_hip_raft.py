@@ -266,6 +266,13 @@ def test_dynamic_tum_sequence_with_raft_flow(tmp_path, golden):
     print(res, ds.flow_stats, len(targets6), len(targets))
     assert ds.flow_stats["pairs"] > 0 and est.pairs == ds.flow_stats["pairs"]
     assert len(targets6) + len(targets) > 0                                  # the flow term ran
+    # flow_stats right after an estimate, with no synchronisation in between: it waits for the last pair itself
+    ds._flow_cache.clear()
+    pairs = est.pairs
+    ds.gt_flow(0, 1)
+    st = ds.flow_stats
+    assert st["pairs"] == est.pairs == pairs + 1
+    assert all(np.isfinite(st[k]) and st[k] > 0 for k in ("ms_per_pair", "ms_first", "ms_rest_mean")), st
     assert np.isfinite(res["ate_rmse"]) and np.isfinite(res["before_opt"]["mean_psnr"]), res
     # each cached target is pair() on the two keyframe images, masked by the keyframes' motion masks
     checked = 0
