@@ -1003,8 +1003,7 @@ static int backward_impl(const Call& c, int P, int D, int M, int R, const float*
 // ---- HexPlane feature field (include/deformation_field.h) -------------------------------------------------------------------
 static int hexplane_check(const gsr_hexplane_field* f, int64_t n, const float* xyz, const float* time, const char* who)
 {
-    static thread_local std::string msg;
-    auto fail = [&](const char* what) { msg = std::string(who) + ": " + what; g_last_error = msg.c_str(); return GSR_ERR_INVALID_ARGUMENT; };
+    auto fail = [&](const char* what) { g_last_error = std::string(who) + ": " + what; return GSR_ERR_INVALID_ARGUMENT; };
     if (!f) return fail("null field descriptor");
     if (n < 0) return fail("negative point count");
     if (f->num_levels < 1 || f->num_levels > GSR_HEXPLANE_MAX_LEVELS) return fail("num_levels outside 1..8");
@@ -1046,6 +1045,18 @@ static void hexplane_launch(const gsr_hexplane_field& f, int64_t n, hipStream_t 
 #undef GSR_HEX_CASE
 }
 
+// Carves the workspace of the field's sorted backward passes (a member template: outside the C-linkage block). Regions of 256-byte granularity
+// taken in order from the caller's buffer; a null base yields null pointers and the same offsets (size queries).
+struct HexCarver {
+    char* base;
+    size_t off;
+    template <typename T> T* take(size_t count)
+    {
+        char* p = base ? base + off : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return reinterpret_cast<T*>(p);
+    }
+};
 
 extern "C" {
 
@@ -1493,86 +1504,125 @@ static void hexsort_plan(const gsr_hexplane_field& f, HexSortPlan* P)
         while ((1 << b) < r) b++;
         P->bits[k] = b;
     }
-    static const int C0[6] = {0, 0, 0, 1, 1, 2}, C1[6] = {1, 2, 3, 2, 3, 3};   // itertools.combinations(range(4), 2)
     int off = 0;
     for (int pl = 0; pl < 6; pl++) {
         // every call of the reference passes ONE time for all points (gaussian_renderer/__init__.py:112): the time families then use a
         // single row of cells, n / 512 points per cell -- give them 16 sub-counters per cell (the spatial families: 2), up to 2^20 counters
-        const int cell_bits = P->bits[C0[pl]] + P->bits[C1[pl]];
-        P->sub_bits[pl] = std::max(0, std::min(C1[pl] == 3 ? 4 : 1, 20 - cell_bits));
+        const int cell_bits = P->bits[hex_c0(pl)] + P->bits[hex_c1(pl)];
+        P->sub_bits[pl] = std::max(0, std::min(hex_c1(pl) == 3 ? 4 : 1, 20 - cell_bits));
         P->key_off[pl] = off;
         off += 1 << (cell_bits + P->sub_bits[pl]);
     }
     P->key_off[6] = off;
 }
 
-// Ordered mode (HexOrd): where the planes' fixed-point sums live. `plane_mask`: the planes the generic walk scatters into (all six, or the three
-// spatial ones of the batched-views path, whose time families keep column sums per view instead: V > 0). Returns the elements of acc / acc_t.
-static void hexord_plan(const gsr_hexplane_field& f, int64_t n, int V, int plane_mask, HexOrd* o, size_t* acc_elems, size_t* acct_elems)
+// ---- the workspace of the sorted backward passes -------------------------------------------------------------------------------
+// What one sorted backward call keeps in its workspace: the sort's regions, the route's own staging of dL/dsample (ws.gs, or vw), the ordered sums.
+struct HexBwdWs {
+    HexSortPlan P;
+    HexSortWs ws;
+    HexViewsWs vw;          // batched views only
+    HexOrd ord;             // acc null: float atomics
+    size_t ord_bytes;       // of acc and acc_t, one region (one memset)
+    size_t total;           // of the whole workspace
+};
+
+// The planes the generic walk scatters into: all six, or the three spatial ones of the batched views (their time families keep column sums per view)
+constexpr int HEX_ALL_PLANES = 63, HEX_SPATIAL_PLANES = (1 << 0) | (1 << 1) | (1 << 3);
+
+static void hexsort_carve_head(HexCarver& c, const gsr_hexplane_field& f, int64_t n, HexBwdWs* L)
 {
-    static const int C0[6] = {0, 0, 0, 1, 1, 2}, C1[6] = {1, 2, 3, 2, 3, 3};
-    HexOrd h{};
-    size_t off = 0;
-    for (int l = 0; l < f.num_levels; l++)
-        for (int pl = 0; pl < 6; pl++) {
-            h.off[l][pl] = off;
-            if ((plane_mask >> pl) & 1) off +=          // (whether or not the plane's gradient is asked for: the size must not depend on it)
-                (size_t)f.levels[l].res[C0[pl]] * f.levels[l].res[C1[pl]] * f.feat_dim;
-        }
-    size_t rows = 0;
-    if (V > 0)
-        for (int j = 0; j < 3; j++) {
-            uint32_t cols = 0;
-            for (int l = 0; l < f.num_levels; l++) { h.tcol[j][l] = cols; cols += (uint32_t)f.levels[l].res[j]; }
-            h.tcols[j] = cols;
-            h.tbase[j] = (uint32_t)rows;
-            rows += (size_t)V * cols;
-        }
-    // a texel receives at most 4 n contributions (four cells, every point once: the views are summed before): the largest one is scaled to just
-    // below 2^budget, the sum stays below 2^62; 40 bits at most, so that HEXSORT_CHUNK of them stay exact in a double
-    int lg = 0;
-    while (((int64_t)1 << lg) < 4 * std::max<int64_t>(n, 1)) lg++;
-    h.budget = std::min(40, 62 - lg);
-    if (o) *o = h;
-    if (acc_elems) *acc_elems = off;
-    if (acct_elems) *acct_elems = rows * f.feat_dim;
+    hexsort_plan(f, &L->P);
+    const size_t nb = (size_t)L->P.key_off[6];
+    HexSortWs& w = L->ws;
+    w.count = c.take<uint32_t>(nb);
+    w.block_sums = c.take<uint32_t>(nb / (1024 * HEXSORT_SCAN_ITEMS) + 1);
+    w.header = c.take<uint32_t>(64);
+    w.coords = c.take<float4>((size_t)n);
+    w.key = c.take<uint32_t>((size_t)6 * n);
+    w.rank = c.take<int>((size_t)6 * n);
+    w.scoords = c.take<float4>((size_t)6 * n);
 }
 
-static size_t hexsort_carve(const gsr_hexplane_field& f, const HexSortPlan& P, int64_t n, char* base, HexSortWs* ws, HexOrd* ord = nullptr,
-                            size_t* ord_bytes = nullptr)
+// Ordered mode (HexOrd): where the fixed-point sums of the planes in `plane_mask` live and, for the V > 0 views of the batched path, the time
+// families' column sums. Closes the carve.
+static void hexord_carve_tail(HexCarver& c, const gsr_hexplane_field& f, int64_t n, int V, int plane_mask, bool ordered, HexBwdWs* L)
 {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    const size_t nb = (size_t)P.key_off[6];
-    HexSortWs w;
-    w.count = reinterpret_cast<uint32_t*>(take(nb * sizeof(uint32_t)));
-    w.block_sums = reinterpret_cast<uint32_t*>(take((nb / (1024 * HEXSORT_SCAN_ITEMS) + 1) * sizeof(uint32_t)));
-    w.header = reinterpret_cast<uint32_t*>(take(256));
-    w.coords = reinterpret_cast<float4*>(take((size_t)n * sizeof(float4)));
-    w.key = reinterpret_cast<uint32_t*>(take((size_t)6 * n * sizeof(uint32_t)));
-    w.rank = reinterpret_cast<int*>(take((size_t)6 * n * sizeof(int)));
-    w.scoords = reinterpret_cast<float4*>(take((size_t)6 * n * sizeof(float4)));
-    w.gs = reinterpret_cast<float*>(take((size_t)6 * n * f.num_levels * f.feat_dim * sizeof(float)));
-    if (g_hex_ordered.load()) {
-        HexOrd h;
-        size_t elems;
-        hexord_plan(f, n, 0, 63, &h, &elems, nullptr);
-        h.acc = reinterpret_cast<unsigned long long*>(take(elems * sizeof(unsigned long long)));
-        if (ord) *ord = h;
-        if (ord_bytes) *ord_bytes = elems * sizeof(unsigned long long);
-    } else if (ord) {
-        *ord = HexOrd{};
+    if (ordered) {
+        HexOrd& h = L->ord;
+        size_t elems = 0, rows = 0;
+        for (int l = 0; l < f.num_levels; l++)
+            for (int pl = 0; pl < 6; pl++) {
+                h.off[l][pl] = elems;
+                if ((plane_mask >> pl) & 1) elems +=    // (whether or not the plane's gradient is asked for: the size must not depend on it)
+                    (size_t)f.levels[l].res[hex_c0(pl)] * f.levels[l].res[hex_c1(pl)] * f.feat_dim;
+            }
+        if (V > 0)
+            for (int j = 0; j < 3; j++) {
+                uint32_t cols = 0;
+                for (int l = 0; l < f.num_levels; l++) { h.tcol[j][l] = cols; cols += (uint32_t)f.levels[l].res[j]; }
+                h.tcols[j] = cols;
+                h.tbase[j] = (uint32_t)rows;
+                rows += (size_t)V * cols;
+            }
+        // a texel receives at most 4 n contributions (four cells, every point once: the views are summed before): the largest one is scaled to just
+        // below 2^budget, the sum stays below 2^62; 40 bits at most, so that HEXSORT_CHUNK of them stay exact in a double
+        int lg = 0;
+        while (((int64_t)1 << lg) < 4 * std::max<int64_t>(n, 1)) lg++;
+        h.budget = std::min(40, 62 - lg);
+        const size_t all = elems + rows * f.feat_dim;
+        h.acc = c.take<unsigned long long>(all);
+        if (V > 0 && h.acc) h.acc_t = h.acc + elems;
+        L->ord_bytes = all * sizeof(unsigned long long);
     }
-    if (ws) *ws = w;
-    return off + 256;
+    L->total = c.off + 256;
+}
+
+static HexBwdWs hexsort_carve(const gsr_hexplane_field& f, int64_t n, bool ordered, char* base)
+{
+    HexBwdWs L{};
+    HexCarver c{base, 0};
+    hexsort_carve_head(c, f, n, &L);
+    L.ws.gs = c.take<float>((size_t)6 * n * f.num_levels * f.feat_dim);
+    hexord_carve_tail(c, f, n, 0, HEX_ALL_PLANES, ordered, &L);
+    return L;
+}
+
+static int hexsort_check_workspace(const char* who, const HexBwdWs& L, size_t workspace_bytes)
+{
+    if (workspace_bytes >= L.total) return 0;
+    g_last_error = std::string(who) + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(L.total) +
+                   " needed (was \"hex_ordered\" set after the size query?)";
+    return GSR_ERR_INVALID_ARGUMENT;
+}
+
+// How both sorted passes begin: clear the counters (ordered mode: the header's maximum and the sums too), count, scan, move the points into
+// sorted order. The single-time pass gives time and dL_dfeatures, the batched one its view_mask.
+static int hexsort_prologue(const gsr_hexplane_field& f, const HexBwdWs& L, int64_t n, const float* xyz, int64_t xyz_stride, const float* time,
+                            int64_t time_stride, const float* dL_dfeatures, const uint32_t* view_mask, hipStream_t stream)
+{
+    const HexSortWs& ws = L.ws;
+    const int nb = L.P.key_off[6], scan_blocks = (nb + 1024 * HEXSORT_SCAN_ITEMS - 1) / (1024 * HEXSORT_SCAN_ITEMS);
+    GSR_HIP_CHECK(hipMemsetAsync(ws.count, 0, (size_t)nb * sizeof(uint32_t), stream));
+    if (L.ord.acc) {
+        GSR_HIP_CHECK(hipMemsetAsync(ws.header, 0, 256, stream));
+        GSR_HIP_CHECK(hipMemsetAsync(L.ord.acc, 0, L.ord_bytes, stream));
+    }
+    hipLaunchKernelGGL(hexsort_count_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, f, L.P, ws, n, xyz, xyz_stride, time, time_stride,
+                       dL_dfeatures, view_mask);
+    hipLaunchKernelGGL(hexsort_scan_sums_kernel, dim3(scan_blocks), dim3(1024), 0, stream, (const uint32_t*)ws.count, nb, ws.block_sums);
+    hipLaunchKernelGGL(hexsort_scan_top_kernel, dim3(1), dim3(1024), 0, stream, ws.block_sums, scan_blocks, ws.header);
+    hipLaunchKernelGGL(hexsort_scan_apply_kernel, dim3(scan_blocks), dim3(1024), 0, stream, ws.count, nb, (const uint32_t*)ws.block_sums);
+    hipLaunchKernelGGL(hexsort_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, n);
+    return 0;
 }
 
 static void hexord_convert(const gsr_hexplane_field& f, const HexOrd& ord, const uint32_t* header, int plane_mask, hipStream_t stream)
 {
     size_t largest = 0;
     for (int l = 0; l < f.num_levels; l++)
-        for (int a = 0; a < 4; a++)
-            for (int b = a + 1; b < 4; b++) largest = std::max(largest, (size_t)f.levels[l].res[a] * f.levels[l].res[b] * f.feat_dim);
+        for (int pl = 0; pl < 6; pl++)
+            largest = std::max(largest, (size_t)f.levels[l].res[hex_c0(pl)] * f.levels[l].res[hex_c1(pl)] * f.feat_dim);
     hipLaunchKernelGGL(hexord_convert_kernel, dim3((unsigned)((largest + 511) / 512), (unsigned)(6 * f.num_levels)), dim3(256), 0, stream, f, ord, header,
                        plane_mask);
 }
@@ -1588,13 +1638,11 @@ static bool hexsort_supported(const gsr_hexplane_field& f, int64_t n)
 size_t gsr_hexplane_backward_workspace_size(const gsr_hexplane_field* field, int64_t n)
 {
     if (!field || n <= 0 || field->num_levels < 1 || field->num_levels > GSR_HEXPLANE_MAX_LEVELS || !hexsort_supported(*field, n)) return 256;
-    HexSortPlan P;
-    hexsort_plan(*field, &P);
-    return hexsort_carve(*field, P, n, nullptr, nullptr);
+    return hexsort_carve(*field, n, g_hex_ordered.load() != 0, nullptr).total;
 }
 
 int gsr_hexplane_backward(const gsr_hexplane_field* field, int64_t n, const float* xyz, int64_t xyz_stride, const float* time,
-                          int64_t time_stride, const float* dL_dfeatures, float* dL_dxyz, char* workspace, void* stream_)
+                          int64_t time_stride, const float* dL_dfeatures, float* dL_dxyz, char* workspace, size_t workspace_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = hexplane_check(field, n, xyz, time, "gsr_hexplane_backward")) return rc;
@@ -1606,26 +1654,12 @@ int gsr_hexplane_backward(const gsr_hexplane_field* field, int64_t n, const floa
         GSR_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    HexSortPlan P;
-    hexsort_plan(f, &P);
-    HexSortWs ws;
-    HexOrd ord;
-    size_t ord_bytes = 0;
-    hexsort_carve(f, P, n, workspace, &ws, &ord, &ord_bytes);
+    const HexBwdWs L = hexsort_carve(f, n, g_hex_ordered.load() != 0, workspace);      // the mode of this call, read once
+    if (int rc = hexsort_check_workspace("gsr_hexplane_backward", L, workspace_bytes)) return rc;
+    if (int rc = hexsort_prologue(f, L, n, xyz, xyz_stride, time, time_stride, dL_dfeatures, nullptr, stream)) return rc;
+    const HexSortWs& ws = L.ws;
+    const HexOrd& ord = L.ord;
     const int ordered = ord.acc != nullptr;
-    const int nb = P.key_off[6], scan_blocks = (nb + 1024 * HEXSORT_SCAN_ITEMS - 1) / (1024 * HEXSORT_SCAN_ITEMS);
-    GSR_HIP_CHECK(hipMemsetAsync(ws.count, 0, (size_t)nb * sizeof(uint32_t), stream));
-    if (ordered) {
-        GSR_HIP_CHECK(hipMemsetAsync(ws.header, 0, 256, stream));
-        GSR_HIP_CHECK(hipMemsetAsync(ord.acc, 0, ord_bytes, stream));
-    }
-    const dim3 per_point((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(hexsort_count_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, f, P, ws, n, xyz, xyz_stride, time, time_stride,
-                       dL_dfeatures, (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(hexsort_scan_sums_kernel, dim3(scan_blocks), dim3(1024), 0, stream, (const uint32_t*)ws.count, nb, ws.block_sums);
-    hipLaunchKernelGGL(hexsort_scan_top_kernel, dim3(1), dim3(1024), 0, stream, ws.block_sums, scan_blocks, ws.header);
-    hipLaunchKernelGGL(hexsort_scan_apply_kernel, dim3(scan_blocks), dim3(1024), 0, stream, ws.count, nb, (const uint32_t*)ws.block_sums);
-    hipLaunchKernelGGL(hexsort_scatter_kernel, per_point, dim3(256), 0, stream, ws, n);
     const int C = f.feat_dim, ppb = HEX_BLOCK / C;
     const dim3 g1((unsigned)((n + ppb - 1) / ppb));
     const int64_t groups = 6 * ((n + HEXSORT_CHUNK - 1) / HEXSORT_CHUNK);
@@ -1644,7 +1678,7 @@ int gsr_hexplane_backward(const gsr_hexplane_field* field, int64_t n, const floa
         break;
     switch (C) { GSR_HEXSORT_CASE(8) GSR_HEXSORT_CASE(16) GSR_HEXSORT_CASE(32) GSR_HEXSORT_CASE(64) }
 #undef GSR_HEXSORT_CASE
-    if (ordered) hexord_convert(f, ord, ws.header, 63, stream);
+    if (ordered) hexord_convert(f, ord, ws.header, HEX_ALL_PLANES, stream);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1655,8 +1689,7 @@ static int hexplane_views_check(const gsr_hexplane_field* f, int64_t n, const fl
     static const float some_time = 0.f;
     if (int rc = hexplane_check(f, n, xyz, &some_time, who)) return rc;
     if (V < 1 || V > GSR_HEXPLANE_MAX_VIEWS || !times) {
-        static thread_local std::string msg;
-        msg = std::string(who) + ": 1 <= V <= GSR_HEXPLANE_MAX_VIEWS times (host pointer) expected"; g_last_error = msg.c_str();
+        g_last_error = std::string(who) + ": 1 <= V <= GSR_HEXPLANE_MAX_VIEWS times (host pointer) expected";
         return GSR_ERR_INVALID_ARGUMENT;
     }
     return 0;
@@ -1691,37 +1724,16 @@ int gsr_hexplane_forward_views(const gsr_hexplane_field* field, int64_t n, const
     return 0;
 }
 
-static size_t hexviews_carve(const gsr_hexplane_field& f, const HexSortPlan& P, int64_t n, int V, char* base, HexSortWs* ws, HexViewsWs* vw,
-                             HexOrd* ord = nullptr, size_t* ord_bytes = nullptr)
+static HexBwdWs hexviews_carve(const gsr_hexplane_field& f, int64_t n, int V, bool ordered, char* base)
 {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    const size_t nb = (size_t)P.key_off[6], row = (size_t)f.num_levels * f.feat_dim;
-    HexSortWs w{};
-    HexViewsWs v{};
-    w.count = reinterpret_cast<uint32_t*>(take(nb * sizeof(uint32_t)));
-    w.block_sums = reinterpret_cast<uint32_t*>(take((nb / (1024 * HEXSORT_SCAN_ITEMS) + 1) * sizeof(uint32_t)));
-    w.header = reinterpret_cast<uint32_t*>(take(256));
-    w.coords = reinterpret_cast<float4*>(take((size_t)n * sizeof(float4)));
-    w.key = reinterpret_cast<uint32_t*>(take((size_t)6 * n * sizeof(uint32_t)));
-    w.rank = reinterpret_cast<int*>(take((size_t)6 * n * sizeof(int)));
-    w.scoords = reinterpret_cast<float4*>(take((size_t)6 * n * sizeof(float4)));
-    v.gs_sp = reinterpret_cast<float*>(take((size_t)3 * n * row * sizeof(float)));
-    v.gs_t = reinterpret_cast<float*>(take((size_t)3 * V * n * row * sizeof(float)));
-    if (g_hex_ordered.load()) {                                     // one region (one memset): the spatial planes' sums, then the time families' column sums
-        HexOrd h;
-        size_t elems, telems;
-        hexord_plan(f, n, V, (1 << 0) | (1 << 1) | (1 << 3), &h, &elems, &telems);
-        h.acc = reinterpret_cast<unsigned long long*>(take((elems + telems) * sizeof(unsigned long long)));
-        h.acc_t = h.acc ? h.acc + elems : nullptr;
-        if (ord) *ord = h;
-        if (ord_bytes) *ord_bytes = (elems + telems) * sizeof(unsigned long long);
-    } else if (ord) {
-        *ord = HexOrd{};
-    }
-    if (ws) *ws = w;
-    if (vw) *vw = v;
-    return off + 256;
+    HexBwdWs L{};
+    HexCarver c{base, 0};
+    hexsort_carve_head(c, f, n, &L);
+    const size_t row = (size_t)f.num_levels * f.feat_dim;
+    L.vw.gs_sp = c.take<float>((size_t)3 * n * row);
+    L.vw.gs_t = c.take<float>((size_t)3 * V * n * row);
+    hexord_carve_tail(c, f, n, V, HEX_SPATIAL_PLANES, ordered, &L);
+    return L;
 }
 
 static bool hexviews_supported(const gsr_hexplane_field& f, int64_t n)
@@ -1734,13 +1746,12 @@ size_t gsr_hexplane_backward_views_workspace_size(const gsr_hexplane_field* fiel
 {
     if (!field || n <= 0 || V < 1 || V > GSR_HEXPLANE_MAX_VIEWS || field->num_levels < 1 || field->num_levels > GSR_HEXPLANE_MAX_LEVELS ||
         !hexviews_supported(*field, n)) return 0;
-    HexSortPlan P;
-    hexsort_plan(*field, &P);
-    return hexviews_carve(*field, P, n, V, nullptr, nullptr, nullptr);
+    return hexviews_carve(*field, n, V, g_hex_ordered.load() != 0, nullptr).total;
 }
 
 int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, const float* xyz, int64_t xyz_stride, int V, const float* times,
-                                const float* dL_dfeatures, const uint32_t* view_mask, float* dL_dxyz, char* workspace, void* stream_)
+                                const float* dL_dfeatures, const uint32_t* view_mask, float* dL_dxyz, char* workspace, size_t workspace_bytes,
+                                void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = hexplane_views_check(field, n, xyz, V, times, "gsr_hexplane_backward_views")) return rc;
@@ -1751,26 +1762,13 @@ int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, cons
         return GSR_ERR_INVALID_ARGUMENT;
     }
     const HexTimes tv = hex_times(V, times);
-    HexSortPlan P;
-    hexsort_plan(f, &P);
-    HexSortWs ws;
-    HexViewsWs vw;
-    HexOrd ord;
-    size_t ord_bytes = 0;
-    hexviews_carve(f, P, n, V, workspace, &ws, &vw, &ord, &ord_bytes);
+    const HexBwdWs L = hexviews_carve(f, n, V, g_hex_ordered.load() != 0, workspace);  // the mode of this call, read once
+    if (int rc = hexsort_check_workspace("gsr_hexplane_backward_views", L, workspace_bytes)) return rc;
+    if (int rc = hexsort_prologue(f, L, n, xyz, xyz_stride, nullptr, 0, nullptr, view_mask, stream)) return rc;
+    const HexSortWs& ws = L.ws;
+    const HexViewsWs& vw = L.vw;
+    const HexOrd& ord = L.ord;
     const int ordered = ord.acc != nullptr;
-    const int nb = P.key_off[6], scan_blocks = (nb + 1024 * HEXSORT_SCAN_ITEMS - 1) / (1024 * HEXSORT_SCAN_ITEMS);
-    GSR_HIP_CHECK(hipMemsetAsync(ws.count, 0, (size_t)nb * sizeof(uint32_t), stream));
-    if (ordered) {
-        GSR_HIP_CHECK(hipMemsetAsync(ws.header, 0, 256, stream));
-        GSR_HIP_CHECK(hipMemsetAsync(ord.acc, 0, ord_bytes, stream));
-    }
-    hipLaunchKernelGGL(hexsort_count_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, f, P, ws, n, xyz, xyz_stride, (const float*)nullptr, (int64_t)0,
-                       (const float*)nullptr, view_mask);
-    hipLaunchKernelGGL(hexsort_scan_sums_kernel, dim3(scan_blocks), dim3(1024), 0, stream, (const uint32_t*)ws.count, nb, ws.block_sums);
-    hipLaunchKernelGGL(hexsort_scan_top_kernel, dim3(1), dim3(1024), 0, stream, ws.block_sums, scan_blocks, ws.header);
-    hipLaunchKernelGGL(hexsort_scan_apply_kernel, dim3(scan_blocks), dim3(1024), 0, stream, ws.count, nb, (const uint32_t*)ws.block_sums);
-    hipLaunchKernelGGL(hexsort_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, n);
     const int C = f.feat_dim, ppb = HEX_BLOCK / C;
     const dim3 g1((unsigned)((n + ppb - 1) / ppb));
     const int gpw = C >= 64 ? 1 : 64 / C;                        // groups per wave (hexsort_phase2_views_kernel)
@@ -1799,7 +1797,7 @@ int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, cons
 #undef GSR_HEXVB_PHASE2
 #undef GSR_HEXVB_CASE
     if (ordered) {
-        hexord_convert(f, ord, ws.header, (1 << 0) | (1 << 1) | (1 << 3), stream);
+        hexord_convert(f, ord, ws.header, HEX_SPATIAL_PLANES, stream);
         int wmax = 1;
         for (int l = 0; l < f.num_levels; l++)
             for (int k = 0; k < 3; k++) wmax = std::max(wmax, (int)f.levels[l].res[k]);

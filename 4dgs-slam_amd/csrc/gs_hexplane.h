@@ -43,9 +43,9 @@ __device__ __forceinline__ HexAxis hex_axis(float coord, int size)
     return a;
 }
 
-// plane index -> the two coordinates it spans, itertools.combinations(range(4), 2) order (hexplane.py:86-88)
-__device__ __forceinline__ constexpr int hex_c0(int p) { return p < 3 ? 0 : (p < 5 ? 1 : 2); }
-__device__ __forceinline__ constexpr int hex_c1(int p) { return p == 0 ? 1 : (p == 1 || p == 3) ? 2 : 3; }
+// plane index -> the two coordinates it spans, itertools.combinations(range(4), 2) order (hexplane.py:86-88); the host plans its workspaces with them too
+__host__ __device__ __forceinline__ constexpr int hex_c0(int p) { return p < 3 ? 0 : (p < 5 ? 1 : 2); }
+__host__ __device__ __forceinline__ constexpr int hex_c1(int p) { return p == 0 ? 1 : (p == 1 || p == 3) ? 2 : 3; }
 
 // How the C channels of a texel are spread over the LPP = C/4 lanes of a point, four per lane:
 //   PLANAR   reference memory [C][H][W]:      lane `sub` holds channels 4 sub + k, k = 0..3, each H*W floats apart

@@ -967,7 +967,8 @@ std::vector<torch::Tensor> hexplane_backward(const std::vector<torch::Tensor>& p
     if (sorted && total > 0) ws = torch::empty({(int64_t)gsr_hexplane_backward_workspace_size(&f, xyz.size(0))}, xyz.options().dtype(torch::kUInt8));
     const int rc = gsr_hexplane_backward(&f, xyz.size(0), xyz.data_ptr<float>(), xyz.stride(0), time.data_ptr<float>(), time.stride(0),
                                          g.data_ptr<float>(), need_xyz ? out[0].data_ptr<float>() : nullptr,
-                                         ws.defined() ? reinterpret_cast<char*>(ws.data_ptr()) : nullptr, reinterpret_cast<void*>(stream));
+                                         ws.defined() ? reinterpret_cast<char*>(ws.data_ptr()) : nullptr, ws.defined() ? (size_t)ws.numel() : 0,
+                                         reinterpret_cast<void*>(stream));
     if (rc < 0) fail("gsr_hexplane_backward", rc);
     return out;
 }

@@ -182,27 +182,16 @@ class _DeformViews(torch.autograd.Function):
             mlp_grads.append(flat_g[off:off + p.numel()].view(p.shape))
             off += p.numel()
         # ---- the field, all views ----
-        levels = [[p.detach() for p in planes[6 * l:6 * l + 6]] for l in range(n_levels)]
-        need_plane = list(ctx.needs_input_grad[4:4 + 6 * n_levels])
-        sizes = [p.numel() if need else 0 for p, need in zip(planes, need_plane)]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)               # one fill for every plane gradient
-        views, o = [], 0
-        for p, need, sz in zip(planes, need_plane, sizes):
-            views.append(torch.as_strided(flat, p.shape, p.stride(), o) if need else None)
-            o += sz
-        gxyz = torch.empty((n, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        field = hp._describe(levels, aabb, [views[6 * l:6 * l + 6] for l in range(n_levels)])
-        size = lib.gsr_hexplane_backward_views_workspace_size(ctypes.byref(field), n, V)
-        if size == 0:
-            raise RuntimeError("deform_network.forward_views: plane geometry not covered by the batched field backward")
-        ws = torch.empty(size, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            lib.gsr_hexplane_backward_views(ctypes.byref(field), n, xyz.data_ptr(), xyz.stride(0), V, ctx.times, dfeat.data_ptr(),
-                                            mask.data_ptr() if use_mask else None, gxyz.data_ptr() if gxyz is not None else None, ws.data_ptr(), stream)
-        if gxyz is not None and xyz.shape[1] > 3:
-            full = torch.zeros_like(xyz)
-            full[:, :3] = gxyz
-            gxyz = full
+        def workspace_size(lib, field):
+            size = lib.gsr_hexplane_backward_views_workspace_size(field, n, V)
+            if size == 0:
+                raise RuntimeError("deform_network.forward_views: plane geometry not covered by the batched field backward")
+            return size
+
+        gxyz, views = hp._field_backward(
+            planes, n_levels, aabb, list(ctx.needs_input_grad[4:4 + 6 * n_levels]), xyz, ctx.needs_input_grad[0], workspace_size,
+            lambda lib, field, gxyz, ws, ws_bytes, stream: lib.gsr_hexplane_backward_views(
+                field, n, xyz.data_ptr(), xyz.stride(0), V, ctx.times, dfeat.data_ptr(), mask.data_ptr() if use_mask else None, gxyz, ws, ws_bytes, stream))
         return (gxyz, None, None, None, *views, *mlp_grads)
 
 

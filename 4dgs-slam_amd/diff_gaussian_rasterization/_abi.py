@@ -182,11 +182,11 @@ FUNCTIONS = {
     "gsr_elastic_backward": (i, [i, i, i, i] + [vp] * 6),
     # deformation_field.h
     "gsr_hexplane_forward": (i, [P(gsr_hexplane_field), i64, vp, i64, vp, i64, vp, vp]),
-    "gsr_hexplane_backward": (i, [P(gsr_hexplane_field), i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "gsr_hexplane_backward": (i, [P(gsr_hexplane_field), i64, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
     "gsr_hexplane_backward_workspace_size": (sz, [P(gsr_hexplane_field), i64]),
     "gsr_hexplane_forward_views": (i, [P(gsr_hexplane_field), i64, vp, i64, i, P(f), vp, vp]),
     "gsr_hexplane_backward_views_workspace_size": (sz, [P(gsr_hexplane_field), i64, i]),
-    "gsr_hexplane_backward_views": (i, [P(gsr_hexplane_field), i64, vp, i64, i, P(f)] + [vp] * 5),
+    "gsr_hexplane_backward_views": (i, [P(gsr_hexplane_field), i64, vp, i64, i, P(f)] + [vp] * 4 + [sz, vp]),
     "gsr_row_mask_workspace_size": (sz, [i, i64]),
     "gsr_row_mask": (i, [i, i64, i] + [vp] * 6),
     "gsr_linear_wgrad_workspace_size": (sz, [i64, i, i]),

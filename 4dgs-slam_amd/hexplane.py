@@ -137,51 +137,59 @@ class _HexPlaneFeatures(torch.autograd.Function):
         xyz, time, aabb, *planes = ctx.saved_tensors
         n_levels = ctx.n_levels
         aabb = aabb if ctx.has_aabb else None
-        if ctx.use_glue:
-            need_plane = list(ctx.needs_input_grad[4:])
-            mode = os.environ.get("GSR_HEX_BINNED", "auto")
-            sorted_bwd = any(need_plane) and mode != "0" and (mode == "1" or xyz.shape[0] >= BINNED_MIN_POINTS)
-            res = _C._glue.hexplane_backward([p.detach() for p in planes], n_levels, xyz, time, aabb, g, need_plane,
-                                             bool(ctx.needs_input_grad[0]), sorted_bwd, _C._stream(g.device))
-            gxyz = res[0]
-            if gxyz is not None and xyz.shape[1] > 3:
-                full = torch.zeros_like(xyz)
-                full[:, :3] = gxyz
-                gxyz = full
-            return (gxyz, None, None, None, *res[1:])
-        levels = [[p.detach() for p in planes[6 * l:6 * l + 6]] for l in range(n_levels)]
         need_plane = list(ctx.needs_input_grad[4:])
-        layout = _plane_layout(levels[0][0])
-        # one zeroed buffer for every plane gradient (one memset instead of 24); each gradient is a view with the plane's strides
-        sizes = [p.numel() if need else 0 for p, need in zip(planes, need_plane)]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=g.device)
-        grads, views, o = [], [], 0
-        for p, need, sz in zip(planes, need_plane, sizes):
-            if not need:
-                views.append(None)
-                continue
-            views.append(torch.as_strided(flat, p.shape, p.stride(), o))      # the plane's own strides (either layout), offset o
-            o += sz
-        grads = [views[6 * l:6 * l + 6] for l in range(n_levels)]
+        n = xyz.shape[0]
+        if ctx.use_glue:
+            res = _C._glue.hexplane_backward([p.detach() for p in planes], n_levels, xyz, time, aabb, g, need_plane,
+                                             bool(ctx.needs_input_grad[0]), _sorted_backward(n, need_plane), _C._stream(g.device))
+            return (_widen_xyz_grad(res[0], xyz), None, None, None, *res[1:])
         g = g.contiguous()
-        gxyz = torch.empty((xyz.shape[0], 3), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
-        field = _describe(levels, aabb, grads)
-        lib = _C.load_library()
-        # large batches on channels-last planes: the binned algorithm (counting sort per plane family, LDS accumulation per plane
-        # region, one flush) -- needs a workspace; small ones: one atomic per (point, corner)
-        ws = None
-        mode = os.environ.get("GSR_HEX_BINNED", "auto")
-        if layout == 1 and any(need_plane) and mode != "0" and (mode == "1" or xyz.shape[0] >= BINNED_MIN_POINTS):
-            ws = torch.empty(lib.gsr_hexplane_backward_workspace_size(ctypes.byref(field), xyz.shape[0]), dtype=torch.uint8, device=g.device)
-        with torch.cuda.device(g.device):
-            lib.gsr_hexplane_backward(ctypes.byref(field), xyz.shape[0], xyz.data_ptr(), xyz.stride(0), time.data_ptr(), time.stride(0),
-                                      g.data_ptr(), gxyz.data_ptr() if gxyz is not None else None,
-                                      ws.data_ptr() if ws is not None else None, _C._stream(g.device))
-        if gxyz is not None and xyz.shape[1] > 3:                  # rows were a slice of a wider tensor
-            full = torch.zeros_like(xyz)
-            full[:, :3] = gxyz
-            gxyz = full
+        sorted_bwd = _plane_layout(planes[0]) == 1 and _sorted_backward(n, need_plane)      # the unsorted path takes either layout, and no workspace
+        gxyz, views = _field_backward(
+            planes, n_levels, aabb, need_plane, xyz, ctx.needs_input_grad[0],
+            lambda lib, field: lib.gsr_hexplane_backward_workspace_size(field, n) if sorted_bwd else 0,
+            lambda lib, field, gxyz, ws, ws_bytes, stream: lib.gsr_hexplane_backward(
+                field, n, xyz.data_ptr(), xyz.stride(0), time.data_ptr(), time.stride(0), g.data_ptr(), gxyz, ws, ws_bytes, stream))
         return (gxyz, None, None, None, *views)
+
+
+def _sorted_backward(n, need_plane) -> bool:
+    """Whether the single-time backward of n points takes the sorted algorithm (counting sort per plane family, one set of atomics per run of
+    points that share a cell): GSR_HEX_BINNED=1 always, 0 never, otherwise for large batches; never when no plane gradient is asked for."""
+    mode = os.environ.get("GSR_HEX_BINNED", "auto")
+    return any(need_plane) and mode != "0" and (mode == "1" or n >= BINNED_MIN_POINTS)
+
+
+def _widen_xyz_grad(gxyz, xyz):
+    """dL_dxyz [n, 3] as the gradient of xyz [n, >= 3] (rows that were a slice of a wider tensor)."""
+    if gxyz is None or xyz.shape[1] == 3:
+        return gxyz
+    full = torch.zeros_like(xyz)
+    full[:, :3] = gxyz
+    return full
+
+
+def _field_backward(planes, n_levels, aabb, need_plane, xyz, need_xyz, workspace_size, call):
+    """The host side of every backward pass of the field (single time, batched views, the fused network's views) -> (dL_dxyz or None, the
+    plane gradients with None where not needed). One zeroed buffer holds every plane gradient (one fill instead of 24), each gradient a view
+    of it with its plane's own strides (either layout). `workspace_size(lib, field)` is the caller's size query (0: no workspace),
+    `call(lib, field, dL_dxyz pointer, workspace pointer, workspace bytes, stream)` its library call; the field arrives by reference."""
+    dev = xyz.device
+    levels = [[p.detach() for p in planes[6 * l:6 * l + 6]] for l in range(n_levels)]
+    sizes = [p.numel() if need else 0 for p, need in zip(planes, need_plane)]
+    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+    views, o = [], 0
+    for p, need, sz in zip(planes, need_plane, sizes):
+        views.append(torch.as_strided(flat, p.shape, p.stride(), o) if need else None)
+        o += sz
+    gxyz = torch.empty((xyz.shape[0], 3), dtype=torch.float32, device=dev) if need_xyz else None
+    field = ctypes.byref(_describe(levels, aabb, [views[6 * l:6 * l + 6] for l in range(n_levels)]))
+    lib = _C.load_library()
+    size = workspace_size(lib, field)
+    ws = torch.empty(size, dtype=torch.uint8, device=dev) if size else None
+    with torch.cuda.device(dev):
+        call(lib, field, gxyz.data_ptr() if gxyz is not None else None, ws.data_ptr() if ws is not None else None, size, _C._stream(dev))
+    return _widen_xyz_grad(gxyz, xyz), views
 
 
 MAX_VIEWS = GSR_HEXPLANE_MAX_VIEWS
@@ -220,32 +228,19 @@ class _HexPlaneFeaturesViews(torch.autograd.Function):
         xyz, aabb, *planes = ctx.saved_tensors
         n_levels, V, n = ctx.n_levels, len(ctx.times), xyz.shape[0]
         aabb = aabb if ctx.has_aabb else None
-        levels = [[p.detach() for p in planes[6 * l:6 * l + 6]] for l in range(n_levels)]
-        need_plane = list(ctx.needs_input_grad[4:])
-        sizes = [p.numel() if need else 0 for p, need in zip(planes, need_plane)]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=g.device)          # one fill for every plane gradient
-        views, o = [], 0
-        for p, need, sz in zip(planes, need_plane, sizes):
-            views.append(torch.as_strided(flat, p.shape, p.stride(), o) if need else None)
-            o += sz
-        grads = [views[6 * l:6 * l + 6] for l in range(n_levels)]
         g = g.contiguous()
-        gxyz = torch.empty((n, 3), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
-        field = _describe(levels, aabb, grads)
-        lib = _C.load_library()
-        size = lib.gsr_hexplane_backward_views_workspace_size(ctypes.byref(field), n, V) if n else 0
-        if n and size == 0:
-            raise RuntimeError("hexplane_features_views: this plane geometry is not covered by the batched backward (channels-last planes, "
-                               "resolutions <= 1024); evaluate the views one by one with hexplane_features")
-        if n:
-            ws = torch.empty(size, dtype=torch.uint8, device=g.device)
-            with torch.cuda.device(g.device):
-                lib.gsr_hexplane_backward_views(ctypes.byref(field), n, xyz.data_ptr(), xyz.stride(0), V, ctx.times, g.data_ptr(), None,
-                                                gxyz.data_ptr() if gxyz is not None else None, ws.data_ptr(), _C._stream(g.device))
-        if gxyz is not None and xyz.shape[1] > 3:
-            full = torch.zeros_like(xyz)
-            full[:, :3] = gxyz
-            gxyz = full
+
+        def workspace_size(lib, field):
+            size = lib.gsr_hexplane_backward_views_workspace_size(field, n, V)                  # (0 for no points, too: that call has nothing to do)
+            if n and size == 0:
+                raise RuntimeError("hexplane_features_views: this plane geometry is not covered by the batched backward (channels-last planes, "
+                                   "resolutions <= 1024); evaluate the views one by one with hexplane_features")
+            return size
+
+        gxyz, views = _field_backward(
+            planes, n_levels, aabb, list(ctx.needs_input_grad[4:]), xyz, ctx.needs_input_grad[0], workspace_size,
+            lambda lib, field, gxyz, ws, ws_bytes, stream: lib.gsr_hexplane_backward_views(
+                field, n, xyz.data_ptr(), xyz.stride(0), V, ctx.times, g.data_ptr(), None, gxyz, ws, ws_bytes, stream))
         return (gxyz, None, None, None, *views)
 
 

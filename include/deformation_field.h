@@ -61,20 +61,22 @@ int gsr_hexplane_forward(const gsr_hexplane_field* field, int64_t n, const float
  * by normalize_aabb or sitting on the sampler's border (GridSampler.h clip_coordinates_set_grad).  Time receives no gradient
  * (the reference builds it with torch.tensor(...).repeat, gaussian_renderer/__init__.py:112). */
 int gsr_hexplane_backward(const gsr_hexplane_field* field, int64_t n, const float* xyz, int64_t xyz_stride, const float* time,
-                          int64_t time_stride, const float* dL_dfeatures, float* dL_dxyz, char* workspace, void* stream);
-/* `workspace` (gsr_hexplane_backward_workspace_size bytes, contents undefined on entry) selects the sorted algorithm: the points
+                          int64_t time_stride, const float* dL_dfeatures, float* dL_dxyz, char* workspace, size_t workspace_bytes, void* stream);
+/* `workspace` (`workspace_bytes` >= gsr_hexplane_backward_workspace_size, contents undefined on entry) selects the sorted algorithm: the points
  * are counting-sorted per plane family by the Morton code of their finest-level cell, dL/dsample is staged in the workspace in
  * sorted order, and runs of points that share a cell are summed in registers before ONE set of four atomics per run
  * (channels-last planes, resolutions <= 1024) -- the fast path for large n, and the one whose cost falls rather than rises when
- * many points share texels.  workspace NULL = one float atomic per (point, corner), no extra memory.
+ * many points share texels.  workspace NULL (whatever workspace_bytes) = one float atomic per (point, corner), no extra memory.
  *
  * Ordered mode (gsr_set_option("hex_ordered", 1), the default; both sorted entry points): the plane gradients are BITWISE reproducible -- run
  * to run and under any permutation of the points. Every product dL/dsample x corner weight is rounded once to a power-of-two quantum
  * (2^-40 of the call's largest |dL/dsample|; 2^-(62 - ceil(log2(4 n))) beyond 1 M points) and from there on only integers are added
  * (registers, LDS and 64-bit integer atomics in the workspace); a last pass converts the sums and ADDS them to grad_planes, one owner per
  * texel. Against the float-atomic mode (0: rounds 1-5) the sums differ by rounding only. The workspace grows by 8 bytes per texel of the
- * planes: read the size AFTER setting the option and do not change the option between the size query and the call. The unsorted
- * path (workspace NULL) keeps its float atomics. */
+ * planes: read the size AFTER setting the option. Each call reads the option once and lays its workspace out for that mode; a
+ * workspace_bytes below what that layout needs (the option went from 0 to 1 after the size query) is detected and refused with
+ * GSR_ERR_INVALID_ARGUMENT before anything is enqueued, a larger buffer (1 to 0) is accepted. The unsorted path (workspace NULL) keeps its
+ * float atomics. */
 size_t gsr_hexplane_backward_workspace_size(const gsr_hexplane_field* field, int64_t n);
 
 /* ---- the views of one mapping iteration at once ---------------------------------------------------------------------------------
@@ -87,7 +89,8 @@ size_t gsr_hexplane_backward_workspace_size(const gsr_hexplane_field* field, int
  *   backward: dL_dfeatures [V][n][L*C]; ONE counting sort of the points for all views, dL/dsample of the spatial planes summed over the
  *             views in registers before the (single) spatial scatter, the time planes' per view; accumulates into grad_planes like V
  *             gsr_hexplane_backward calls, WRITES dL_dxyz [n,3] = the sum over the views. Needs channels-last planes, resolutions
- *             <= 1024 and a workspace of gsr_hexplane_backward_views_workspace_size() bytes (0 = unsupported geometry: call view by view).
+ *             <= 1024 and a workspace of workspace_bytes >= gsr_hexplane_backward_views_workspace_size() (0 = unsupported geometry: call
+ *             view by view).
  *             Ordered mode (above): the spatial planes as there; the time families keep integer column sums per view and the last pass
  *             applies each view's two time-row weights, views in their order. */
 #define GSR_HEXPLANE_MAX_VIEWS 12
@@ -98,7 +101,8 @@ size_t gsr_hexplane_backward_views_workspace_size(const gsr_hexplane_field* fiel
  * memory: gsr_deform_mlp_backward_rows does not write the rows it was not given); points whose bits are all clear are left out of the sort.
  * NULL = every row is read. gsr_row_mask below builds the mask from the network's [V][n][10] cotangent. */
 int gsr_hexplane_backward_views(const gsr_hexplane_field* field, int64_t n, const float* xyz, int64_t xyz_stride, int V, const float* times,
-                                const float* dL_dfeatures, const uint32_t* view_mask, float* dL_dxyz, char* workspace, void* stream);
+                                const float* dL_dfeatures, const uint32_t* view_mask, float* dL_dxyz, char* workspace, size_t workspace_bytes,
+                                void* stream);
 
 /* Which rows of a batched cotangent g [V][n][width] are not zero -- in a mapping iteration most (view, Gaussian) pairs receive no gradient at
  * all (outside the frustum, or behind saturated pixels: 63 % at BASELINE config #3). view_mask[i] bit v = row (v, i) has a non-zero element;

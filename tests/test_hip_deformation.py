@@ -3,6 +3,7 @@
   * the pinned CPU oracle (oracle/deformation_oracle.py) in fp64 on seeded inputs at the shipped geometry,
   * torch's own F.grid_sample composition on the GPU (an independent fp32 statement of the same op).
 Tolerances: values rel-L1 <= 1e-5 (north_star asks 1e-4), gradients rel-L1 <= 1e-4 (north_star asks 1e-3)."""
+import ctypes
 import itertools
 import os
 
@@ -688,6 +689,69 @@ def test_plane_gradients_are_bitwise_reproducible_and_do_not_depend_on_the_point
         assert rel(a, b) < 1e-5
 
 
+def test_a_workspace_sized_under_the_other_mode_is_refused_or_accepted():
+    """Each sorted backward call reads "hex_ordered" once, lays its workspace out for that mode and compares the layout's total with the
+    caller's byte count before it enqueues anything (include/deformation_field.h). A size queried under 0 and passed to a call under 1 is too
+    small by the 64-bit sums: GSR_ERR_INVALID_ARGUMENT, gsr_last_error names the function and both sizes, nothing is written. (The buffers
+    behind the stale byte counts ARE large enough here: were the check missing, the call would stay inside them.) The other way round -- the
+    size of mode 1, the call under 0 -- the buffer is merely larger than needed and the result is that of a fresh unordered call, to the
+    tolerance test_plane_gradients_are_bitwise_reproducible_... uses between the two modes."""
+    from diff_gaussian_rasterization import _C
+    lib = _C.load_library()
+    module = _shipped_field(seed=9)
+    planes = [p.detach() for lv in module.grids for p in lv]
+    levels = [planes[6 * l:6 * l + 6] for l in range(4)]
+    n, V = 60000, 3
+    g = torch.Generator(device="cpu").manual_seed(13)
+    xyz = (torch.rand((n, 3), generator=g) * 3.0 - 1.5).to(DEV)
+    time = torch.full((n, 1), 0.3, device=DEV)
+    times = (ctypes.c_float * V)(-0.5, 0.0, 0.8)
+    cot = torch.randn((V, n, module.feat_dim), generator=g).to(DEV)
+    stream = _C._stream(DEV)
+    routes = {"single": "gsr_hexplane_backward", "views": "gsr_hexplane_backward_views"}
+
+    def sizes():
+        f = ctypes.byref(hexplane._describe(levels, module.aabb))
+        return {"single": lib.gsr_hexplane_backward_workspace_size(f, n), "views": lib.gsr_hexplane_backward_views_workspace_size(f, n, V)}
+
+    def call(route, grads, gxyz, ws, ws_bytes):
+        f = ctypes.byref(hexplane._describe(levels, module.aabb, [grads[6 * l:6 * l + 6] for l in range(4)]))
+        if route == "single":
+            lib.gsr_hexplane_backward(f, n, xyz.data_ptr(), 3, time.data_ptr(), 1, cot[0].data_ptr(), gxyz.data_ptr(), ws.data_ptr(), ws_bytes, stream)
+        else:
+            lib.gsr_hexplane_backward_views(f, n, xyz.data_ptr(), 3, V, times, cot.data_ptr(), None, gxyz.data_ptr(), ws.data_ptr(), ws_bytes, stream)
+        torch.cuda.synchronize()
+
+    def outputs():
+        return [torch.zeros_like(p) for p in planes], torch.zeros((n, 3), device=DEV)
+
+    old = _C.set_option("hex_ordered", 0)
+    try:
+        small, fresh = sizes(), {}
+        for route in routes:
+            fresh[route] = outputs()
+            call(route, *fresh[route], torch.empty(small[route], dtype=torch.uint8, device=DEV), small[route])
+            assert sum(float(a.abs().sum()) for a in fresh[route][0]) > 0
+        _C.set_option("hex_ordered", 1)
+        large = sizes()
+        for route, name in routes.items():
+            assert large[route] > small[route]
+            ws = torch.empty(large[route], dtype=torch.uint8, device=DEV)
+            grads, gxyz = outputs()
+            with pytest.raises(RuntimeError, match=rf"failed \(code -1\): {name}: workspace of {small[route]} bytes, {large[route]} needed"):
+                call(route, grads, gxyz, ws, small[route])
+            torch.cuda.synchronize()
+            assert not any(bool(a.any()) for a in grads) and not bool(gxyz.any())
+            _C.set_option("hex_ordered", 0)                  # the size of mode 1, the call under mode 0
+            call(route, grads, gxyz, ws, large[route])
+            _C.set_option("hex_ordered", 1)
+            for a, b in zip(grads + [gxyz], fresh[route][0] + [fresh[route][1]]):
+                assert float((a - b).abs().max()) <= 2e-5 * float(b.abs().max()) + 1e-30
+                assert rel(a, b) < 1e-5
+    finally:
+        _C.set_option("hex_ordered", old)
+
+
 def test_ordered_plane_gradients_scale_with_the_cotangent():
     """The fixed-point quantum follows the call's largest |dL/dsample|: cotangents scaled by 2^-60 or 2^+40 give gradients scaled by exactly
     that power of two (no overflow, no flush to zero)."""
@@ -708,7 +772,7 @@ def test_ordered_plane_gradients_scale_with_the_cotangent():
 
 
 def test_ordered_plane_gradients_beyond_a_million_points():
-    """n > 2^20: the fixed-point budget shrinks below 40 bits (62 - ceil(log2 4n), gs_capi.hip hexord_plan) so that 4 n contributions of the
+    """n > 2^20: the fixed-point budget shrinks below 40 bits (62 - ceil(log2 4n), gs_capi.hip hexord_carve_tail) so that 4 n contributions of the
     largest magnitude cannot overflow 63 bits. Every point in ONE texel with the same sign -- the worst case for the sum --: finite,
     reproducible, and equal to the float-atomic mode's sums to its own rounding noise."""
     from diff_gaussian_rasterization import _C
