@@ -2876,6 +2876,34 @@ int gsr_frame_prepare(int width, int height, const unsigned char* rgb, const flo
     return 0;
 }
 
+int gsr_frame_export(int views, int width, int height, const float* colour, int64_t colour_stride, const float* depth, int64_t depth_stride,
+                     const unsigned char* lut, float depth_vmax, float depth_scale, unsigned char* rgb8, unsigned char* depth_rgb8,
+                     unsigned short* depth_u16, void* stream_)
+{
+    if (!colour || !lut || !rgb8) { g_last_error = "gsr_frame_export: colour, lut and rgb8 must not be NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+    if ((depth_rgb8 || depth_u16) && !depth) { g_last_error = "gsr_frame_export: a depth output was asked for without depth"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (views <= 0 || views > 65535 || width <= 0 || height <= 0 || (long long)width * height * 3 > 0x7fffffffLL) {
+        g_last_error = "gsr_frame_export: views must be in [1, 65535], width and height positive and width * height * 3 below 2^31";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    const long long n = (long long)width * height;
+    if (colour_stride < 3 * n || (depth && depth_stride < n)) {
+        g_last_error = "gsr_frame_export: a view stride is smaller than the view (3 * width * height floats of colour, width * height of depth)";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!(depth_vmax > 0.0f)) { g_last_error = "gsr_frame_export: depth_vmax must be positive"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (((size_t)rgb8 | (size_t)depth_rgb8) & 3 || ((size_t)depth_u16 & 7)) {
+        g_last_error = "gsr_frame_export: rgb8 and depth_rgb8 must be 4-byte aligned, depth_u16 8-byte aligned";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long threads = (long long)((width + 3) / 4) * height;
+    hipLaunchKernelGGL(frame_export_kernel, dim3((unsigned)((threads + FRAME_BLOCK - 1) / FRAME_BLOCK), (unsigned)views), dim3(FRAME_BLOCK), 0, stream,
+                       width, height, colour, colour_stride, depth, depth_stride, lut, depth_vmax, depth_scale, rgb8, depth_rgb8, depth_u16);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // min_side: the smallest side a pyramid level may have (the pyramid: 1; the lookup divides by (side - 1): 2)
 static bool raft_size_ok(const char* who, int h, int w, int min_side)
 {

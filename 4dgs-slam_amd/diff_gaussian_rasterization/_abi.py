@@ -229,6 +229,7 @@ FUNCTIONS = {
     "gsr_multi_add": (i, [i, P(gsr_multi_add_item), vp]),
     # frame_io.h
     "gsr_frame_prepare": (i, [i, i, vp, vp, vp, vp, f, vp, vp, vp]),
+    "gsr_frame_export": (i, [i, i, i, vp, i64, vp, i64, vp, f, f, vp, vp, vp, vp]),
     # optical_flow.h
     "gsr_raft_corr_pyramid": (i, [i, i, i, vp, vp, P(vp), P(vp), vp]),
     "gsr_raft_corr_lookup": (i, [i, i, i, P(vp), vp, vp, vp]),

@@ -852,6 +852,54 @@ class ControlNodes(nn.Module):
         return elastic_error(nodes_t, nn_weight, nn_idx)
 
 
+# ---- deform.pth (gaussian_splatting/scene/deform_model.py:54-69: torch.save of the warp's state_dict) ----------------------------------
+NODE_ENTRIES = ("nodes", "_node_radius", "_node_weight")
+# The one place where a name of the reference's ControlNodeWarp.state_dict() (tests/golden/reference_deform_state.json) meets this module's:
+# prefix -> this model's prefix, or None for what has no counterpart here and is ignored (buffers of the reference's bookkeeping; encoders and
+# heads the shipped configuration leaves off). Longest prefix first; a name no prefix covers raises.
+REFERENCE_NAMES = (
+    ("network.linear.", "network.linear."),
+    ("network.gaussian_warp.", "network.gaussian_warp."),
+    ("network.gaussian_rotation.", "network.gaussian_rotation."),
+    ("network.gaussian_scaling.", "network.gaussian_scaling."),
+    ("network.local_rotation.", "network.local_rotation."),
+    ("_node_radius", "_node_radius"),
+    ("_node_weight", "_node_weight"),
+    ("nodes", "nodes"),
+    ("inited", None),                             # the flag buffer (time_utils.py:823): implied by the node rows being there
+    ("network.embed_time_fn.", None),             # step counters of the progressive-band encodings (progressive_brand_time: off)
+    ("network.embed_fn.", None),
+    ("network.color_hash_encoding.", None),       # hash-grid colour encoder and the opacity / colour heads (pred_opacity, pred_color: off)
+    ("network.gaussian_opacity.", None),
+    ("network.gaussian_color.", None),
+)
+
+
+def rename_reference_entries(sd, what):
+    """A state_dict under the reference's names -> under this module's, through REFERENCE_NAMES; a name outside the table raises."""
+    out = {}
+    for name, value in sd.items():
+        for prefix, mine in REFERENCE_NAMES:
+            if name == prefix or (prefix.endswith(".") and name.startswith(prefix)):
+                if mine is not None:
+                    out[mine + name[len(prefix):]] = value
+                break
+        else:
+            raise KeyError(f"{what} has an entry {name!r} that the rename table (deform_model.REFERENCE_NAMES) does not cover")
+    return out
+
+
+def weights_path(model_path, iteration):
+    return os.path.join(model_path, "deform", f"iteration_{int(iteration)}", "deform.pth")
+
+
+def latest_iteration(model_path):
+    """The highest N of deform/iteration_<N>/ under model_path (the reference's searchForMaxIteration); None when there is none."""
+    d = os.path.join(model_path, "deform")
+    found = [int(n.split("_")[-1]) for n in (os.listdir(d) if os.path.isdir(d) else ()) if n.startswith("iteration_") and n.split("_")[-1].isdigit()]
+    return max(found) if found else None
+
+
 class DeformModel:
     """gaussian_splatting/scene/deform_model.py:20-118: holder of the node warp + its optimizer."""
 
@@ -876,6 +924,39 @@ class DeformModel:
             self.optimizer = DeviceCountAdam(groups, lr=0.0, eps=1e-15)
         else:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15, **({"fused": True, "capturable": True} if on_device else {}))
+
+    def save_weights(self, model_path, iteration):
+        """deform_model.py:54-58: deform/iteration_<N>/deform.pth, a torch.save of the warp's state_dict()."""
+        path = weights_path(model_path, iteration)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save({k: v.detach().cpu() for k, v in self.deform.state_dict().items()}, path)
+        return path
+
+    def load_weights(self, model_path, iteration=-1):
+        """deform_model.py:60-69: reads deform/iteration_<N>/deform.pth (the highest N for -1) into the warp. The node tensors of a fresh
+        model have 0 rows: they are sized from the file first. A missing, extra or misshapen entry raises and names the file and the entry.
+        The optimizer (if any) belonged to the replaced tensors and is dropped: call train_setting() before training the loaded model."""
+        from .pretrained import check_entries, strip_module_prefix
+        if iteration == -1:
+            iteration = latest_iteration(model_path)
+            if iteration is None:
+                raise FileNotFoundError(f"{os.path.join(model_path, 'deform')}: no iteration_<N> directory with deform weights")
+        path = weights_path(model_path, iteration)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: no such file")
+        sd = rename_reference_entries(strip_module_prefix(torch.load(path, map_location="cpu", weights_only=True), path), path)
+        d = self.deform
+        want = {k: tuple(v.shape) for k, v in d.state_dict().items()}
+        rows = sd["nodes"].shape[0] if isinstance(sd.get("nodes"), torch.Tensor) and sd["nodes"].dim() == 2 else 0
+        want.update({"nodes": (rows, 3), "_node_radius": (rows,), "_node_weight": (rows, 1)})
+        check_entries(sd, want, path)
+        for name in NODE_ENTRIES:
+            setattr(d, name, nn.Parameter(torch.zeros(want[name], dtype=torch.float32, device=d.device)))
+        d.load_state_dict(sd)
+        d.inited = rows > 0
+        d.end_iteration()
+        self.optimizer = None
+        return path
 
     def step(self, x, time_input, iteration=0, feature=None, motion_mask=None, camera_center=None, time_interval=None, **kw):
         """deform_model.py:32-33."""

@@ -467,6 +467,24 @@ def rotation_to_quaternion(R):
     return np.array([x, y, z, w])
 
 
+def tum_stamp(i, t0=1000.0, hz=30.0):
+    """The time stamp of frame i of a written sequence, as the six-decimal text its files and lists are named by."""
+    return f"{t0 + i / hz:.6f}"
+
+
+def write_tum_lists(root, stamps, c2w_poses, origin="written from an in-memory dataset"):
+    """rgb.txt, depth.txt and groundtruth.txt (C2W as tx ty tz qx qy qz qw) of a sequence whose images are rgb/<stamp>.png, depth/<stamp>.png."""
+    rgb_lines = [f"{t} rgb/{t}.png" for t in stamps]
+    depth_lines = [f"{t} depth/{t}.png" for t in stamps]
+    pose_lines = [f"{t} " + " ".join(f"{v:.12f}" for v in (*c2w[:3, 3], *rotation_to_quaternion(c2w[:3, :3]))) for t, c2w in zip(stamps, c2w_poses)]
+    for name, header, lines in (("rgb.txt", f"# color images\n# file: {origin}\n# timestamp filename\n", rgb_lines),
+                                ("depth.txt", f"# depth maps\n# file: {origin}\n# timestamp filename\n", depth_lines),
+                                ("groundtruth.txt", f"# ground truth trajectory\n# file: {origin}\n"
+                                                    "# timestamp tx ty tz qx qy qz qw\n", pose_lines)):
+        with open(os.path.join(root, name), "w") as f:
+            f.write(header + "\n".join(lines) + "\n")
+
+
 def write_tum_sequence(dataset, root, masks=False, t0=1000.0, hz=30.0):
     """Write the frames of an in-memory dataset (slam/dataset.py interface) in the TUM layout: rgb/*.png = round(colour * 255),
     depth/*.png = round(depth * 5000) as 16-bit, groundtruth.txt (C2W as tx ty tz qx qy qz qw) and, with masks=True, render_mask/*.png
@@ -474,24 +492,17 @@ def write_tum_sequence(dataset, root, masks=False, t0=1000.0, hz=30.0):
     from PIL import Image
     for d in ("rgb", "depth") + (("render_mask",) if masks else ()):
         os.makedirs(os.path.join(root, d), exist_ok=True)
-    rgb_lines, depth_lines, pose_lines = [], [], []
+    stamps, c2ws = [], []
     for i in range(len(dataset)):
         color, depth, pose, motion = dataset[i]
-        t = t0 + i / hz
+        t = tum_stamp(i, t0, hz)
         c = np.rint(color.clamp(0, 1).permute(1, 2, 0).cpu().numpy().astype(np.float64) * 255).astype(np.uint8)
-        Image.fromarray(c).save(os.path.join(root, "rgb", f"{t:.6f}.png"))
-        Image.fromarray(np.rint(np.asarray(depth, np.float64) * 5000).astype(np.uint16)).save(os.path.join(root, "depth", f"{t:.6f}.png"))
+        Image.fromarray(c).save(os.path.join(root, "rgb", f"{t}.png"))
+        Image.fromarray(np.rint(np.asarray(depth, np.float64) * 5000).astype(np.uint16)).save(os.path.join(root, "depth", f"{t}.png"))
         if masks:
             Image.fromarray(np.where(motion.cpu().numpy(), 0, 255).astype(np.uint8)).save(os.path.join(root, "render_mask", f"mask_{i}.png"))
-        c2w = np.linalg.inv(pose.double().cpu().numpy())
-        rgb_lines.append(f"{t:.6f} rgb/{t:.6f}.png")
-        depth_lines.append(f"{t:.6f} depth/{t:.6f}.png")
-        pose_lines.append(f"{t:.6f} " + " ".join(f"{v:.12f}" for v in (*c2w[:3, 3], *rotation_to_quaternion(c2w[:3, :3]))))
-    for name, header, lines in (("rgb.txt", "# color images\n# file: written from an in-memory dataset\n# timestamp filename\n", rgb_lines),
-                                ("depth.txt", "# depth maps\n# file: written from an in-memory dataset\n# timestamp filename\n", depth_lines),
-                                ("groundtruth.txt", "# ground truth trajectory\n# file: written from an in-memory dataset\n"
-                                                    "# timestamp tx ty tz qx qy qz qw\n", pose_lines)):
-        with open(os.path.join(root, name), "w") as f:
-            f.write(header + "\n".join(lines) + "\n")
+        stamps.append(t)
+        c2ws.append(np.linalg.inv(pose.double().cpu().numpy()))
+    write_tum_lists(root, stamps, c2ws)
     return {"fx": float(dataset.fx), "fy": float(dataset.fy), "cx": float(dataset.cx), "cy": float(dataset.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
             "p2": 0.0, "k3": 0.0, "distorted": False, "width": int(dataset.width), "height": int(dataset.height), "depth_scale": 5000.0}

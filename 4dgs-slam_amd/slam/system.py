@@ -3,6 +3,7 @@ front-end and back-end from a configuration with the reference's YAML structure 
 sequence, evaluates ATE / PSNR (utils/eval_utils.py). GUI, wandb and multiprocessing queues are out of scope; any object with the
 interface of slam/dataset.py can be passed as the dataset (recorded TUM / Bonn / CoFusion sequences: slam/recorded.py, slam/config.py)."""
 import copy
+import os
 import time
 import types
 
@@ -111,6 +112,16 @@ class SLAM:
         if self.save_dir:
             save_gaussians(self.gaussians, self.save_dir, "final", final=True)
         return self.result
+
+    def save_map(self, directory=None):
+        """Write the finished map -- Gaussians, node network, tracked poses, exposures and times -- so that slam.map_io.load_map can open it
+        in another process (default directory: <save_dir>/map). Never called implicitly."""
+        from .map_io import save_map
+        if directory is None:
+            if not self.save_dir:
+                raise ValueError("SLAM.save_map: no directory given and the run has no save_dir")
+            directory = os.path.join(self.save_dir, "map")
+        return save_map(self, directory)
 
     def _eval_frames(self):
         """Cameras of the tracked frames; non-keyframes were cleaned (their images dropped) but keep pose, intrinsics and time."""

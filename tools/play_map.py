@@ -1,0 +1,36 @@
+#!/usr/bin/env python
+"""Play a saved 4D map (slam/map_io.py) back to image files (slam/playback.py):
+  play_map.py --map DIR --path tracked|frozen-time:T|frozen-camera:I:N|resample:N --out DIR [--depth16] [--no-depth-vis]
+writes rgb/*.png, depth_vis/*.png (jet, 0-6 m) and, with --depth16, depth/*.png plus the lists of a TUM sequence; prints one JSON line with
+the frames written, the seconds, frames per second and the time the loop waited for the writer thread."""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "4dgs-slam_amd")):
+    sys.path.insert(0, p)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--map", required=True, help="directory written by SLAM.save_map / run_slam.py --save-map")
+    ap.add_argument("--path", default="tracked", help="tracked | frozen-time:T | frozen-camera:I:N | resample:N")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--depth16", action="store_true", help="also write 16-bit depth and the TUM lists")
+    ap.add_argument("--no-depth-vis", action="store_true", help="do not write the jet-coloured depth pictures")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    from slam.map_io import load_map
+    from slam.playback import Playback, parse_path
+    loaded = load_map(args.map, args.device)
+    poses, times = parse_path(loaded, args.path)
+    res = Playback(loaded).write(poses, times, args.out, depth16=args.depth16, depth_colour=not args.no_depth_vis)
+    print(json.dumps({"map": args.map, "path": args.path, "out": args.out, "frames": res["frames"], "seconds": res["seconds"],
+                      "fps": res["fps"], "writer_wait_s": res["writer_wait_s"], "gaussians": int(loaded.gaussians.get_xyz.shape[0]),
+                      "dynamic": loaded.dynamic}))
+
+
+if __name__ == "__main__":
+    main()

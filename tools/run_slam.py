@@ -7,7 +7,8 @@ dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py),
 device ms per pair. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
 (slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame.
 With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and the LPIPS v0.1 linear layers) the rendering evaluation
-reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair."""
+reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair.
+With --save-map [DIR] the finished map is saved after the evaluations (slam/map_io.py) for tools/play_map.py."""
 import argparse
 import json
 import os
@@ -39,6 +40,8 @@ def parse_args(argv=None):
                                                          "loader's object classes")
     ap.add_argument("--lpips-weights", nargs=2, default=None, metavar=("ALEXNET", "LIN"),
                     help="torchvision AlexNet state_dict and LPIPS v0.1 linear layers: mean_lpips in the rendering evaluation")
+    ap.add_argument("--save-map", nargs="?", const="", default=None, metavar="DIR",
+                    help="after the evaluations, save the map for tools/play_map.py (default DIR: <save dir>/map)")
     args = ap.parse_args(argv)
     if args.raft_weights and not args.dynamic:
         warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
@@ -84,6 +87,8 @@ def main(argv=None):
     ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow, segmenter=segmenter)
     slam = SLAM(config, ds, save_dir=save_dir, lpips=lpips)
     res = slam.run()
+    if args.save_map is not None:
+        res = dict(res, saved_map=slam.save_map(args.save_map or None))
     res["graph_stats"] = slam.frontend.graph_stats
     res["mapping_graph_stats"] = {"static": dict(getattr(slam.backend, "graph_stats", {}) or {}),
                                   "dynamic": dict(getattr(slam.backend, "dynamic_graph_stats", {}) or {}),

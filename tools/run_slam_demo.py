@@ -13,7 +13,9 @@ for p in (REPO, os.path.join(REPO, "4dgs-slam_amd")):
 from slam.dataset import SyntheticRGBDDataset  # noqa: E402
 from slam.system import SLAM, default_config, merge_config  # noqa: E402
 
-# --only <substring>: run the matching scenarios only; --profile: cProfile each run and print the 25 most expensive functions to stderr
+# --only <substring>: run the matching scenarios only; --profile: cProfile each run and print the 25 most expensive functions to stderr;
+# --save-map DIR: after a scenario's evaluations, save its map to DIR/<scenario> (slam/map_io.py) for tools/play_map.py
+save_map = sys.argv[sys.argv.index("--save-map") + 1] if "--save-map" in sys.argv else None
 only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
 profile = "--profile" in sys.argv
 out = {}
@@ -43,6 +45,8 @@ for name, dyn, graph, frames, wh in (("static_640x480_eager", False, False, 40, 
         pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(20)
     else:
         res = slam.run()
+    if save_map:
+        res = dict(res, saved_map=slam.save_map(os.path.join(save_map, name)))
     res["graph_stats"] = slam.frontend.graph_stats
     res["mapping_graph_stats"] = {"static": dict(getattr(slam.backend, "graph_stats", {}) or {}), "dynamic": dict(getattr(slam.backend, "dynamic_graph_stats", {}) or {}),
                               "initialize_map": dict(getattr(slam.backend, "init_graph_stats", {}) or {}),
