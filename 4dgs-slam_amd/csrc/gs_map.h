@@ -397,8 +397,14 @@ __global__ void __launch_bounds__(256) edge_intensity_kernel(const float* __rest
         }
     }
     // Scharr, normalised by 16 (slam_utils.py:5-22): conv_x = [[3,10,3],[0,0,0],[-3,-10,-3]] -> "v", conv_y = its transpose -> "h"
-    float gv = (1.0f / 16.0f) * ((3.f * p[0][0] + 10.f * p[0][1] + 3.f * p[0][2]) - (3.f * p[2][0] + 10.f * p[2][1] + 3.f * p[2][2]));
-    float gh = (1.0f / 16.0f) * ((3.f * p[0][0] + 10.f * p[1][0] + 3.f * p[2][0]) - (3.f * p[0][2] + 10.f * p[1][2] + 3.f * p[2][2]));
+    float gv, gh;
+    {
+        // contraction off for the two stencils: a fused a - 3 p rounds one side's product and not the other's, so a flat region (every tap
+        // equal) came out as 2^-25 instead of the 0 the tensor program gives -- and with it the median of a frame that is mostly flat
+#pragma clang fp contract(off)
+        gv = (1.0f / 16.0f) * ((3.f * p[0][0] + 10.f * p[0][1] + 3.f * p[0][2]) - (3.f * p[2][0] + 10.f * p[2][1] + 3.f * p[2][2]));
+        gh = (1.0f / 16.0f) * ((3.f * p[0][0] + 10.f * p[1][0] + 3.f * p[2][0]) - (3.f * p[0][2] + 10.f * p[1][2] + 3.f * p[2][2]));
+    }
     if (!valid) { gv = 0.f; gh = 0.f; }
     intensity[(size_t)y * W + x] = sqrtf(gv * gv + gh * gh);
 }
