@@ -40,6 +40,8 @@
 #include "gs_map.h"
 #include "../../include/frame_io.h"
 #include "gs_frame.h"
+#include "../../include/video_io.h"
+#include "gs_jpeg.h"
 #include "../../include/optical_flow.h"
 #include "gs_raft.h"
 #include "../../include/segmentation.h"
@@ -2900,6 +2902,67 @@ int gsr_frame_export(int views, int width, int height, const float* colour, int6
     const long long threads = (long long)((width + 3) / 4) * height;
     hipLaunchKernelGGL(frame_export_kernel, dim3((unsigned)((threads + FRAME_BLOCK - 1) / FRAME_BLOCK), (unsigned)views), dim3(FRAME_BLOCK), 0, stream,
                        width, height, colour, colour_stride, depth, depth_stride, lut, depth_vmax, depth_scale, rgb8, depth_rgb8, depth_u16);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_jpeg_encode: coefficients [V, blocks, 64] int16 | bit lengths, then offsets [V, blocks] u32 | total bits [V] u32 | the bit
+// buffers [V, raw_words] u32; every part starts on a multiple of 16 bytes
+struct JpegLayout { JpegShape shape; size_t coef, lengths, totals, raw, bytes; };
+static bool jpeg_layout(int views, int width, int height, JpegLayout& l)
+{
+    if (views <= 0 || views > 65535 || width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
+    const long long cols = (width + 15) / 16, rows = (height + 15) / 16, blocks = cols * rows * 6;
+    if (blocks > 1290000) return false;                              // blocks * 1664 bits stay below 2^31
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    l.shape.W = width; l.shape.H = height; l.shape.mcu_cols = (int)cols; l.shape.blocks = (int)blocks;
+    l.shape.raw_words = (size_t)blocks * JPEG_BLOCK_WORDS + JPEG_TAIL_WORDS;
+    l.coef = 0;
+    l.lengths = l.coef + up((size_t)views * blocks * 64 * sizeof(short));
+    l.totals = l.lengths + up((size_t)views * blocks * sizeof(uint32_t));
+    l.raw = l.totals + up((size_t)views * sizeof(uint32_t));
+    l.bytes = l.raw + (size_t)views * l.shape.raw_words * sizeof(uint32_t);
+    return true;
+}
+
+size_t gsr_jpeg_workspace_size(int views, int width, int height)
+{
+    JpegLayout l;
+    return jpeg_layout(views, width, height, l) ? l.bytes : 0;
+}
+
+int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8, const unsigned short* qtables, unsigned char* scan,
+                    int64_t scan_stride, int* sizes, short* coefficients, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    JpegLayout l;
+    if (!jpeg_layout(views, width, height, l)) {
+        g_last_error = "gsr_jpeg_encode: views, width and height must be in [1, 65535], with at most 1290000 8x8 blocks per view";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!rgb8 || !qtables || !scan || !sizes || !workspace) {
+        g_last_error = "gsr_jpeg_encode: rgb8, qtables, scan, sizes and workspace must not be NULL";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (scan_stride <= 0) { g_last_error = "gsr_jpeg_encode: scan_stride must be positive"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (workspace_bytes < l.bytes || ((size_t)workspace & 15)) {
+        g_last_error = "gsr_jpeg_encode: workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_jpeg_workspace_size), got " +
+                       std::to_string(workspace_bytes);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = static_cast<char*>(workspace);
+    short* coef = reinterpret_cast<short*>(ws + l.coef);
+    uint32_t* lengths = reinterpret_cast<uint32_t*>(ws + l.lengths);
+    uint32_t* totals = reinterpret_cast<uint32_t*>(ws + l.totals);
+    uint32_t* raw = reinterpret_cast<uint32_t*>(ws + l.raw);
+    const dim3 per_block((unsigned)((l.shape.blocks + JPEG_WAVES - 1) / JPEG_WAVES), (unsigned)views);
+    hipLaunchKernelGGL(jpeg_transform_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, rgb8, qtables, coef, coefficients, lengths, raw);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3((unsigned)views), dim3(JPEG_SCAN_BLOCK), 0, stream, l.shape, coef, lengths, totals);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, coef, lengths, raw);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)views), dim3(JPEG_SCAN_BLOCK), 0, stream, l.shape, raw, totals, scan, (long long)scan_stride, sizes);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -230,6 +230,9 @@ FUNCTIONS = {
     # frame_io.h
     "gsr_frame_prepare": (i, [i, i, vp, vp, vp, vp, f, vp, vp, vp]),
     "gsr_frame_export": (i, [i, i, i, vp, i64, vp, i64, vp, f, f, vp, vp, vp, vp]),
+    # video_io.h
+    "gsr_jpeg_workspace_size": (sz, [i, i, i]),
+    "gsr_jpeg_encode": (i, [i, i, i, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
     # optical_flow.h
     "gsr_raft_corr_pyramid": (i, [i, i, i, vp, vp, P(vp), P(vp), vp]),
     "gsr_raft_corr_lookup": (i, [i, i, i, P(vp), vp, vp, vp]),

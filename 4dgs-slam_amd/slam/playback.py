@@ -4,7 +4,8 @@ Playback(map_like) takes a map_io.LoadedMap or the live SLAM object. render(pose
 gaussian_renderer.render_views (one launch per pipeline stage for the chunk), with ONE batched evaluation of the node network and one blend
 launch for the distinct times of a chunk (ControlNodes.begin_iteration(blend=...)). write(...) exports every chunk with one gsr_frame_export
 launch, copies the bytes into pinned ring buffers on a side stream and hands them to one writer thread (slam/png.py); the loop waits only
-when it must reuse a ring slot, and once at the end.
+when it must reuse a ring slot, and once at the end. write_video(...) sends the same exported bytes through the device's JPEG encoder
+(slam/mjpeg.py, gsr_jpeg_encode) instead and writes one Motion-JPEG AVI file per image kind; the host copies only the compressed bytes.
 
 Camera paths are plain functions that return (poses, times): poses float32 [N, 4, 4] world-to-camera matrices on the host, times a list of
 floats in the map's normalised time. The reference's `novel=` argument of render() is dead code there and has no counterpart."""
@@ -16,7 +17,7 @@ import time as _time
 import numpy as np
 import torch
 
-from . import frame_io, png
+from . import frame_io, mjpeg, png
 from .map_io import LoadedMap
 
 CHUNK = 12                     # views per render_views call (diff_gaussian_rasterization.views.MAX_VIEWS)
@@ -343,3 +344,126 @@ class Playback:
                 "writer_wait_at_end_s": wait_end, "export_ms": export_ms, "export_ms_per_view": export_ms / max(N, 1),
                 "calibration": {"fx": float(k.fx), "fy": float(k.fy), "cx": float(k.cx), "cy": float(k.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
                                 "p2": 0.0, "k3": 0.0, "distorted": False, "width": W, "height": H, "depth_scale": float(depth_scale)}}
+
+    @torch.no_grad()
+    def write_video(self, poses, times, out_dir, fps=30.0, quality=90, depth_colour=True, depth_vmax=DEPTH_VMAX, files=True, capacity=None):
+        """Render and write rgb.avi and depth_vis.avi (jet, 0 .. depth_vmax; depth_colour=False: not written): Motion-JPEG in AVI 1.0
+        (slam/mjpeg.py), each frame a baseline JPEG of the given quality, compressed on the device from the bytes gsr_frame_export writes (one
+        gsr_jpeg_encode call per chunk and image kind). capacity: the bytes a compressed frame may take (default max(W * H * 3, 65536)); a
+        frame that needs more raises RuntimeError with its index and its size, after the files are closed validly. files=False runs everything
+        but the disk (for measurements). Returns write()'s dict plus "files", "bytes" (the JPEG bytes of all frames) and "encode_ms"
+        (gsr_jpeg_encode by device events, read after the last chunk)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Playback.write_video allocates pinned buffers and synchronises with its writer: not while a graph is being captured")
+        dev, H, W = self.device, self.height, self.width
+        t0 = _time.perf_counter()
+        qtables = mjpeg.quant_tables(quality)
+        header = mjpeg.jfif_header(W, H, qtables)
+        cap = int(capacity) if capacity is not None else max(W * H * 3, 65536)
+        if cap < 1:
+            raise ValueError(f"capacity must be positive, got {capacity}")
+        cams = self._cameras(poses, times)
+        N = len(cams)
+        kinds = ["rgb"] + (["depth_vis"] if depth_colour else [])
+        paths = {k: os.path.join(out_dir, k + ".avi") for k in kinds}
+        writers = {}
+        if files:
+            os.makedirs(out_dir, exist_ok=True)
+            writers = {k: mjpeg.AviWriter(paths[k], W, H, fps) for k in kinds}
+        # a slot owns the exported bytes, the compressed bytes and their sizes on the device, and the pinned copies of the last two
+        slots = [{"dev": {k: torch.empty((CHUNK, H, W, 3), dtype=torch.uint8, device=dev) for k in kinds},
+                  "scan": {k: torch.empty((CHUNK, cap), dtype=torch.uint8, device=dev) for k in kinds},
+                  "sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32, device=dev),
+                  "host": {k: torch.empty((CHUNK, cap), dtype=torch.uint8).pin_memory() for k in kinds},
+                  "host_sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32).pin_memory()}
+                 for _ in range(min(RING, max(1, -(-N // CHUNK))))]
+        lut = torch.from_numpy(frame_io.jet_lut().copy()).to(dev)
+        q_dev = torch.from_numpy(qtables.astype(np.int16)).to(dev)
+        workspace = torch.empty(mjpeg.jpeg_workspace_size(CHUNK, W, H), dtype=torch.uint8, device=dev)   # shared: the encodes run in stream order
+        free, jobs, errors = queue.Queue(), queue.Queue(), []
+        total = [0]
+        for s in slots:
+            free.put(s)
+        main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+
+        def writer():
+            while True:
+                job = jobs.get()
+                if job is None:
+                    return
+                slot, lo, n, sized = job
+                try:
+                    sized.synchronize()                              # the sizes are on the host: copy just the bytes that were used
+                    sizes = slot["host_sizes"].numpy()[:, :n].copy()
+                    if (sizes < 0).any():
+                        ki, v = (int(a[0]) for a in np.nonzero(sizes < 0))
+                        raise RuntimeError(f"frame {lo + v} ({kinds[ki]}) needs {-int(sizes[ki, v])} bytes as a JPEG, its capacity is {cap}: "
+                                           f"pass a larger capacity or a lower quality")
+                    if errors:
+                        continue
+                    with torch.cuda.stream(side):
+                        for ki, k in enumerate(kinds):
+                            for v in range(n):
+                                slot["host"][k][v, :int(sizes[ki, v])].copy_(slot["scan"][k][v, :int(sizes[ki, v])], non_blocking=True)
+                        done = torch.cuda.Event()
+                        done.record(side)
+                    done.synchronize()
+                    for ki, k in enumerate(kinds):
+                        a = slot["host"][k].numpy()
+                        for v in range(n):
+                            total[0] += len(header) + int(sizes[ki, v]) + 2
+                            if files:
+                                writers[k].add(header + a[v, :int(sizes[ki, v])].tobytes() + mjpeg.EOI)
+                except BaseException as e:                           # surfaced by the caller after the loop
+                    errors.append(e)
+                finally:
+                    free.put(slot)
+
+        thread = threading.Thread(target=writer, name="playback-video-writer", daemon=True)
+        thread.start()
+        timing, export_timing = [], []
+        wait = 0.0
+        try:
+            for lo, colour, depth, _ in self._chunks(cams):
+                n = int(colour.shape[0])
+                w0 = _time.perf_counter()
+                slot = free.get()                                    # the only wait inside the loop: every slot is still with the writer
+                wait += _time.perf_counter() - w0
+                if errors:
+                    break
+                out = {k: t[:n] for k, t in slot["dev"].items()}
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record(main)
+                frame_io.frame_export(colour, depth, lut, depth_vmax, DEPTH_SCALE, out["rgb"], out.get("depth_vis"), None, main)
+                ev[1].record(main)
+                for ki, k in enumerate(kinds):
+                    mjpeg.jpeg_encode(out[k], q_dev, slot["scan"][k][:n], slot["sizes"][ki, :n], None, workspace, main)
+                ev[2].record(main)
+                export_timing.append((ev[0], ev[1]))
+                timing.append((ev[1], ev[2]))
+                side.wait_event(ev[2])
+                with torch.cuda.stream(side):
+                    slot["host_sizes"].copy_(slot["sizes"], non_blocking=True)
+                    sized = torch.cuda.Event()
+                    sized.record(side)
+                jobs.put((slot, lo, n, sized))
+        finally:
+            jobs.put(None)
+            w0 = _time.perf_counter()
+            thread.join()                                            # the one wait at the end
+            wait_end = _time.perf_counter() - w0
+            for w in writers.values():
+                w.close()
+        if errors:
+            raise errors[0]
+        torch.cuda.synchronize(dev)
+        seconds = _time.perf_counter() - t0
+        export_ms = sum(a.elapsed_time(b) for a, b in export_timing)
+        encode_ms = sum(a.elapsed_time(b) for a, b in timing)
+        k = self._like
+        return {"frames": N, "seconds": seconds, "fps": N / seconds if seconds > 0 else float("inf"), "writer_wait_s": wait,
+                "writer_wait_at_end_s": wait_end, "export_ms": export_ms, "export_ms_per_view": export_ms / max(N, 1),
+                "files": [paths[k] for k in kinds] if files else [], "bytes": total[0], "encode_ms": encode_ms,
+                "encode_ms_per_view": encode_ms / max(N, 1),
+                "calibration": {"fx": float(k.fx), "fy": float(k.fy), "cx": float(k.cx), "cy": float(k.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
+                                "p2": 0.0, "k3": 0.0, "distorted": False, "width": W, "height": H, "depth_scale": float(DEPTH_SCALE)}}

@@ -4,7 +4,11 @@
   * playback frames/s without files (render + export + copy to pinned memory) and with files, and the time the loop waited for the writer;
   * the yardstick: the same frames produced without this module -- per-frame render(), (clamp * 255).to(uint8).permute(1, 2, 0).cpu(),
     PIL's Image.save, matplotlib's jet for the depth picture.
---frames N: frames played (default 120, resampled along the tracked path); --out PATH."""
+--frames N: frames played (default 120, resampled along the tracked path); --out PATH.
+--video [--repeats R] [--quality Q]: the video mode instead. On the same map and path it alternates Playback.write (PNG files of rgb and
+depth_vis) and Playback.write_video (Motion-JPEG AVI, compressed on the device), each with files and with files=False, R times each, and
+times gsr_jpeg_encode by device events at V = 1 and 12; writes profiles/playback_video.json. --encode-only: only that last timing (the
+form to run under a kernel profiler)."""
 import argparse
 import json
 import os
@@ -59,6 +63,51 @@ def time_export(colour, depth, repeats=50):
     return {"views": V, "ms_per_call": ms, "us_per_view": ms * 1e3 / V, "bytes_moved": moved, "GB_per_s": moved / (ms * 1e-3) / 1e9}
 
 
+def time_encode(pb, colour, depth, quality, repeats=20):
+    """ms per call of gsr_jpeg_encode on the exported bytes of the given views, by device events around `repeats` back-to-back calls."""
+    from slam import mjpeg
+    V, _, H, W = colour.shape
+    dev = colour.device
+    lut = torch.from_numpy(frame_io.jet_lut().copy()).to(dev)
+    rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+    frame_io.frame_export(colour, depth, lut, DEPTH_VMAX, DEPTH_SCALE, rgb)
+    q = torch.from_numpy(mjpeg.quant_tables(quality).astype(np.int16)).to(dev)
+    scan = torch.empty((V, W * H * 3), dtype=torch.uint8, device=dev)
+    sizes = torch.empty((V,), dtype=torch.int32, device=dev)
+    ws = torch.empty(mjpeg.jpeg_workspace_size(V, W, H), dtype=torch.uint8, device=dev)
+    for _ in range(3):
+        mjpeg.jpeg_encode(rgb, q, scan, sizes, None, ws)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(repeats):
+        mjpeg.jpeg_encode(rgb, q, scan, sizes, None, ws)
+    b.record()
+    b.synchronize()
+    ms = a.elapsed_time(b) / repeats
+    out = [int(v) for v in sizes.cpu()]
+    return {"views": V, "quality": quality, "ms_per_call": ms, "us_per_view": ms * 1e3 / V, "scan_bytes_per_view": sum(out) / V,
+            "rgb_bytes_per_view": W * H * 3, "workspace_bytes": int(ws.numel())}
+
+
+def video_mode(pb, poses, times, tmp, repeats, quality):
+    keep = ("frames", "seconds", "fps", "writer_wait_s", "writer_wait_at_end_s", "export_ms_per_view")
+    vkeep = keep + ("encode_ms_per_view", "bytes")
+    pb.write(poses[:24], times[:24], os.path.join(tmp, "warm_png"))                      # first-use costs stay out of every figure
+    pb.write_video(poses[:24], times[:24], os.path.join(tmp, "warm_avi"), quality=quality)
+    runs = {"png_files": [], "png_no_files": [], "video_files": [], "video_no_files": []}
+    for r in range(repeats):
+        a = pb.write(poses, times, os.path.join(tmp, f"png{r}"))
+        runs["png_files"].append({k: a[k] for k in keep})
+        b = pb.write_video(poses, times, os.path.join(tmp, f"avi{r}"), quality=quality)
+        runs["video_files"].append({k: b[k] for k in vkeep})
+        c = pb.write(poses, times, os.path.join(tmp, f"png_none{r}"), files=False)
+        runs["png_no_files"].append({k: c[k] for k in keep})
+        d = pb.write_video(poses, times, os.path.join(tmp, f"avi_none{r}"), quality=quality, files=False)
+        runs["video_no_files"].append({k: d[k] for k in vkeep})
+    summary = {k: {"fps_min": min(x["fps"] for x in v), "fps_max": max(x["fps"] for x in v)} for k, v in runs.items()}
+    return {"runs": runs, "summary": summary}
+
+
 def yardstick(pb, poses, times, out_dir):
     """The frames as the code before this module could produce them: one render() per frame, torch's clamp / scale / permute / .cpu(), PIL's
     encoder, matplotlib's colormap for the depth picture."""
@@ -100,8 +149,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--frames", type=int, default=120)
     ap.add_argument("--map", default=None, help="a saved map to play (default: run the dynamic 640x480 synthetic SLAM first)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "playback.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/playback.json, or profiles/playback_video.json with --video")
+    ap.add_argument("--video", action="store_true", help="the video mode: PNG files and Motion-JPEG AVI files alternated on the same path")
+    ap.add_argument("--encode-only", action="store_true", help="with --video: only the gsr_jpeg_encode timing")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--quality", type=int, default=90)
     args = ap.parse_args(argv)
+    args.out = args.out or os.path.join(REPO, "profiles", "playback_video.json" if args.video else "playback.json")
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         directory = args.map or build_map(os.path.join(tmp, "map"))
@@ -110,6 +164,17 @@ def main(argv=None):
         pb = Playback(loaded)
         poses, times = resampled(loaded, args.frames)
         colour, depth, _ = pb.render(poses[:12], times[:12])
+        if args.video:
+            out = {"device": torch.cuda.get_device_name(0), "resolution": [pb.width, pb.height], "frames": args.frames,
+                   "gaussians": int(loaded.gaussians.get_xyz.shape[0]), "quality": args.quality,
+                   "gsr_jpeg_encode": [time_encode(pb, colour[:1], depth[:1], args.quality), time_encode(pb, colour, depth, args.quality)]}
+            if not args.encode_only:
+                out.update(video_mode(pb, poses, times, tmp, args.repeats, args.quality))
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+            print(json.dumps(out))
+            return
         export = [time_export(colour[:1], depth[:1]), time_export(colour, depth)]
         pb.write(poses[:24], times[:24], os.path.join(tmp, "warm"))                      # first-use costs (streams, pinned memory, zlib) stay out
         keep = ("frames", "seconds", "fps", "writer_wait_s", "writer_wait_at_end_s", "export_ms_per_view")

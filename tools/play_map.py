@@ -2,7 +2,10 @@
 """Play a saved 4D map (slam/map_io.py) back to image files (slam/playback.py):
   play_map.py --map DIR --path tracked|frozen-time:T|frozen-camera:I:N|resample:N --out DIR [--depth16] [--no-depth-vis]
 writes rgb/*.png, depth_vis/*.png (jet, 0-6 m) and, with --depth16, depth/*.png plus the lists of a TUM sequence; prints one JSON line with
-the frames written, the seconds, frames per second and the time the loop waited for the writer thread."""
+the frames written, the seconds, frames per second and the time the loop waited for the writer thread.
+  play_map.py --map DIR --path ... --out DIR --video [--fps F] [--quality Q] [--no-depth-vis]
+writes rgb.avi and depth_vis.avi instead: Motion-JPEG in AVI, compressed on the device (slam/mjpeg.py); the JSON line gains "video": true,
+"bytes" and "encode_ms"."""
 import argparse
 import json
 import os
@@ -20,16 +23,26 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--depth16", action="store_true", help="also write 16-bit depth and the TUM lists")
     ap.add_argument("--no-depth-vis", action="store_true", help="do not write the jet-coloured depth pictures")
+    ap.add_argument("--video", action="store_true", help="write Motion-JPEG AVI files (rgb.avi, depth_vis.avi) instead of PNG folders")
+    ap.add_argument("--fps", type=float, default=30.0, help="frame rate of the video files")
+    ap.add_argument("--quality", type=int, default=90, help="JPEG quality of the video frames, 1 .. 100")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     from slam.map_io import load_map
     from slam.playback import Playback, parse_path
     loaded = load_map(args.map, args.device)
     poses, times = parse_path(loaded, args.path)
-    res = Playback(loaded).write(poses, times, args.out, depth16=args.depth16, depth_colour=not args.no_depth_vis)
+    if args.video and args.depth16:
+        ap.error("--depth16 has no video form: the 16-bit depth is written as PNG files only")
+    extra = {}
+    if args.video:
+        res = Playback(loaded).write_video(poses, times, args.out, fps=args.fps, quality=args.quality, depth_colour=not args.no_depth_vis)
+        extra = {"video": True, "bytes": res["bytes"], "encode_ms": res["encode_ms"]}
+    else:
+        res = Playback(loaded).write(poses, times, args.out, depth16=args.depth16, depth_colour=not args.no_depth_vis)
     print(json.dumps({"map": args.map, "path": args.path, "out": args.out, "frames": res["frames"], "seconds": res["seconds"],
                       "fps": res["fps"], "writer_wait_s": res["writer_wait_s"], "gaussians": int(loaded.gaussians.get_xyz.shape[0]),
-                      "dynamic": loaded.dynamic}))
+                      "dynamic": loaded.dynamic, **extra}))
 
 
 if __name__ == "__main__":
