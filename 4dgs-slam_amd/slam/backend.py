@@ -24,6 +24,7 @@ import mapping_shard
 import slam_losses
 
 from .deform_model import draw_loss_times
+from .schedule import catch_up
 
 
 class _IsotropicLoss(torch.autograd.Function):
@@ -178,22 +179,26 @@ class BackEnd:
                     pkg = done_pkg
                     mapping_iteration += run
                     continue
-            self.iteration_count += 1
-            pkg = self._render(viewpoint, (None, None, None))
-            # (no name for the loss: a local that outlives the iteration keeps its autograd graph -- and the default-stream AccumulateGrad nodes of
-            # the camera parameters -- alive into the next graph run's capture)
-            slam_losses.get_loss_mapping(self.config, pkg["render"], pkg["depth"], viewpoint, pkg["opacity"], initialization=True,
-                                         rm_dynamic=rm_dynamic, compute_value=self.loss_values).backward()
-            with torch.no_grad():
-                self._view_stats(pkg)
+            pkg = self._initialize_map_iteration(viewpoint, rm_dynamic, mapping_iteration)
+            mapping_iteration += 1
+        self.occ_aware_visibility[cur_frame_idx] = (self._final_touched(viewpoint, pkg) > 0).long()
+        return pkg
+
+    def _initialize_map_iteration(self, viewpoint, rm_dynamic, mapping_iteration=None):
+        """One eager iteration of initialize_map; `mapping_iteration`: its index when it may densify or reset opacities, None inside a plain run."""
+        self.iteration_count += 1
+        pkg = self._render(viewpoint, (None, None, None))
+        slam_losses.get_loss_mapping(self.config, pkg["render"], pkg["depth"], viewpoint, pkg["opacity"], initialization=True,
+                                     rm_dynamic=rm_dynamic, compute_value=self.loss_values).backward()
+        with torch.no_grad():
+            self._view_stats(pkg)
+            if mapping_iteration is not None:
                 if mapping_iteration % self.init_gaussian_update == 0:
                     self.gaussians.densify_and_prune(self.opt_params.densify_grad_threshold, self.init_gaussian_th, self.init_gaussian_extent, None)
                 if self.iteration_count == self.init_gaussian_reset or self.iteration_count == self.opt_params.densify_from_iter:
                     self.gaussians.reset_opacity()
-                self.gaussians.optimizer.step()
-                self.gaussians.optimizer.zero_grad(set_to_none=True)
-            mapping_iteration += 1
-        self.occ_aware_visibility[cur_frame_idx] = (self._final_touched(viewpoint, pkg) > 0).long()
+            self.gaussians.optimizer.step()
+            self.gaussians.optimizer.zero_grad(set_to_none=True)
         return pkg
 
     def _plain_init_run(self, mapping_iteration):
@@ -211,8 +216,7 @@ class BackEnd:
         None when nothing was executed (the caller goes on eagerly)."""
         from .mapping_graph import InitGraph, INIT_CAPTURE_OPTIONS
         from . import graph_run
-        g = self.gaussians
-        if graph_run.broken(self, "init_graph") or g.optimizer.scheduled_segments() is None:
+        if graph_run.broken(self, "init_graph") or self.gaussians.optimizer.scheduled_segments() is None:
             return None
         try:
             ig = InitGraph(self, viewpoint, rm_dynamic, run)
@@ -220,19 +224,10 @@ class BackEnd:
             graph_run.note_failure(self, "init_graph", e)
             return None
         done = graph_run.replay_run(self, ig, run, min(self.graph_warmup, run), kind="init_graph", options=INIT_CAPTURE_OPTIONS)
-        self.iteration_count += done
-        g.optimizer.advance_steps(ig.todo, done)
+        catch_up(self, ig.todo, done, sent=False, learning_rate=False)
         pkg = ig.pkg if done == run else None
-        if done < run:                     # finish the run eagerly, iteration by iteration (plain ones: no densification inside a run)
-            for _ in range(run - done):
-                self.iteration_count += 1
-                pkg = self._render(viewpoint, (None, None, None))
-                slam_losses.get_loss_mapping(self.config, pkg["render"], pkg["depth"], viewpoint, pkg["opacity"], initialization=True,
-                                             rm_dynamic=rm_dynamic, compute_value=self.loss_values).backward()
-                with torch.no_grad():
-                    self._view_stats(pkg)
-                    g.optimizer.step()
-                    g.optimizer.zero_grad(set_to_none=True)
+        for _ in range(run - done):        # finish the run eagerly, iteration by iteration (plain ones: no densification inside a run)
+            pkg = self._initialize_map_iteration(viewpoint, rm_dynamic)
         return pkg
 
     def _final_touched(self, viewpoint, pkg):
@@ -492,7 +487,7 @@ class BackEnd:
     @property
     def keyframe_operands(self):
         if getattr(self, "_kf_operands", None) is None:
-            from .mapping_graph import KeyframeOperands
+            from .keyframe_slots import KeyframeOperands
             self._kf_operands = KeyframeOperands()
         return self._kf_operands
 
@@ -514,7 +509,7 @@ class BackEnd:
             graph_run.note_failure(self, "graph", e)
             return 0
         done = graph_run.replay_run(self, mg, run, min(self.graph_warmup, run), kind="graph", options=CAPTURE_OPTIONS)
-        self._finish_run(mg, done)
+        catch_up(self, mg.todo, done)
         if done < run:
             for j, extras_idx in enumerate(draws[done:], done):
                 self._map_static_iteration(current_window, viewpoint_stack, random_viewpoint_stack, False, last and j == run - 1, extras_idx=extras_idx)
@@ -522,15 +517,6 @@ class BackEnd:
             with torch.no_grad():
                 self._publish_visibility(current_window, {k: mg.pkgs[k]["n_touched"] for k in range(len(viewpoint_stack))})
         return run
-
-    def _finish_run(self, mg, n):
-        """Host-side state after `n` graph iterations: what n eager iterations would have left (counters, Adam's step counts, learning rate)."""
-        g = self.gaussians
-        self.iteration_count += n
-        self.last_sent += n
-        g.optimizer.advance_steps(mg.todo, n)
-        if n:
-            g.update_learning_rate(self.iteration_count)
 
     def _clear_camera_grads(self, cams):
         for v in cams:

@@ -10,7 +10,7 @@ What the host decides per iteration in the reference -- and what therefore had t
 recorded once and replayed:
 
   * which two RANDOM keyframes are rendered (:344-349): two persistent *slots* (camera + ground truth + loss weights, filled by
-    gsr_slot_gather from a device table of the candidates' buffer addresses, slam/mapping_graph.py) -- plus, here, the slot's TIME, its
+    gsr_slot_gather from a device table of the candidates' buffer addresses, slam/keyframe_slots.py) -- plus, here, the slot's TIME, its
     flow PARTNER (the closest earlier keyframe, :299-304,:479-509: a second slot camera) and the pair's flow targets (six image planes,
     moved by a second gather through the same entry point), and the partner's time;
   * the random TIME SAMPLES of the two regularisers (:517-519,:646-648; 12 per window view, 10 per random keyframe): drawn on the host
@@ -29,21 +29,18 @@ moving pixels in the first half; :337-338,:765-770: the Gaussians only step in t
 boundary. Warm-up, capture, replays and undo are slam/graph_run.py's: a replayed forward pass that outgrows its binning buffer is detected
 after the run (sticky overflow counters), the run is then undone from a snapshot (``state_tensors()``) and repeated directly; so is the rest
 of a run whose capture fails."""
-import ctypes as C
 import os
 
-import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C
-from diff_gaussian_rasterization._abi import gsr_keyframe_entry
 import control_nodes
 import slam_losses
 
-from . import graph_run
+from . import graph_run, keyframe_slots
 from .camera import Camera
 from .deform_model import draw_loss_times, time_key
 from .mapping_graph import N_INDEX_WORDS
+from .schedule import Schedule, adam_rows, camera_gradients, catch_up, densification_statistics, gaussian_state, network_state, window_state, xyz_lr_rule
 
 # Head room of the binning buffers a captured iteration lays out (include/gs_rasterizer.h): while the node network trains alone (first half
 # of a call) the moving object's Gaussians can swell and pile up for a few iterations -- measured: instance counts +10 %, the longest tile
@@ -64,6 +61,10 @@ WINDOW_SAMPLES, EXTRA_SAMPLES = (4, 8), (2, 8)        # (ARAP, elastic) time sam
 _region = torch.autograd.profiler.record_function          # names a part of the iteration for the profiler (tools/mapping_iteration_launches.py)
 
 
+def _planes(f6):          # a [6, H, W] flow-target tensor as the four planes gsr_slot_gather moves (gt_image[3], gt_depth, w_rgb, w_depth)
+    return f6[0:3], f6[3:4], f6[4:5], f6[5:6]
+
+
 def eligible(be, views, candidates):
     """Can this map() call run in the fixed layout? (Else BackEnd.map's eager body takes it: sharded runs, test doubles, monocular input,
     fewer than three nodes, keyframes without a motion mask.)"""
@@ -79,8 +80,7 @@ def eligible(be, views, candidates):
 
 class _Run:
     """`rows` consecutive iterations of one phase: their schedule in device memory."""
-    __slots__ = ("i0", "rows", "dyn", "stepping", "with_flow", "flow_weight", "layout", "tables", "todo", "table", "row_words", "coef_lo", "samples_lo",
-                 "n_rest", "current", "count0", "draws")
+    __slots__ = ("i0", "rows", "dyn", "stepping", "with_flow", "flow_weight", "layout", "tables", "todo", "schedule", "count0", "draws")
 
 
 class DynamicMapping:
@@ -101,15 +101,12 @@ class DynamicMapping:
         self.has_flow_data = hasattr(be.dataset, "gt_flow")
         self.n_slots = min(N_INDEX_WORDS, len(self.candidates))
         any_flow = self.has_flow_data and max(self.flow_weights.values()) > 0
-        mk = lambda uid: Camera(uid, None, None, torch.eye(4), proto.projection_matrix, proto.fx, proto.fy, proto.cx, proto.cy, proto.FoVx, proto.FoVy,
-                                self.H, self.W, 0.0, None, device=dev)
-        z = lambda c: torch.zeros((c, self.H, self.W), device=dev)
-        self.slots = [mk(-1 - s) for s in range(self.n_slots)]
-        self.slot_ops = [(z(3), z(1), z(1), z(1)) for _ in range(self.n_slots)]
-        self.partner_slots = [mk(-101 - s) for s in range(self.n_slots)] if any_flow else []
-        self.partner_flow = [z(6) for _ in range(self.n_slots)] if any_flow else []
-        self.slot_dst = self._entries([(c, o) for c, o in zip(self.slots, self.slot_ops)])
-        self.partner_dst = self._entries([(c, (f[0:3], f[3:4], f[4:5], f[5:6])) for c, f in zip(self.partner_slots, self.partner_flow)])
+        self.slots = [keyframe_slots.blank_camera(proto, -1 - s, dev) for s in range(self.n_slots)]
+        self.slot_ops = [keyframe_slots.slot_buffers(self.H, self.W, dev) for _ in range(self.n_slots)]
+        self.partner_slots = [keyframe_slots.blank_camera(proto, -101 - s, dev) for s in range(self.n_slots)] if any_flow else []
+        self.partner_flow = [torch.zeros((6, self.H, self.W), device=dev) for _ in range(self.n_slots)] if any_flow else []
+        self.slot_dst = keyframe_slots.entries(list(zip(self.slots, self.slot_ops)))
+        self.partner_dst = keyframe_slots.entries([(c, _planes(f)) for c, f in zip(self.partner_slots, self.partner_flow)])
         self._zero6 = None
         self.slot_clips = torch.zeros((max(1, self.n_slots), 8), dtype=torch.int32, device=dev)       # per slot: its rectangle, its partner's
         self._layouts, self._tables, self._window_ops = {}, {}, {}
@@ -117,17 +114,6 @@ class DynamicMapping:
         self.run, self.pkgs = None, None
         self.stats = graph_run.stats(be, "dynamic_graph")
         self.stats.setdefault("special", 0)
-
-    @staticmethod
-    def _entries(pairs):
-        if not pairs:
-            return None
-        arr = (gsr_keyframe_entry * len(pairs))()
-        for d, (cam, ops) in zip(arr, pairs):
-            d.viewmatrix, d.full_proj, d.campos = cam._view.data_ptr(), cam._full.data_ptr(), cam._campos.data_ptr()
-            d.exposure_a, d.exposure_b = cam.exposure_a.data_ptr(), cam.exposure_b.data_ptr()
-            d.gt_image, d.gt_depth, d.w_rgb, d.w_depth = (t.data_ptr() for t in ops)
-        return arr
 
     # ---- per-call constants --------------------------------------------------------------------------------------------------------------
     def phase(self, i):
@@ -163,8 +149,7 @@ class DynamicMapping:
             # hold what they point at
             budget = self.be.__dict__.get("_flow_targets6_budget")
             if budget is None:
-                from .mapping_graph import device_store_budget
-                budget = self.be.__dict__["_flow_targets6_budget"] = device_store_budget(self.device, FLOW_TARGET_BUDGET_FRACTION)
+                budget = self.be.__dict__["_flow_targets6_budget"] = keyframe_slots.device_store_budget(self.device, FLOW_TARGET_BUDGET_FRACTION)
             each = hit.numel() * hit.element_size()
             while cache and (len(cache) >= FLOW_TARGET_CACHE_MAX or (len(cache) + 1) * each > budget):
                 cache.pop(next(iter(cache)))
@@ -209,15 +194,9 @@ class DynamicMapping:
         if hit is None:
             be, dev = self.be, self.device
             store, cfg = be.keyframe_operands, be.config
-            rows, prow, times, keep, clip_rows = [], [], [], [], []
+            ops, partners, flows, times, clip_rows = [], [], [], [], []
             for c in self.candidates:
-                ops = store.get(cfg, c, dev, rm_dynamic=False, dynamic=dyn)
-                for tns in ops[:4]:
-                    if tns.dtype != torch.float32 or not tns.is_contiguous():
-                        raise RuntimeError("DynamicMapping: loss operands must be contiguous float32 tensors")
-                keep.append(ops)
-                rows.append([c.world_view_transform.data_ptr(), c.full_proj_transform.data_ptr(), c.camera_center.data_ptr(), c.exposure_a.data_ptr(),
-                             c.exposure_b.data_ptr(), ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), ops[3].data_ptr()])
+                ops.append(store.get(cfg, c, dev, rm_dynamic=False, dynamic=dyn))
                 if with_flow:
                     p = self.partner_of(c)
                     if p is None:               # no earlier keyframe: the candidate stands in for its partner with an all-zero target and mask --
@@ -227,19 +206,18 @@ class DynamicMapping:
                         f6 = self._zero6
                     else:
                         f6 = self.flow6(c, p)
-                    keep.append(f6)
-                    step = self.pixels * 4
-                    prow.append([p.world_view_transform.data_ptr(), p.full_proj_transform.data_ptr(), p.camera_center.data_ptr(), p.exposure_a.data_ptr(),
-                                 p.exposure_b.data_ptr(), f6.data_ptr(), f6.data_ptr() + 3 * step, f6.data_ptr() + 4 * step, f6.data_ptr() + 5 * step])
+                    partners.append(p)
+                    flows.append(f6)
                     times.append([time_key(c.time), time_key(p.time)])
                     # (rows 2 c and 2 c + 1: the rectangles the two flow images of the pair are read in; the stand-in pair reads nothing)
                     clip_rows += [self.flow_clip(c), self.flow_clip(p)] if p is not c else [torch.zeros(4, dtype=torch.int32, device=dev)] * 2
                 else:
                     times.append([time_key(c.time)])
-            up = lambda a, dt: torch.tensor(a, dtype=dt).pin_memory().to(dev, non_blocking=True)
+            up = keyframe_slots.upload_rows
             hit = self._tables[(dyn, with_flow)] = {
-                "keep": keep, "kf": up(rows, torch.int64) if rows else None, "partner": up(prow, torch.int64) if prow else None,
-                "times": up(times, torch.float32) if times else None, "clips": torch.stack(clip_rows).reshape(len(self.candidates), 8) if clip_rows else None}
+                "keep": ops + flows, "kf": up(keyframe_slots.address_rows(self.candidates, [o[:4] for o in ops]), torch.int64, dev),
+                "partner": up(keyframe_slots.address_rows(partners, [_planes(f) for f in flows]), torch.int64, dev), "times": up(times, torch.float32, dev),
+                "clips": torch.stack(clip_rows).reshape(len(self.candidates), 8) if clip_rows else None}
         return hit
 
     # ---- a run's schedule -------------------------------------------------------------------------------------------------------------------
@@ -265,26 +243,10 @@ class DynamicMapping:
                 plan = draw_loss_times(v.time, arap_delta if window else 5 * ti, WINDOW_SAMPLES[0] if window else EXTRA_SAMPLES[0], 5 * ti)
                 samples += [time_key(x) for x in plan["arap"] + plan["elastic"]]
             r.draws.append((extra_idx, samples))
-        r.n_rest = nv * sum(WINDOW_SAMPLES) + self.n_slots * sum(EXTRA_SAMPLES)
-        opt = g.optimizer
-        r.todo = opt.scheduled_segments() if r.stepping else None
-        n_coef = 2 * len(r.todo) if r.todo else 0
-        r.coef_lo, r.samples_lo = N_INDEX_WORDS, N_INDEX_WORDS + n_coef
-        r.row_words = r.samples_lo + r.n_rest
+        r.todo = g.optimizer.scheduled_segments() if r.stepping else None
         r.count0 = be.iteration_count
-        table = np.zeros((rows, r.row_words), dtype=np.uint32)
-        fl = table.view(np.float32)
-        for j, (extra_idx, samples) in enumerate(r.draws):
-            for s, c in enumerate(extra_idx[:N_INDEX_WORDS]):
-                table[j, s] = c
-            for k, (group, p) in enumerate(r.todo or ()):
-                lr = group["lr"]
-                if j > 0 and group.get("name") == "xyz":          # update_learning_rate(iteration_count) ran after the previous step (GM:492-505)
-                    lr = g.xyz_lr_at(r.count0 + j)
-                fl[j, r.coef_lo + 2 * k], fl[j, r.coef_lo + 2 * k + 1] = opt.coefficients(lr, group["betas"], int(opt.state[p]["step"]) + j + 1)
-            fl[j, r.samples_lo:] = np.asarray(samples, dtype=np.float32)
-        r.table = torch.from_numpy(table.view(np.int32)).pin_memory().to(self.device, non_blocking=True)
-        r.current = torch.zeros(r.row_words, dtype=torch.int32, device=self.device)
+        r.schedule = Schedule(rows, self.device, index_words=[d[0] for d in r.draws], samples=[d[1] for d in r.draws], counter=self.counter,
+                              adam=adam_rows(g.optimizer, r.todo, rows, xyz_lr_rule(g, r.count0)) if r.todo else None)
         self.counter.zero_()
         self.run = r
         return r
@@ -296,21 +258,18 @@ class DynamicMapping:
         be, g, nodes, r, dev = self.be, self.g, self.nodes, self.run, self.device
         lay, tab = r.layout, r.tables
         self.pkgs = None            # (the previous iteration's autograd graph dies here, not while the next one is being built)
-        L = _C.load_library()
-        with torch.cuda.device(dev):
-            L.gsr_schedule_advance(self.counter.data_ptr(), r.table.data_ptr(), r.row_words, r.rows, r.current.data_ptr(), _C._stream(dev))
-            if self.n_slots:
-                entries = lambda t: C.cast(t.data_ptr(), C.POINTER(gsr_keyframe_entry))      # a device table of the candidates
-                L.gsr_slot_gather(self.n_slots, entries(tab["kf"]), r.current.data_ptr(), self.slot_dst, self.pixels, _C._stream(dev))
-                if r.with_flow:
-                    L.gsr_slot_gather(self.n_slots, entries(tab["partner"]), r.current.data_ptr(), self.partner_dst, self.pixels, _C._stream(dev))
+        r.schedule.advance()
+        slot_index = r.schedule.indices(self.n_slots)
+        keyframe_slots.gather(self.n_slots, tab["kf"], slot_index, self.slot_dst, self.pixels, dev)
+        if r.with_flow:
+            keyframe_slots.gather(self.n_slots, tab["partner"], slot_index, self.partner_dst, self.pixels, dev)
         # ---- the iteration's time samples, in the fixed layout ------------------------------------------------------------------------------
         # (the _region ranges only name the iteration's parts for tools/mapping_iteration_launches.py; no effect on the work)
         with _region("gsr.network"):
             parts = [lay["wtimes"]]
             if self.n_slots:
-                parts.append(tab["times"].index_select(0, r.current[:self.n_slots].long()).reshape(-1))
-            parts.append(r.current.view(torch.float32)[r.samples_lo:r.samples_lo + r.n_rest])
+                parts.append(tab["times"].index_select(0, slot_index.long()).reshape(-1))
+            parts.append(r.schedule.samples())
             it = nodes.begin_iteration_indexed(torch.cat(parts), lay["n_full"], blend=(g.get_dygs_xyz.detach(), g.motion_mask))
         nv, ne = len(self.views), self.n_slots
         with _region("gsr.regularisers"):
@@ -358,7 +317,7 @@ class DynamicMapping:
             from gaussian_renderer import render_flow_views
             requests, pairs, clips = [], [], []
             if self.n_slots and tab["clips"] is not None:
-                torch.index_select(tab["clips"], 0, r.current[:self.n_slots].long(), out=self.slot_clips[:self.n_slots])
+                torch.index_select(tab["clips"], 0, slot_index.long(), out=self.slot_clips[:self.n_slots])
             for k, v in enumerate(views):
                 if k < nv:
                     other, f6 = lay["partners"][k], lay["flow6"][k]
@@ -407,7 +366,7 @@ class DynamicMapping:
             g.deform.optimizer.zero_grad(set_to_none=True)
             if r.stepping:                                                    # :765-770
                 if special is None:
-                    g.optimizer.step_scheduled(r.todo, r.current[r.coef_lo:].data_ptr())
+                    g.optimizer.step_scheduled(r.todo, r.schedule.coefficients_ptr())
                 else:
                     g.optimizer.step()
                     g.update_learning_rate(be.iteration_count)
@@ -446,15 +405,6 @@ class DynamicMapping:
         be.__dict__.setdefault("flow_clip_checks", []).append({"masked_images_equal": same, "gradient_rel_diff": rel, "gaussians_drawn": drawn})
 
     # ---- executing a run ---------------------------------------------------------------------------------------------------------------
-    def finish(self, n):
-        """Host-side state after `n` plain iterations of the current run: what n eager iterations would have left."""
-        be, g, r = self.be, self.g, self.run
-        be.last_sent += n
-        if r.stepping and n:
-            be.iteration_count += n
-            g.optimizer.advance_steps(r.todo, n)
-            g.update_learning_rate(be.iteration_count)
-
     def direct(self, n):
         for _ in range(n):
             self.iteration()
@@ -462,19 +412,9 @@ class DynamicMapping:
 
     # ---- for slam/graph_run.py -------------------------------------------------------------------------------------------------------
     def state_tensors(self):
-        g, r = self.g, self.run
-        tensors = [p for grp in g.optimizer.param_groups for p in grp["params"]]
-        if r.todo:
-            tensors += [g.optimizer.state[p][k] for _, p in r.todo for k in ("exp_avg", "exp_avg_sq")]
-        net = g.deform.optimizer
-        for grp in net.param_groups:
-            for p in grp["params"]:
-                tensors.append(p)
-                tensors += [v for v in net.state.get(p, {}).values() if torch.is_tensor(v)]
-        tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D, self.counter]
-        for v in self.views:
-            tensors += [v._R, v._T, v._adam, v._converged, v.exposure_a, v.exposure_b, v.cam_rot_delta, v.cam_trans_delta]
-        return tensors
+        g = self.g
+        return (gaussian_state(g.optimizer, [p for grp in g.optimizer.param_groups for p in grp["params"]], self.run.todo)
+                + network_state(g.deform.optimizer) + densification_statistics(g) + [self.counter] + window_state(self.views))
 
     def discard(self):
         for v in self.views:
@@ -494,7 +434,7 @@ class DynamicMapping:
             options = dict(CAPTURE_OPTIONS, cap_test_shrink_permille=int(be.config["Training"].get("graph_test_shrink_permille", 0)))
             done = graph_run.replay_run(be, self, rows, min(be.dynamic_graph_warmup, rows), kind="dynamic_graph", options=options)
         self.direct(rows - done)
-        self.finish(rows)
+        catch_up(be, r.todo, rows, counts_iterations=r.stepping)
 
     def execute(self):
         """All iterations of the call. Returns gaussian_split of the last one (:336,:745)."""
@@ -577,16 +517,7 @@ class NetworkInit:
         return pkg
 
     def state_tensors(self):
-        g, v = self.g, self.viewpoint
-        net = g.deform.optimizer
-        tensors = []
-        for grp in net.param_groups:
-            for p in grp["params"]:
-                tensors.append(p)
-                tensors += [s for s in net.state.get(p, {}).values() if torch.is_tensor(s)]
-        tensors += [g.xyz_gradient_accum, g.denom, g.max_radii2D]
-        tensors += [p.grad for p in (v.cam_rot_delta, v.cam_trans_delta, v.exposure_a, v.exposure_b) if p is not None and p.grad is not None]
-        return tensors
+        return network_state(self.g.deform.optimizer) + densification_statistics(self.g) + camera_gradients(self.viewpoint)
 
     def discard(self):
         """(the view's camera gradients are part of the snapshot: they accumulate across the loop on purpose, see iteration())"""

@@ -27,6 +27,7 @@ import slam_losses
 
 from .camera import Camera
 from .graph_run import capture_options
+from .keyframe_slots import blank_camera, slot_buffers
 
 # GSR_TRACK_STEP=0: the iteration through autograd (render -> weighted_l1_loss -> backward -> pose_step: ten launches), as rounds 2-5 ran it
 FUSED_STEP = os.environ.get("GSR_TRACK_STEP", "1") not in ("", "0")
@@ -36,13 +37,8 @@ class TrackingGraph:
     def __init__(self, gaussians, pipeline_params, background, config, proto: Camera):
         self.gaussians, self.pipe, self.background, self.config = gaussians, pipeline_params, background, config
         dev = proto.device
-        H, W = int(proto.image_height), int(proto.image_width)
-        self.cam = Camera(1, None, None, torch.eye(4), proto.projection_matrix, proto.fx, proto.fy, proto.cx, proto.cy, proto.FoVx, proto.FoVy,
-                          H, W, 0.0, None, device=dev)
-        self.gt_image = torch.zeros((3, H, W), device=dev)
-        self.gt_depth = torch.zeros((1, H, W), device=dev)
-        self.w_rgb = torch.zeros((1, H, W), device=dev)
-        self.w_dep = torch.zeros((1, H, W), device=dev)
+        self.cam = blank_camera(proto, 1, dev)
+        self.gt_image, self.gt_depth, self.w_rgb, self.w_dep = slot_buffers(int(proto.image_height), int(proto.image_width), dev)
         self.alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
         lr = config["Training"]["lr"]
         self.lrs = (lr["cam_rot_delta"], lr["cam_trans_delta"], 0.01)

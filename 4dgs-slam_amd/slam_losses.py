@@ -227,7 +227,7 @@ def on_drop_keyframe_constants(method):
 
 def drop_keyframe_constants(viewpoint=None):
     """Forget the cached constants of one viewpoint (or of all): call it where the reference calls Camera.clean(). Stores registered through
-    on_drop_keyframe_constants (the graphs' per-keyframe operands, slam/mapping_graph.py) drop their entries of that viewpoint too."""
+    on_drop_keyframe_constants (the graphs' per-keyframe operands, slam/keyframe_slots.py) drop their entries of that viewpoint too."""
     if viewpoint is None:
         _CONST_CACHE.clear()
     else:

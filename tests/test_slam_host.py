@@ -198,10 +198,10 @@ def test_overlap_fractions_in_groups_equal_one_batched_projection(monkeypatch):
 
 
 def test_keyframe_operand_store_is_bounded_by_bytes_and_shares_ground_truth(monkeypatch):
-    """slam.mapping_graph.KeyframeOperands: one ground-truth copy per keyframe whatever the flag variant, a byte budget with
+    """slam.keyframe_slots.KeyframeOperands: one ground-truth copy per keyframe whatever the flag variant, a byte budget with
     least-recently-used eviction, and Camera.clean()'s hook (slam_losses.drop_keyframe_constants) drops the keyframe's entry."""
     import slam_losses
-    from slam import mapping_graph as mg
+    from slam import keyframe_slots as mg
     calls = []
 
     def fake_operands(config, viewpoint, device, rm_dynamic=False, mask=None, dynamic=False):
