@@ -42,6 +42,8 @@
 #include "gs_frame.h"
 #include "../../include/video_io.h"
 #include "gs_jpeg.h"
+#include "../../include/stereo_depth.h"
+#include "gs_stereo.h"
 #include "../../include/optical_flow.h"
 #include "gs_raft.h"
 #include "../../include/segmentation.h"
@@ -2963,6 +2965,86 @@ int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8,
     hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, coef, lengths, raw);
     GSR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)views), dim3(JPEG_SCAN_BLOCK), 0, stream, l.shape, raw, totals, scan, (long long)scan_stride, sizes);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_stereo_depth: census codes of the left and of the right image [H, W] u64 | S [H, W, D] u16 (unused when the caller
+// gives cost_sum); every part starts on a multiple of 16 bytes
+struct StereoLayout { size_t code_l, code_r, cost, bytes; };
+static bool stereo_layout(int width, int height, int D, StereoLayout& l)
+{
+    if (width < 1 || height < 1 || (D != 64 && D != 128) || (long long)width * height * D > 0x7fffffffLL) return false;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n = (size_t)width * height;
+    l.code_l = 0;
+    l.code_r = l.code_l + up(n * sizeof(uint64_t));
+    l.cost = l.code_r + up(n * sizeof(uint64_t));
+    l.bytes = l.cost + up(n * D * sizeof(unsigned short));
+    return true;
+}
+
+size_t gsr_stereo_workspace_size(int width, int height, int num_disparities)
+{
+    StereoLayout l;
+    return stereo_layout(width, height, num_disparities, l) ? l.bytes : 0;
+}
+
+int gsr_stereo_depth(int width, int height, int num_disparities, int p1, int p2, int uniqueness_ratio, int disp12_max_diff, float bf,
+                     const unsigned char* left_raw, const unsigned char* right_raw, const float* map_left, const float* map_right,
+                     const float* lut, unsigned char* left_rect, unsigned char* right_rect, float* image, short* disparity16, float* depth,
+                     unsigned short* cost_sum, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_stereo_depth: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    StereoLayout l;
+    if (!stereo_layout(width, height, num_disparities, l))
+        return fail("width and height must be positive, num_disparities 64 or 128 (got " + std::to_string(num_disparities) +
+                    ") and width * height * num_disparities below 2^31");
+    if (!(p1 > 0 && p1 < p2 && p2 <= 2047)) return fail("the penalties must satisfy 0 < p1 < p2 <= 2047, got p1 " + std::to_string(p1) + ", p2 " + std::to_string(p2));
+    if (uniqueness_ratio < 0 || uniqueness_ratio > 99) return fail("uniqueness_ratio must be in [0, 99], got " + std::to_string(uniqueness_ratio));
+    if (disp12_max_diff < -1) return fail("disp12_max_diff must be -1 (no check) or larger, got " + std::to_string(disp12_max_diff));
+    if (!left_raw || !right_raw || !disparity16 || !workspace) return fail("left_raw, right_raw, disparity16 and workspace must not be NULL");
+    if ((map_left != nullptr) != (map_right != nullptr)) return fail("map_left and map_right go together: both or neither");
+    if (map_left && (!left_rect || !right_rect)) return fail("left_rect and right_rect must not be NULL when maps are given");
+    if (image && !lut) return fail("image needs lut");
+    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
+        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_stereo_workspace_size), got " +
+                    std::to_string(workspace_bytes));
+    if ((num_disparities == 128 && cost_sum && ((size_t)cost_sum & 3))) return fail("cost_sum must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = static_cast<char*>(workspace);
+    uint64_t* code_l = reinterpret_cast<uint64_t*>(ws + l.code_l);
+    uint64_t* code_r = reinterpret_cast<uint64_t*>(ws + l.code_r);
+    unsigned short* S = cost_sum ? cost_sum : reinterpret_cast<unsigned short*>(ws + l.cost);
+    const size_t n = (size_t)width * height;
+    const unsigned pixel_blocks = (unsigned)((n + STEREO_BLOCK - 1) / STEREO_BLOCK);
+    if (map_left || left_rect || right_rect || image) {
+        hipLaunchKernelGGL(stereo_rectify_kernel, dim3(pixel_blocks, 2), dim3(STEREO_BLOCK), 0, stream, width, height, left_raw, right_raw,
+                           reinterpret_cast<const float2*>(map_left), reinterpret_cast<const float2*>(map_right), lut, left_rect, right_rect, image);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    const unsigned char* img_l = map_left ? left_rect : left_raw;
+    const unsigned char* img_r = map_left ? right_rect : right_raw;
+    hipLaunchKernelGGL(stereo_census_kernel, dim3(pixel_blocks, 2), dim3(STEREO_BLOCK), 0, stream, width, height, img_l, img_r, code_l, code_r);
+    GSR_HIP_CHECK(hipGetLastError());
+    static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
+    for (int r = 0; r < 8; ++r) {
+        const int dx = dirs[r][0], dy = dirs[r][1];
+        const unsigned paths = (unsigned)(dy == 0 ? height : dx == 0 ? width : width + height - 1);
+        if (num_disparities == 64)
+            hipLaunchKernelGGL(stereo_path_kernel<1>, dim3(paths), dim3(64), 0, stream, width, height, dx, dy, p1, p2, code_l, code_r, S, (int)(r == 0));
+        else
+            hipLaunchKernelGGL(stereo_path_kernel<2>, dim3(paths), dim3(64), 0, stream, width, height, dx, dy, p1, p2, code_l, code_r, S, (int)(r == 0));
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    const float bf16 = (float)((double)bf * 16.0);                       // formed in double, rounded once
+    const unsigned select_blocks = (unsigned)((n + STEREO_BLOCK / 64 - 1) / (STEREO_BLOCK / 64));
+    if (num_disparities == 64)
+        hipLaunchKernelGGL(stereo_select_kernel<1>, dim3(select_blocks), dim3(STEREO_BLOCK), 0, stream, width, height, uniqueness_ratio, disp12_max_diff,
+                           bf16, S, disparity16, depth);
+    else
+        hipLaunchKernelGGL(stereo_select_kernel<2>, dim3(select_blocks), dim3(STEREO_BLOCK), 0, stream, width, height, uniqueness_ratio, disp12_max_diff,
+                           bf16, S, disparity16, depth);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -233,6 +233,9 @@ FUNCTIONS = {
     # video_io.h
     "gsr_jpeg_workspace_size": (sz, [i, i, i]),
     "gsr_jpeg_encode": (i, [i, i, i, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
+    # stereo_depth.h
+    "gsr_stereo_workspace_size": (sz, [i, i, i]),
+    "gsr_stereo_depth": (i, [i] * 7 + [f] + [vp] * 12 + [sz, vp]),
     # optical_flow.h
     "gsr_raft_corr_pyramid": (i, [i, i, i, vp, vp, P(vp), P(vp), vp]),
     "gsr_raft_corr_lookup": (i, [i, i, i, P(vp), vp, vp, vp]),

@@ -166,6 +166,15 @@ class SyntheticRGBDDataset:
         self._cache[idx] = item
         return item
 
+    def right_view(self, idx, baseline):
+        """The colour image [3,H,W] of frame idx seen from the camera displaced by `baseline` metres along its own +x (the right camera
+        of a rectified stereo pair): a left pixel x at depth z matches the right pixel x - fx * baseline / z."""
+        pose = self.poses[idx].clone()
+        pose[0, 3] -= float(baseline)
+        xyz, rgb = self.gt_gaussians(idx)
+        color, _, _ = self._raster(xyz, rgb, pose, torch.zeros(3, device=self.device))
+        return color.clamp(0, 1).contiguous()
+
     def gt_flow(self, idx_from, idx_to):
         """NDC flow [H,W,2] of frame idx_from's surface points into frame idx_to (what the reference asks RAFT for, scaled as
         utils/camera_utils.py:412-413 does: pixels / (W, H) * 2), plus a validity mask. Cached per pair, like the reference keeps RAFT's

@@ -39,3 +39,20 @@ def decode_frame(color_path, depth_path, mask_path, width, height, depth_scale, 
             raise ValueError(f"{path}: {what} image of shape {a.shape}, the calibration says {want}")
     depth = (d.astype(np.float32) / np.float32(depth_scale)) if depth_float32 else (d / depth_scale).astype(np.float32)
     return HostFrame(rgb, mask, depth, (time.perf_counter() - t0) * 1e3)
+
+
+class StereoFrame:
+    __slots__ = ("left", "right", "decode_ms")
+
+    def __init__(self, left, right, decode_ms):
+        self.left, self.right, self.decode_ms = left, right, decode_ms
+
+
+def decode_stereo_frame(left_path, right_path, width, height):
+    """The left and the right image of a stereo frame as 8-bit grey [H, W] (cv2.imread(path, 0) of the reference's StereoDataset)."""
+    t0 = time.perf_counter()
+    left, right = _load(left_path, "L"), _load(right_path, "L")
+    for path, a in ((left_path, left), (right_path, right)):
+        if a.shape != (height, width):
+            raise ValueError(f"{path}: grey image of shape {a.shape}, the calibration says {(height, width)}")
+    return StereoFrame(left, right, (time.perf_counter() - t0) * 1e3)

@@ -14,6 +14,10 @@ COCO classes are cleared from its motion mask (slam/segmentation.py dataset_clas
 with the file masks; CoFusion person / clock / teddy bear, and no YOLO when mask files exist); without one, motion masks come only from
 mask files.
 
+Stereo sequences in the EuRoC layout (``parse_euroc`` / ``EurocDataset``, the reference's EuRoCParser and StereoDataset,
+utils/dataset.py:183-248, 376-487) have no depth files: the two grey images are rectified and matched on the side stream
+(gsr_stereo_depth, include/stereo_depth.h, slam/stereo.py) and the depth handed out is bf / disparity.
+
 What the reference does and this does not: EXR depth (CoFusion's depth_noise/*.exr raises), and its TUM mask list is not sliced by
 Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
 import collections
@@ -168,6 +172,58 @@ def parse_cofusion(datapath):
     return FrameList(colors, depths[:n], poses, masks or None, depth_float32=True)
 
 
+class StereoFrameList(FrameList):
+    """A stereo sequence on disk: per frame the left (cam0) and the right (cam1) image and the W2C pose of the left camera."""
+
+    def __init__(self, left_paths, right_paths, poses):
+        super().__init__(left_paths, [], poses)
+        self.right_paths = list(right_paths)
+
+    def sliced(self, start, end):
+        end = len(self) if end == -1 else end
+        return StereoFrameList(self.color_paths[start:end], self.right_paths[start:end], self.poses[start:end])
+
+
+# utils/dataset.py:217-224: the cam0 extrinsic of the EuRoC rig (body frame <- cam0)
+EUROC_T_I_C0 = ((0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975),
+                (0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768),
+                (-0.0257744366974, 0.00375618835797, 0.999660727178, 0.00981073058949),
+                (0.0, 0.0, 0.0, 1.0))
+
+
+def parse_euroc(datapath, T_i_c0=None):
+    """EuRoCParser (utils/dataset.py:183-248): mav0/cam0/data/*.png and mav0/cam1/data/*.png, sorted and paired by position, and
+    mav0/state_groundtruth_estimate0/data.csv (timestamp, p x y z, q w x y z, ...; the first line is a header). Per frame the pose row with
+    the nearest time stamp to the left image's file name; W2C = (T_w_i T_i_c0)^-1, T_i_c0 the EuRoC cam0 extrinsic unless given."""
+    left = sorted(glob.glob(os.path.join(datapath, "mav0", "cam0", "data", "*.png")))
+    right = sorted(glob.glob(os.path.join(datapath, "mav0", "cam1", "data", "*.png")))
+    if not left or len(left) != len(right):
+        raise ValueError(f"{datapath}: {len(left)} mav0/cam0/data/*.png and {len(right)} mav0/cam1/data/*.png (need at least one frame and "
+                         "as many right images as left ones)")
+    csv_path = os.path.join(datapath, "mav0", "state_groundtruth_estimate0", "data.csv")
+    if not os.path.isfile(csv_path):
+        raise FileNotFoundError(f"{csv_path}: a stereo sequence needs its ground-truth poses")
+    rows = []
+    with open(csv_path, "r") as f:
+        for k, line in enumerate(f):
+            line = line.strip()
+            if k == 0 or not line or line.startswith("#"):
+                continue
+            rows.append([float(v) for v in line.split(",")[:8]])
+    if not rows:
+        raise ValueError(f"{csv_path}: no pose rows")
+    data = np.array(rows, dtype=np.float64)
+    T_i_c0 = np.asarray(EUROC_T_I_C0 if T_i_c0 is None else T_i_c0, dtype=np.float64).reshape(4, 4)
+    poses = []
+    for path in left:
+        stamp = float(os.path.basename(path).split(".")[0])
+        row = data[int(np.argmin(np.abs(data[:, 0] - stamp)))]
+        T_w_i = quaternion_matrix(row[4:8])
+        T_w_i[:3, 3] = row[1:4]
+        poses.append(np.linalg.inv(T_w_i @ T_i_c0))
+    return StereoFrameList(left, right, poses)
+
+
 def undistort_map(width, height, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
     """cv2.initUndistortRectifyMap(K, (k1, k2, p1, p2, k3), R = I, newK = K, (width, height), CV_32FC1) restated in float64, stored as
     float32 [H,W,2] = (map_x, map_y): where the undistorted pixel (u, v) samples the distorted frame."""
@@ -195,8 +251,8 @@ def decode_frame(frames, idx, width, height, depth_scale):
 class _Reader:
     """Decoding ahead of the consumer in one thread, and a small bounded cache; holds no reference to the dataset object."""
 
-    def __init__(self, tasks, depth, cache):
-        self.tasks, self.n, self.depth = tasks, len(tasks), depth
+    def __init__(self, tasks, depth, cache, decode=frame_decode.decode_frame):
+        self.tasks, self.n, self.depth, self.decode = tasks, len(tasks), depth, decode
         # a thread that runs PIL and numpy only: it never touches the device, so it cannot disturb a graph capture on the caller's thread
         # (a decoding process measured no faster, DESIGN.md)
         self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="frame-decode") if depth > 0 else None
@@ -206,7 +262,7 @@ class _Reader:
         self.stats = {"decode_ms": [], "wait_ms": 0.0, "prefetched": 0, "on_demand": 0, "cached": 0}
 
     def _decode(self, idx):
-        return frame_decode.decode_frame(*self.tasks[idx])
+        return self.decode(*self.tasks[idx])
 
     def _done(self, f):
         self.stats["decode_ms"].append(f.decode_ms)
@@ -217,7 +273,7 @@ class _Reader:
             return
         for k in range(first, min(first + self.depth, self.n)):
             if k not in self.pending and k not in self.cache:
-                self.pending[k] = self.pool.submit(frame_decode.decode_frame, *self.tasks[k])
+                self.pending[k] = self.pool.submit(self.decode, *self.tasks[k])
 
     def get(self, idx):
         t0 = time.perf_counter()
@@ -284,9 +340,7 @@ class RecordedRGBDDataset:
             self._map = torch.tensor(m, device=self.device)
         torch.cuda.synchronize(self.device)             # the tables exist before the side stream reads them
         self._side = torch.cuda.Stream(self.device)
-        tasks = [(frames.color_paths[i], frames.depth_paths[i], frames.mask_paths[i] if frames.mask_paths else None, self.width, self.height,
-                  self.depth_scale, frames.depth_float32) for i in range(self.num_imgs)]
-        self._reader = _Reader(tasks, int(prefetch), cache=int(prefetch) + 4)
+        self._reader = _Reader(self._decode_tasks(frames), int(prefetch), cache=int(prefetch) + 4, decode=self._decode)
         self._finalizer = weakref.finalize(self, self._reader.close)
         self._reader.schedule(0)
         self._reader.get(0)                             # the reader is up and frame 0 is decoded before the dataset is handed out
@@ -301,6 +355,12 @@ class RecordedRGBDDataset:
         self.seg_classes = list(seg_classes) if self._segmenter is not None else None
         self._seg_cache = collections.OrderedDict()   # frame -> its motion mask with the instance masks cleared
         self._seg_log = EventLog(self.device)
+
+    _decode = staticmethod(frame_decode.decode_frame)     # what the read-ahead thread runs on one entry of _decode_tasks
+
+    def _decode_tasks(self, frames):
+        return [(frames.color_paths[i], frames.depth_paths[i], frames.mask_paths[i] if frames.mask_paths else None, self.width, self.height,
+                 self.depth_scale, frames.depth_float32) for i in range(self.num_imgs)]
 
     def __len__(self):
         return self.num_imgs
@@ -432,11 +492,94 @@ class CoFusionDataset(RecordedRGBDDataset):
                          seg_classes=dataset_classes("CoFusion", d, bool(frames.mask_paths)))
 
 
-SUPPORTED_TYPES = ("tum", "CoFusion")
+class EurocDataset(RecordedRGBDDataset):
+    """Stereo sequences in the EuRoC layout (utils/dataset.py:376-487, 710-718): Dataset.type 'euroc'. Calibration has ``cam0`` / ``cam1``,
+    each with ``raw`` (fx fy cx cy k1 k2 p1 p2 k3), ``opt`` (fx fy cx cy of the rectified camera) and ``R`` {data: 9 numbers}; ``distorted``
+    (rectify, or take the images as they are), ``width``, ``height``, ``bf`` (baseline x focal length, default the reference's constant)
+    and an optional ``T_i_c0``. Dataset.stereo may set the matcher's num_disparities, p1, p2, uniqueness_ratio and disp12_max_diff
+    (slam/stereo.py StereoMatcher). The image handed out is the rectified left picture, grey in three channels; the depth is bf / disparity,
+    0 where the matcher found no match; every pixel is static."""
+
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+        import torch
+        from .stereo import REFERENCE_BF, StereoMatcher, rectify_map
+        from .pretrained import EventLog
+        if segmenter is not None:
+            raise ValueError("Dataset.type 'euroc' takes no segmenter: the reference names no classes to segment for its stereo sequences")
+        d, c = config["Dataset"], config["Dataset"]["Calibration"]
+        frames = parse_euroc(d["dataset_path"], c.get("T_i_c0")).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+        opt = c["cam0"]["opt"]
+        flat = {"fx": opt["fx"], "fy": opt["fy"], "cx": opt["cx"], "cy": opt["cy"], "width": c["width"], "height": c["height"], "depth_scale": 1.0}
+        super().__init__(frames, flat, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow)
+        self.bf = float(c.get("bf", REFERENCE_BF))
+        self.matcher = StereoMatcher(self.width, self.height, bf=self.bf, device=self.device, **dict(d.get("stereo") or {}))
+        self._maps = None
+        if bool(c.get("distorted", False)):
+            K = lambda p: [[p["fx"], 0.0, p["cx"]], [0.0, p["fy"], p["cy"]], [0.0, 0.0, 1.0]]
+            self._maps = tuple(torch.tensor(rectify_map(K(c[cam]["raw"]), [c[cam]["raw"].get(k, 0.0) for k in ("k1", "k2", "p1", "p2", "k3")],
+                                                        c[cam]["R"]["data"], K(c[cam]["opt"]), self.width, self.height), device=self.device)
+                               for cam in ("cam0", "cam1"))
+        torch.cuda.synchronize(self.device)             # the maps and the matcher's table exist before the side stream reads them
+        self._motion = torch.ones((self.height, self.width), dtype=torch.bool, device=self.device)
+        self._stereo_log = EventLog(self.device)
+        self._depth_wait_ms, self._valid_share = 0.0, []
+
+    _decode = staticmethod(frame_decode.decode_stereo_frame)
+
+    def _decode_tasks(self, frames):
+        return [(frames.color_paths[i], frames.right_paths[i], self.width, self.height) for i in range(self.num_imgs)]
+
+    @property
+    def stereo_stats(self):
+        """Frames matched, the device ms per frame (rectify + match + depth), the host ms spent waiting for the depth copies, and the mean
+        share of pixels with a depth."""
+        t = self._stereo_log.summary()
+        return {"frames": t["calls"], **self.matcher.params, "ms_per_frame": t["ms_per_item"], "ms_first": t["ms_first"],
+                "ms_rest_mean": t["ms_per_item_rest"], "depth_wait_ms_total": self._depth_wait_ms,
+                "depth_density_mean": float(np.mean(self._valid_share)) if self._valid_share else None}
+
+    @property
+    def ingest_stats(self):
+        return dict(super().ingest_stats, stereo=self.stereo_stats)
+
+    def __getitem__(self, idx):
+        if not 0 <= idx < self.num_imgs:
+            raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
+        image, depth_h, done = self._prepare(self._reader.get(idx), host_depth=True)
+        t0 = time.perf_counter()
+        done.synchronize()                              # the interface hands out a host array: wait for the copy into pinned memory
+        self._depth_wait_ms += (time.perf_counter() - t0) * 1e3
+        depth = depth_h.numpy().copy()
+        self._valid_share.append(float((depth > 0).mean()))
+        return image, depth, self.poses[idx].clone(), self._motion.clone()
+
+    def _prepare(self, hf, segment=False, host_depth=False):
+        """(image, pinned host depth, event) -- rectify, match and bf / disparity on the side stream, then the copy of the depth to pinned
+        memory; the caller's stream waits for the image. Without host_depth only the image matters (a keyframe the flow term reads again)."""
+        import torch
+        dev = self.device
+        main = torch.cuda.current_stream(dev)
+        left_h, right_h = torch.from_numpy(hf.left).pin_memory(), torch.from_numpy(hf.right).pin_memory()
+        depth_h = done = None
+        with torch.cuda.stream(self._side):
+            left, right = left_h.to(dev, non_blocking=True), right_h.to(dev, non_blocking=True)
+            with self._stereo_log.timed(self._side):
+                image, _, depth = self.matcher(left, right, maps=self._maps, stream=self._side)
+            if host_depth:
+                depth_h = torch.empty((self.height, self.width), dtype=torch.float32).pin_memory()
+                depth_h.copy_(depth, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        main.wait_event(done)
+        image.record_stream(main)
+        return image, depth_h, done
+
+
+SUPPORTED_TYPES = ("tum", "CoFusion", "euroc")
 
 
 def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
-    """utils/dataset.py:962-976 for the recorded RGB-D types this project reads: 'tum' (TUM, Bonn) and 'CoFusion'. flow: an optical-flow
+    """utils/dataset.py:962-976 for the recorded types this project reads: 'tum' (TUM, Bonn), 'CoFusion' and 'euroc' (stereo). flow: an optical-flow
     estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None. segmenter: a YOLO instance segmenter
     (slam/segmentation.py YoloSeg) whose masks of the loader's classes are cleared from the motion masks, or None."""
     kind = config["Dataset"].get("type")
@@ -444,7 +587,9 @@ def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None
         return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
     if kind == "CoFusion":
         return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
-    raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn) and 'CoFusion'")
+    if kind == "euroc":
+        return EurocDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
+    raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn), 'CoFusion' and 'euroc' (stereo)")
 
 
 # ---- writing a sequence (tests, measurements, exporting the synthetic generator) --------------------------------------------------
@@ -506,3 +651,42 @@ def write_tum_sequence(dataset, root, masks=False, t0=1000.0, hz=30.0):
     write_tum_lists(root, stamps, c2ws)
     return {"fx": float(dataset.fx), "fy": float(dataset.fy), "cx": float(dataset.cx), "cy": float(dataset.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
             "p2": 0.0, "k3": 0.0, "distorted": False, "width": int(dataset.width), "height": int(dataset.height), "depth_scale": 5000.0}
+
+
+def euroc_stamp(i, t0=1000.0, hz=30.0):
+    """The nanosecond time stamp of frame i of a written stereo sequence: what its images are named by and its csv rows start with."""
+    return int(round((t0 + i / hz) * 1e9))
+
+
+def grey_bytes(color):
+    """8-bit luma (ITU-R BT.601 weights, rounded) of a [3, H, W] colour image in [0, 1]."""
+    c = color.clamp(0, 1).double().cpu().numpy()
+    return np.rint((0.299 * c[0] + 0.587 * c[1] + 0.114 * c[2]) * 255).astype(np.uint8)
+
+
+def write_euroc_sequence(dataset, root, baseline, t0=1000.0, hz=30.0):
+    """Write the frames of an in-memory dataset that has ``right_view`` (slam/dataset.py) as a rectified stereo sequence in the EuRoC
+    layout: mav0/cam0/data/<ns>.png and mav0/cam1/data/<ns>.png (8-bit grey), mav0/state_groundtruth_estimate0/data.csv with the left
+    camera's C2W pose as the body pose (so the Calibration carries T_i_c0 = identity). Returns the Calibration block of a config for it:
+    both cameras with the dataset's intrinsics, no distortion, R = I, bf = fx * baseline."""
+    from PIL import Image
+    dirs = {k: os.path.join(root, "mav0", k, "data") for k in ("cam0", "cam1")}
+    gt_dir = os.path.join(root, "mav0", "state_groundtruth_estimate0")
+    for d in (*dirs.values(), gt_dir):
+        os.makedirs(d, exist_ok=True)
+    lines = ["#timestamp, p_RS_R_x [m], p_RS_R_y [m], p_RS_R_z [m], q_RS_w [], q_RS_x [], q_RS_y [], q_RS_z []"]
+    for i in range(len(dataset)):
+        color, _, pose, _ = dataset[i]
+        stamp = euroc_stamp(i, t0, hz)
+        Image.fromarray(grey_bytes(color)).save(os.path.join(dirs["cam0"], f"{stamp}.png"))
+        Image.fromarray(grey_bytes(dataset.right_view(i, baseline))).save(os.path.join(dirs["cam1"], f"{stamp}.png"))
+        c2w = np.linalg.inv(pose.double().cpu().numpy())
+        x, y, z, w = rotation_to_quaternion(c2w[:3, :3])
+        lines.append(",".join([str(stamp)] + [f"{v:.12f}" for v in (*c2w[:3, 3], w, x, y, z)]))
+    with open(os.path.join(gt_dir, "data.csv"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    k = {"fx": float(dataset.fx), "fy": float(dataset.fy), "cx": float(dataset.cx), "cy": float(dataset.cy)}
+    cam = {"raw": dict(k, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0), "opt": dict(k), "R": {"data": [float(v) for v in np.eye(3).reshape(-1)]}}
+    return {"cam0": cam, "cam1": {"raw": dict(cam["raw"]), "opt": dict(k), "R": {"data": list(cam["R"]["data"])}}, "distorted": False,
+            "width": int(dataset.width), "height": int(dataset.height), "bf": float(dataset.fx) * float(baseline),
+            "T_i_c0": [[float(v) for v in row] for row in np.eye(4)]}

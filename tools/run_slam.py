@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """The SLAM system on a recorded sequence, as the reference's `slam.py --config X.yaml [--eval] [--dynamic]` (slam.py:250-276): the config
-(with its inherit_from chain, slam/config.py) names a TUM / Bonn or CoFusion sequence on disk (slam/recorded.py). Prints the JSON document
+(with its inherit_from chain, slam/config.py) names a TUM / Bonn, CoFusion or EuRoC-layout stereo sequence on disk (slam/recorded.py; a stereo
+sequence gets its depth from the on-device matcher, slam/stereo.py, and a `stereo` block reports its device ms per frame). Prints the JSON document
 of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the time the loop waited for a frame, and how many frames
 came from the read-ahead thread vs were decoded on demand. With --dynamic --raft-weights PATH (the reference's pretrained/raft-things.pth) the
 dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py), and a `flow` block reports the pairs estimated and the
@@ -96,6 +97,8 @@ def main(argv=None):
                                   "initialize_network": dict(getattr(slam.backend, "network_init_graph_stats", {}) or {})}
     res["resolution"] = [ds.width, ds.height]
     res["ingest"] = ds.ingest_stats
+    if hasattr(ds, "stereo_stats"):
+        res["stereo"] = ds.stereo_stats
     if flow is not None:
         res["flow"] = ds.flow_stats
     if segmenter is not None:
