@@ -19,10 +19,12 @@ _KNN = namedtuple("KNN", "dists idx knn")
 _lib = _C.load_library          # the declared library under its former name
 
 
-def _f32(t, name):
+def _f32(t, name, shape=None):
     _C._require_device(t, name)
     if t.dtype != torch.float32:
         raise ValueError(f"{name} must be fp32, got {t.dtype}")
+    if shape is not None and t.shape != shape:
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
     return t.detach().contiguous()
 
 
@@ -204,269 +206,134 @@ def quaternion_to_matrix(q):
 
 
 RADIUS_IS_LOG, WEIGHT_IS_LOGIT = GSR_NODE_RADIUS_IS_LOG, GSR_NODE_WEIGHT_IS_LOGIT
+# the node attributes of a blend, and their first columns in the packed layout's one [B, m, 14] matrix
+_ATTRS = (("node_trans", 3), ("node_rot", 4), ("node_scale", 3), ("local_rotation", 4))
+ATTR_COLS = (0, 3, 7, 10)
+
+
+def _flat(t):
+    return None if t is None else t.reshape(-1)
+
+
+def _blend_inputs(layout, x, motion_mask, nodes, node_radius, node_weight, attrs):
+    """The inputs of a blend as contiguous fp32 device tensors with their shapes checked: (shared, attrs, n, m, B). layout "single": attrs
+    are node_trans [m, 3], node_rot [m, 4], node_scale [m, 3], local_rotation [m, 4] | None, or nothing at all (weights only); "batch": the
+    same four with a leading axis B; "packed": one matrix [B, m, 14]."""
+    x, nodes = _f32(x, "x"), _f32(nodes, "nodes")
+    if x.dim() != 2 or x.shape[1] != 3 or nodes.dim() != 2 or nodes.shape[1] < 3:
+        raise ValueError(f"node blend expects x [N, 3] and nodes [M, >=3], got {tuple(x.shape)} and {tuple(nodes.shape)}")
+    n, m = x.shape[0], nodes.shape[0]
+    motion_mask = None if motion_mask is None else _f32(motion_mask, "motion_mask")
+    if motion_mask is not None and motion_mask.numel() != n:
+        raise ValueError(f"motion_mask must have one value per Gaussian ({n}), got {tuple(motion_mask.shape)}")
+    node_radius = _f32(node_radius, "node_radius").reshape(-1)
+    node_weight = None if node_weight is None else _f32(node_weight, "node_weight").reshape(-1)
+    if node_radius.numel() != m or (node_weight is not None and node_weight.numel() != m):
+        raise ValueError("node_radius / node_weight must have one value per node")
+    if not attrs or attrs[0] is None:                     # weights only
+        attrs = [None] * len(attrs)
+    lead = ()
+    if layout != "single":
+        if attrs[0] is None or attrs[0].dim() != 3:
+            raise ValueError(f"node blend ({layout}) expects node attributes [B, M, .], got {getattr(attrs[0], 'shape', None)}")
+        lead = (attrs[0].shape[0],)
+    spec = (("attrs", 14),) if layout == "packed" else _ATTRS
+    attrs = [None if t is None else _f32(t, name, (*lead, m, c)) for t, (name, c) in zip(attrs, spec)]
+    shared = dict(x=x, motion_mask=motion_mask, nodes=nodes, node_radius=node_radius, node_weight=node_weight)
+    return shared, attrs, n, m, (lead[0] if lead else 1)
+
+
+def _attr_ptrs(tensors, packed):
+    """Where the four attributes (or their gradients) start: column ranges of the one matrix, or the four tensors' own (None: absent)."""
+    if packed:
+        return [tensors[0].data_ptr() + 4 * c for c in ATTR_COLS]
+    return [t.data_ptr() if t is not None else None for t in tensors] + [None] * (4 - len(tensors))
+
+
+def _descriptor(scalars, shared, attrs):
+    """gsr_node_blend of a call, for its forward and its backward stage (the tensors behind the pointers: `shared` and `attrs`, kept by the caller)."""
+    a = gsr_node_blend(**scalars)
+    for k, t in shared.items():
+        setattr(a, k, t.data_ptr() if t is not None else None)
+    a.node_trans, a.node_rot, a.node_scale, a.node_local_rotation = _attr_ptrs(attrs, scalars["attr_stride"] != 0)
+    return a
 
 
 class _NodeBlend(torch.autograd.Function):
-    """(nn_weight, nn_dist, nn_idx, d_xyz, d_rotation, d_scaling) from per-node tensors; gradients to node_radius, node_weight,
-    node_trans, node_rot, node_scale, local_rotation.  x and nodes are constants of the op (detached in the reference)."""
+    """The SC-GS node blend for every layout of the node attributes (see _blend_inputs). "single": one blend, outputs (nn_weight, nn_dist, nn_idx,
+    d_xyz, d_rotation, d_scaling). "batch" / "packed": B blends of the same Gaussians and nodes with B sets of attributes in one launch per stage
+    -- the views and flow partners of one mapping iteration --, outputs d_xyz [B, n, 3], d_rotation [B, n, 4], d_scaling [B, n, 3]; packed: the
+    node network's heads as its single head layer produces them (gsr_node_blend.attr_stride / grad_stride), no per-attribute copies on the way in
+    and one [B, m, 14] gradient on the way out. Gradients to node_radius, node_weight and the attributes; x and nodes are constants of the op
+    (detached in the reference)."""
 
     @staticmethod
-    def forward(ctx, x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation, K,
-                rot_as_residual, raw):
+    def forward(ctx, layout, x, motion_mask, nodes, node_radius, node_weight, K, rot_as_residual, raw, *attrs):
         if not 1 <= K <= BLEND_MAX_K:
             raise ValueError(f"node blend: K = {K} outside 1..{BLEND_MAX_K}")
-        glue = _C._glue
-        if glue is not None and hasattr(glue, "node_blend_forward"):      # native host glue (csrc/torch_glue.cpp): ~10x less host time
+        flags = (RADIUS_IS_LOG | WEIGHT_IS_LOGIT) if raw else 0
+        ctx.n_attrs, ctx.glue_args, glue = len(attrs), None, _C._glue
+        ctx.set_materialize_grads(False)
+        if layout == "single" and glue is not None and hasattr(glue, "node_blend_forward"):      # native host glue (csrc/torch_glue.cpp): ~10x less host time
             _C._require_device(x, "x")
             det = lambda t: None if t is None else t.detach()
-            args = (x.detach(), det(motion_mask), nodes.detach(), node_radius.detach(), det(node_weight), det(node_trans), det(node_rot),
-                    det(node_scale), det(local_rotation) if node_trans is not None else None, int(K), bool(rot_as_residual),
-                    (RADIUS_IS_LOG | WEIGHT_IS_LOGIT) if raw else 0)
+            trans, rot, scale, local = attrs or (None,) * 4
+            ctx.glue_args = (x.detach(), det(motion_mask), nodes.detach(), node_radius.detach(), det(node_weight), det(trans), det(rot), det(scale),
+                             det(local) if trans is not None else None, int(K), bool(rot_as_residual), flags)
             try:
-                w, dist, idx, d_xyz, d_rot, d_scale = glue.node_blend_forward(*args, _C._stream(x.device))
+                w, dist, idx, *outs = glue.node_blend_forward(*ctx.glue_args, _C._stream(x.device))
             except RuntimeError as e:
                 raise ValueError(str(e)) from e
-            # (w, dist, idx are OUTPUTS: kept through save_for_backward -- as plain attributes of ctx they form a reference cycle output ->
-            # grad_fn -> ctx -> output that only the cyclic collector breaks, and the whole upstream graph, the network's AccumulateGrad
-            # nodes included, lingers until then)
-            ctx.glue_args = args
-            ctx.save_for_backward(w, dist, idx)
-            ctx.mark_non_differentiable(dist, idx)
-            return w, dist, idx, d_xyz, d_rot, d_scale
-        x, nodes, node_radius = _f32(x, "x"), _f32(nodes, "nodes"), _f32(node_radius, "node_radius").reshape(-1)
-        if x.dim() != 2 or x.shape[1] != 3 or nodes.dim() != 2 or nodes.shape[1] < 3:
-            raise ValueError(f"node blend expects x [N, 3] and nodes [M, >=3], got {tuple(x.shape)} and {tuple(nodes.shape)}")
-        n, m = x.shape[0], nodes.shape[0]
-        blend = node_trans is not None
-        opt = lambda t, name, shape: None if t is None else _checked(_f32(t, name), name, shape)
-        motion_mask = opt(motion_mask, "motion_mask", None)
-        if motion_mask is not None and motion_mask.numel() != n:
-            raise ValueError(f"motion_mask must have one value per Gaussian ({n}), got {tuple(motion_mask.shape)}")
-        node_weight = None if node_weight is None else _f32(node_weight, "node_weight").reshape(-1)
-        if node_radius.numel() != m or (node_weight is not None and node_weight.numel() != m):
-            raise ValueError("node_radius / node_weight must have one value per node")
-        node_trans, node_rot = opt(node_trans, "node_trans", (m, 3)), opt(node_rot, "node_rot", (m, 4))
-        node_scale = opt(node_scale, "node_scale", (m, 3))
-        local_rotation = opt(local_rotation, "local_rotation", (m, 4)) if blend else None
-        keep = dict(x=x, motion_mask=motion_mask, nodes=nodes, node_radius=node_radius, node_weight=node_weight, node_trans=node_trans,
-                    node_rot=node_rot, node_scale=node_scale, node_local_rotation=local_rotation)
-        scalars = dict(n=n, m=m, K=K, local_frame=int(local_rotation is not None), rot_as_residual=int(bool(rot_as_residual)),
-                       node_stride=nodes.shape[1], flags=(RADIUS_IS_LOG | WEIGHT_IS_LOGIT) if raw else 0)
-        a = gsr_node_blend(**scalars)
-        for k, t in keep.items():
-            setattr(a, k, t.data_ptr() if t is not None else None)
-        dev = x.device
-        w = torch.empty((n, K), dtype=torch.float32, device=dev)
-        dist = torch.empty((n, K), dtype=torch.float32, device=dev)
-        idx = torch.empty((n, K), dtype=torch.int64, device=dev)
-        outs = [torch.empty((n, c), dtype=torch.float32, device=dev) if blend else None for c in (3, 4, 3)]
-        lib = _C.load_library()
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_forward(ctypes.byref(a), w.data_ptr(), dist.data_ptr(), idx.data_ptr(),
-                                       *(o.data_ptr() if o is not None else None for o in outs), _C._stream(dev))
-        ctx.keep, ctx.scalars, ctx.glue_args = keep, scalars, None
+        else:
+            shared, attrs, n, m, B = _blend_inputs(layout, x, motion_mask, nodes, node_radius, node_weight, attrs)
+            packed, blend = layout == "packed", bool(attrs) and attrs[0] is not None
+            scalars = dict(n=n, m=m, K=K, local_frame=int(packed or (blend and attrs[3] is not None)), rot_as_residual=int(bool(rot_as_residual)),
+                           node_stride=shared["nodes"].shape[1], flags=flags, attr_stride=14 if packed else 0, grad_stride=14 if packed else 0)
+            a = _descriptor(scalars, shared, attrs)
+            dev, lead = shared["x"].device, () if layout == "single" else (B,)
+            w = torch.empty((n, K), dtype=torch.float32, device=dev)
+            dist = torch.empty((n, K), dtype=torch.float32, device=dev)
+            idx = torch.empty((n, K), dtype=torch.int64, device=dev)
+            outs = [torch.empty((*lead, n, c) if blend else (0, c), dtype=torch.float32, device=dev) for c in (3, 4, 3)]
+            with torch.cuda.device(dev):
+                _C.load_library().gsr_node_blend_forward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(),
+                                                               *([o.data_ptr() for o in outs] if blend else (None, None, None)), _C._stream(dev))
+            ctx.call = a, shared, attrs, B                # (shared and attrs: the tensors the descriptor points to)
+        # (w, dist, idx are OUTPUTS: kept through save_for_backward -- as plain attributes of ctx they form a reference cycle output ->
+        # grad_fn -> ctx -> output that only the cyclic collector breaks, and the whole upstream graph, the network's AccumulateGrad
+        # nodes included, lingers until then)
         ctx.save_for_backward(w, dist, idx)
+        if layout != "single":                            # (B sets of attributes share one nn_weight: the library takes its cotangent for a single blend only)
+            return tuple(outs)
         ctx.mark_non_differentiable(dist, idx)
-        empty = torch.empty(0, device=dev)
-        return (w, dist, idx, *(o if o is not None else empty for o in outs))
+        return (w, dist, idx, *outs)
 
     @staticmethod
-    def backward(ctx, g_w, _g_dist, _g_idx, g_xyz, g_rot, g_scale):
-        if ctx.glue_args is not None:
-            w, dist, idx = ctx.saved_tensors
-            some = lambda g: g if g is not None and g.numel() else None
-            g_radius, g_weight, g_trans, g_nrot, g_nscale, g_local = _C._glue.node_blend_backward(
-                *ctx.glue_args, w, dist, idx, some(g_w), some(g_xyz), some(g_rot), some(g_scale), _C._stream(w.device))
-            return None, None, None, g_radius, g_weight, g_trans, g_nrot, g_nscale, g_local, None, None, None
-        keep, sc = ctx.keep, ctx.scalars
-        n, m = sc["n"], sc["m"]
+    def backward(ctx, *grads):
+        g_w, (g_xyz, g_rot, g_scale) = grads[0] if len(grads) == 6 else None, grads[-3:]
         w, dist, idx = ctx.saved_tensors
         dev = w.device
-        blend = keep["node_trans"] is not None
-        a = gsr_node_blend(**sc)
-        for k, t in keep.items():
-            setattr(a, k, t.data_ptr() if t is not None else None)
-        cot = lambda g: g.contiguous() if g is not None and g.numel() else None
-        g_w, g_xyz, g_rot, g_scale = cot(g_w), cot(g_xyz) if blend else None, cot(g_rot) if blend else None, cot(g_scale) if blend else None
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        g_radius = new(m)
-        g_weight = new(m) if keep["node_weight"] is not None else None
-        g_trans, g_nrot, g_nscale = (new(m, 3), new(m, 4), new(m, 3)) if blend else (None, None, None)
-        g_local = new(m, 4) if keep["node_local_rotation"] is not None else None
-        lib = _C.load_library()
-        ws = torch.empty((lib.gsr_node_blend_workspace_size(n, m),), dtype=torch.uint8, device=dev)
-        p = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_backward(ctypes.byref(a), w.data_ptr(), dist.data_ptr(), idx.data_ptr(), p(g_xyz), p(g_rot), p(g_scale),
-                                        p(g_w), p(g_trans), p(g_nrot), p(g_nscale), p(g_local), p(g_radius), p(g_weight), ws.data_ptr(),
-                                        _C._stream(dev))
-        # inputs: x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation, K, residual, raw
-        return None, None, None, g_radius, g_weight, g_trans, g_nrot, g_nscale, g_local, None, None, None
-
-
-class _NodeBlendBatch(torch.autograd.Function):
-    """B blends of the same Gaussians and nodes with B sets of node attributes in one launch per stage (gsr_node_blend_*_batch): the
-    views and flow partners of one mapping iteration. Inputs: x [n,3], motion_mask [n] | None, nodes [m,>=3], node_radius [m], node_weight
-    [m] | None, node_trans [B,m,3], node_rot [B,m,4], node_scale [B,m,3], local_rotation [B,m,4] | None. Outputs d_xyz [B,n,3],
-    d_rotation [B,n,4], d_scaling [B,n,3]."""
-
-    @staticmethod
-    def forward(ctx, x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation, K, rot_as_residual, raw):
-        if not 1 <= K <= BLEND_MAX_K:
-            raise ValueError(f"node blend: K = {K} outside 1..{BLEND_MAX_K}")
-        x, nodes, node_radius = _f32(x, "x"), _f32(nodes, "nodes"), _f32(node_radius, "node_radius").reshape(-1)
-        n, m, B = x.shape[0], nodes.shape[0], node_trans.shape[0]
-        if x.dim() != 2 or x.shape[1] != 3 or nodes.dim() != 2 or nodes.shape[1] < 3 or node_trans.dim() != 3:
-            raise ValueError(f"node blend batch expects x [N, 3], nodes [M, >=3], node_trans [B, M, 3]; got {tuple(x.shape)}, {tuple(nodes.shape)}, {tuple(node_trans.shape)}")
-        opt = lambda t, name, shape: None if t is None else _checked(_f32(t, name), name, shape)
-        motion_mask = opt(motion_mask, "motion_mask", None)
-        if motion_mask is not None and motion_mask.numel() != n:
-            raise ValueError(f"motion_mask must have one value per Gaussian ({n}), got {tuple(motion_mask.shape)}")
-        node_weight = None if node_weight is None else _f32(node_weight, "node_weight").reshape(-1)
-        if node_radius.numel() != m or (node_weight is not None and node_weight.numel() != m):
-            raise ValueError("node_radius / node_weight must have one value per node")
-        keep = dict(x=x, motion_mask=motion_mask, nodes=nodes, node_radius=node_radius, node_weight=node_weight,
-                    node_trans=opt(node_trans, "node_trans", (B, m, 3)), node_rot=opt(node_rot, "node_rot", (B, m, 4)),
-                    node_scale=opt(node_scale, "node_scale", (B, m, 3)), node_local_rotation=opt(local_rotation, "local_rotation", (B, m, 4)))
-        scalars = dict(n=n, m=m, K=K, local_frame=int(local_rotation is not None), rot_as_residual=int(bool(rot_as_residual)),
-                       node_stride=nodes.shape[1], flags=(RADIUS_IS_LOG | WEIGHT_IS_LOGIT) if raw else 0)
-        a = gsr_node_blend(**scalars)
-        for k, t in keep.items():
-            setattr(a, k, t.data_ptr() if t is not None else None)
-        dev = x.device
-        w = torch.empty((n, K), dtype=torch.float32, device=dev)
-        dist = torch.empty((n, K), dtype=torch.float32, device=dev)
-        idx = torch.empty((n, K), dtype=torch.int64, device=dev)
-        outs = [torch.empty((B, n, c), dtype=torch.float32, device=dev) for c in (3, 4, 3)]
-        lib = _C.load_library()
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_forward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(), *(o.data_ptr() for o in outs), _C._stream(dev))
-        ctx.keep, ctx.scalars, ctx.saved, ctx.B = keep, scalars, (w, dist, idx), B
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, g_xyz, g_rot, g_scale):
-        keep, sc, B = ctx.keep, ctx.scalars, ctx.B
-        n, m = sc["n"], sc["m"]
-        w, dist, idx = ctx.saved
-        dev = w.device
-        a = gsr_node_blend(**sc)
-        for k, t in keep.items():
-            setattr(a, k, t.data_ptr() if t is not None else None)
-        cot = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        g_xyz, g_rot, g_scale = cot(g_xyz), cot(g_rot), cot(g_scale)
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        g_radius = new(B, m)
-        g_weight = new(B, m) if keep["node_weight"] is not None else None
-        g_trans, g_nrot, g_nscale = new(B, m, 3), new(B, m, 4), new(B, m, 3)
-        g_local = new(B, m, 4) if keep["node_local_rotation"] is not None else None
-        lib = _C.load_library()
-        ws = torch.empty((lib.gsr_node_blend_workspace_size_batch(n, m, B),), dtype=torch.uint8, device=dev)
-        p = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_backward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(), p(g_xyz), p(g_rot), p(g_scale), None,
-                                              p(g_trans), p(g_nrot), p(g_nscale), p(g_local), p(g_radius), p(g_weight), ws.data_ptr(), _C._stream(dev))
-        # radius / weight are shared by the B blends: their gradient is the sum of the rows
-        g_radius = g_radius.sum(0).view(ctx.keep["node_radius"].shape)
-        g_weight = None if g_weight is None else g_weight.sum(0)
-        # inputs: x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation, K, residual, raw
-        return None, None, None, g_radius, g_weight, g_trans, g_nrot, g_nscale, g_local, None, None, None
-
-
-def node_blend_batch(x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation=None, K: int = 3,
-                     d_rot_as_res: bool = True, raw: bool = True):
-    """node_blend for B sets of node attributes at once: node_trans [B, M, 3], node_rot [B, M, 4], node_scale [B, M, 3], local_rotation
-    [B, M, 4] | None -> (d_xyz [B, N, 3], d_rotation [B, N, 4], d_scaling [B, N, 3]). Values and gradients are those of B node_blend calls
-    (the radius / weight gradients are their sum)."""
-    return _NodeBlendBatch.apply(x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), node_trans, node_rot, node_scale, local_rotation,
-                                 K, d_rot_as_res, raw)
-
-
-class _NodeBlendBatchPacked(torch.autograd.Function):
-    """_NodeBlendBatch with the four node attributes as ONE matrix attrs [B, m, 14] = [d_xyz | d_rotation | d_scaling | local_rotation] -- the
-    node network's heads as its single head layer produces them (gsr_node_blend.attr_stride / grad_stride): no per-attribute copies on the way
-    in, one [B, m, 14] gradient on the way out (instead of four tensors that autograd concatenates)."""
-
-    COLS = (0, 3, 7, 10, 14)              # column ranges of d_xyz, d_rotation, d_scaling, local_rotation
-
-    @staticmethod
-    def forward(ctx, x, motion_mask, nodes, node_radius, node_weight, attrs, K, rot_as_residual, raw):
-        if not 1 <= K <= BLEND_MAX_K:
-            raise ValueError(f"node blend: K = {K} outside 1..{BLEND_MAX_K}")
-        x, nodes, node_radius = _f32(x, "x"), _f32(nodes, "nodes"), _f32(node_radius, "node_radius").reshape(-1)
-        attrs = _f32(attrs, "attrs")
-        n, m = x.shape[0], nodes.shape[0]
-        if x.dim() != 2 or x.shape[1] != 3 or nodes.dim() != 2 or nodes.shape[1] < 3 or attrs.dim() != 3 or tuple(attrs.shape[1:]) != (m, 14):
-            raise ValueError(f"node blend (packed) expects x [N, 3], nodes [M, >=3], attrs [B, M, 14]; got {tuple(x.shape)}, {tuple(nodes.shape)}, {tuple(attrs.shape)}")
-        B = attrs.shape[0]
-        motion_mask = None if motion_mask is None else _f32(motion_mask, "motion_mask")
-        if motion_mask is not None and motion_mask.numel() != n:
-            raise ValueError(f"motion_mask must have one value per Gaussian ({n}), got {tuple(motion_mask.shape)}")
-        node_weight = None if node_weight is None else _f32(node_weight, "node_weight").reshape(-1)
-        if node_radius.numel() != m or (node_weight is not None and node_weight.numel() != m):
-            raise ValueError("node_radius / node_weight must have one value per node")
-        keep = dict(x=x, motion_mask=motion_mask, nodes=nodes, node_radius=node_radius, node_weight=node_weight, attrs=attrs)
-        scalars = dict(n=n, m=m, K=K, local_frame=1, rot_as_residual=int(bool(rot_as_residual)), node_stride=nodes.shape[1],
-                       flags=(RADIUS_IS_LOG | WEIGHT_IS_LOGIT) if raw else 0, attr_stride=14, grad_stride=14)
-        a = _NodeBlendBatchPacked._descriptor(scalars, keep)
-        dev = x.device
-        w = torch.empty((n, K), dtype=torch.float32, device=dev)
-        dist = torch.empty((n, K), dtype=torch.float32, device=dev)
-        idx = torch.empty((n, K), dtype=torch.int64, device=dev)
-        outs = [torch.empty((B, n, c), dtype=torch.float32, device=dev) for c in (3, 4, 3)]
-        lib = _C.load_library()
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_forward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(), *(o.data_ptr() for o in outs), _C._stream(dev))
-        ctx.keep, ctx.scalars, ctx.saved, ctx.B = keep, scalars, (w, dist, idx), B
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
-
-    @staticmethod
-    def _descriptor(scalars, keep):
-        a = gsr_node_blend(**scalars)
-        for k in ("x", "motion_mask", "nodes", "node_radius", "node_weight"):
-            setattr(a, k, keep[k].data_ptr() if keep[k] is not None else None)
-        base, c = keep["attrs"].data_ptr(), _NodeBlendBatchPacked.COLS
-        a.node_trans, a.node_rot, a.node_scale, a.node_local_rotation = base + 4 * c[0], base + 4 * c[1], base + 4 * c[2], base + 4 * c[3]
-        return a
-
-    @staticmethod
-    def backward(ctx, g_xyz, g_rot, g_scale):
-        keep, sc, B = ctx.keep, ctx.scalars, ctx.B
-        n, m = sc["n"], sc["m"]
-        w, dist, idx = ctx.saved
-        dev = w.device
-        a = _NodeBlendBatchPacked._descriptor(sc, keep)
-        cot = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        g_xyz, g_rot, g_scale = cot(g_xyz), cot(g_rot), cot(g_scale)
-        g_radius = torch.empty((B, m), dtype=torch.float32, device=dev)
-        g_weight = torch.empty((B, m), dtype=torch.float32, device=dev) if keep["node_weight"] is not None else None
-        g_attrs = torch.empty((B, m, 14), dtype=torch.float32, device=dev)
-        lib = _C.load_library()
-        ws = torch.empty((lib.gsr_node_blend_workspace_size_batch(n, m, B),), dtype=torch.uint8, device=dev)
-        p = lambda t: t.data_ptr() if t is not None else None
-        base, c = g_attrs.data_ptr(), _NodeBlendBatchPacked.COLS
-        with torch.cuda.device(dev):
-            lib.gsr_node_blend_backward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(), p(g_xyz), p(g_rot), p(g_scale), None,
-                                              base + 4 * c[0], base + 4 * c[1], base + 4 * c[2], base + 4 * c[3], p(g_radius), p(g_weight), ws.data_ptr(),
-                                              _C._stream(dev))
-        g_radius = g_radius.sum(0).view(keep["node_radius"].shape)
-        g_weight = None if g_weight is None else g_weight.sum(0)
-        # inputs: x, motion_mask, nodes, node_radius, node_weight, attrs, K, residual, raw
-        return None, None, None, g_radius, g_weight, g_attrs, None, None, None
-
-
-def node_blend_batch_packed(x, motion_mask, nodes, node_radius, node_weight, attrs, K: int = 3, d_rot_as_res: bool = True, raw: bool = True):
-    """node_blend_batch (local frame) with the node attributes as one matrix attrs [B, M, 14] = [d_xyz | d_rotation | d_scaling |
-    local_rotation]: same values and gradients, no copies of the four column ranges and one gradient matrix."""
-    return _NodeBlendBatchPacked.apply(x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), attrs, K, d_rot_as_res, raw)
-
-
-def _checked(t, name, shape):
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
+        cot = lambda g: None if g is None or not g.numel() else g.to(torch.float32).contiguous()
+        cots = [cot(g) for g in (g_xyz, g_rot, g_scale, g_w)]
+        if ctx.glue_args is not None:
+            g_radius, g_weight, *g_attrs = _C._glue.node_blend_backward(*ctx.glue_args, w, dist, idx, cots[3], *cots[:3], _C._stream(dev))
+        else:
+            a, shared, attrs, B = ctx.call
+            n, m = a.n, a.m
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            rows = (B, m) if B > 1 else (m,)
+            g_radius, g_weight = new(*rows), new(*rows) if shared["node_weight"] is not None else None
+            g_attrs = [None if t is None else new(*t.shape) for t in attrs]
+            lib = _C.load_library()
+            ws = torch.empty((lib.gsr_node_blend_workspace_size_batch(n, m, B),), dtype=torch.uint8, device=dev)
+            p = lambda t: t.data_ptr() if t is not None else None
+            with torch.cuda.device(dev):
+                lib.gsr_node_blend_backward_batch(ctypes.byref(a), B, w.data_ptr(), dist.data_ptr(), idx.data_ptr(), *[p(g) for g in cots],
+                                                  *_attr_ptrs(g_attrs, a.grad_stride != 0), p(g_radius), p(g_weight), ws.data_ptr(), _C._stream(dev))
+            if B > 1:                                     # radius / weight are shared by the B blends: their gradient is the sum of the rows
+                g_radius, g_weight = g_radius.sum(0), None if g_weight is None else g_weight.sum(0)
+        # inputs: layout, x, motion_mask, nodes, node_radius, node_weight, K, residual, raw, *attrs
+        return (None, None, None, None, g_radius, g_weight, None, None, None, *g_attrs[:ctx.n_attrs])
 
 
 def cal_nn_weight(x, nodes, node_radius, node_weight=None, K: int = 3, raw: bool = True):
@@ -474,12 +341,7 @@ def cal_nn_weight(x, nodes, node_radius, node_weight=None, K: int = 3, raw: bool
     parameters _node_radius [M] / _node_weight [M, 1] and exp / sigmoid (:893-898) happen in the kernel; raw=False: they are the
     activated properties.  node_weight None: with_node_weight False.  Returns (nn_weight [N, K], nn_dist [N, K], nn_idx [N, K] int64)
     with gradients to node_radius / node_weight."""
-    w, dist, idx, *_ = _NodeBlend.apply(x, None, nodes, node_radius.reshape(-1), _flat(node_weight), None, None, None, None, K, True, raw)
-    return w, dist, idx
-
-
-def _flat(node_weight):
-    return None if node_weight is None else node_weight.reshape(-1)
+    return _NodeBlend.apply("single", x, None, nodes, node_radius.reshape(-1), _flat(node_weight), K, True, raw)[:3]
 
 
 def node_blend(x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation=None, K: int = 3,
@@ -488,6 +350,21 @@ def node_blend(x, motion_mask, nodes, node_radius, node_weight, node_trans, node
     node_trans = node_attrs['d_xyz'], node_rot = node_attrs['d_rotation'], node_scale = node_attrs['d_scaling'].
     local_rotation [M, 4] (node_attrs['local_rotation'], :1207) selects the local-frame translation; None = the global one.
     raw: see cal_nn_weight.  Returns {'d_xyz', 'd_rotation', 'd_scaling', 'nn_weight', 'nn_dist', 'nn_idx'}."""
-    w, dist, idx, d_xyz, d_rot, d_scale = _NodeBlend.apply(x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), node_trans,
-                                                           node_rot, node_scale, local_rotation, K, d_rot_as_res, raw)
+    w, dist, idx, d_xyz, d_rot, d_scale = _NodeBlend.apply("single", x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), K, d_rot_as_res,
+                                                           raw, node_trans, node_rot, node_scale, local_rotation)
     return {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": d_scale, "nn_weight": w, "nn_dist": dist, "nn_idx": idx}
+
+
+def node_blend_batch(x, motion_mask, nodes, node_radius, node_weight, node_trans, node_rot, node_scale, local_rotation=None, K: int = 3,
+                     d_rot_as_res: bool = True, raw: bool = True):
+    """node_blend for B sets of node attributes at once: node_trans [B, M, 3], node_rot [B, M, 4], node_scale [B, M, 3], local_rotation
+    [B, M, 4] | None -> (d_xyz [B, N, 3], d_rotation [B, N, 4], d_scaling [B, N, 3]). Values and gradients are those of B node_blend calls
+    (the radius / weight gradients are their sum)."""
+    return _NodeBlend.apply("batch", x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), K, d_rot_as_res, raw, node_trans, node_rot,
+                            node_scale, local_rotation)
+
+
+def node_blend_batch_packed(x, motion_mask, nodes, node_radius, node_weight, attrs, K: int = 3, d_rot_as_res: bool = True, raw: bool = True):
+    """node_blend_batch (local frame) with the node attributes as one matrix attrs [B, M, 14] = [d_xyz | d_rotation | d_scaling |
+    local_rotation]: same values and gradients, no copies of the four column ranges and one gradient matrix."""
+    return _NodeBlend.apply("packed", x, motion_mask, nodes, node_radius.reshape(-1), _flat(node_weight), K, d_rot_as_res, raw, attrs)

@@ -2386,8 +2386,7 @@ static size_t node_ws_shared_bytes(int64_t n, int32_t m)  // once per call (any 
 
 size_t gsr_node_blend_workspace_size(int64_t n, int32_t m)
 {
-    if (m < 1) return 256;
-    return node_ws_floats(n, m) * sizeof(float) + node_ws_shared_bytes(n, m) + 512;
+    return gsr_node_blend_workspace_size_batch(n, m, 1);
 }
 
 size_t gsr_node_blend_workspace_size_batch(int64_t n, int32_t m, int B)

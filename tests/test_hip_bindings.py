@@ -1,6 +1,8 @@
 """Both host bindings of the C ABI on the GPU (the driver's run only ever used the native glue): the same small scene
 through GSR_GLUE=native and GSR_GLUE=ctypes in two processes -- plain rasterizer API, raw (fused prologue) route with deltas and a
-mask, fused tracking loss, FusedAdam -- must give bitwise the same images and gradients (same kernels, only the marshalling differs)."""
+mask, fused tracking loss, FusedAdam -- must give bitwise the same images and gradients (same kernels, only the marshalling differs); and
+one control-node blend (control_nodes.node_blend: the glue's own entry points against the ctypes descriptor), tensor by tensor."""
+import functools
 import json
 import os
 import subprocess
@@ -56,10 +58,23 @@ eat(m._xyz); eat(m._opacity)
 mask = m.dygs == False
 res2 = gr.render(view, m, pipe, torch.ones(3, device="cuda"), mask=mask)
 eat(res2["render"]); eat(res2["n_touched"])
-print("RESULT " + json.dumps({{"binding": _C.binding(), "digest": h.hexdigest()}}))
+# control_nodes.node_blend, n = 300 (two blocks), m = 5, K = 3, local frame, node weight and motion mask: outputs and all six gradients
+import control_nodes as cn
+gen = torch.Generator(device="cpu").manual_seed(5)
+R = lambda *s, sc=1.0, rg=False: (torch.randn(*s, generator=gen) * sc).to("cuda").requires_grad_(rg)
+bx, bnodes, bmask = R(300, 3, sc=0.5), R(5, 3, sc=0.5), (0.2 + 0.8 * torch.rand(300, 1, generator=gen)).to("cuda")
+leaves = [R(5, sc=0.2, rg=True), R(5, 1, rg=True), R(5, 3, sc=0.1, rg=True), R(5, 4, sc=0.2, rg=True), R(5, 3, sc=0.1, rg=True), R(5, 4, sc=0.3, rg=True)]
+r = cn.node_blend(bx, bmask, bnodes, *leaves, K=3)
+outs = [r[k] for k in ("d_xyz", "d_rotation", "d_scaling", "nn_weight")]
+torch.autograd.backward(outs, [R(*o.shape) for o in outs])
+sha = lambda t: hashlib.sha256(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()).hexdigest()
+blend = {{k: sha(r[k]) for k in sorted(r)}}
+blend.update({{"grad_" + k: sha(t.grad) for k, t in zip(("radius", "weight", "trans", "rot", "scale", "local_rotation"), leaves)}})
+print("RESULT " + json.dumps({{"binding": _C.binding(), "digest": h.hexdigest(), "node_blend": blend}}))
 '''
 
 
+@functools.lru_cache(maxsize=None)                  # (one process per binding serves every test of the pair)
 def _run(glue):
     env = dict(os.environ, GSR_GLUE=glue)
     env.pop("GSR_LIB", None)
@@ -73,6 +88,20 @@ def test_native_and_ctypes_bindings_agree_bitwise():
     a, b = _run("native"), _run("ctypes")
     assert a["binding"] == "native" and b["binding"] == "ctypes"
     assert a["digest"] == b["digest"]
+
+
+def test_node_blend_native_and_ctypes_bindings_agree_bitwise():
+    """control_nodes.node_blend through the native glue's node_blend_forward / _backward and through the ctypes descriptor: the six outputs and
+    the six gradients (cotangents on the three deltas and on nn_weight) are the same bits."""
+    sys.path[:0] = [REPO, os.path.join(REPO, "4dgs-slam_amd")]
+    from diff_gaussian_rasterization import _C
+    if _C._glue is None or not hasattr(_C._glue, "node_blend_forward"):
+        pytest.skip("native glue not built")
+    a, b = _run("native"), _run("ctypes")
+    assert a["binding"] == "native" and b["binding"] == "ctypes"
+    assert len(a["node_blend"]) == 12 and a["node_blend"].keys() == b["node_blend"].keys()
+    for k in a["node_blend"]:
+        assert a["node_blend"][k] == b["node_blend"][k], k
 
 
 def test_cpp_autograd_node_equals_the_python_node_bitwise():

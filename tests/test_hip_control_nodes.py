@@ -372,3 +372,71 @@ def test_node_blend_batch_packed_equals_the_per_attribute_call():
     assert all(torch.equal(a, b) for a, b in zip(o1, o2))
     assert all(torch.equal(a, b) for a, b in zip(g1, g2))
     assert float(g1[0].abs().sum()) > 0
+
+
+def blend_case(n, m, K, device=DEV):
+    """Seeded inputs of one blend, local frame, node weight and motion mask present: (x, mask, nodes, leaves rr / wr / tr / ro / sc / lr that
+    require gradients, cotangents of d_xyz / d_rotation / d_scaling / nn_weight). Radii of the order of the node spacing, so that a Gaussian's K
+    weights are all well above the 1e-7 floor."""
+    g = torch.Generator(device="cpu").manual_seed(1000 * m + K)
+    R = lambda *s, sc=1.0, rg=False: (torch.randn(*s, generator=g) * sc).to(device).requires_grad_(rg)
+    x, nodes = (torch.rand(n, 3, generator=g) * 2 - 1).to(device), (torch.rand(m, 3, generator=g) * 2 - 1).to(device)
+    mask = (0.2 + 0.8 * torch.rand(n, 1, generator=g)).to(device)
+    spacing = 2.0 / m ** (1 / 3)
+    leaves = dict(rr=torch.log(spacing * (0.4 + 0.5 * torch.rand(m, generator=g))).to(device).requires_grad_(True), wr=R(m, 1, rg=True),
+                  tr=R(m, 3, sc=0.1, rg=True), ro=R(m, 4, sc=0.2, rg=True), sc=R(m, 3, sc=0.1, rg=True), lr=R(m, 4, sc=0.3, rg=True))
+    return x, mask, nodes, leaves, [R(n, 3), R(n, 4), R(n, 3), R(n, K)]
+
+
+@pytest.mark.parametrize("m,K", [(5, 3), (800, 5)])
+def test_the_four_entry_points_agree_at_one_sample(m, K):
+    """node_blend, node_blend_batch with a leading axis of 1 and node_blend_batch_packed on the concatenated [1, m, 14] matrix are one call
+    into the library with three layouts of the same numbers: n = 300 (two blocks, the second partial), outputs bit for bit. Gradients of the
+    attributes, node_radius and node_weight: bit for bit at K = 3 (K <= NODE_DET_MAX_K: ordered sums, and one sample has no sum over samples);
+    at K = 5, m = 800 (m > NODE_LDS_MAX: global float atomics, order-dependent rounding) to rtol 1e-4 / atol 1e-6. cal_nn_weight: the same
+    weights, distances and indices as node_blend's."""
+    n = 300
+    x, mask, nodes, L, cots = blend_case(n, m, K)
+    names = ("tr", "ro", "sc", "lr")
+
+    def run(form):
+        if form == "single":
+            r = cn.node_blend(x, mask, nodes, L["rr"], L["wr"], *(L[k] for k in names), K=K)
+            out = [r["d_xyz"], r["d_rotation"], r["d_scaling"]]
+        elif form == "batch":
+            out = [o[0] for o in cn.node_blend_batch(x, mask, nodes, L["rr"], L["wr"], *(L[k][None] for k in names), K=K)]
+        else:
+            out = [o[0] for o in cn.node_blend_batch_packed(x, mask, nodes, L["rr"], L["wr"], torch.cat([L[k] for k in names], -1)[None], K=K)]
+        grads = torch.autograd.grad(out, [L[k] for k in names + ("rr", "wr")], cots[:3])
+        return [o.detach() for o in out], grads
+
+    (o1, g1), (o2, g2), (o3, g3) = run("single"), run("batch"), run("packed")
+    for o, g in ((o2, g2), (o3, g3)):
+        assert all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(o1, o))
+        for a, b in zip(g1, g):
+            assert a.shape == b.shape and (torch.equal(a, b) if K <= 4 else torch.allclose(a, b, rtol=1e-4, atol=1e-6))
+    assert all(float(a.abs().sum()) > 0 for a in g1)
+    r = cn.node_blend(x, mask, nodes, L["rr"], L["wr"], *(L[k] for k in names), K=K)
+    for a, b in zip(cn.cal_nn_weight(x, nodes, L["rr"], L["wr"], K=K), (r["nn_weight"], r["nn_dist"], r["nn_idx"])):
+        assert torch.equal(a, b)
+
+
+def test_blend_outputs_and_nn_weight_carry_cotangents_in_one_backward():
+    """node_blend with cotangents on d_xyz, d_rotation, d_scaling AND nn_weight in the same backward call (g_nn_weight next to the delta
+    cotangents: one code path in the library and in the autograd node) against the fp64 oracle's node_blend + cal_nn_weight: values rel-L1
+    < 2e-5, gradients < 2e-4."""
+    n, m, K = 300, 5, 3
+    x, mask, nodes, L, cots = blend_case(n, m, K)
+    r = cn.node_blend(x, mask, nodes, L["rr"], L["wr"], L["tr"], L["ro"], L["sc"], L["lr"], K=K)
+    got = [r["d_xyz"], r["d_rotation"], r["d_scaling"], r["nn_weight"]]
+    torch.autograd.backward(got, cots)
+    l64 = {k: v.detach().double().cpu().requires_grad_(True) for k, v in L.items()}
+    x64, nodes64 = x.double().cpu(), nodes.double().cpu()
+    want = list(O.node_blend(x64, mask.double().cpu(), nodes64, l64["rr"], l64["wr"], l64["tr"], l64["ro"], l64["sc"], l64["lr"], K, True, True))
+    w64, dist64, idx64 = O.cal_nn_weight(x64, nodes64, l64["rr"], l64["wr"], K)
+    torch.autograd.backward(want + [w64], [c.double().cpu() for c in cots])
+    assert torch.equal(r["nn_idx"].cpu(), idx64) and rel(r["nn_dist"].cpu(), dist64) < 2e-5
+    for k, a, b in zip(("d_xyz", "d_rotation", "d_scaling", "nn_weight"), got, want + [w64]):
+        assert rel(a.detach().cpu(), b.detach()) < 2e-5, k
+    for k in L:
+        assert rel(L[k].grad.cpu(), l64[k].grad) < 2e-4, (k, rel(L[k].grad.cpu(), l64[k].grad))
