@@ -46,6 +46,7 @@
 #include "gs_stereo.h"
 #include "../../include/optical_flow.h"
 #include "gs_raft.h"
+#include "gs_gma.h"
 #include "../../include/segmentation.h"
 #include "gs_yolo.h"
 #include "../../include/perceptual.h"
@@ -3115,6 +3116,42 @@ int gsr_raft_upsample(int batch, int h, int w, const float* flow, const float* m
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(raft_upsample_kernel, dim3((unsigned)((out_w + 255) / 256), out_h, batch), dim3(256), 0, stream, h, w, flow, mask, pad_left,
                        pad_top, out_w, out_h, ndc, out);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static bool gma_args_ok(const char* who, int batch, int dim, int h, int w, bool pointers)
+{
+    if (batch < 1 || batch > GMA_MAX_BATCH || dim <= 0 || dim % 4 != 0 || h < 1 || w < 1 || (long long)h * w > 65535) {
+        g_last_error = std::string(who) + ": batch must be 1 or 2, dim a positive multiple of 4, h and w at least 1 and h * w at most 65535 (got batch " +
+                       std::to_string(batch) + ", dim " + std::to_string(dim) + ", " + std::to_string(h) + " x " + std::to_string(w) + ")";
+        return false;
+    }
+    if (!pointers) { g_last_error = std::string(who) + ": a pointer is NULL"; return false; }
+    return true;
+}
+
+int gsr_gma_attention(int batch, int dim, int h, int w, const float* q, const float* k, float scale, float* attn, void* stream_)
+{
+    if (!gma_args_ok("gsr_gma_attention", batch, dim, h, w, q && k && attn)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N = h * w;
+    const unsigned tiles = (unsigned)((N + GMA_TILE - 1) / GMA_TILE);
+    hipLaunchKernelGGL(gma_sim_kernel, dim3(tiles, tiles, batch), dim3(GMA_BLOCK), 0, stream, dim, N, q, k, scale, attn);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(gma_softmax_kernel, dim3(N, batch), dim3(GMA_BLOCK), 0, stream, N, attn);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_gma_aggregate(int batch, int dim, int h, int w, const float* attn, const float* v, const float* x, float gamma, float* out, void* stream_)
+{
+    if (!gma_args_ok("gsr_gma_aggregate", batch, dim, h, w, attn && v && x && out)) return GSR_ERR_INVALID_ARGUMENT;
+    if (out == x || out == v) { g_last_error = "gsr_gma_aggregate: out must not alias x or v"; return GSR_ERR_INVALID_ARGUMENT; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N = h * w;
+    hipLaunchKernelGGL(gma_aggregate_kernel, dim3((unsigned)((N + GMA_TILE - 1) / GMA_TILE), (unsigned)((dim + GMA_TILE - 1) / GMA_TILE), batch),
+                       dim3(GMA_AGG_THREADS), 0, stream, dim, N, attn, v, x, gamma, out);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -240,6 +240,8 @@ FUNCTIONS = {
     "gsr_raft_corr_pyramid": (i, [i, i, i, vp, vp, P(vp), P(vp), vp]),
     "gsr_raft_corr_lookup": (i, [i, i, i, P(vp), vp, vp, vp]),
     "gsr_raft_upsample": (i, [i, i, i, vp, vp] + [i] * 5 + [vp, vp]),
+    "gsr_gma_attention": (i, [i, i, i, i, vp, vp, f, vp, vp]),
+    "gsr_gma_aggregate": (i, [i, i, i, i, vp, vp, vp, f, vp, vp]),
     # segmentation.h
     "gsr_yolo_workspace_size": (sz, [i]),
     "gsr_yolo_detect": (i, [i, P(i), P(f), P(vp), P(vp), i, i, P(i), i, f, f, i, vp, vp, i, vp, vp]),

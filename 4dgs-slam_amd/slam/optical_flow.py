@@ -8,7 +8,13 @@ scaling. The convolutions of the two encoders and of the update block are torch.
 The network is written here as functions over a flat parameter table whose names and shapes are those of the reference's RAFT
 state_dict (179 entries), so the published raft-things.pth loads unchanged. ``RaftFlow.pair`` computes both directions of a pair with
 one correlation product and the two directions batched through the update block; each image's encoder outputs are cached (bounded,
-by the caller's key), so a keyframe that appears in two pairs is encoded once."""
+by the caller's key), so a keyframe that appears in two pairs is encoded once.
+
+``GmaFlow`` is the reference's second estimator, GMA (Jiang et al., ICCV 2021; GMA/network.py RAFTGMA as utils/camera_utils.py:372-373
+would call it: one head, content-only attention): RAFT plus an attention over all low-resolution pixels of image 1's context features,
+computed once per pair, with which every iteration aggregates the motion features globally (motion + gamma * attn @ to_v(motion)) as a
+third input of the GRU. The attention and the aggregation are HIP (csrc/gs_gma.h); everything else is RaftFlow's code, which GmaFlow
+parametrises by its parameter table and two hooks."""
 import collections
 import ctypes as C
 import math
@@ -57,8 +63,8 @@ def _encoder_entries(prefix, norm, out_dim):
     return e + _conv_entries(f"{prefix}.conv2", out_dim, 128, 1)
 
 
-def param_shapes():
-    """name -> shape of every entry of RAFT-basic's state_dict, in its order."""
+def _entries(gru_extra):
+    """RAFT-basic's entries; the GRU's input is hidden + context + motion (+ gru_extra: GMA's aggregated motion) channels wide."""
     u = "update_block"
     e = _encoder_entries("fnet", "instance", 256) + _encoder_entries("cnet", "batch", HDIM + CDIM)
     e += (_conv_entries(f"{u}.encoder.convc1", 256, CORR_CHANNELS, 1) + _conv_entries(f"{u}.encoder.convc2", 192, 256, 3)
@@ -66,9 +72,29 @@ def param_shapes():
           + _conv_entries(f"{u}.encoder.conv", 128 - 2, 64 + 192, 3))
     for d, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
         for g in "zrq":
-            e += _conv_entries(f"{u}.gru.conv{g}{d}", HDIM, HDIM + 128 + HDIM, kh, kw)
+            e += _conv_entries(f"{u}.gru.conv{g}{d}", HDIM, HDIM + 128 + HDIM + gru_extra, kh, kw)
     e += _conv_entries(f"{u}.flow_head.conv1", 256, HDIM, 3) + _conv_entries(f"{u}.flow_head.conv2", 2, 256, 3)
     e += _conv_entries(f"{u}.mask.0", 256, 128, 3) + _conv_entries(f"{u}.mask.2", MASK_CHANNELS, 256, 1)
+    return e
+
+
+def param_shapes():
+    """name -> shape of every entry of RAFT-basic's state_dict, in its order."""
+    return collections.OrderedDict(_entries(0))
+
+
+GMA_MAX_POS = 160                                       # RAFTGMA's Attention(max_pos_size=160): the size of the unused pos_emb tables
+GMA_QK_GAIN = 105.0                                     # gma_recipe_state_dict: see there
+
+
+def gma_param_shapes():
+    """name -> shape of every entry of RAFTGMA's state_dict (GMA/network.py), in its order: RAFT-basic's names with a GRU 128 channels
+    wider, then the aggregator (gamma before to_v: a module's own parameters precede its children's) and the attention. The pos_emb
+    entries are in every GMA checkpoint but unused (position_only and position_and_content are hard-coded off)."""
+    e = _entries(128)
+    e += [("update_block.aggregator.gamma", (1,)), ("update_block.aggregator.to_v.weight", (128, 128, 1, 1)),
+          ("att.to_qk.weight", (2 * CDIM, CDIM, 1, 1)), ("att.pos_emb.rel_ind", (GMA_MAX_POS, GMA_MAX_POS)),
+          ("att.pos_emb.rel_height.weight", (2 * GMA_MAX_POS - 1, CDIM)), ("att.pos_emb.rel_width.weight", (2 * GMA_MAX_POS - 1, CDIM))]
     return collections.OrderedDict(e)
 
 
@@ -76,8 +102,12 @@ def recipe_state_dict(seed=0):
     """Seeded stand-in weights (no checkpoint needed to build or test): per entry a generator pretrained.entry_rng(seed, name);
     conv weights U(+-sqrt(1 / fan_in)), norm weights U(0.8, 1.2), other vectors U(+-0.05), running_mean U(+-0.1), running_var
     U(0.5, 1.5), num_batches_tracked 0. Flows from them are finite and mostly inside the image, but carry no meaning."""
+    return _recipe(param_shapes(), seed)
+
+
+def _recipe(shapes, seed):
     out = collections.OrderedDict()
-    for name, shape in param_shapes().items():
+    for name, shape in shapes.items():
         rng = pretrained.entry_rng(seed, name)
         if name.endswith("num_batches_tracked"):
             out[name] = torch.tensor(0, dtype=torch.int64)
@@ -97,6 +127,21 @@ def recipe_state_dict(seed=0):
     return out
 
 
+def gma_recipe_state_dict(seed=0):
+    """recipe_state_dict's rules for gma_param_shapes(), with two exceptions without which the stand-in would exercise nothing:
+    aggregator.gamma ~ U(0.5, 1.5) (the module initialises it to 0, which switches the aggregation off), and att.to_qk.weight is its
+    U(+-sqrt(1 / 128)) draw times GMA_QK_GAIN: with the plain draw every attention row is uniform to three digits; with the gain the
+    reference's rows on the fixture images are peaked but not one-hot (mean row entropy / log N in [0.3, 0.8]; tests/golden/
+    make_golden_gma.py asserts it). pos_emb.rel_ind is the module's own index table."""
+    out = _recipe(gma_param_shapes(), seed)
+    out["update_block.aggregator.gamma"] = torch.from_numpy(
+        pretrained.entry_rng(seed, "update_block.aggregator.gamma").uniform(0.5, 1.5, (1,)).astype(np.float32))
+    out["att.to_qk.weight"] = out["att.to_qk.weight"] * GMA_QK_GAIN
+    r = torch.arange(GMA_MAX_POS)
+    out["att.pos_emb.rel_ind"] = r.view(1, -1) - r.view(-1, 1) + GMA_MAX_POS - 1
+    return out
+
+
 def check_state_dict(sd):
     """Strip DataParallel's `module.` prefix and check the entries against param_shapes(): a missing, extra or misshapen entry raises
     and names it. Returns the stripped dict."""
@@ -104,6 +149,17 @@ def check_state_dict(sd):
     if any(".conv3." in k for k in sd) or tuple(getattr(sd.get("update_block.encoder.convc1.weight"), "shape", ())) == (96, 196, 1, 1):
         raise ValueError("this is a RAFT-small checkpoint; only RAFT-basic (raft-things.pth and its kind) is supported")
     pretrained.check_entries(sd, param_shapes(), "RAFT checkpoint")
+    return sd
+
+
+def check_gma_state_dict(sd):
+    """check_state_dict for a GMA checkpoint (gma-things.pth and its kind) against gma_param_shapes(), the unused pos_emb entries
+    included. A RAFT-basic checkpoint raises with a message that says so."""
+    sd = pretrained.strip_module_prefix(sd, "GMA checkpoint")
+    if not any(k.startswith(("att.", "update_block.aggregator.")) for k in sd) and "update_block.gru.convz1.weight" in sd:
+        raise ValueError("this is a RAFT checkpoint (it has no attention or aggregator entries), not a GMA one: load it with RaftFlow "
+                         "(tools/run_slam.py --raft-weights)")
+    pretrained.check_entries(sd, gma_param_shapes(), "GMA checkpoint")
     return sd
 
 
@@ -125,6 +181,14 @@ def check_size(height, width):
         raise ValueError(f"a {width}x{height} image pads to {wp}x{hp}: RAFT needs a padded size of at least 128x128 "
                          f"(the coarsest correlation level would have a side of 1)")
     return hp, wp
+
+
+def attention_bytes(height, width, batch=2):
+    """The bytes of GMA's attention for `batch` directions of a height x width image: batch * N^2 * 4 with N the low-resolution pixel
+    count of the padded image."""
+    l, r, t, b = pad_amounts(height, width)
+    n = ((height + t + b) // 8) * ((width + l + r) // 8)
+    return batch * n * n * 4
 
 
 # ---- kernels (ctypes binding of include/optical_flow.h) -------------------------------------------------------------------------------
@@ -182,14 +246,44 @@ def upsample(flow, mask, pad, out_hw, ndc=True):
     return out
 
 
+def gma_attention(q, k, scale, out=None):
+    """GMA's attention: q, k [B, D, h, w] (B = 1 or 2) -> softmax_j(sum_c (scale q[b, c, i]) k[b, c, j]) as [B, N, N], N = h * w."""
+    B, D, h, w = (int(s) for s in q.shape)
+    _C.dev_f32(q, "q", (B, D, h, w))
+    _C.dev_f32(k, "k", (B, D, h, w))
+    N = h * w
+    if out is None:
+        out = torch.empty((B, N, N), dtype=torch.float32, device=q.device)
+    _C.dev_f32(out, "attn", (B, N, N))
+    with torch.cuda.device(q.device):
+        _C.load_library().gsr_gma_attention(B, D, h, w, q.data_ptr(), k.data_ptr(), float(scale), out.data_ptr(), _C._stream(q.device))
+    return out
+
+
+def gma_aggregate(attn, v, x, gamma, out=None):
+    """GMA's aggregation: x + gamma * (attn @ v over the pixels); attn [B, N, N], v and x [B, D, h, w] -> [B, D, h, w]."""
+    B, D, h, w = (int(s) for s in x.shape)
+    _C.dev_f32(attn, "attn", (B, h * w, h * w))
+    _C.dev_f32(v, "v", (B, D, h, w))
+    _C.dev_f32(x, "x", (B, D, h, w))
+    if out is None:
+        out = torch.empty_like(x)
+    _C.dev_f32(out, "out", (B, D, h, w))
+    with torch.cuda.device(x.device):
+        _C.load_library().gsr_gma_aggregate(B, D, h, w, attn.data_ptr(), v.data_ptr(), x.data_ptr(), float(gamma), out.data_ptr(),
+                                            _C._stream(x.device))
+    return out
+
+
 # ---- the network ---------------------------------------------------------------------------------------------------------------------
 class RaftFlow:
     """RAFT-basic inference (hidden = context = 128, 4 levels, radius 4, 20 iterations) on one device."""
 
     _loaded = {}                  # pretrained.load_once: a checkpoint is read once per process
+    _check = staticmethod(check_state_dict)
 
     def __init__(self, state_dict, device="cuda:0", cache_frames=8):
-        sd = check_state_dict(state_dict)
+        sd = self._check(state_dict)
         self.device = torch.device(device)
         # the projection shortcut's norm is one module under two names; loading a state_dict leaves it with downsample.1's values
         self.p = {k: v.detach().to(self.device, torch.float32 if v.is_floating_point() else v.dtype).contiguous() for k, v in sd.items()}
@@ -234,6 +328,7 @@ class RaftFlow:
             raise ValueError(f"expected a [3, H, W] image, got {tuple(image.shape)}")
         H, W = int(image.shape[1]), int(image.shape[2])
         check_size(H, W)
+        self._admit(H, W)
         x = image.to(self.device, torch.float32)[None] * 255
         x = F.pad(x, list(pad_amounts(H, W)), mode="replicate")
         return 2 * (x / 255.0) - 1.0
@@ -259,15 +354,27 @@ class RaftFlow:
     def forget(self, key):
         self._enc.pop(key, None)
 
+    # -- what GmaFlow adds: nothing here
+    def _admit(self, H, W):
+        """Called with an image's size before anything is allocated for it."""
+
+    def _attention(self, inp, trace):
+        """Per pair, from the stacked context features inp [2, 128, h, w]: what _motion_inputs receives in every iteration."""
+        return None
+
+    def _motion_inputs(self, motion, attention, trace):
+        """The motion features' part of the GRU's input, as a tuple of [B, *, h, w] tensors."""
+        return (motion,)
+
     # -- update block
-    def _update(self, net, inp, corr, flow, with_mask):
+    def _update(self, net, inp, corr, flow, with_mask, attention=None, trace=None):
         u = "update_block"
         c = F.relu(self._conv(corr, f"{u}.encoder.convc1"))
         c = F.relu(self._conv(c, f"{u}.encoder.convc2", 1, 1))
         f = F.relu(self._conv(flow, f"{u}.encoder.convf1", 1, 3))
         f = F.relu(self._conv(f, f"{u}.encoder.convf2", 1, 1))
         motion = torch.cat([F.relu(self._conv(torch.cat([c, f], 1), f"{u}.encoder.conv", 1, 1)), flow], 1)
-        x = torch.cat([inp, motion], 1)
+        x = torch.cat([inp, *self._motion_inputs(motion, attention, trace)], 1)
         h = net
         for d, pad in (("1", (0, 2)), ("2", (2, 0))):          # the separable GRU: a 1x5 pass, then a 5x1 pass
             hx = torch.cat([h, x], 1)
@@ -304,13 +411,14 @@ class RaftFlow:
         coords0 = torch.stack([xs, ys]).float()[None].expand(2, 2, h, w).contiguous()
         coords1 = coords0.clone()
         corr = torch.empty((2, CORR_CHANNELS, h, w), dtype=torch.float32, device=self.device)
+        attention = self._attention(inp, trace)
         if trace is not None:
             trace.update(fmap_i=f_i, fmap_j=f_j, net_i=net_i, inp_i=inp_i, net_j=net_j, inp_j=inp_j, pyramid=levels)
         mask = None
         for it in range(iters):
             corr_lookup(levels, coords1, corr)
             flow = coords1 - coords0
-            net, mask, delta = self._update(net, inp, corr, flow, with_mask=it == iters - 1)
+            net, mask, delta = self._update(net, inp, corr, flow, it == iters - 1, attention, trace if it == 0 else None)
             coords1 = coords1 + delta
             if trace is not None and it == 0:
                 trace.update(corr1=corr.clone(), flow1=(coords1 - coords0).clone())
@@ -320,3 +428,42 @@ class RaftFlow:
         up = upsample(flow, mask.contiguous(), pad, (H, W), ndc=ndc)
         self.pairs += 1
         return up[0], up[1]
+
+
+class GmaFlow(RaftFlow):
+    """GMA inference (RAFT-basic plus one-head content attention and global motion aggregation, 20 iterations) on one device: RaftFlow's
+    interface and behaviour (pair, encode, forget, from_checkpoint, the encoder cache and its counters) with a GMA checkpoint. The
+    attention of a pair, [2, N, N] float32, is computed once from the cached context features and lives for that pair only; a pair whose
+    attention would exceed max_attention_bytes raises ValueError before anything is allocated for it."""
+
+    _loaded = {}
+    _check = staticmethod(check_gma_state_dict)
+
+    def __init__(self, state_dict, device="cuda:0", cache_frames=8, max_attention_bytes=2 << 30):
+        super().__init__(state_dict, device, cache_frames)
+        self.max_attention_bytes = int(max_attention_bytes)
+        sd = pretrained.strip_module_prefix(state_dict, "GMA checkpoint")
+        self.gamma = float(sd["update_block.aggregator.gamma"].detach().reshape(-1)[0])    # read on the host, once: no sync per pair
+        self.scale = float(CDIM) ** -0.5                                                    # Attention.scale = dim_head ** -0.5
+
+    def _admit(self, H, W):
+        need = attention_bytes(H, W)
+        if need > self.max_attention_bytes:
+            l, r, t, b = pad_amounts(H, W)
+            n = ((H + t + b) // 8) * ((W + l + r) // 8)
+            raise ValueError(f"GMA's attention for a {W}x{H} image is 2 x {n} x {n} float32 = {need} bytes, more than max_attention_bytes = "
+                             f"{self.max_attention_bytes}")
+
+    def _attention(self, inp, trace):
+        qk = F.conv2d(inp, self.p["att.to_qk.weight"])
+        attn = gma_attention(qk[:, :CDIM].contiguous(), qk[:, CDIM:].contiguous(), self.scale)
+        if trace is not None:
+            trace["attention"] = attn
+        return attn
+
+    def _motion_inputs(self, motion, attention, trace):
+        v = F.conv2d(motion, self.p["update_block.aggregator.to_v.weight"])
+        glob = gma_aggregate(attention, v, motion.contiguous(), self.gamma)
+        if trace is not None:
+            trace["motion_global"] = glob
+        return (motion, glob)

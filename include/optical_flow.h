@@ -1,7 +1,9 @@
 /*
  * optical_flow.h -- C ABI of the RAFT-specific kernels of the optical-flow estimator (libgs_rasterizer_hip.so): the all-pairs
  * correlation pyramid of RAFT/corr.py CorrBlock in both directions, its 9x9 window lookup, and RAFT.upsample_flow's convex upsampling
- * with the InputPadder crop and the NDC scaling of utils/camera_utils.py:412-413. The convolutions of the network stay with the caller.
+ * with the InputPadder crop and the NDC scaling of utils/camera_utils.py:412-413; and of the two kernels GMA (GMA/gma.py, RAFT with
+ * global motion aggregation) adds: the attention over all low-resolution pixels and its aggregation of the motion features. The
+ * convolutions of the network stay with the caller.
  * All pointers are DEVICE pointers, float32, contiguous. Returns 0 or a negative GSR_ERR_* code (gs_rasterizer.h); gsr_last_error()
  * has the text. stream: hipStream_t or NULL.
  */
@@ -38,6 +40,24 @@ int gsr_raft_corr_lookup(int batch, int h, int w, const float* const* pyr, const
  * ndc != 0 the flow is divided by (out_w, out_h) and multiplied by 2. */
 int gsr_raft_upsample(int batch, int h, int w, const float* flow, const float* mask, int pad_left, int pad_top, int out_w, int out_h, int ndc,
                       float* out, void* stream);
+
+/* gsr_gma_attention: GMA/gma.py Attention.forward with one head and content only, for `batch` (1 or 2) maps q, k [batch, dim, h, w]
+ * (the two halves of to_qk's output). With N = h * w and pixels flattened row-major,
+ *   sim[b][i][j]  = sum_c (scale * q[b][c][i]) k[b][c][j]     (q is scaled before the product; c ascending, exact f32 products)
+ *   attn[b][i][j] = exp(sim[b][i][j] - max_j sim[b][i]) / sum_j exp(sim[b][i][j] - max_j sim[b][i])
+ * attn: [batch, N, N], written as sim and normalised in place. The row maximum is subtracted, and every sum is taken in one fixed order
+ * with no atomics, so the result is bitwise the same on every call and a batch-2 call equals two batch-1 calls. Needs dim % 4 == 0,
+ * h, w >= 1 and N <= 65535. */
+int gsr_gma_attention(int batch, int dim, int h, int w, const float* q, const float* k, float scale, float* attn, void* stream);
+
+/* gsr_gma_aggregate: GMA/gma.py Aggregate.forward after its to_v convolution (one head, no projection), one launch for the batch:
+ *   out[b][c][i] = x[b][c][i] + gamma * sum_j attn[b][i][j] v[b][c][j]
+ * attn: [batch, N, N] (gsr_gma_attention); v, x, out: [batch, dim, h, w]; out must not alias x or v. Each element is reduced by one block
+ * in one fixed order (exact f32 products; four interleaved partial sums, s_g over the j with j / 32 mod 4 = g ascending, added as (s0 + s1) + (s2 + s3); no split
+ * across blocks, no atomics): bitwise the same on every call, and a batch-2 call equals two batch-1 calls. The same size limits as
+ * gsr_gma_attention. */
+int gsr_gma_aggregate(int batch, int dim, int h, int w, const float* attn, const float* v, const float* x, float gamma, float* out,
+                      void* stream);
 
 #ifdef __cplusplus
 }

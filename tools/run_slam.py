@@ -5,7 +5,8 @@ sequence gets its depth from the on-device matcher, slam/stereo.py, and a `stere
 of tools/run_slam_demo.py plus an `ingest` block: host decode ms per frame, the time the loop waited for a frame, and how many frames
 came from the read-ahead thread vs were decoded on demand. With --dynamic --raft-weights PATH (the reference's pretrained/raft-things.pth) the
 dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py), and a `flow` block reports the pairs estimated and the
-device ms per pair. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
+device ms per pair; --gma-weights PATH (a GMA checkpoint, gma-things.pth and its kind) runs the term on GMA's flows instead (RAFT with global
+motion aggregation, the reference's second estimator), and the `flow` block's `estimator` says which. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
 (slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame.
 With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and the LPIPS v0.1 linear layers) the rendering evaluation
 reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair.
@@ -36,7 +37,9 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=None, help="use the first N frames (after Calibration start / end)")
     ap.add_argument("--save-dir", default=None, help="where results go (default: slam.py's Results.save_dir/<scene>/<name>_<time>)")
     ap.add_argument("--prefetch", type=int, default=4, help="frames decoded ahead of the loop")
-    ap.add_argument("--raft-weights", default=None, help="RAFT-basic checkpoint (raft-things.pth): the flow term of --dynamic runs")
+    est = ap.add_mutually_exclusive_group()
+    est.add_argument("--raft-weights", default=None, help="RAFT-basic checkpoint (raft-things.pth): the flow term of --dynamic runs")
+    est.add_argument("--gma-weights", default=None, help="GMA checkpoint (gma-things.pth): the flow term of --dynamic runs, on GMA's flows")
     ap.add_argument("--yolo-weights", default=None, help="YOLO-seg checkpoint (yolov9e-seg.pt): motion masks of people and the "
                                                          "loader's object classes")
     ap.add_argument("--lpips-weights", nargs=2, default=None, metavar=("ALEXNET", "LIN"),
@@ -47,6 +50,9 @@ def parse_args(argv=None):
     if args.raft_weights and not args.dynamic:
         warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
         args.raft_weights = None
+    if args.gma_weights and not args.dynamic:
+        warnings.warn("--gma-weights only serves the flow term of --dynamic runs; ignored")
+        args.gma_weights = None
     if args.yolo_weights and not os.path.isfile(args.yolo_weights):
         ap.error(f"--yolo-weights {args.yolo_weights}: no such file")
     for path in args.lpips_weights or ():
@@ -75,6 +81,9 @@ def main(argv=None):
     if args.raft_weights:
         from slam.optical_flow import RaftFlow
         flow = RaftFlow.from_checkpoint(args.raft_weights, "cuda:0")
+    elif args.gma_weights:
+        from slam.optical_flow import GmaFlow
+        flow = GmaFlow.from_checkpoint(args.gma_weights, "cuda:0")
     segmenter = None
     if args.yolo_weights:
         from slam.segmentation import YoloSeg
@@ -100,7 +109,7 @@ def main(argv=None):
     if hasattr(ds, "stereo_stats"):
         res["stereo"] = ds.stereo_stats
     if flow is not None:
-        res["flow"] = ds.flow_stats
+        res["flow"] = dict(ds.flow_stats, estimator="gma" if args.gma_weights else "raft")
     if segmenter is not None:
         res["segmentation"] = ds.segmentation_stats
     if lpips is not None:
