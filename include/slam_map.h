@@ -112,9 +112,15 @@ int gsr_camera_steps_launch(int n, const gsr_camera_step* steps /* host array */
  *     g_* fields are ignored. projmatrix_raw: the projection without the view (P^T), as gsr_backward_raw takes it.
  *   loss: alpha * mean_{3,H,W}(w_rgb |exp(a) I + b - gt_image|) + (1 - alpha) * mean_{H,W}(w_depth |D - gt_depth|); opacity_weights = 1
  *     (tracking): w_rgb *= rendered opacity, w_depth *= (opacity > opacity_depth_threshold). Weights may be NULL (= 1).
- *   workspace (gsr_track_workspace_size bytes, 16-byte aligned), as floats: dL_dimage [3 N] | dL_ddepth [N] | exposure partial sums [2 T] |
- *     dL_dtau [6] | dL_dexposure [2]  (N = width * height, T = 16 x 16 tiles) -- readable after the call (tests compare them with the
- *     autograd route: images and dL_dtau bit-identical, the exposure sums equal to rounding: per tile here, per 256 strided pixels there).
+ *   workspace (gsr_track_workspace_size bytes = (4 N + 2 T + 8) floats, 16-byte aligned; N = width * height, T = ceil(width / 16) *
+ *     ceil(height / 16) tiles, tile = tile_y * ceil(width / 16) + tile_x). THE layout, in floats from the start of the workspace:
+ *         [0, 3 N)                  dL_dimage, [3, H, W]
+ *         [3 N, 4 N)                dL_ddepth, [H, W]
+ *         [4 N, 4 N + 2 T)          exposure partial sums: 2 * tile + 0 = the tile's share of dL/d exposure_a, 2 * tile + 1 = of dL/d exposure_b
+ *         [4 N + 2 T, + 6)          dL_dtau = [rho (-> trans_delta) 3 | theta (-> rot_delta) 3]
+ *         [4 N + 2 T + 6, + 2)      dL_dexposure = [d/d exposure_a, d/d exposure_b] (the sums of the partials; formed without the pair too)
+ *     Every float is written by every successful call and readable after it (tests/test_hip_track_step.py compares them with the autograd
+ *     route: images and dL_dtau bit-identical, the exposure sums equal to rounding: per tile here, per 256 strided pixels there).
  * Returns what gsr_forward_raw returns (instances, or the speculative capacity in lazy mode); < 0: error. Outputs as gsr_forward_raw. */
 typedef struct gsr_track_loss {
     const float* gt_image; const float* gt_depth; const float* w_rgb; const float* w_depth;

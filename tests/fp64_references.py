@@ -1,6 +1,8 @@
-"""Plain fp64 restatements of the small per-iteration operations (rotations of the node graph, ARAP, elastic, the edge intensity), for the
-GPU comparisons of tests/test_hip_small_kernels_fp64.py. Test infrastructure only: tests/test_fp64_references.py pins every one of them to the
-outputs recorded from the reference under tests/golden/, so that the GPU tests compare against the right thing."""
+"""Plain fp64 restatements of the small per-iteration operations (rotations of the node graph, ARAP, elastic, the edge intensity, the
+exposure-gradient terms of the weighted L1 loss), for the GPU comparisons of tests/test_hip_small_kernels_fp64.py and
+tests/test_hip_track_step.py. Test infrastructure only: tests/test_fp64_references.py pins every one of them to the
+outputs recorded from the reference under tests/golden/ (the exposure terms: to autograd through oracle/loss_oracle.py, which those
+outputs pin), so that the GPU tests compare against the right thing."""
 import torch
 
 
@@ -73,3 +75,25 @@ def edge_intensity64(image, eps=0.01):
         for dx in range(3):
             valid &= tap(dy, dx).abs() > eps
     return torch.sqrt(gv * gv + gh * gh) * valid
+
+
+def weighted_l1_exposure_terms64(image, gt_image, w_rgb, exposure_a, exposure_b, alpha, opacity=None):
+    """Per element of the image, the two terms whose sums are dL/d(exposure_a) and dL/d(exposure_b) of the weighted L1 tracking loss
+    (slam_losses.weighted_l1_loss; get_loss_tracking, utils/slam_utils.py:57-62,118-135), from its definition:
+
+        L_rgb = alpha * mean_{3,H,W}( w |r| ),   r = exp(a) I + b - gt,   w = w_rgb (1 if None) * opacity (if given: a constant weight)
+        dL/da = sum alpha / (3 N) * w * sign(r) * exp(a) * I            dL/db = sum alpha / (3 N) * w * sign(r)
+
+    (the depth term does not depend on the exposure). image / gt_image [3, H, W], w_rgb / opacity [H, W] or [1, H, W] or None, exposure_a /
+    exposure_b floats (0.0 and 0.0 without the pair). Returns (terms_a, terms_b, r), each [3, H, W] float64."""
+    I, gt = image.detach().to(torch.float64), gt_image.detach().to(torch.float64)
+    _, H, W = I.shape
+    w = torch.ones((1, H, W), dtype=torch.float64)
+    if w_rgb is not None:
+        w = w * w_rgb.detach().to(torch.float64).reshape(1, H, W)
+    if opacity is not None:
+        w = w * opacity.detach().to(torch.float64).reshape(1, H, W)
+    ea = torch.exp(torch.tensor(float(exposure_a), dtype=torch.float64))
+    r = ea * I + float(exposure_b) - gt
+    dL_dr = float(alpha) / (3.0 * H * W) * w * torch.sign(r)
+    return dL_dr * ea * I, dL_dr.expand(3, H, W).clone(), r

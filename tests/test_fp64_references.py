@@ -79,3 +79,22 @@ def test_fp64_edge_intensity_reproduces_the_recorded_edge_mask():
     flat = inten.reshape(-1)
     median = torch.sort(flat)[0][(flat.numel() - 1) // 2]
     assert np.array_equal((inten > median * 1.1)[None].numpy(), S["gradmask_mask"])
+
+
+@pytest.mark.parametrize("weights", [False, True])
+def test_fp64_exposure_terms_sum_to_the_gradient_of_the_loss_program(weights):
+    """weighted_l1_exposure_terms64 (written from the loss's definition) against autograd through oracle/loss_oracle.py in fp64 -- the
+    program that reproduces the reference's recorded loss values: the terms add up to dL/d(exposure_a) and dL/d(exposure_b)."""
+    from oracle.loss_oracle import weighted_l1_loss_reference
+    g = torch.Generator().manual_seed(5)
+    H, W = 9, 13
+    R = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)
+    image, depth, gt_image, gt_depth = R(3, H, W), R(1, H, W), R(3, H, W), R(1, H, W)
+    w_rgb, opacity = (R(1, H, W), R(1, H, W)) if weights else (None, None)
+    a = torch.tensor([0.03], dtype=torch.float64, requires_grad=True)
+    b = torch.tensor([-0.01], dtype=torch.float64, requires_grad=True)
+    weighted_l1_loss_reference(image, depth, gt_image, gt_depth, w_rgb=w_rgb, exposure_a=a, exposure_b=b, alpha=0.9, opacity=opacity).backward()
+    ta, tb, r = ref64.weighted_l1_exposure_terms64(image, gt_image, w_rgb, 0.03, -0.01, 0.9, opacity=opacity)
+    assert ta.dtype == tb.dtype == r.dtype == torch.float64 and ta.shape == tb.shape == r.shape == (3, H, W)
+    assert abs(float(ta.sum()) - float(a.grad)) <= 1e-14 and abs(float(tb.sum()) - float(b.grad)) <= 1e-14
+    assert float(a.grad) != 0.0 and float(b.grad) != 0.0
