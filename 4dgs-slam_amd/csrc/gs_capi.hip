@@ -814,8 +814,20 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     const int order = views_order_word(opt.order_items, d.T);
     {
         ScopedKernelTimer tm(K_PREPROCESS, stream);
-        if (in->delta_mode) hipLaunchKernelGGL((preprocess_views_kernel<true, true>), gv, dim3(GB), hist_lds_bytes, stream, a, t, d);
-        else hipLaunchKernelGGL(preprocess_views_kernel<true>, gv, dim3(GB), hist_lds_bytes, stream, a, t, d);
+        // SH rows through LDS under the conditions of the single-view call (forward_impl): the two evaluations of the SH polynomial are
+        // contracted differently by the compiler, so a batch that took the per-lane one differed from V single-view calls in the last bit
+        // of the colours at M = 9 / 16, D > 0
+        const bool sh_win = opt.sh_rows && D > 0 && (M == 9 || M == 16) && !flow;
+        a.sh_win_offset = sh_win ? (int)((hist_lds_bytes + 15) & ~size_t(15)) : 0;
+        const size_t pre_lds = sh_win ? (size_t)a.sh_win_offset + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float) : hist_lds_bytes;
+        if (sh_win) {
+            static std::atomic<unsigned long long> attr_set[2];
+            const void* fn = in->delta_mode ? reinterpret_cast<const void*>(preprocess_views_kernel<true, true>) : reinterpret_cast<const void*>(preprocess_views_kernel<true>);
+            const int rc = ensure_dynamic_lds(fn, (int)PRE_LDS_MAX, attr_set[in->delta_mode ? 1 : 0]);
+            if (rc) return rc;
+        }
+        if (in->delta_mode) hipLaunchKernelGGL((preprocess_views_kernel<true, true>), gv, dim3(GB), pre_lds, stream, a, t, d);
+        else hipLaunchKernelGGL(preprocess_views_kernel<true>, gv, dim3(GB), pre_lds, stream, a, t, d);
     }
     {
         ScopedKernelTimer tm(K_SCAN, stream);
@@ -860,7 +872,11 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
         spec.last_max_tile = hdr[HDR_MAX_TILE];
         w.num_rendered = (int)R;
         if (flg & FLAG_OVERFLOW) {
-            const int rc = forward_one_view(opt, w, slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier,
+            // (without speculation: the counts are known, the redo is laid out for exactly them. A speculative redo would overflow a
+            // second time under "cap_test_shrink_permille" and count the same frame twice in the sticky overflow counter.)
+            Options exact = opt;
+            exact.speculate = false;
+            const int rc = forward_one_view(exact, w, slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier,
                                             tan_fovx, tan_fovy, debug, stream_);
             if (rc) return rc;
         }

@@ -398,6 +398,11 @@ __device__ __forceinline__ int raw_slot(const RawInputs& r, size_t row) { return
 // PRE (delta_mode 1): row of the network's output that belongs to raw row `row`, and the distance between rows of a delta tensor
 __device__ __forceinline__ int pre_slot(const RawInputs& r, size_t row) { return r.dyn_slot ? r.dyn_slot[row] : (int)row; }
 __device__ __forceinline__ int pre_stride(const RawInputs& r, int width) { return r.delta_stride ? r.delta_stride : width; }
+// PRE: the sums of a parameter and its delta leave the loaders as values the optimiser cannot look into, like the loaded values and
+// branch-merged sums of the plain instantiation. With floating-point contraction on, the compiler otherwise fuses the expressions
+// behind a loader differently in the two instantiations, and delta_mode differed in the last bits from the same kernels run on
+// parameters the caller had summed (render(dynamic=True) per camera against views.rasterize_views_net).
+__device__ __forceinline__ void pre_value(float& x) { asm volatile("" : "+v"(x)); }
 template <bool PRE = false>
 __device__ __forceinline__ f3 load_mean(const float* means3D, const RawInputs& r, size_t i)
 {
@@ -407,6 +412,7 @@ __device__ __forceinline__ f3 load_mean(const float* means3D, const RawInputs& r
     if constexpr (PRE) {
         const int sl = pre_slot(r, i);
         if (sl >= 0 && r.dx) { const float* d = r.dx + (size_t)pre_stride(r, 3) * sl; m.x += d[0]; m.y += d[1]; m.z += d[2]; }
+        pre_value(m.x); pre_value(m.y); pre_value(m.z);
         return m;
     }
     const int sl = raw_slot(r, i);
@@ -422,7 +428,12 @@ __device__ __forceinline__ void load_scale(const float* scales, const RawInputs&
         const int sl = pre_slot(r, i);
         const float* d = sl >= 0 && r.ds ? r.ds + (size_t)pre_stride(r, 3) * sl : nullptr;
 #pragma unroll
-        for (int k = 0; k < 3; k++) s[k] = expf(r.log_scales[r.scale_dim == 1 ? i : 3 * i + k] + (d ? d[k] : 0.f));
+        for (int k = 0; k < 3; k++) {
+            float l = r.log_scales[r.scale_dim == 1 ? i : 3 * i + k] + (d ? d[k] : 0.f);
+            pre_value(l);
+            s[k] = expf(l);
+            pre_value(s[k]);
+        }
         return;
     }
     if (r.scale_dim == 1) { s[0] = s[1] = s[2] = expf(r.log_scales[i]); }
@@ -439,9 +450,11 @@ __device__ __forceinline__ void load_rot(const float* rotations, const RawInputs
     if constexpr (PRE) {                         // normalize(_rotation + dr) (:156)
         const int sl = pre_slot(r, i);
         if (sl >= 0 && r.dr) { const float* e = r.dr + (size_t)pre_stride(r, 4) * sl; a += e[0]; b += e[1]; c += e[2]; d += e[3]; }
+        pre_value(a); pre_value(b); pre_value(c); pre_value(d);
     }
     const float inv = 1.0f / fmaxf(sqrtf(a * a + b * b + c * c + d * d), 1e-12f);     // torch.nn.functional.normalize
     q[0] = a * inv; q[1] = b * inv; q[2] = c * inv; q[3] = d * inv;
+    if constexpr (PRE) { pre_value(q[0]); pre_value(q[1]); pre_value(q[2]); pre_value(q[3]); }
     if constexpr (!PRE) {
         const int sl = raw_slot(r, i);
         if (sl >= 0 && r.dr) { q[0] += r.dr[4 * sl]; q[1] += r.dr[4 * sl + 1]; q[2] += r.dr[4 * sl + 2]; q[3] += r.dr[4 * sl + 3]; }

@@ -75,8 +75,10 @@ def forward_status_views() -> int:
 
 
 def set_option(name: str, value: int = -1) -> int:
-    """gsr_set_option (include/gs_rasterizer.h): "speculate" | "lazy" | "mailbox" | "cap_margin_permille"; returns the previous value
-    (value < 0: query)."""
+    """gsr_set_option (include/gs_rasterizer.h): "speculate" | "lazy" | "mailbox" | "cap_margin_permille" | "cap_tile_margin_permille" |
+    "cap_floor" | "view_slot_group" | "cap_test_shrink_permille" per host thread, "order_items" | "sh_rows" | "hex_ordered" process-wide;
+    returns the previous value (value < 0: query). "views_batched" is read-only, whatever the value: the number of multi-view calls of
+    this thread that took the one-launch-per-stage path (tests assert the route a call took with it)."""
     return load_library().gsr_set_option(name.encode(), int(value))
 
 

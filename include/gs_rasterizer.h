@@ -191,9 +191,13 @@ int gsr_backward_raw(int P, int D, int M, int R,
  * parameters once (gsr_raw_inputs; `gather` is not available here, the flow mode is chosen per call through the views) and V <= GSR_MAX_VIEWS view descriptors; every
  * stage of the pipeline is launched once with the view as a second grid dimension. Results per view are those of gsr_forward_raw /
  * gsr_backward_raw; the parameter gradients of `out` are the sum over the views, added in view order with one rounding per view --
- * with GSR_BACKWARD_ACCUMULATE exactly what V consecutive gsr_backward_raw calls in accumulate mode leave in the buffers.
+ * with GSR_BACKWARD_ACCUMULATE exactly what V consecutive gsr_backward_raw calls in accumulate mode leave in the buffers (the rows of
+ * Gaussians no view saw are left as they were). Without GSR_BACKWARD_ACCUMULATE every row of `out` is written: the first view that saw a
+ * Gaussian assigns, the later ones add, and the rows of Gaussians no view saw are zeros.
  * Binning capacities are speculated per view slot (the v-th view of consecutive calls is assumed to look alike); the first call of a
- * slot, debug mode and frames that outgrow their capacity go through the single-view path inside the call. */
+ * slot, debug mode and frames that outgrow their capacity go through the single-view path inside the call. The sort kernels of a
+ * batched call are chosen once for all its views, from the longest tile list ANY of its view slots saw last (plus
+ * "cap_tile_margin_permille"); a view whose longest list outgrows that choice counts as overflowed, whatever its instance count. */
 #define GSR_MAX_VIEWS 12
 typedef struct gsr_view {
     const float* viewmatrix; const float* projmatrix; const float* projmatrix_raw; const float* cam_pos;   /* [16], [16], [16], [3] */
@@ -287,7 +291,9 @@ int gsr_debug_item_block(unsigned int n_items, unsigned int n_partial, unsigned 
  *                results are bit-identical either way (every piece writes its own instances' slots); 0 = tile order. Read by the FORWARD
  *                pass (which writes the work-item table).
  *   "sh_rows" (default 1): the SH coefficients of a wave's 64 Gaussians move as whole rows through LDS (one DMA instruction / one store per
- *                row) instead of one strided access per coefficient and lane; same arithmetic, bit-identical results. 0 = per lane.
+ *                row) instead of one strided access per coefficient and lane; same arithmetic -- bit-identical results in the exact-math build, within
+ *                2e-6 in the product build, where the compiler contracts the two forms of the SH polynomial differently. 0 = per lane.
+ *                gsr_forward_views follows the option like gsr_forward_raw does, so that a batch and V single calls take the same form.
  *   "hex_ordered" (default 1; value < 0 only reads): the HexPlane field's sorted backward passes (deformation_field.h) sum the plane
  *                gradients as fixed-point integers -- bitwise reproducible; 0 = float atomics. Environment: GSR_HEX_ORDERED.
  *   "cap_test_shrink_permille" (default 0 = off): TEST facility -- lay speculative buffers out for this fraction of the previous

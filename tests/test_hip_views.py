@@ -118,7 +118,9 @@ def test_views_equal_single_view_calls(kw):
 
 
 def test_views_without_accumulation_match_autograd_sum():
-    """No attached bucket: the parameter gradients are returned and must equal autograd's sum of the per-view gradients."""
+    """No attached bucket: the parameter gradients are returned and must equal autograd's sum of the per-view gradients bit for bit. The
+    V backward passes run one after the other, so autograd adds the views' dense gradients to .grad in view order, one fp32 rounding each;
+    rows a view did not see are zero and 0 + g is exact: the arithmetic views_reduce_kernel promises (csrc/gs_views.h)."""
     par, settings, cots, slot, deltas, poses = _scene(P=8000, V=4)
     for rep in range(2):
         _clear(par, deltas, poses)
@@ -128,7 +130,7 @@ def test_views_without_accumulation_match_autograd_sum():
         _multi(par, settings, cots, slot, deltas, poses)
         for k, want in ref.items():
             got = par[k].grad
-            assert torch.allclose(got, want, rtol=1e-5, atol=1e-9), (rep, k, float((got - want).abs().max()))
+            assert torch.equal(got, want), (rep, k, float((got - want).abs().max()))
 
 
 def test_render_views_matches_render():
