@@ -2799,6 +2799,38 @@ int gsr_edge_mask(const float* image, int height, int width, float edge_threshol
     return 0;
 }
 
+size_t gsr_mono_keyframe_depth_workspace_size(int height, int width)
+{
+    return height > 0 && width > 0 ? MONO_WS_KEYS + (size_t)height * (size_t)width * sizeof(uint32_t) : MONO_WS_KEYS;
+}
+
+int gsr_mono_keyframe_depth(const float* depth, const float* opacity, const float* gt_image, int height, int width, float rgb_boundary_threshold,
+                            const float* noise, float* out, float* stats, char* workspace, void* stream_)
+{
+    if (!depth || !opacity || !gt_image || !noise || !out || !stats || !workspace || height < 1 || width < 1 || (long long)height * width > (1ll << 28)) {
+        g_last_error = "gsr_mono_keyframe_depth: null argument or an image of less than 1 or more than 2^28 pixels"; return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) { g_last_error = "gsr_mono_keyframe_depth: the workspace must be 16-byte aligned"; return GSR_ERR_INVALID_ARGUMENT; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n = height * width;
+    uint32_t* state = reinterpret_cast<uint32_t*>(workspace);
+    uint32_t* n_valid = reinterpret_cast<uint32_t*>(workspace + MONO_WS_COUNT);
+    float* median = reinterpret_cast<float*>(workspace + MONO_WS_MEDIAN);
+    double* partial = reinterpret_cast<double*>(workspace + MONO_WS_PARTIAL);
+    uint32_t* keys = reinterpret_cast<uint32_t*>(workspace + MONO_WS_KEYS);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    GSR_HIP_CHECK(hipMemsetAsync(workspace, 0, MONO_WS_PARTIAL, stream));            // select state, n_valid, the select's output
+    hipLaunchKernelGGL(mono_keys_kernel, dim3(blocks), dim3(256), 0, stream, depth, opacity, gt_image, n, rgb_boundary_threshold, keys, n_valid);
+    for (int shift = 24; shift >= 0; shift -= 8)
+        hipLaunchKernelGGL(radix_select_counted_pass_kernel, dim3(SELECT_BLOCKS), dim3(1024), 0, stream, reinterpret_cast<const float*>(keys), n,
+                           (const uint32_t*)n_valid, shift, state, median);
+    hipLaunchKernelGGL(mono_moments_kernel, dim3(SELECT_BLOCKS), dim3(1024), 0, stream, (const uint32_t*)keys, n, (const uint32_t*)n_valid, (const float*)median, partial);
+    hipLaunchKernelGGL(mono_depth_kernel, dim3(blocks), dim3(256), 0, stream, depth, opacity, gt_image, noise, n, rgb_boundary_threshold,
+                       (const uint32_t*)n_valid, (const float*)median, (const double*)partial, out, stats);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 size_t gsr_isotropic_loss_workspace_size(int P) { return P > 0 ? (size_t)((P + 255) / 256) * sizeof(float) + 16 : 16; }
 
 int gsr_isotropic_loss_forward(int P, const float* raw_scales, float* loss, char* workspace, void* stream_)

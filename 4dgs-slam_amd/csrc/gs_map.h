@@ -416,8 +416,7 @@ __global__ void __launch_bounds__(256) edge_intensity_kernel(const float* __rest
 // element and narrows (prefix, mask, k) for the next launch. state: {prefix, mask, k, ticket, hist[256]}, zero before the first launch.
 // (Round 2 ran ONE block over the whole image four times: 1.9 ms per 640x480 frame on textured input.)
 constexpr int SELECT_BLOCKS = 64;
-__global__ void __launch_bounds__(1024) radix_select_pass_kernel(const float* __restrict__ x, int n, int k0, int shift, uint32_t* __restrict__ state,
-                                                                 float* __restrict__ out)
+__device__ __forceinline__ void radix_select_pass(const float* __restrict__ x, int n, int k0, int shift, uint32_t* __restrict__ state, float* __restrict__ out)
 {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_last;
@@ -465,6 +464,100 @@ __global__ void __launch_bounds__(1024) radix_select_pass_kernel(const float* __
         if (shift == 0) out[0] = __uint_as_float(np);
     }
     if (threadIdx.x < 256) __hip_atomic_store(&state[4 + threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next digit
+}
+
+__global__ void __launch_bounds__(1024) radix_select_pass_kernel(const float* __restrict__ x, int n, int k0, int shift, uint32_t* __restrict__ state,
+                                                                 float* __restrict__ out)
+{
+    radix_select_pass(x, n, k0, shift, state, out);
+}
+
+// ---- keyframe depth of a monocular run: FrontEnd.add_new_keyframe, utils/slam_frontend.py:133-174 (the use_inv_depth = False arm) with
+// get_median_depth, utils/slam_utils.py:367-378 ------------------------------------------------------------------------------------------
+// The reference: ~20 torch launches, a boolean gather (host synchronisation) and a host copy per keyframe. Here, with no host read:
+//   (1) mono_keys_kernel       per pixel: valid = depth > 0 && opacity > 0.95 && rgb_ok; key = valid ? bits(depth) : 0xffffffff (above every
+//                              finite depth in the select's unsigned order); n_valid by one integer atomic per wave
+//   (2) the radix select, four launches, with k = (n_valid - 1) / 2 read on the device -> the lower median of the valid depths
+//   (3) mono_moments_kernel    sum (d - median) and sum (d - median)^2 over the valid depths in double precision, per block in a fixed tree
+//   (4) mono_depth_kernel      the unbiased std from the 64 partial pairs in a fixed order (shifted by the median the difference of the two
+//                              sums does not cancel; a constant depth gives exactly 0), then the per-pixel rule and the stats block
+// workspace (bytes): [0, 1040) select state, 260 words | [1040] n_valid | [1044] the select's output | [1056, 2080) 64 x {s1, s2} doubles |
+// [2080, + 4 n) keys.
+constexpr size_t MONO_WS_COUNT = 1040, MONO_WS_MEDIAN = 1044, MONO_WS_PARTIAL = 1056, MONO_WS_KEYS = 2080;
+
+__global__ void __launch_bounds__(1024) radix_select_counted_pass_kernel(const float* __restrict__ x, int n, const uint32_t* __restrict__ n_selected,
+                                                                         int shift, uint32_t* __restrict__ state, float* __restrict__ out)
+{
+    const uint32_t m = n_selected[0];                          // written by the launch before the first pass
+    radix_select_pass(x, n, m ? (int)((m - 1u) / 2u) : 0, shift, state, out);
+}
+
+__device__ __forceinline__ bool mono_rgb_ok(const float* __restrict__ gt_image, size_t N, size_t i, float threshold)
+{
+    return (gt_image[i] + gt_image[N + i]) + gt_image[2 * N + i] > threshold;          // gt_img.sum(dim=0) > rgb_boundary_threshold
+}
+
+__global__ void __launch_bounds__(256) mono_keys_kernel(const float* __restrict__ depth, const float* __restrict__ opacity, const float* __restrict__ gt_image,
+                                                        int n, float threshold, uint32_t* __restrict__ keys, uint32_t* __restrict__ n_valid)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool valid = false;
+    if (i < n) {
+        const float d = depth[i];
+        valid = d > 0.f && opacity[i] > 0.95f && mono_rgb_ok(gt_image, (size_t)n, (size_t)i, threshold);
+        keys[i] = valid ? __float_as_uint(d) : 0xffffffffu;
+    }
+    const unsigned long long votes = __ballot(valid);
+    if ((threadIdx.x & 63) == 0 && votes) atomicAdd(n_valid, (uint32_t)__popcll(votes));
+}
+
+__global__ void __launch_bounds__(1024) mono_moments_kernel(const uint32_t* __restrict__ keys, int n, const uint32_t* __restrict__ n_valid,
+                                                            const float* __restrict__ median, double* __restrict__ partial)
+{
+    __shared__ double s1[1024], s2[1024];
+    double a = 0.0, b = 0.0;
+    if (n_valid[0] >= 2u) {
+        const double med = (double)median[0];
+        for (int i = blockIdx.x * 1024 + (int)threadIdx.x; i < n; i += SELECT_BLOCKS * 1024) {
+            const uint32_t key = keys[i];
+            if (key != 0xffffffffu) { const double t = (double)__uint_as_float(key) - med; a += t; b += t * t; }
+        }
+    }
+    s1[threadIdx.x] = a; s2[threadIdx.x] = b;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) { s1[threadIdx.x] += s1[threadIdx.x + w]; s2[threadIdx.x] += s2[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s1[0]; partial[2 * blockIdx.x + 1] = s2[0]; }
+}
+
+__global__ void __launch_bounds__(256) mono_depth_kernel(const float* __restrict__ depth, const float* __restrict__ opacity, const float* __restrict__ gt_image,
+                                                         const float* __restrict__ noise, int n, float threshold, const uint32_t* __restrict__ n_valid,
+                                                         const float* __restrict__ median, const double* __restrict__ partial, float* __restrict__ out,
+                                                         float* __restrict__ stats)
+{
+    __shared__ float s_std;
+    const uint32_t m = n_valid[0];
+    if (threadIdx.x == 0) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < SELECT_BLOCKS; k++) { a += partial[2 * k]; b += partial[2 * k + 1]; }
+        const double var = m >= 2u ? (b - a * a / (double)m) / (double)(m - 1u) : 0.0;
+        s_std = (float)sqrt(var > 0.0 ? var : 0.0);
+    }
+    __syncthreads();
+    const float med = m >= 2u ? median[0] : 0.f, sd = s_std;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { stats[0] = med; stats[1] = sd; reinterpret_cast<int*>(stats)[2] = (int)m; }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float r = 0.f;
+    if (m >= 2u && mono_rgb_ok(gt_image, (size_t)n, (size_t)i, threshold)) {
+#pragma clang fp contract(off)
+        const float d = depth[i];
+        const bool bad = !(d > 0.f && opacity[i] > 0.95f) || d > med + sd || d < med - sd;
+        r = (bad ? med : d) + noise[i] * (bad ? 0.5f * sd : 0.2f * sd);
+    }
+    out[i] = r;
 }
 
 __global__ void __launch_bounds__(256) edge_compare_kernel(const float* __restrict__ intensity, int n, const float* __restrict__ median, float edge_threshold,

@@ -172,6 +172,8 @@ FUNCTIONS = {
     "gsr_schedule_advance": (i, [vp, vp, i, i, vp, vp]),
     "gsr_slot_gather": (i, [i, P(gsr_keyframe_entry), vp, P(gsr_keyframe_entry), i, vp]),
     "gsr_edge_mask": (i, [vp, i, i, f, f, vp, vp, vp, vp]),
+    "gsr_mono_keyframe_depth_workspace_size": (sz, [i, i]),
+    "gsr_mono_keyframe_depth": (i, [vp, vp, vp, i, i, f, vp, vp, vp, vp, vp]),
     "gsr_kabsch_rotations": (i, [i, vp, vp, vp]),
     "gsr_isotropic_loss_workspace_size": (sz, [i]),
     "gsr_isotropic_loss_forward": (i, [i, vp, vp, vp, vp]),

@@ -331,15 +331,37 @@ class BackEnd:
         g.reset_opacity_nonvisible([self.shard.union(seen)])
 
     def _window_full_bookkeeping(self, current_window):
-        """What remains of the reference's covisibility pruning (:663-696 / :1140-1170) for RGB-D input: once the window is full, the
-        per-Gaussian observation counts are refreshed (one stacked reduction over the window's visibility sets) and the map counts as
-        initialised. The pruning itself applies to monocular input only, which this back-end does not take (slam/frontend.py refuses it)."""
+        """The reference's covisibility step (:663-696 / :1140-1170): once the window is full, the per-Gaussian observation counts are
+        refreshed (one stacked reduction over the window's visibility sets) and the map counts as initialised. With monocular input the
+        Gaussians seen from too few window keyframes are pruned first (_covisibility_prune); RGB-D input never prunes here."""
         if len(current_window) != self.config["Training"]["window_size"]:
+            return
+        if self.monocular:
+            self._covisibility_prune(current_window)
+            self.initialized = True
             return
         g = self.gaussians
         if self.occ_aware_visibility:
             g.n_obs.copy_(torch.stack([v != 0 for v in self.occ_aware_visibility.values()]).sum(dim=0).to(g.n_obs.dtype))
         self.initialized = True
+
+    def _covisibility_prune(self, current_window):
+        """:669-699 / :1138-1166 for monocular input: n_obs = the sum of the window's visibility rows; the rule of
+        keyframes.covisibility_prune_mask; prune_points, and the same rows leave every visibility row of the window."""
+        from .keyframes import covisibility_prune_mask
+        g = self.gaussians
+        rows = list(self.occ_aware_visibility.values())
+        if not rows:
+            return
+        g.n_obs.copy_(torch.stack(rows).sum(dim=0).to(g.n_obs.dtype))
+        to_prune = covisibility_prune_mask(g.n_obs, g.unique_kfIDs, current_window, self.config["Training"]["prune_mode"], self.initialized)
+        if to_prune is None:
+            return
+        g.prune_points(to_prune)
+        keep = ~to_prune
+        for kf_idx in current_window:
+            if kf_idx in self.occ_aware_visibility:
+                self.occ_aware_visibility[kf_idx] = self.occ_aware_visibility[kf_idx][keep]
 
     def _regulariser_weights(self, n_window, n_random):
         """1e-3 per window view, 1e-4 per random keyframe (:520-524,:649-652) as a device vector, built once per (window size, extras):
@@ -461,8 +483,9 @@ class BackEnd:
     def _graph_ok(self, viewpoint_stack):
         from .camera import Camera
         g = self.gaussians
-        return (all(isinstance(v, Camera) and v.depth is not None for v in viewpoint_stack) and g.get_xyz.shape[0] > 0
-                and getattr(g.optimizer, "_fused_acc", False) and not self.config["Training"].get("monocular", False))
+        # (a keyframe needs its sensor depth for the RGB-D loss only: monocular input scores the image alone, slam_losses.mapping_loss_operands)
+        return (all(isinstance(v, Camera) and (self.monocular or v.depth is not None) for v in viewpoint_stack) and g.get_xyz.shape[0] > 0
+                and getattr(g.optimizer, "_fused_acc", False))
 
     def graph_streams(self, dev):
         """(warm-up stream, capture stream) of the mapping graphs, created once per device."""

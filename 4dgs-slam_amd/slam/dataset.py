@@ -3,6 +3,7 @@ back wall, floor, side walls, a few boxes; optionally one moving object) rendere
 repository's rasterizer. It has the interface the reference's loops expect from ``utils/dataset.py`` datasets:
 
     dataset[idx] -> (gt_color [3,H,W] float cuda, gt_depth [H,W] float32 numpy, gt_pose [4,4] W2C tensor, motion_mask [H,W] bool cuda)
+                    (gt_depth is None with sensor_depth=False: the sequence as a monocular camera records it)
     dataset.fx / fy / cx / cy / fovx / fovy / width / height / num_imgs / device / dynamic_objects / dystart
 
 ``motion_mask`` follows the reference's convention: True = static pixel (``~motion_mask`` selects the moving object,
@@ -89,7 +90,7 @@ def trajectory(num_frames, step=0.006, rot_step=0.0035):
 
 class SyntheticRGBDDataset:
     def __init__(self, num_frames=40, width=320, height=240, seed=0, dynamic=False, dystart=None, spacing=0.03, device="cuda:0",
-                 step=0.006, rot_step=0.0035, depth_noise=0.0):
+                 step=0.006, rot_step=0.0035, depth_noise=0.0, sensor_depth=True):
         self.device = torch.device(device)
         self.num_imgs, self.width, self.height = num_frames, width, height
         s = width / 640.0
@@ -104,6 +105,7 @@ class SyntheticRGBDDataset:
         self.ball_xyz0, self.ball_rgb = (torch.tensor(a, device=self.device) for a in build_ball((-0.5, 0.2, 1.9), spacing=spacing, seed=seed + 1))
         self.spacing = spacing
         self.depth_noise = depth_noise
+        self.sensor_depth = bool(sensor_depth)      # False: frames carry depth = None (monocular input; the flow ground truth keeps its own)
         self._rng = torch.Generator(device="cpu").manual_seed(seed + 7)
         self.projection_matrix = getProjectionMatrix2(0.01, 100.0, self.cx, self.cy, self.fx, self.fy, width, height).transpose(0, 1).to(self.device)
         self._cache = {}
@@ -145,6 +147,10 @@ class SyntheticRGBDDataset:
         return color, depth, opacity
 
     def __getitem__(self, idx):
+        color, depth, pose, motion = self._frame(idx)
+        return color, (depth if self.sensor_depth else None), pose, motion
+
+    def _frame(self, idx):
         if idx in self._cache:
             return self._cache[idx]
         pose = self.poses[idx]
@@ -182,7 +188,7 @@ class SyntheticRGBDDataset:
         hit = self._flow_cache.get((idx_from, idx_to))
         if hit is not None:
             return hit
-        color, depth, pose, motion = self[idx_from]
+        color, depth, pose, motion = self._frame(idx_from)
         H, W, dev = self.height, self.width, self.device
         d = torch.as_tensor(depth, device=dev)
         v, u = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")

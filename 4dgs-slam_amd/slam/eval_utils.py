@@ -48,6 +48,34 @@ def ate_rmse(gt_traj, est_traj):
     return float(np.sqrt(np.mean(err * err)))
 
 
+def align_sim3(model, data):
+    """Umeyama's similarity fit of two 3xn point sets, data ~ scale * rot @ model + trans -- what evo's align_trajectory(correct_scale=True)
+    applies in evaluate_evo (utils/eval_utils.py:112-152) for monocular input. Returns (rot 3x3, trans 3x1, scale, per-point error [n]).
+    A model without extent (every point the same) has no scale to fit: scale = 1."""
+    model, data = np.asarray(model, np.float64), np.asarray(data, np.float64)
+    n = model.shape[1]
+    mz = model - model.mean(1, keepdims=True)
+    dz = data - data.mean(1, keepdims=True)
+    U, D, Vh = np.linalg.svd(dz @ mz.T / n)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vh) < 0:
+        S[2, 2] = -1
+    rot = U @ S @ Vh
+    var = float(np.sum(mz * mz)) / n
+    scale = float(np.trace(np.diag(D) @ S)) / var if var > 1e-20 else 1.0            # (1e-10 of the unit of length: rounding of the mean)
+    trans = data.mean(1, keepdims=True) - scale * rot @ model.mean(1, keepdims=True)
+    err = scale * rot @ model + trans - data
+    return rot, trans, scale, np.sqrt(np.sum(err * err, 0))
+
+
+def ate_sim3(gt_traj, est_traj):
+    """(RMSE, mean, scale) of the translation error after the similarity fit of the estimate onto the ground truth."""
+    gt = np.stack([np.asarray(p)[:3, 3] for p in gt_traj]).T
+    est = np.stack([np.asarray(p)[:3, 3] for p in est_traj]).T
+    _, _, scale, err = align_sim3(est, gt)
+    return float(np.sqrt(np.mean(err * err))), float(err.mean()), scale
+
+
 def _pose_c2w(R, T):
     m = np.eye(4)
     m[:3, :3] = R.detach().cpu().numpy()
@@ -57,11 +85,16 @@ def _pose_c2w(R, T):
 
 def eval_ate(frames, kf_ids, save_dir=None, iterations=0, final=False, monocular=False):
     """utils/eval_utils.py:221-297 without the plots: trajectory json + ATE. `frames` = {frame id: Camera}. Returns the RMSE; with
-    final=True every tracked frame counts (:238-249), otherwise the keyframes."""
+    final=True every tracked frame counts (:238-249), otherwise the keyframes. monocular=True: the estimate is fitted onto the ground
+    truth with scale (align_sim3; the map of an RGB-only run has no metric scale) and the json also records the fitted `scale`."""
     ids = sorted(frames.keys()) if final else list(kf_ids)
     est = [_pose_c2w(frames[i].R, frames[i].T) for i in ids]
     gt = [_pose_c2w(frames[i].R_gt, frames[i].T_gt) for i in ids]
-    out = {"trj_id": ids, "ate_rmse": ate_rmse(gt, est) if len(ids) >= 3 else 0.0, "ate_mean": evaluate_ate(gt, est) if len(ids) >= 3 else 0.0}
+    if monocular:
+        rmse, mean, scale = ate_sim3(gt, est) if len(ids) >= 3 else (0.0, 0.0, 1.0)
+        out = {"trj_id": ids, "ate_rmse": rmse, "ate_mean": mean, "scale": scale}
+    else:
+        out = {"trj_id": ids, "ate_rmse": ate_rmse(gt, est) if len(ids) >= 3 else 0.0, "ate_mean": evaluate_ate(gt, est) if len(ids) >= 3 else 0.0}
     if save_dir:
         plot_dir = os.path.join(save_dir, "plot")
         os.makedirs(plot_dir, exist_ok=True)
@@ -82,6 +115,8 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_in
                    lpips=None):
     """utils/eval_utils.py:300-428: render every frame at its estimated pose and compare with the sensor image: PSNR over the valid
     pixels (:371-381), SSIM, depth L1 (:383-388). `deltas_for(frame)` -> (dx, ds, dr) supplies the dynamic subset's deformation.
+    A frame without sensor depth (monocular input: the dataset hands out None) is scored on every pixel with colour and adds nothing to
+    the depth L1; `l1_depth` is None when no frame had depth.
     `lpips` (a slam.perceptual.Lpips): the clamped render against the whole sensor image (:352, :378), scores kept on the device and
     read once after the loop; the result and final_result.json gain `mean_lpips`."""
     psnrs, ssims, depths = [], [], []
@@ -93,7 +128,8 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_in
         dx, ds, dr = deltas_for(frame) if deltas_for is not None else (0, 0, 0)
         pkg = render(frame, gaussians, pipe, background, dynamic=False, dx=dx, ds=ds, dr=dr)
         image = torch.clamp(pkg["render"], 0.0, 1.0)
-        valid_depth = torch.as_tensor(gt_depth > 0, device=image.device)
+        has_depth = gt_depth is not None
+        valid_depth = torch.as_tensor(gt_depth > 0, device=image.device) if has_depth else torch.ones(image.shape[-2:], dtype=torch.bool, device=image.device)
         mask = gt_image > 0
         if deltas_for is None and motion_mask is not None:                        # static map: the moving region is not evaluated (:372-376)
             mask = mask & motion_mask.view(1, *valid_depth.shape) & valid_depth[None]
@@ -102,11 +138,13 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, kf_in
             mask = mask & valid_depth[None]
         psnrs.append(float(psnr(image[mask].unsqueeze(0), gt_image[mask].unsqueeze(0))))
         ssims.append(float(slam_losses.ssim(image, gt_image)))
-        l1 = torch.abs(torch.as_tensor(gt_depth, device=image.device)[None] - pkg["depth"]) * valid_depth[None]
-        depths.append(float(l1.sum() / (valid_depth.sum() + 1e-7)))
+        if has_depth:
+            l1 = torch.abs(torch.as_tensor(gt_depth, device=image.device)[None] - pkg["depth"]) * valid_depth[None]
+            depths.append(float(l1.sum() / (valid_depth.sum() + 1e-7)))
         if lpips is not None:
-            lpips_scores[len(depths) - 1:len(depths)] = lpips(image[None], gt_image[None])
-    out = {"mean_psnr": float(np.mean(psnrs)), "mean_ssim": float(np.mean(ssims)), "l1_depth": float(np.mean(depths)), "frames": len(psnrs)}
+            lpips_scores[len(psnrs) - 1:len(psnrs)] = lpips(image[None], gt_image[None])
+    out = {"mean_psnr": float(np.mean(psnrs)), "mean_ssim": float(np.mean(ssims)), "l1_depth": float(np.mean(depths)) if depths else None,
+           "frames": len(psnrs)}
     if lpips is not None:
         mean_lpips = float(np.mean(lpips_scores.cpu().numpy().astype(np.float64)))
         out = {"mean_psnr": out["mean_psnr"], "mean_ssim": out["mean_ssim"], "mean_lpips": mean_lpips, "l1_depth": out["l1_depth"],

@@ -28,16 +28,19 @@ def _load(path, mode=None):
 
 def decode_frame(color_path, depth_path, mask_path, width, height, depth_scale, depth_float32):
     """Colour HWC uint8, mask L uint8 (or None), depth float32 [H,W]: float32(u16 / scale) divided in float64 (TUM), or
-    float32(u16) / float32(scale) (CoFusion, depth_float32)."""
+    float32(u16) / float32(scale) (CoFusion, depth_float32). depth_path None (a monocular sequence): depth None."""
     t0 = time.perf_counter()
     rgb = _load(color_path, "RGB")
     mask = None if mask_path is None else _load(mask_path, "L")
-    d = _load(depth_path)
+    d = None if depth_path is None else _load(depth_path)
     for what, path, a, want in (("colour", color_path, rgb, (height, width, 3)), ("mask", mask_path, mask, (height, width)),
                                 ("depth", depth_path, d, (height, width))):
         if a is not None and a.shape != want:
             raise ValueError(f"{path}: {what} image of shape {a.shape}, the calibration says {want}")
-    depth = (d.astype(np.float32) / np.float32(depth_scale)) if depth_float32 else (d / depth_scale).astype(np.float32)
+    if d is None:
+        depth = None
+    else:
+        depth = (d.astype(np.float32) / np.float32(depth_scale)) if depth_float32 else (d / depth_scale).astype(np.float32)
     return HostFrame(rgb, mask, depth, (time.perf_counter() - t0) * 1e3)
 
 

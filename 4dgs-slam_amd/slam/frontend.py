@@ -1,5 +1,5 @@
-"""Tracking front-end for RGB-D input, single process -- the role of the reference's ``utils/slam_frontend.py`` FrontEnd in its
-``single_thread: True`` schedule (the front-end hands every keyframe to the back-end and waits for it, :664-666). The public methods
+"""Tracking front-end for RGB-D, stereo and monocular input, single process -- the role of the reference's ``utils/slam_frontend.py``
+FrontEnd in its ``single_thread: True`` schedule (the front-end hands every keyframe to the back-end and waits for it, :664-666). The public methods
 keep the reference's names and meaning (add_new_keyframe :128-187, initialize :189-207, tracking :335-470, is_keyframe :472-499,
 add_to_window :501-562, run :603-833) so that code written against it keeps working; the GUI / wandb / queue plumbing does not exist
 here, the back-end is called directly.
@@ -75,6 +75,7 @@ class FrontEnd:
         self.graph_stats = {"captures": 0, "replayed_frames": 0, "eager_frames": 0, "overflow_redos": 0}
         self.log = []
         self.init_done_at = None
+        self.resets = 0                    # monocular input: how often the map was started over (a failed initialisation)
 
     def set_hyperparams(self):
         """:115-126."""
@@ -88,17 +89,34 @@ class FrontEnd:
     def thresholds(self):
         return kf.KeyframeThresholds.from_config(self.config)
 
-    # ---- keyframe depth (:128-187, RGB-D branch) ---------------------------------------------------------------------
+    # ---- keyframe depth (:128-187) ---------------------------------------------------------------------------------------
     def add_new_keyframe(self, frame_idx, depth=None, opacity=None, init=False):
-        if self.monocular:         # (utils/slam_frontend.py:135-178 is not part of the RGB-D configurations shipped)
-            raise NotImplementedError("monocular initialisation is not built: RGB-D input only")
         self.kf_indices += [frame_idx]
         viewpoint = self.cameras[frame_idx]
         gt_img = viewpoint.original_image.to(self.device)
+        if self.monocular:
+            return self._monocular_seed_depth(gt_img, depth, opacity)
         usable = gt_img.sum(dim=0) > self.config["Training"]["rgb_boundary_threshold"]
         if self.dynamic_model and viewpoint.motion_mask is not None:
             usable = usable & viewpoint.motion_mask                       # :185-186: seed the static map from static pixels only
         return viewpoint.depth_device() * usable                          # :180-181 (no host round trip, unlike x[mask] = 0)
+
+    def _monocular_seed_depth(self, gt_img, depth, opacity):
+        """:133-174, the use_inv_depth = False arm. The noise comes from the model's generator (tests pin it). First keyframe (no rendering
+        yet): 2 + 0.3 noise as three torch launches. Later keyframes: gsr_mono_keyframe_depth (keyframes.mono_keyframe_depth) on the tracked
+        frame's rendered depth and opacity; the result stays on the device and feeds gsr_seed_from_rgbd. Fewer than two valid pixels (the
+        reference raises or seeds NaN): the kernel returns zeros, nothing is seeded, and the map is started over at the next frame -- the
+        count is the one host read of this branch, taken after the kernel is queued."""
+        H, W = int(gt_img.shape[-2]), int(gt_img.shape[-1])
+        noise = torch.randn((H, W), device=gt_img.device, generator=self.backend.gaussians.generator)
+        threshold = self.config["Training"]["rgb_boundary_threshold"]
+        if depth is None:
+            return (2.0 + 0.3 * noise) * (gt_img.sum(dim=0) > threshold)
+        seed_depth, stats = kf.mono_keyframe_depth(depth, opacity, gt_img, threshold, noise)
+        if int(stats.view(torch.int32)[2]) < 2:
+            self.reset = True
+            self.log.append(("reset", "no valid depth to seed a keyframe from"))
+        return seed_depth
 
     def initialize(self, frame_idx, viewpoint):
         """:189-207."""
@@ -190,8 +208,14 @@ class FrontEnd:
         return bool(wanted or forced or new_object), reported
 
     def _insert_keyframe(self, cur_frame_idx, viewpoint, visibility, render_pkg, overlap):
-        self.current_window, _ = self.add_to_window(cur_frame_idx, visibility, self.occ_aware_visibility, self.current_window)
+        self.current_window, removed = self.add_to_window(cur_frame_idx, visibility, self.occ_aware_visibility, self.current_window)
+        if self.monocular and not self.initialized and removed is not None:       # :771-776: the next frame starts the map over
+            self.reset = True
+            self.log.append(("reset", cur_frame_idx, "keyframes lack the overlap to initialise the map"))
+            return
         depth_map = self.add_new_keyframe(cur_frame_idx, depth=render_pkg["depth"], opacity=render_pkg["opacity"], init=False)
+        if self.reset:                                                            # no valid depth to seed from (_monocular_seed_depth)
+            return
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))
         self.log.append(("keyframe", cur_frame_idx, overlap))
         viewpoint.clean_key()
@@ -205,9 +229,11 @@ class FrontEnd:
             viewpoint = Camera.init_from_dataset(self.dataset, cur_frame_idx, self.dataset.projection_matrix)
             viewpoint.compute_grad_mask(self.config)
             self.cameras[cur_frame_idx] = viewpoint
-            if self.reset:                                # first frame: build the map from it
+            if self.reset:                                # first frame (monocular input: or a failed initialisation): build the map from it
+                self.resets += 1 if cur_frame_idx > 0 else 0
                 self.initialize(cur_frame_idx, viewpoint)
                 self.current_window += [cur_frame_idx]
+                previous_kf = cur_frame_idx
                 torch.cuda.synchronize(self.device)
                 self.init_done_at = time.perf_counter()   # map initialisation (hundreds of iterations on one frame) is reported apart
                 continue
@@ -219,7 +245,7 @@ class FrontEnd:
             wanted, overlap = self._wants_keyframe(cur_frame_idx, newest_kf, frames_since_kf, visibility)
             if wanted:
                 self._insert_keyframe(cur_frame_idx, viewpoint, visibility, render_pkg, overlap)
-            else:
+            if not wanted or self.reset:                  # (a frame whose insertion ended in a reset is no keyframe: it keeps its pose only)
                 self.cleanup(cur_frame_idx)
             self.dynamic_objects = self.dataset.dynamic_objects
         if self.save_results and self.save_dir:

@@ -144,7 +144,8 @@ class GaussianModel:
         else:
             depth = cam.depth_device()
             if self.config["Dataset"]["sensor_type"] == "monocular":
-                depth = (torch.ones_like(depth) + (torch.randn(depth.shape, device=depth.device, generator=self.generator) - 0.5) * 0.05) * scale
+                shape = tuple(cam.original_image.shape[-2:])              # (the frame may carry no depth map at all)
+                depth = (torch.ones(shape, device=self.device) + (torch.randn(shape, device=self.device, generator=self.generator) - 0.5) * 0.05) * scale
         return self.create_pcd_from_image_and_depth(cam, cam.original_image, depth, init)
 
     def create_pcd_from_image_and_depth(self, cam, rgb, depth, init=False):
@@ -154,6 +155,8 @@ class GaussianModel:
         point_size = ds["point_size"]
         if ds.get("adaptive_pointsize", False):
             sensor = cam.depth_device()
+            if sensor is None:                          # monocular input without a depth map: the depth being seeded stands in for the sensor's
+                sensor = depth
             point_size = min(0.05, point_size * np_median(sensor[sensor > 0.1]))                   # :192-194 (np.median: the MEAN of the two middle values)
         depth = depth.contiguous()
         # Open3D: depth_trunc = 100 zeroes everything beyond, project_valid_depth_only keeps d > 0, random_down_sample(1 / factor)

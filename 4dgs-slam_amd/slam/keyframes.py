@@ -167,3 +167,40 @@ def keyframe_selection_overlap(newest, viewpoints, time, intrinsics, pose_window
     if permutation is None:
         permutation = lambda a: a[torch.randperm(len(a)).numpy()]
     return [int(k) for k in permutation(selected)[:8 - pose_window]]
+
+
+# ---- monocular input ---------------------------------------------------------------------------------------------------------------
+def covisibility_prune_mask(n_obs, unique_kfIDs, current_window, prune_mode, initialized):
+    """Which Gaussians the full-window prune call of a monocular run removes (utils/slam_backend.py:669-699, :1138-1166), as a bool row
+    on the device of `n_obs` (None for an unknown prune_mode, as in the reference):
+      "odometry"  seen from fewer than three window keyframes;
+      "slam"      seen from at most three, and seeded by one of the three newest window keyframes -- by any keyframe while the map is
+                  not initialised yet."""
+    if prune_mode == "odometry":
+        return n_obs < 3
+    if prune_mode == "slam":
+        newest = sorted(current_window, reverse=True)
+        since = newest[2] if initialized else 0
+        return (n_obs <= 3) & (unique_kfIDs.to(n_obs.device) >= since)
+    return None
+
+
+def mono_keyframe_depth(depth, opacity, gt_image, rgb_boundary_threshold, noise):
+    """The seed depth of a monocular keyframe from the tracked frame's rendering (utils/slam_frontend.py:133-174): ONE C call,
+    gsr_mono_keyframe_depth (include/slam_map.h), nothing read by the host. depth / opacity [H,W] or [1,H,W], gt_image [3,H,W], noise [H,W]
+    standard-normal samples. Returns (seed depth [H,W], stats): stats is a device tensor of three 32-bit words {median, std as float32,
+    n_valid as int32 -- ``stats.view(torch.int32)[2]``}."""
+    from diff_gaussian_rasterization import _C
+    H, W = int(gt_image.shape[-2]), int(gt_image.shape[-1])
+    dev = gt_image.device
+    plane = lambda t: t.detach().to(torch.float32).reshape(H, W).contiguous()
+    depth, opacity, noise = plane(depth), plane(opacity), plane(noise)
+    image = gt_image.detach().to(torch.float32).contiguous()
+    out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    stats = torch.empty((3,), dtype=torch.float32, device=dev)
+    L = _C.load_library()
+    ws = torch.empty((int(L.gsr_mono_keyframe_depth_workspace_size(H, W)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.gsr_mono_keyframe_depth(depth.data_ptr(), opacity.data_ptr(), image.data_ptr(), H, W, float(rgb_boundary_threshold), noise.data_ptr(),
+                                  out.data_ptr(), stats.data_ptr(), ws.data_ptr(), _C._stream(dev))
+    return out, stats

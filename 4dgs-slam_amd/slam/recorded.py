@@ -109,9 +109,23 @@ def associate_frames(tstamp_image, tstamp_depth, tstamp_pose, max_dt=0.08):
     return out
 
 
-def parse_tum(datapath, frame_rate=32, max_dt=0.08):
+def sequence_has_depth(config):
+    """The reference's ``has_depth`` (utils/dataset.py:303,534): a sequence is read without depth files only when ``Dataset.sensor_type``
+    is 'monocular' AND the calibration has no ``depth_scale``; any other configuration needs its depth files, and says so when they are missing."""
+    d = config["Dataset"]
+    return not (d.get("sensor_type") == "monocular" and "depth_scale" not in d["Calibration"])
+
+
+def tum_frames(config):
+    """The FrameList of a 'tum' configuration: parsed (without depth files for a monocular sequence, sequence_has_depth), then start / end."""
+    c = config["Dataset"]["Calibration"]
+    return parse_tum(config["Dataset"]["dataset_path"], depth=sequence_has_depth(config)).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+
+
+def parse_tum(datapath, frame_rate=32, max_dt=0.08, depth=True):
     """TUMParser (utils/dataset.py:85-181): rgb.txt / depth.txt / groundtruth.txt (else pose.txt, first line skipped), association,
-    frame-rate subsampling, W2C poses, and per kept frame the render_mask/*.png at its rgb.txt row (masks sorted by trailing number)."""
+    frame-rate subsampling, W2C poses, and per kept frame the render_mask/*.png at its rgb.txt row (masks sorted by trailing number).
+    depth=False (a monocular sequence): depth.txt is not read, a colour frame only needs a pose within max_dt, and every depth path is None."""
     pose_list = None
     for name in ("groundtruth.txt", "pose.txt"):
         if os.path.isfile(os.path.join(datapath, name)):
@@ -122,15 +136,23 @@ def parse_tum(datapath, frame_rate=32, max_dt=0.08):
     mask_dir = os.path.join(datapath, "render_mask")
     mask_all = sorted(glob.glob(os.path.join(mask_dir, "*.png")), key=extract_number) if os.path.isdir(mask_dir) else None
     image_data = read_list(os.path.join(datapath, "rgb.txt"))
-    depth_data = read_list(os.path.join(datapath, "depth.txt"))
+    depth_data = read_list(os.path.join(datapath, "depth.txt")) if depth else None
     pose_vecs = np.array([[float(x) for x in r] for r in read_list(pose_list, skiprows=1)], dtype=np.float64)
-    if not image_data or not depth_data or not len(pose_vecs):
-        raise ValueError(f"{datapath}: rgb.txt, depth.txt and the pose file must each list at least one entry")
-    tstamp_image = np.array([float(r[0]) for r in image_data])
-    tstamp_depth = np.array([float(r[0]) for r in depth_data])
-    assoc = associate_frames(tstamp_image, tstamp_depth, pose_vecs[:, 0], max_dt)
-    if not assoc:
-        raise ValueError(f"{datapath}: no colour frame has a depth frame and a pose within {max_dt} s")
+    if depth:
+        if not image_data or not depth_data or not len(pose_vecs):
+            raise ValueError(f"{datapath}: rgb.txt, depth.txt and the pose file must each list at least one entry")
+        tstamp_image = np.array([float(r[0]) for r in image_data])
+        tstamp_depth = np.array([float(r[0]) for r in depth_data])
+        assoc = associate_frames(tstamp_image, tstamp_depth, pose_vecs[:, 0], max_dt)
+        if not assoc:
+            raise ValueError(f"{datapath}: no colour frame has a depth frame and a pose within {max_dt} s")
+    else:
+        if not image_data or not len(pose_vecs):
+            raise ValueError(f"{datapath}: rgb.txt and the pose file must each list at least one entry")
+        tstamp_image = np.array([float(r[0]) for r in image_data])
+        assoc = [(i, None, k) for i, _, k in associate_frames(tstamp_image, tstamp_image, pose_vecs[:, 0], max_dt)]
+        if not assoc:
+            raise ValueError(f"{datapath}: no colour frame has a pose within {max_dt} s")
     keep = [0]
     for ix in range(1, len(assoc)):
         if tstamp_image[assoc[ix][0]] - tstamp_image[assoc[keep[-1]][0]] > 1.0 / frame_rate:
@@ -139,7 +161,7 @@ def parse_tum(datapath, frame_rate=32, max_dt=0.08):
     for ix in keep:
         i, j, k = assoc[ix]
         colors.append(os.path.join(datapath, image_data[i][1]))
-        depths.append(os.path.join(datapath, depth_data[j][1]))
+        depths.append(os.path.join(datapath, depth_data[j][1]) if depth else None)
         poses.append(pose_from_tum(pose_vecs[k]))
         if mask_all is not None:
             if i >= len(mask_all):
@@ -148,19 +170,25 @@ def parse_tum(datapath, frame_rate=32, max_dt=0.08):
     return FrameList(colors, depths, poses, masks if mask_all is not None else None)
 
 
-def parse_cofusion(datapath):
+def parse_cofusion(datapath, depth=True):
     """CoFusion (utils/dataset.py:490-575): colour/*.png, depth/*.png, mask_colour/*.png, trajectories/gt-cam-0.txt (identity poses
-    without it). EXR depth (depth_noise/*.exr) needs an OpenEXR reader this project does not have."""
+    without it). EXR depth (depth_noise/*.exr) needs an OpenEXR reader this project does not have. depth=False (a monocular sequence):
+    the depth folders are not looked at and every depth path is None."""
     colors = sorted(glob.glob(os.path.join(datapath, "colour", "*.png")))
-    exr = sorted(glob.glob(os.path.join(datapath, "depth_noise", "*.exr")))
-    if exr:
-        raise NotImplementedError(f"{os.path.join(datapath, 'depth_noise')}: EXR depth is not supported (no OpenEXR reader); "
-                                  "provide depth/*.png instead")
-    depths = sorted(glob.glob(os.path.join(datapath, "depth", "*.png")))
     masks = sorted(glob.glob(os.path.join(datapath, "mask_colour", "*.png")))
     n = len(colors)
-    if n == 0 or len(depths) < n:
-        raise ValueError(f"{datapath}: {n} colour/*.png and {len(depths)} depth/*.png (need at least one frame and a depth per frame)")
+    if depth:
+        exr = sorted(glob.glob(os.path.join(datapath, "depth_noise", "*.exr")))
+        if exr:
+            raise NotImplementedError(f"{os.path.join(datapath, 'depth_noise')}: EXR depth is not supported (no OpenEXR reader); "
+                                      "provide depth/*.png instead")
+        depths = sorted(glob.glob(os.path.join(datapath, "depth", "*.png")))
+        if n == 0 or len(depths) < n:
+            raise ValueError(f"{datapath}: {n} colour/*.png and {len(depths)} depth/*.png (need at least one frame and a depth per frame)")
+    else:
+        depths = [None] * n
+        if n == 0:
+            raise ValueError(f"{datapath}: no colour/*.png")
     traj = os.path.join(datapath, "trajectories", "gt-cam-0.txt")
     if os.path.isfile(traj):
         rows = read_list(traj)
@@ -326,7 +354,8 @@ class RecordedRGBDDataset:
         self.fx, self.fy, self.cx, self.cy = float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"])
         self.width, self.height = int(c["width"]), int(c["height"])
         self.fovx, self.fovy = fov_from_focal(self.fx, self.width), fov_from_focal(self.fy, self.height)
-        self.depth_scale = float(c["depth_scale"])
+        # (a monocular sequence read without depth files, sequence_has_depth: no scale either, and every frame's depth is None)
+        self.depth_scale = None if (frames.depth_paths and frames.depth_paths[0] is None) else float(c["depth_scale"])
         self.num_imgs = len(frames)
         self.dynamic_objects = 0
         self.projection_matrix = getProjectionMatrix2(0.01, 100.0, self.cx, self.cy, self.fx, self.fy, self.width,
@@ -473,7 +502,7 @@ class TUMDataset(RecordedRGBDDataset):
     def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
         from .segmentation import dataset_classes
         c = config["Dataset"]["Calibration"]
-        frames = parse_tum(config["Dataset"]["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+        frames = tum_frames(config)
         super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames, flow=flow,
                          segmenter=segmenter, seg_classes=dataset_classes("tum", config["Dataset"], bool(frames.mask_paths)))
 
@@ -484,10 +513,12 @@ class CoFusionDataset(RecordedRGBDDataset):
     def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
         from .segmentation import dataset_classes
         c, d = config["Dataset"]["Calibration"], config["Dataset"]
-        frames = parse_cofusion(d["dataset_path"]).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
+        has_depth = sequence_has_depth(config)
+        frames = parse_cofusion(d["dataset_path"], depth=has_depth).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
         if d.get("seg_teddy", False) or d.get("seg_clock", False):           # :545-547, after the slicing
             frames.color_paths = sorted(frames.color_paths, key=extract_number)
-            frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
+            if has_depth:
+                frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
         super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter,
                          seg_classes=dataset_classes("CoFusion", d, bool(frames.mask_paths)))
 

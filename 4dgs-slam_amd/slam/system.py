@@ -59,6 +59,9 @@ class SLAM:
         self.opt_params, self.pipeline_params = ns(config["opt_params"]), ns(config["pipeline_params"])
         self.monocular = config["Dataset"]["sensor_type"] == "monocular"
         config["Training"]["monocular"] = self.monocular
+        if self.monocular and config["model_params"]["dynamic_model"]:
+            raise ValueError("Dataset.sensor_type = 'monocular' cannot be combined with model_params.dynamic_model = True: the control nodes "
+                             "and the motion masks are seeded from sensor depth (static map only for RGB-only input)")
         config["Results"]["save_dir"] = save_dir
         sh_degree = 3 if config["Training"]["spherical_harmonics"] else 0
         dev = dataset.device
@@ -92,7 +95,9 @@ class SLAM:
         fe = self.frontend
         self.gaussians = fe.gaussians
         self.result = {"frames": len(fe.cameras), "keyframes": list(fe.kf_indices), "seconds": dt, "fps": len(fe.cameras) / dt,
-                       "gaussians": int(self.gaussians.get_xyz.shape[0])}
+                       "gaussians": int(self.gaussians.get_xyz.shape[0]), "sensor_type": self.config["Dataset"]["sensor_type"]}
+        if self.monocular:
+            self.result["resets"] = fe.resets
         if fe.init_done_at is not None and len(fe.cameras) > 1:          # frames per second once the map exists (tracking + keyframe mapping)
             self.result["seconds_init"] = fe.init_done_at - t0
             self.result["fps_after_init"] = (len(fe.cameras) - 1) / max(1e-9, t0 + dt - fe.init_done_at)

@@ -39,7 +39,8 @@ class TrackingGraph:
         dev = proto.device
         self.cam = blank_camera(proto, 1, dev)
         self.gt_image, self.gt_depth, self.w_rgb, self.w_dep = slot_buffers(int(proto.image_height), int(proto.image_width), dev)
-        self.alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
+        # (monocular input: load() leaves the two depth planes of the slot zero and the loss is the RGB term alone, alpha = 1)
+        self.alpha = 1.0 if config["Training"].get("monocular", False) else (config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95)
         lr = config["Training"]["lr"]
         self.lrs = (lr["cam_rot_delta"], lr["cam_trans_delta"], 0.01)
         self._one = torch.ones((), dtype=torch.float32, device=dev)
@@ -81,8 +82,7 @@ class TrackingGraph:
         c.exposure_b.copy_(viewpoint.exposure_b)
         c.cam_rot_delta.zero_()
         c.cam_trans_delta.zero_()
-        gt_image, gt_depth, _, _, t_rgb, t_dep = slam_losses._keyframe_constants(self.config, viewpoint, c.device)
-        w_rgb, w_dep = slam_losses.tracking_loss_weights(self.config, viewpoint, gt_image, gt_depth, rm_dynamic=True, mask=None, base=(t_rgb, t_dep))
+        gt_image, gt_depth, w_rgb, w_dep, _ = slam_losses.tracking_loss_operands(self.config, viewpoint, c.device, rm_dynamic=True, mask=None)
         self.gt_image.copy_(gt_image)
         self.gt_depth.copy_(gt_depth.view_as(self.gt_depth))
         self.w_rgb.copy_(w_rgb.view_as(self.w_rgb))

@@ -191,7 +191,8 @@ _CONST_CACHE_MAX = 24
 
 def _keyframe_constants(config, viewpoint, device):
     """(gt_image, gt_depth, rgb mask, depth mask, tracking rgb mask, tracking depth mask) on `device` (slam_utils.py:276-284, 65-77).
-    gt_depth and the depth masks are None for frames without a depth map (monocular)."""
+    ``viewpoint.depth`` may be None (a frame without a depth map: monocular input): gt_depth and the two depth masks are None then, and the
+    RGB-only forms of the losses put a shared plane of zeros in their place (_zero_plane)."""
     grad_mask = getattr(viewpoint, "grad_mask", None)
     key = (id(viewpoint.depth), id(viewpoint.original_image), str(device), float(config["Training"]["rgb_boundary_threshold"]), id(grad_mask))
     ent = _CONST_CACHE.get(id(viewpoint))
@@ -215,6 +216,20 @@ def _keyframe_constants(config, viewpoint, device):
     while len(_CONST_CACHE) > _CONST_CACHE_MAX:
         _CONST_CACHE.popitem(last=False)
     return data
+
+
+_ZERO_PLANES = {}
+
+
+def _zero_plane(like):
+    """A [1,H,W] plane of zeros on the device of `like` [.,H,W], one per (device, H, W) and never written: with monocular input it is both the
+    ground-truth depth and the depth weight of the fused weighted L1 -- alpha = 1 and zero depth weights make
+    alpha * mean(w_rgb |..|) + (1 - alpha) * mean(w_depth |..|) the RGB-only loss with a zero depth cotangent, no kernel of its own."""
+    key = (str(like.device), int(like.shape[-2]), int(like.shape[-1]))
+    z = _ZERO_PLANES.get(key)
+    if z is None:
+        z = _ZERO_PLANES[key] = torch.zeros((1, key[1], key[2]), dtype=torch.float32, device=like.device)
+    return z
 
 
 _DROP_LISTENERS = []          # weak references to callables(viewpoint | None): other per-keyframe stores that follow Camera.clean()
@@ -265,15 +280,16 @@ def mapping_loss_weights(config, viewpoint, gt_image, gt_depth, rm_dynamic=False
 
 def get_loss_mapping(config, image, depth, viewpoint, opacity, initialization=False, alpha=None, rm_dynamic=False, mask=None,
                      dynamic=False, split=False, compute_value=True):
-    """utils/slam_utils.py:252-259, same arguments and value. RGB-D, non-split calls (every call of utils/slam_backend.py with
-    the shipped configs) run fused; `monocular` and `split=True` are evaluated with the reference's tensor expression.
+    """utils/slam_utils.py:252-259, same arguments and value. Non-split calls (every call of utils/slam_backend.py with the shipped
+    configs) run fused -- monocular input (get_loss_mapping_rgb, :262-272: the boundary mask only, no depth map touched) as the same
+    kernel with alpha = 1 and zero depth weights; `split=True` is evaluated with the reference's tensor expression.
     compute_value=False (fused path only): the scalar is left uninitialised -- for callers that only back-propagate it."""
     _C._require_device(image, "image")
     gt_image, gt_depth, base_rgb, base_dep, _, _ = _keyframe_constants(config, viewpoint, image.device)
     exposure = (None, None) if initialization else (viewpoint.exposure_a, viewpoint.exposure_b)
-    if config["Training"]["monocular"]:                                           # never touches the depth map (there is none)
-        image_ab = image if initialization else torch.exp(exposure[0]) * image + exposure[1]
-        return torch.abs(image_ab * base_rgb - gt_image * base_rgb).mean()       # get_loss_mapping_rgb, :262-272
+    if config["Training"]["monocular"]:
+        zero = _zero_plane(gt_image)
+        return weighted_l1_loss(image, depth, gt_image, zero, base_rgb, zero, exposure[0], exposure[1], 1.0, compute_value=compute_value)
     if alpha is None:
         alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
     if split:                                                                     # :292-303
@@ -304,10 +320,12 @@ def _cached_mapping_weights(config, viewpoint, gt_image, gt_depth, base_rgb, bas
 def mapping_loss_operands(config, viewpoint, device, rm_dynamic=False, mask=None, dynamic=False):
     """(gt_image [3,H,W], gt_depth [1,H,W], w_rgb [1,H,W], w_depth [1,H,W], alpha): the constant operands the fused get_loss_mapping call of
     this keyframe hands to weighted_l1_loss -- the SAME tensors (values and, while the constants' cache holds the keyframe, storage). The
-    graph-captured mapping iteration (slam/mapping_graph.py) keeps them per keyframe and calls weighted_l1_loss itself. RGB-D only."""
-    if config["Training"]["monocular"]:
-        raise RuntimeError("mapping_loss_operands: RGB-D keyframes only")
+    graph-captured mapping iteration (slam/mapping_graph.py) keeps them per keyframe and calls weighted_l1_loss itself. Monocular input:
+    the boundary mask, the shared zero plane for both depth operands and alpha = 1, whatever the flags (get_loss_mapping_rgb has none)."""
     gt_image, gt_depth, base_rgb, base_dep, _, _ = _keyframe_constants(config, viewpoint, device)
+    if config["Training"]["monocular"]:
+        zero = _zero_plane(gt_image)
+        return gt_image, zero, base_rgb, zero, 1.0
     w_rgb, w_dep = _cached_mapping_weights(config, viewpoint, gt_image, gt_depth, base_rgb, base_dep, rm_dynamic, mask, dynamic)
     alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
     return gt_image, gt_depth, w_rgb, w_dep, alpha
@@ -331,22 +349,26 @@ def tracking_loss_weights(config, viewpoint, gt_image, gt_depth, rm_dynamic=Fals
     return w_rgb.to(torch.float32), w_dep.to(torch.float32)
 
 
-def get_loss_tracking(config, image, depth, opacity, viewpoint, initialization=False, rm_dynamic=False, mask=None, save_img=False):
-    """utils/slam_utils.py:57-61, same arguments and value (RGB-D: fused; monocular: the reference's tensor expression; save_img
-    is a debugging aid of the reference and is ignored). The exposure is always applied (:58)."""
-    _C._require_device(image, "image")
-    gt_image, gt_depth, _, _, t_rgb, t_dep = _keyframe_constants(config, viewpoint, image.device)
+def tracking_loss_operands(config, viewpoint, device, rm_dynamic=False, mask=None):
+    """(gt_image, gt_depth, w_rgb, w_depth, alpha) of the fused tracking loss of this frame, the rendered-opacity factors left to the kernel.
+    RGB-D: tracking_loss_weights and Training.alpha. Monocular input (get_loss_tracking_rgb, slam_utils.py:64-105): the boundary mask x
+    grad_mask -- get_loss_tracking hands that function neither rm_dynamic nor mask (:60), so both are ignored here as well -- the shared
+    zero plane for both depth operands and alpha = 1."""
+    gt_image, gt_depth, _, _, t_rgb, t_dep = _keyframe_constants(config, viewpoint, device)
     if t_rgb is None:
         raise RuntimeError("get_loss_tracking: viewpoint.grad_mask is not set (call compute_grad_mask first, utils/slam_frontend.py:678)")
-    if config["Training"]["monocular"]:                                           # get_loss_tracking_rgb, :64-105: no depth involved
-        w_rgb = t_rgb if mask is None else mask.view(*t_rgb.shape) * t_rgb
-        motion = getattr(viewpoint, "motion_mask", None)
-        if motion is not None and rm_dynamic and viewpoint.uid > 0:
-            w_rgb = motion.view(*t_rgb.shape) * w_rgb
-        image_ab = torch.exp(viewpoint.exposure_a) * image + viewpoint.exposure_b
-        return (opacity * torch.abs(image_ab * w_rgb - gt_image * w_rgb)).mean()
+    if config["Training"]["monocular"]:
+        zero = _zero_plane(gt_image)
+        return gt_image, zero, t_rgb, zero, 1.0
     w_rgb, w_dep = tracking_loss_weights(config, viewpoint, gt_image, gt_depth, rm_dynamic, mask, base=(t_rgb, t_dep))
-    alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
+    return gt_image, gt_depth, w_rgb, w_dep, config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
+
+
+def get_loss_tracking(config, image, depth, opacity, viewpoint, initialization=False, rm_dynamic=False, mask=None, save_img=False):
+    """utils/slam_utils.py:57-61, same arguments and value, fused for RGB-D and monocular input alike (tracking_loss_operands; save_img
+    is a debugging aid of the reference and is ignored). The exposure is always applied (:58)."""
+    _C._require_device(image, "image")
+    gt_image, gt_depth, w_rgb, w_dep, alpha = tracking_loss_operands(config, viewpoint, image.device, rm_dynamic, mask)
     return weighted_l1_loss(image, depth, gt_image, gt_depth, w_rgb, w_dep, viewpoint.exposure_a, viewpoint.exposure_b, alpha,
                             opacity=opacity, opacity_depth_threshold=0.95)
 

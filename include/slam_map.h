@@ -160,6 +160,20 @@ int gsr_slot_gather(int n_slots, const gsr_keyframe_entry* table /* device */, c
 int gsr_edge_mask(const float* image, int height, int width, float edge_threshold, float eps, float* intensity, float* median,
                   unsigned char* mask, void* stream);
 
+/* ---- seed depth of a monocular keyframe: FrontEnd.add_new_keyframe, utils/slam_frontend.py:133-174 (the use_inv_depth = False arm) with
+ * get_median_depth, utils/slam_utils.py:367-378 ------------------------------------------------------------------------------------
+ * depth [H*W], opacity [H*W]: the rendering of the tracked frame; gt_image [3,H,W]; noise [H*W]: standard-normal samples drawn by the caller.
+ *   rgb_ok = sum_c gt_image > rgb_boundary_threshold;  valid = depth > 0 && opacity > 0.95 && rgb_ok
+ *   median = torch.median of the valid depths (the lower of the two middle values);  std = their unbiased standard deviation
+ *   bad = !valid || depth > median + std || depth < median - std
+ *   out = rgb_ok ? (bad ? median : depth) + noise * (bad ? 0.5 std : 0.2 std) : 0             (fp32, no contraction)
+ * stats: {float median, float std, int32 n_valid}, device memory. Fewer than two valid pixels (the reference raises or yields NaN): out is
+ * all zeros, stats = {0, 0, n_valid}. Seven launches and one memset, no host read; the sums run in a fixed order (the same bits every call).
+ * workspace: gsr_mono_keyframe_depth_workspace_size bytes, 16-byte aligned, private to the call while it runs. */
+size_t gsr_mono_keyframe_depth_workspace_size(int height, int width);
+int gsr_mono_keyframe_depth(const float* depth, const float* opacity, const float* gt_image, int height, int width, float rgb_boundary_threshold,
+                            const float* noise, float* out, float* stats, char* workspace, void* stream);
+
 /* ---- best-fit rotations for the ARAP regulariser of the control nodes: estimate_rotation, utils/deform_utils.py:130-166 ----------------
  * S, R: n row-major 3x3 matrices. R = V U^T of S = U Sigma V^T, with the reference's reflection rule (the column of the smallest singular
  * value is flipped when det <= 0): always a proper rotation; S = 0 -> identity. One thread per matrix, double precision inside. */

@@ -10,6 +10,8 @@ motion aggregation, the reference's second estimator), and the `flow` block's `e
 (slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame.
 With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and the LPIPS v0.1 linear layers) the rendering evaluation
 reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair.
+`Dataset.sensor_type: monocular` runs on the images alone (a sequence whose Calibration has no depth_scale is read without depth files; the
+ATE is scale-aligned); it cannot be combined with --dynamic.
 With --save-map [DIR] the finished map is saved after the evaluations (slam/map_io.py) for tools/play_map.py."""
 import argparse
 import json
@@ -67,6 +69,9 @@ def main(argv=None):
     config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
     if args.dataset_path:
         config["Dataset"]["dataset_path"] = args.dataset_path
+    if config["Dataset"].get("sensor_type") == "monocular" and config["model_params"]["dynamic_model"]:
+        raise SystemExit("Dataset.sensor_type 'monocular' cannot run with model_params.dynamic_model (--dynamic): the dynamic model is seeded "
+                         "from sensor depth")
     save_dir = args.save_dir
     if save_dir is None and config["Results"]["save_results"]:          # slam.py:278-285
         path = config["Dataset"]["dataset_path"].rstrip("/").split("/")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """BASELINE config #4 in its asset-free form: the whole SLAM system (slam/system.py) on the synthetic RGB-D sequence (slam/dataset.py),
-static and dynamic, eager tracking and hipGraph tracking; prints ATE / PSNR / fps as one JSON document."""
+static and dynamic, eager tracking and hipGraph tracking; prints ATE / PSNR / fps as one JSON document. With --monocular the static
+sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every frame's depth is None; the ATE is scale-aligned)."""
 import json
 import os
 import sys
@@ -18,14 +19,19 @@ from slam.system import SLAM, default_config, merge_config  # noqa: E402
 save_map = sys.argv[sys.argv.index("--save-map") + 1] if "--save-map" in sys.argv else None
 only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
 profile = "--profile" in sys.argv
+monocular = "--monocular" in sys.argv
 out = {}
-for name, dyn, graph, frames, wh in (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
-                                     ("dynamic_320x240_eager", True, False, 36, (320, 240)), ("dynamic_320x240_graph", True, True, 36, (320, 240)),
-                                     ("dynamic_640x480_graph", True, True, 36, (640, 480))):
+scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
+             ("dynamic_320x240_eager", True, False, 36, (320, 240)), ("dynamic_320x240_graph", True, True, 36, (320, 240)),
+             ("dynamic_640x480_graph", True, True, 36, (640, 480)))
+if monocular:
+    scenarios = (("monocular_320x240_graph", False, True, 40, (320, 240)),)
+for name, dyn, graph, frames, wh in scenarios:
     if only not in name:
         continue
     torch.manual_seed(0)
-    ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=0.025 if wh[0] > 320 else 0.03)
+    ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=0.025 if wh[0] > 320 else 0.03,
+                              sensor_depth=not monocular)
     cfg = merge_config(default_config(), {"Training": {"init_itr_num": 400, "init_gaussian_update": 100, "init_gaussian_reset": 200, "tracking_itr_num": 60,
                                                        "static_map_iters": 30, "dynamic_map_iters": 80, "network_init_iters": 50, "gaussian_update_every": 60,
                                                        "gaussian_update_offset": 20, "tracking_graph": graph,
@@ -33,6 +39,8 @@ for name, dyn, graph, frames, wh in (("static_640x480_eager", False, False, 40, 
                                                        "loss_values": os.environ.get("GSR_LOSS_VALUES", "0") == "1"},
                                           "Dataset": {"pcd_downsample": 32, "pcd_downsample_init": 8}, "opt_params": {"densify_from_iter": 150},
                                           "model_params": {"dynamic_model": dyn}})
+    if monocular:      # (kf_interval 2, window 4: the window fills -- and the map counts as initialised -- within the 40 frames)
+        cfg = merge_config(cfg, {"Dataset": {"sensor_type": "monocular"}, "Training": {"kf_interval": 2, "window_size": 4}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
