@@ -221,26 +221,75 @@ struct Call {
 
 // small launches are latency-bound: the per-Gaussian kernels then request every row they may need up front (gs_forward.h)
 constexpr int EAGER_MAX_P = 512 * 1024;
-// render_fwd's blocks take the tiles of their XCD band by list length, dealt over the band's CUs (gs_forward.h F3c), DEAL_HEAVY lists per CU
-// held back for the CUs with one block less. Needs the work-item ranking block (order_items) and the LDS histogram. Returns the scatter
-// launch's argument: 0 = band order, 1 + DEAL_HEAVY otherwise.
 constexpr int DEAL_HEAVY = 1;
-static int order_fwd_tiles(bool order_items, int T) { return order_items && T / 8 >= ORDER_FWD_MIN_BAND ? 1 + DEAL_HEAVY : 0; }
-// the same choices as gs_views.h takes them in one word: bit 0 = ordered work items, bit 1 = ordered render_fwd tiles, bits 2.. = DEAL_HEAVY
-static int views_order_word(bool order_items, int T) { return order_items ? 1 | (order_fwd_tiles(true, T) ? 2 | DEAL_HEAVY << 2 : 0) : 0; }
-// Longest tile list the speculative launches are sized for, from the last frame's (plus head room): picks the sort kernels (and the chunk
-// grid of the long-list sort).
+// where tile lists of up to `longest_list` entries get sorted (gs_views.h: SortTier)
+static SortTier sort_tier(uint32_t longest_list)
+{
+    if (longest_list <= (uint32_t)SORT_SMALL_CAP) return {SortTier::NONE, 0};
+    if (longest_list <= (uint32_t)SORT_MID_CAP) return {SortTier::MID, 0};
+    return {SortTier::FULL, longest_list > (uint32_t)SORT_LDS_CAP ? (longest_list + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP : 0};
+}
+// Longest tile list the speculative launches are sized for, from the last frame's (plus head room): the longest of its tier (and chunk grid)
 static uint32_t tile_list_capacity(uint32_t last_max_tile)
 {
-    const uint32_t want = last_max_tile + (uint32_t)((unsigned long long)last_max_tile * tile_margin() / 1000ull);
-    return want <= (uint32_t)SORT_SMALL_CAP ? (uint32_t)SORT_SMALL_CAP
-         : want <= (uint32_t)SORT_MID_CAP ? (uint32_t)SORT_MID_CAP
-         : want <= (uint32_t)SORT_LDS_CAP ? (uint32_t)SORT_LDS_CAP
-         : (want + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP * (uint32_t)SORT_LDS_CAP;
+    const SortTier t = sort_tier(last_max_tile + (uint32_t)((unsigned long long)last_max_tile * tile_margin() / 1000ull));
+    return t.kind == SortTier::NONE ? (uint32_t)SORT_SMALL_CAP : t.kind == SortTier::MID ? (uint32_t)SORT_MID_CAP : std::max(t.chunks, 1u) * (uint32_t)SORT_LDS_CAP;
 }
 // preprocess_fwd's dynamic LDS at its largest: the tile histogram of a frame of HIST_LDS_TILES tiles, then one SH window per wave
 constexpr size_t PRE_LDS_MAX = (((size_t)HIST_LDS_TILES * sizeof(uint32_t) + 15) & ~size_t(15)) + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float);
 static_assert(PRE_LDS_MAX <= 160 * 1024, "preprocess_fwd's LDS must fit gfx950's 160 KiB per workgroup");
+
+static FwdPlan plan_forward(const Options& opt, int P, int D, int M, int width, int height, bool flow, bool colors_precomp)
+{
+    FwdPlan p;
+    p.d = view_dims(P, width, height); p.eager = P <= EAGER_MAX_P ? 1 : 0; p.wide_offsets = p.d.nblocks > TO_SEGS * 16;
+    p.lds_hist = use_lds_hist((size_t)p.d.T); p.hist_lds_bytes = p.lds_hist ? (size_t)p.d.T * sizeof(uint32_t) : 0;
+    p.order_items = opt.order_items && p.lds_hist;
+    const bool fwd_tiles = p.order_items && p.d.T / 8 >= ORDER_FWD_MIN_BAND;
+    p.order_fwd = fwd_tiles ? 1 + DEAL_HEAVY : 0; p.order_word = p.order_items ? 1 | (fwd_tiles ? 2 | DEAL_HEAVY << 2 : 0) : 0;
+    p.sh_win = opt.sh_rows && p.lds_hist && D > 0 && !colors_precomp && (M == 9 || M == 16) && !flow;
+    p.sh_win_offset = p.sh_win ? (int)((p.hist_lds_bytes + 15) & ~size_t(15)) : 0;
+    p.pre_lds = p.sh_win ? (size_t)p.sh_win_offset + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float) : p.hist_lds_bytes;
+    return p;
+}
+// f(shape): the <SEGS, RMAX> of the plan's tile_offsets kernel, as a type (gs_views.h: OffsetsShape)
+template <typename F> static void with_tile_offsets(const FwdPlan& p, F&& f) { if (p.wide_offsets) f(OffsetsShape<TO_SEGS_BIG, 32>{}); else f(OffsetsShape<TO_SEGS, 16>{}); }
+// f(k): the <RAW, PRE> of the call's preprocess / geometry kernel, as a type (gs_views.h: RawPre) -- <true, true> for raw inputs in delta_mode, <true, false>
+// for other raw inputs, <false, false> for activated ones, which RAW_ONLY leaves out (the batched kernels exist for raw inputs only)
+template <bool RAW_ONLY = false, typename F> static auto with_raw_pre(bool raw, bool delta_mode, F&& f)
+{
+    if (raw && delta_mode) return f(RawPre<true, true>{});
+    if constexpr (RAW_ONLY) return f(RawPre<true, false>{});
+    else return raw ? f(RawPre<true, false>{}) : f(RawPre<false, false>{});
+}
+// A preprocess launch with the plan's dynamic LDS. The SH windows take it beyond the 64 KB default: the attribute is a cap set once per (kernel,
+// device), to the largest frame's bytes, so that a later frame with more tiles than the first still launches (a launch passes only what it uses)
+template <auto KERNEL, typename... Args> static int launch_preprocess(const FwdPlan& p, dim3 grid, hipStream_t stream, const Args&... args)
+{
+    static std::atomic<unsigned long long> raised;   // (one per kernel instantiation)
+    if (p.sh_win) { const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), (int)PRE_LDS_MAX, raised); if (rc) return rc; }
+    hipLaunchKernelGGL(KERNEL, grid, dim3(GB), p.pre_lds, stream, args...);
+    return 0;
+}
+// The fields of the preprocess / geometry kernels' arguments that do not depend on the view, the rest zero: a single-view call then sets the buffer
+// pointers on the host, a batch leaves them to the device (gs_views.h: view_geom / view_image)
+static PreprocessArgs preprocess_args(const FwdPlan& p, int D, int M, float scale_modifier, float tan_fovx, float tan_fovy, int prefiltered, const RawInputs& raw)
+{
+    PreprocessArgs a{};
+    a.P = p.d.P; a.D = D; a.M = M; a.W = p.d.W; a.H = p.d.H; a.gx = p.d.gx; a.gy = p.d.gy;
+    a.scale_modifier = scale_modifier; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
+    a.focal_y = p.d.H / (2.0f * tan_fovy); a.focal_x = p.d.W / (2.0f * tan_fovx);   // rasterizer_impl.cu:225-226
+    a.prefiltered = prefiltered; a.eager = p.eager; a.sh_win_offset = p.sh_win_offset; a.raw = raw;
+    return a;
+}
+static GeomBwdArgs geom_bwd_args(const Options& opt, const ViewDims& d, int D, int M, float scale_modifier, float tan_fovx, float tan_fovy, bool pose_only, const RawInputs& raw, int scale_dim)
+{
+    GeomBwdArgs a{};
+    a.P = d.P; a.D = D; a.M = M; a.W = d.W; a.H = d.H; a.scale_modifier = scale_modifier;
+    a.focal_y = d.H / (2.0f * tan_fovy); a.focal_x = d.W / (2.0f * tan_fovx); a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
+    a.pose_only = pose_only ? 1 : 0; a.sh_rows = opt.sh_rows ? 1 : 0; a.raw = raw; a.rawg.scale_dim = scale_dim;
+    return a;
+}
 
 static int ensure_mailbox(SpecState& s)
 {
@@ -279,6 +328,17 @@ static int wait_for_header(hipStream_t stream, const SpecState& s, bool& use_mai
     }
     GSR_HIP_CHECK(hipMemcpyAsync(out, device_header, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     GSR_HIP_CHECK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// The header the host waited for: the frame's counts, which become the slot's estimates for the next frame
+struct FrameCounts { uint32_t R, R_alloc, flags, max_tile; };
+static int absorb_header(SpecState& spec, const uint32_t hdr[4], const char* who, FrameCounts& f)
+{
+    f = {hdr[HDR_R], hdr[HDR_R_ALLOC], hdr[HDR_FLAGS], hdr[HDR_MAX_TILE]};
+    if (f.R > 0x7fffffffu || f.R_alloc > 0x7fffffffu) { g_last_error = std::string(who) + ": more than 2^31 instances"; return GSR_ERR_INVALID_ARGUMENT; }
+    spec.last_R_alloc = std::max<size_t>(1, f.R_alloc > f.R ? f.R_alloc : f.R);     // (never 0: 0 means "no estimate yet"; a frame may legitimately have no instance)
+    spec.last_max_tile = f.max_tile;
     return 0;
 }
 
@@ -441,8 +501,30 @@ struct FwdInputs {
     const float* scales = nullptr; const float* rotations = nullptr; const float* cov3D_precomp = nullptr; int prefiltered = 0;
     const gsr_raw_inputs* raw = nullptr;
 };
-struct FwdCamera { const float* viewmatrix; const float* projmatrix; const float* cam_pos; float tan_fovx, tan_fovy; };
+struct FwdCamera { const float* viewmatrix; const float* projmatrix; const float* cam_pos; float tan_fovx, tan_fovy; const float* projmatrix_raw = nullptr; /* backward only */ };
 struct FwdOutputs { float* color; float* depth; float* opacity; int* radii; int* n_touched; };
+// backward_impl: what the forward pass left (radii NULL: the geometry buffer's own), the cotangents of its outputs, the gradients wanted. Intermediate ones the caller does not
+// want stay NULL (dL_dconic, dL_dcolor, dL_ddepth, dL_dcov3D; dL_dtau when dL_dtau_sum is given): the kernel then keeps them in registers only. gsr_backward requires them all.
+struct BwdState { char* geom_buffer; char* binning_buffer; char* image_buffer; const int* radii; int R; };
+struct BwdCotangents { const float* dL_dpix; const float* dL_dpix_depth; };
+struct BwdGrads {
+    float *dL_dmean2D = nullptr, *dL_dconic = nullptr, *dL_dopacity = nullptr, *dL_dcolor = nullptr, *dL_ddepth = nullptr, *dL_dmean3D = nullptr, *dL_dcov3D = nullptr;
+    float *dL_dsh = nullptr, *dL_dscale = nullptr, *dL_drot = nullptr, *dL_dtau = nullptr, *dL_dtau_sum = nullptr;
+};
+// view `w` of a multi-view call as a single-view descriptor: the call's raw inputs with the view's deltas and flow pointers
+static gsr_raw_inputs view_raw_inputs(gsr_raw_inputs one, const gsr_view& w)
+{
+    one.dx = w.dx; one.ds = w.ds; one.dr = w.dr; one.flow_dx2 = w.flow_dx2; one.flow_proj1 = w.flow_proj1; one.flow_proj2 = w.flow_proj2;
+    return one;
+}
+// ... and as a row of the batched kernels' table: what the forward and the backward pass both read
+static void fill_view_slot(ViewSlot& s, const gsr_view& w)
+{
+    s.viewmatrix = w.viewmatrix; s.projmatrix = w.projmatrix; s.projmatrix_raw = w.projmatrix_raw; s.cam_pos = w.cam_pos;
+    s.dx = w.dx; s.ds = w.ds; s.dr = w.dr;
+    s.flow_dx2 = w.flow_dx2; s.flow_proj1 = w.flow_proj1; s.flow_proj2 = w.flow_proj2;
+    s.geom = w.geom_buffer; s.image = w.image_buffer; s.binning = w.binning_buffer; s.radii = w.radii;
+}
 struct FwdAllocs { gsr_alloc_fn geometry; void* geometry_user; gsr_alloc_fn binning; void* binning_user; gsr_alloc_fn image; void* image_user; };
 
 static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, const float* background, int width, int height, const FwdInputs& in,
@@ -464,7 +546,10 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
         if (!in.colors_precomp && (!in.shs || M <= 0)) { g_last_error = "gsr_forward: need shs (M>0) or colors_precomp"; return GSR_ERR_INVALID_ARGUMENT; }
         if (!in.colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M)) { g_last_error = "gsr_forward: sh degree out of range for M"; return GSR_ERR_INVALID_ARGUMENT; }
     }
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y, T = gx * gy;
+    const bool flow = raw && raw->flow_proj1;
+    const FwdPlan plan = plan_forward(c.opt, P, D, M, width, height, flow, in.colors_precomp != nullptr);
+    const int gx = plan.d.gx, gy = plan.d.gy, T = plan.d.T, nblocks = plan.d.nblocks;
+    const bool lds_hist = plan.lds_hist, order_items = plan.order_items;
     const size_t N = (size_t)width * height;
     SpecState& spec = *c.spec;
     const int prefiltered = in.prefiltered;
@@ -474,11 +559,7 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
     if (!gchunk || !ichunk) { g_last_error = "gsr_forward: allocation callback returned NULL"; return GSR_ERR_ALLOC; }
     GeomState geom = GeomState::from(gchunk, (size_t)P);
     ImageState img = ImageState::from(ichunk, N, (size_t)T, (size_t)P);
-    const bool lds_hist = use_lds_hist((size_t)T);
-    const size_t hist_lds_bytes = lds_hist ? (size_t)T * sizeof(uint32_t) : 0;
-    const bool order_items = c.opt.order_items && lds_hist;        // (the ordering block keeps the tiles' list lengths in the same dynamic LDS)
-    const int order_fwd = order_fwd_tiles(order_items, T);
-    const int* const flow_clip = raw && raw->flow_proj1 ? c.flow_clip : nullptr;
+    const int* const flow_clip = flow ? c.flow_clip : nullptr;
     int* const radii = out.radii ? out.radii : geom.internal_radii;   // rasterizer_impl.cu:232-235
 
     // Zero-filled scratch: the flag word only when someone can raise it (prefiltered; the reference's callers never set it), the
@@ -490,51 +571,29 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
     else if (prefiltered)
         GSR_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(uint32_t), stream));
 
-    const int nblocks = (P + GB - 1) / GB;
-    const int eager = P <= EAGER_MAX_P ? 1 : 0;
     if (P > 0) {
-        PreprocessArgs a;
-        a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.gx = gx; a.gy = gy;
-        a.means3D = in.means3D; a.scales = in.scales; a.scale_modifier = scale_modifier; a.rotations = in.rotations; a.opacities = in.opacities;
+        PreprocessArgs a = preprocess_args(plan, D, M, scale_modifier, cam.tan_fovx, cam.tan_fovy, prefiltered, to_device_view(raw, flow_clip));
+        a.means3D = in.means3D; a.scales = in.scales; a.rotations = in.rotations; a.opacities = in.opacities;
         a.shs = in.shs; a.cov3D_precomp = in.cov3D_precomp; a.colors_precomp = in.colors_precomp;
         a.viewmatrix = cam.viewmatrix; a.projmatrix = cam.projmatrix; a.cam_pos = cam.cam_pos;
-        a.tan_fovx = cam.tan_fovx; a.tan_fovy = cam.tan_fovy;
-        a.focal_y = height / (2.0f * cam.tan_fovy); a.focal_x = width / (2.0f * cam.tan_fovx);   // rasterizer_impl.cu:225-226
-        a.prefiltered = prefiltered; a.radii = radii; a.n_touched = out.n_touched;
+        a.radii = radii; a.n_touched = out.n_touched;
         a.rec = geom.rec; a.cov3D = geom.cov3D;
         a.clamped = geom.clamped; a.tiles_touched = geom.tiles_touched; a.block_sums = geom.block_sums; a.tile_count = img.tile_count;
         a.flags = flags; a.block_tile_base = lds_hist ? img.block_tile_base : nullptr;
-        a.raw = to_device_view(raw, flow_clip);
         {
             ScopedKernelTimer tm(K_PREPROCESS, stream);
-            a.eager = eager;
-            // SH rows through LDS (gs_device.h: stage_rows): one 6.25 KB window per wave behind the tile histogram, reserved only when coefficients
-            // above the DC band are read (the LDS histogram path: the windows sit in the same dynamic allocation)
-            const bool sh_win = c.opt.sh_rows && lds_hist && D > 0 && !in.colors_precomp && (M == 9 || M == 16) && !(raw && raw->flow_proj1);
-            a.sh_win_offset = sh_win ? (int)((hist_lds_bytes + 15) & ~size_t(15)) : 0;
-            const size_t pre_lds = sh_win ? (size_t)a.sh_win_offset + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float) : hist_lds_bytes;
-            if (sh_win) {
-                // the attribute is a cap set once per (kernel, device): the largest frame's bytes, so that a later frame with more tiles than
-                // the first one still launches (each launch still passes only the bytes it uses)
-                static std::atomic<unsigned long long> attr_set[3];
-                const void* fn = raw && raw->delta_mode ? reinterpret_cast<const void*>(preprocess_fwd_kernel<true, true>)
-                               : raw ? reinterpret_cast<const void*>(preprocess_fwd_kernel<true>) : reinterpret_cast<const void*>(preprocess_fwd_kernel<false>);
-                const int rc = ensure_dynamic_lds(fn, (int)PRE_LDS_MAX, attr_set[raw && raw->delta_mode ? 2 : raw ? 1 : 0]);
-                if (rc) return rc;
-            }
-            if (raw && raw->delta_mode) hipLaunchKernelGGL((preprocess_fwd_kernel<true, true>), dim3(nblocks), dim3(GB), pre_lds, stream, a);
-            else if (raw) hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(nblocks), dim3(GB), pre_lds, stream, a);
-            else hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3(nblocks), dim3(GB), pre_lds, stream, a);
+            const int rc = with_raw_pre(raw != nullptr, raw && raw->delta_mode, [&](auto k) {
+                return launch_preprocess<preprocess_fwd_kernel<k.raw, k.pre>>(plan, dim3(nblocks), stream, a);
+            });
+            if (rc) return rc;
         }
         GSR_STAGE("preprocess_fwd");   // (returns the launch's error: hipGetLastError)
         if (lds_hist) {
             ScopedKernelTimer tm(K_SCAN, stream);
-            if (nblocks <= TO_SEGS * 16)
-                hipLaunchKernelGGL((tile_offsets_kernel<TO_SEGS, 16>), dim3((T + TO_COLS - 1) / TO_COLS), dim3(TO_COLS * TO_SEGS), 0, stream, nblocks, T,
-                               img.block_tile_base, img.tile_count, img.tile_cursor);      // (tile_cursor: free on this path; holds the dense list lengths)
-            else
-                hipLaunchKernelGGL((tile_offsets_kernel<TO_SEGS_BIG, 32>), dim3((T + TO_COLS - 1) / TO_COLS), dim3(TO_COLS * TO_SEGS_BIG), 0, stream, nblocks, T,
-                               img.block_tile_base, img.tile_count, img.tile_cursor);
+            with_tile_offsets(plan, [&](auto s) {      // (tile_cursor: free on this path; holds the dense list lengths)
+                hipLaunchKernelGGL((tile_offsets_kernel<s.segs, s.rmax>), dim3((T + TO_COLS - 1) / TO_COLS), dim3(TO_COLS * s.segs), 0, stream, nblocks, T, img.block_tile_base,
+                                   img.tile_count, img.tile_cursor);
+            });
         }
         GSR_STAGE("tile_offsets");
     } else if (lds_hist) {
@@ -596,25 +655,21 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
                 sis.chunk_base = img.chunk_base; sis.flags = prefiltered ? flags : (const uint32_t*)nullptr; sis.cap_R = (uint32_t)cap; sis.cap_tile_list = cap_tile;
                 sis.host_mailbox = c.opt.mailbox ? spec.mailbox_dev : nullptr; sis.seq = spec.seq;
             }
-            hipLaunchKernelGGL(scatter_instances_kernel, dim3(nblocks + (order_items || sis.dense_total ? 1 : 0)), dim3(GB), hist_lds_bytes, stream, P, gx, gy, radii, geom.rec,
+            hipLaunchKernelGGL(scatter_instances_kernel, dim3(nblocks + (order_items || sis.dense_total ? 1 : 0)), dim3(GB), plan.hist_lds_bytes, stream, P, gx, gy, radii, geom.rec,
                                geom.tiles_touched, geom.block_base, geom.point_offsets, img.tile_cursor, img.ranges,
                                lds_hist ? img.block_tile_base : nullptr, bin.keys, bin.inst_gauss, geom.header, spec_launch ? 1 : 0,
-                               (uint32_t)carve_R, (uint32_t)cap_sorted, eager, flow_clip,
-                               order_items ? img.tile_count : (uint32_t*)nullptr, order_fwd, sis);
+                               (uint32_t)carve_R, (uint32_t)cap_sorted, plan.eager, flow_clip,
+                               order_items ? img.tile_count : (uint32_t*)nullptr, plan.order_fwd, sis);
         }
         GSR_STAGE("scatter_instances");
-        if (longest_list > (uint32_t)SORT_SMALL_CAP) {   // lists of up to SORT_SMALL_CAP entries are sorted inside render_fwd; longer ones here
+        if (const SortTier tier = sort_tier(longest_list); tier.kind != SortTier::NONE) {
             ScopedKernelTimer tm(K_SORT, stream);
-            // one launch: 18 KiB blocks (eight per CU) when no list exceeds 2048 keys, 36 KiB blocks (four per CU) otherwise. Splitting
-            // the tiles between two launches by length was measured: the two tails cost more than the occupancy returns (99 -> 131 us).
-            if (longest_list <= (uint32_t)SORT_MID_CAP)
-                hipLaunchKernelGGL((sort_tiles_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
-                                   bin.keys, bin.inst_gauss, bin.sorted, chk);
+            if (tier.kind == SortTier::MID)
+                hipLaunchKernelGGL((sort_tiles_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges, bin.keys, bin.inst_gauss, bin.sorted, chk);
             else
-                hipLaunchKernelGGL((sort_tiles_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges,
-                                   bin.keys, bin.inst_gauss, bin.sorted, chk);
-            if (longest_list > (uint32_t)SORT_LDS_CAP) {   // chunk-wise LDS sort + rank by counting (gs_forward.h F4b)
-                const dim3 g((unsigned)T, (longest_list + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP);
+                hipLaunchKernelGGL((sort_tiles_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), dim3(T), dim3(256), 0, stream, T, img.ranges, bin.keys, bin.inst_gauss, bin.sorted, chk);
+            if (tier.chunks) {
+                const dim3 g((unsigned)T, tier.chunks);
                 hipLaunchKernelGGL((sort_long_chunks_kernel<SORT_LDS_CAP>), g, dim3(256), 0, stream, img.ranges, bin.keys, chk, (uint32_t)SORT_LDS_CAP);
                 hipLaunchKernelGGL((rank_long_chunks_kernel<SORT_LDS_CAP>), g, dim3(256), 0, stream, img.ranges, (const uint64_t*)bin.keys,
                                    (const uint32_t*)bin.inst_gauss, bin.sorted, chk, (uint32_t)SORT_LDS_CAP);
@@ -625,7 +680,7 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
         launch_render_fwd(T, gx, img.ranges, bin.sorted, width, height, geom.rec, background, img.final_T, img.n_contrib, out.color, out.depth,
                           out.opacity, out.n_touched, img.final_C, bin.ckpt, chk, (const uint64_t*)bin.keys, (const uint32_t*)bin.inst_gauss, bin.sorted,
                           (const uint32_t*)img.chunk_base, bin.chunk_info, order_items ? (const uint32_t*)img.tile_count : (const uint32_t*)nullptr,
-                          order_fwd ? 1 : 0);
+                          plan.order_fwd ? 1 : 0);
         GSR_STAGE("render_fwd");
         return 0;
     };
@@ -641,17 +696,16 @@ static int forward_impl(Call& c, const FwdAllocs& alloc, int P, int D, int M, co
     // The one host wait of the forward pass (the reference's is the blocking cudaMemcpy at rasterizer_impl.cu:283-284).
     uint32_t hdr[4];
     { const int rc = wait_for_header(stream, spec, c.opt.mailbox, geom.header, spec.seq, hdr); if (rc) return rc; }
-    const uint32_t R = hdr[HDR_R], flg = hdr[HDR_FLAGS], R_alloc = hdr[HDR_R_ALLOC], max_tile_list = hdr[HDR_MAX_TILE];
-    if (flg & FLAG_PREFILTERED) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return GSR_ERR_PREFILTERED; }
-    if (R > 0x7fffffffu || R_alloc > 0x7fffffffu) { g_last_error = "gsr_forward: more than 2^31 instances"; return GSR_ERR_INVALID_ARGUMENT; }
-    spec.last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);     // (never 0: 0 means "no estimate yet"; a frame may legitimately have no instance)
-    spec.last_max_tile = max_tile_list;
-    if (speculate && !(flg & FLAG_OVERFLOW)) return (int)R;
+    if (hdr[HDR_FLAGS] & FLAG_PREFILTERED) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return GSR_ERR_PREFILTERED; }
+    FrameCounts f;
+    { const int rc = absorb_header(spec, hdr, "gsr_forward", f); if (rc) return rc; }
+    const uint32_t R = f.R, R_alloc = f.R_alloc;
+    if (speculate && !(f.flags & FLAG_OVERFLOW)) return (int)R;
 
     if (R > 0) {
         bchunk = alloc.binning(alloc.binning_user, binning_bytes((size_t)R, (size_t)R_alloc, (size_t)T));
         if (!bchunk) { g_last_error = "gsr_forward: binning allocation callback returned NULL"; return GSR_ERR_ALLOC; }
-        const int rc = enqueue_binning_and_render(bchunk, (size_t)R, (size_t)R_alloc, false, R_alloc != R, max_tile_list);
+        const int rc = enqueue_binning_and_render(bchunk, (size_t)R, (size_t)R_alloc, false, R_alloc != R, f.max_tile);
         if (rc) return rc;
     } else {
         if (!bchunk) bchunk = alloc.binning(alloc.binning_user, binning_bytes(0, 0, (size_t)T));
@@ -714,33 +768,7 @@ struct CapturedAllocs {
     CapturedAlloc g, b, i;
     FwdAllocs fns() { return {captured_alloc, &g, captured_alloc, &b, captured_alloc, &i}; }
 };
-ViewDims view_dims(int P, int width, int height)
-{
-    ViewDims d;
-    d.P = P; d.W = width; d.H = height; d.gx = (width + TILE_X - 1) / TILE_X; d.gy = (height + TILE_Y - 1) / TILE_Y; d.T = d.gx * d.gy;
-    d.nblocks = (P + GB - 1) / GB;
-    return d;
-}
 }  // namespace
-
-// view `vw` of a gsr_forward_views call through the single-view path, on view slot `slot`
-static int forward_one_view(const Options& opt, gsr_view& vw, int slot, gsr_alloc_fn geometry_alloc, gsr_alloc_fn binning_alloc, gsr_alloc_fn image_alloc,
-                            int P, int D, int M, const float* background, int width, int height, const gsr_raw_inputs* in, float scale_modifier,
-                            float tan_fovx, float tan_fovy, int debug, void* stream)
-{
-    gsr_raw_inputs one = *in;
-    one.dx = vw.dx; one.ds = vw.ds; one.dr = vw.dr;
-    one.flow_dx2 = vw.flow_dx2; one.flow_proj1 = vw.flow_proj1; one.flow_proj2 = vw.flow_proj2;
-    Call c{opt, &spec_state(slot), vw.flow_clip};
-    FwdInputs fin;
-    fin.raw = &one;
-    CapturedAllocs al{{geometry_alloc, vw.geometry_user, nullptr}, {binning_alloc, vw.binning_user, nullptr}, {image_alloc, vw.image_user, nullptr}};
-    const int rc = forward_impl(c, al.fns(), P, D, M, background, width, height, fin, scale_modifier, {vw.viewmatrix, vw.projmatrix, vw.cam_pos, tan_fovx, tan_fovy},
-                                {vw.out_color, vw.out_depth, vw.out_opacity, vw.radii, vw.n_touched}, debug, stream);
-    if (rc < 0) return rc;
-    vw.geom_buffer = al.g.got; vw.binning_buffer = al.b.got; vw.image_buffer = al.i.got; vw.num_rendered = rc;
-    return 0;
-}
 
 extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_alloc, gsr_alloc_fn binning_alloc, gsr_alloc_fn image_alloc, int P, int D, int M,
                                  const float* background, int width, int height, const gsr_raw_inputs* in, float scale_modifier, float tan_fovx,
@@ -754,8 +782,7 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     const bool flow = views[0].flow_proj1 != nullptr;      // render_flow views: every view of the call, or none
     for (int v = 0; v < V; v++) {
         const gsr_view& w = views[v];
-        gsr_raw_inputs probe = *in; probe.dx = w.dx; probe.ds = w.ds; probe.dr = w.dr;
-        probe.flow_dx2 = w.flow_dx2; probe.flow_proj1 = w.flow_proj1; probe.flow_proj2 = w.flow_proj2;
+        const gsr_raw_inputs probe = view_raw_inputs(*in, w);
         if (!w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.out_color || !w.out_depth || !w.out_opacity || !w.radii || !w.n_touched ||
             (w.flow_proj1 != nullptr) != flow || !raw_inputs_ok(&probe, M)) {
             g_last_error = "gsr_forward_views: null / inconsistent view descriptor"; return GSR_ERR_INVALID_ARGUMENT;
@@ -765,15 +792,28 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     // several (view_slot_group): a slot shared by two calls per iteration sees its estimate flip between two cameras -- eager calls then redo
     // the view through the single-view path every time, captured ones overflow at every replay
     const int slot0 = 1 + t_view_slot_group * 2 * MAX_VIEWS + (flow ? MAX_VIEWS : 0);
-    const ViewDims d = view_dims(P, width, height);
     Options opt = read_options();
+    auto forward_one_view = [&](const Options& o, int v) -> int {   // view v through the single-view path, on its view slot
+        gsr_view& vw = views[v];
+        const gsr_raw_inputs one = view_raw_inputs(*in, vw);
+        Call c{o, &spec_state(slot0 + v), vw.flow_clip};
+        FwdInputs fin;
+        fin.raw = &one;
+        CapturedAllocs al{{geometry_alloc, vw.geometry_user, nullptr}, {binning_alloc, vw.binning_user, nullptr}, {image_alloc, vw.image_user, nullptr}};
+        const int rc = forward_impl(c, al.fns(), P, D, M, background, width, height, fin, scale_modifier, {vw.viewmatrix, vw.projmatrix, vw.cam_pos, tan_fovx, tan_fovy},
+                                    {vw.out_color, vw.out_depth, vw.out_opacity, vw.radii, vw.n_touched}, debug, stream_);
+        if (rc < 0) return rc;
+        vw.geom_buffer = al.g.got; vw.binning_buffer = al.b.got; vw.image_buffer = al.i.got; vw.num_rendered = rc;
+        return 0;
+    };
+    const FwdPlan plan = plan_forward(opt, P, D, M, width, height, flow, false);
+    const ViewDims& d = plan.d;
     // the batched path needs a capacity estimate for every slot (the first iteration of a window goes view by view and leaves one)
-    bool batched = !debug && opt.speculate && use_lds_hist((size_t)d.T) && V > 1;
+    bool batched = !debug && opt.speculate && plan.lds_hist && V > 1;
     for (int v = 0; v < V && batched; v++) batched = spec_state(slot0 + v).last_R_alloc != 0;
     if (!batched) {
         for (int v = 0; v < V; v++) {
-            const int rc = forward_one_view(opt, views[v], slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in,
-                                            scale_modifier, tan_fovx, tan_fovy, debug, stream_);
+            const int rc = forward_one_view(opt, v);
             if (rc) return rc;
         }
         return 0;
@@ -795,65 +835,45 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
         w.binning_buffer = binning_alloc(w.binning_user, binning_bytes(cap, cap, (size_t)d.T));
         if (!w.geom_buffer || !w.image_buffer || !w.binning_buffer) { g_last_error = "gsr_forward_views: allocation callback returned NULL"; return GSR_ERR_ALLOC; }
         ViewSlot& s = t.v[v];
-        s.viewmatrix = w.viewmatrix; s.projmatrix = w.projmatrix; s.projmatrix_raw = w.projmatrix_raw; s.cam_pos = w.cam_pos;
-        s.dx = w.dx; s.ds = w.ds; s.dr = w.dr;
-        s.flow_dx2 = w.flow_dx2; s.flow_proj1 = w.flow_proj1; s.flow_proj2 = w.flow_proj2; s.flow_clip = flow ? w.flow_clip : nullptr;
-        s.geom = w.geom_buffer; s.image = w.image_buffer; s.binning = w.binning_buffer;
-        s.out_color = w.out_color; s.out_depth = w.out_depth; s.out_opacity = w.out_opacity; s.radii = w.radii; s.n_touched = w.n_touched;
+        fill_view_slot(s, w);
+        s.flow_clip = flow ? w.flow_clip : nullptr;
+        s.out_color = w.out_color; s.out_depth = w.out_depth; s.out_opacity = w.out_opacity; s.n_touched = w.n_touched;
         s.mailbox = opt.mailbox ? spec.mailbox_dev : nullptr; s.cap = (uint32_t)std::min<size_t>(cap, 0x7fffffffu); s.cap_tile = cap_tile; s.seq = spec.seq;
     }
-    PreprocessArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.gx = d.gx; a.gy = d.gy;
-    a.scale_modifier = scale_modifier; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-    a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx);
-    a.prefiltered = 0; a.eager = P <= EAGER_MAX_P ? 1 : 0;
-    a.raw = to_device_view(in, nullptr);
+    const PreprocessArgs a = preprocess_args(plan, D, M, scale_modifier, tan_fovx, tan_fovy, 0, to_device_view(in, nullptr));
     const dim3 gv((unsigned)d.nblocks, (unsigned)V), tv((unsigned)d.T, (unsigned)V);
-    const size_t hist_lds_bytes = (size_t)d.T * sizeof(uint32_t);
-    const int order = views_order_word(opt.order_items, d.T);
     {
         ScopedKernelTimer tm(K_PREPROCESS, stream);
-        // SH rows through LDS under the conditions of the single-view call (forward_impl): the two evaluations of the SH polynomial are
-        // contracted differently by the compiler, so a batch that took the per-lane one differed from V single-view calls in the last bit
-        // of the colours at M = 9 / 16, D > 0
-        const bool sh_win = opt.sh_rows && D > 0 && (M == 9 || M == 16) && !flow;
-        a.sh_win_offset = sh_win ? (int)((hist_lds_bytes + 15) & ~size_t(15)) : 0;
-        const size_t pre_lds = sh_win ? (size_t)a.sh_win_offset + (size_t)(GB / 64) * SH_WIN_FLOATS * sizeof(float) : hist_lds_bytes;
-        if (sh_win) {
-            static std::atomic<unsigned long long> attr_set[2];
-            const void* fn = in->delta_mode ? reinterpret_cast<const void*>(preprocess_views_kernel<true, true>) : reinterpret_cast<const void*>(preprocess_views_kernel<true>);
-            const int rc = ensure_dynamic_lds(fn, (int)PRE_LDS_MAX, attr_set[in->delta_mode ? 1 : 0]);
-            if (rc) return rc;
-        }
-        if (in->delta_mode) hipLaunchKernelGGL((preprocess_views_kernel<true, true>), gv, dim3(GB), pre_lds, stream, a, t, d);
-        else hipLaunchKernelGGL(preprocess_views_kernel<true>, gv, dim3(GB), pre_lds, stream, a, t, d);
+        const int rc = with_raw_pre<true>(true, in->delta_mode, [&](auto k) {
+            return launch_preprocess<preprocess_views_kernel<k.raw, k.pre>>(plan, gv, stream, a, t, d);
+        });
+        if (rc) return rc;
     }
     {
         ScopedKernelTimer tm(K_SCAN, stream);
-        const dim3 go((unsigned)((d.T + TO_COLS - 1) / TO_COLS), (unsigned)V);
-        if (d.nblocks <= TO_SEGS * 16) hipLaunchKernelGGL((tile_offsets_views_kernel<TO_SEGS, 16>), go, dim3(TO_COLS * TO_SEGS), 0, stream, t, d);
-        else hipLaunchKernelGGL((tile_offsets_views_kernel<TO_SEGS_BIG, 32>), go, dim3(TO_COLS * TO_SEGS_BIG), 0, stream, t, d);
+        with_tile_offsets(plan, [&](auto s) {
+            hipLaunchKernelGGL((tile_offsets_views_kernel<s.segs, s.rmax>), dim3((unsigned)((d.T + TO_COLS - 1) / TO_COLS), (unsigned)V), dim3(TO_COLS * s.segs), 0, stream, t, d);
+        });
         hipLaunchKernelGGL(scan_views_kernel, dim3(1, (unsigned)V), dim3(1024), 0, stream, t, d);
     }
     {
         ScopedKernelTimer tm(K_SCATTER, stream);
-        hipLaunchKernelGGL(scatter_views_kernel, dim3((unsigned)d.nblocks + (opt.order_items ? 1u : 0u), (unsigned)V), dim3(GB), hist_lds_bytes, stream, t, d, a.eager,
-                           order);
+        hipLaunchKernelGGL(scatter_views_kernel, dim3((unsigned)d.nblocks + (plan.order_items ? 1u : 0u), (unsigned)V), dim3(GB), plan.hist_lds_bytes, stream, t, d, plan.eager,
+                           plan.order_word);
     }
-    if (cap_tile > (uint32_t)SORT_SMALL_CAP) {   // lists of up to SORT_SMALL_CAP entries are sorted inside render_fwd
+    if (const SortTier tier = sort_tier(cap_tile); tier.kind != SortTier::NONE) {
         ScopedKernelTimer tm(K_SORT, stream);
-        if (cap_tile <= (uint32_t)SORT_MID_CAP) hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
+        if (tier.kind == SortTier::MID) hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_MID_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
         else hipLaunchKernelGGL((sort_tiles_views_kernel<SORT_LDS_CAP, SORT_SMALL_CAP>), tv, dim3(256), 0, stream, t, d);
-        if (cap_tile > (uint32_t)SORT_LDS_CAP) {
-            const dim3 gl((unsigned)d.T, (cap_tile + (uint32_t)SORT_LDS_CAP - 1) / (uint32_t)SORT_LDS_CAP, (unsigned)V);
+        if (tier.chunks) {
+            const dim3 gl((unsigned)d.T, tier.chunks, (unsigned)V);
             hipLaunchKernelGGL((sort_long_chunks_views_kernel<SORT_LDS_CAP>), gl, dim3(256), 0, stream, t, d, (uint32_t)SORT_LDS_CAP);
             hipLaunchKernelGGL((rank_long_chunks_views_kernel<SORT_LDS_CAP>), gl, dim3(256), 0, stream, t, d, (uint32_t)SORT_LDS_CAP);
         }
     }
     {
         ScopedKernelTimer tm(K_RENDER_FWD, stream);
-        hipLaunchKernelGGL(render_fwd_views_kernel, tv, dim3(RB), 0, stream, t, d, background, 1, order);
+        hipLaunchKernelGGL(render_fwd_views_kernel, tv, dim3(RB), 0, stream, t, d, background, 1, plan.order_word);
     }
     GSR_HIP_CHECK(hipGetLastError());
     // one wait per view (they are all long done by the time the host has enqueued the tile kernels); a view that outgrew its capacity is
@@ -866,18 +886,15 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
         char* gp = w.geom_buffer;
         const GeomState geom = GeomState::from(gp, (size_t)P);
         { const int rc = wait_for_header(stream, spec, opt.mailbox, geom.header, t.v[v].seq, hdr); if (rc) return rc; }
-        const uint32_t R = hdr[HDR_R], flg = hdr[HDR_FLAGS], R_alloc = hdr[HDR_R_ALLOC];
-        if (R > 0x7fffffffu || R_alloc > 0x7fffffffu) { g_last_error = "gsr_forward_views: more than 2^31 instances"; return GSR_ERR_INVALID_ARGUMENT; }
-        spec.last_R_alloc = std::max<size_t>(1, R_alloc > R ? R_alloc : R);
-        spec.last_max_tile = hdr[HDR_MAX_TILE];
-        w.num_rendered = (int)R;
-        if (flg & FLAG_OVERFLOW) {
+        FrameCounts f;
+        { const int rc = absorb_header(spec, hdr, "gsr_forward_views", f); if (rc) return rc; }
+        w.num_rendered = (int)f.R;
+        if (f.flags & FLAG_OVERFLOW) {
             // (without speculation: the counts are known, the redo is laid out for exactly them. A speculative redo would overflow a
             // second time under "cap_test_shrink_permille" and count the same frame twice in the sticky overflow counter.)
             Options exact = opt;
             exact.speculate = false;
-            const int rc = forward_one_view(exact, w, slot0 + v, geometry_alloc, binning_alloc, image_alloc, P, D, M, background, width, height, in, scale_modifier,
-                                            tan_fovx, tan_fovy, debug, stream_);
+            const int rc = forward_one_view(exact, v);
             if (rc) return rc;
         }
     }
@@ -915,10 +932,8 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
             g_last_error = "gsr_backward_views: null / inconsistent view argument"; return GSR_ERR_INVALID_ARGUMENT;
         }
         ViewSlot& s = t.v[v];
-        s.viewmatrix = w.viewmatrix; s.projmatrix = w.projmatrix; s.projmatrix_raw = w.projmatrix_raw; s.cam_pos = w.cam_pos;
-        s.dx = w.dx; s.ds = w.ds; s.dr = w.dr;
-        s.flow_dx2 = w.flow_dx2; s.flow_proj1 = w.flow_proj1; s.flow_proj2 = w.flow_proj2; s.ddx2 = w.ddx2;
-        s.geom = w.geom_buffer; s.image = w.image_buffer; s.binning = w.binning_buffer; s.radii = w.radii;
+        fill_view_slot(s, w);
+        s.ddx2 = w.ddx2;
         s.dL_dpix = w.dL_dcolor; s.dL_dpix_depth = w.dL_ddepth; s.dL_dmean2D = w.dL_dmean2D; s.ddx = w.ddx; s.dds = w.dds; s.ddr = w.ddr; s.tau_sum = w.dL_dtau_sum;
         s.part = pose_only ? nullptr : reinterpret_cast<float*>(sp + (size_t)v * row_bytes);
         s.cap = (uint32_t)std::max(0, w.num_rendered);
@@ -930,19 +945,12 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
             hipLaunchKernelGGL(render_bwd_views_kernel, dim3((unsigned)(max_R / CHUNK + d.T), (unsigned)V), dim3(RB), 0, stream, t, d, background);
         }
     }
-    GeomBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.scale_modifier = scale_modifier;
-    a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx); a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-    a.pose_only = pose_only ? 1 : 0;
-    a.sh_rows = opt.sh_rows ? 1 : 0;
-    a.raw = to_device_view(in, nullptr);
-    a.rawg = RawGrads{};
-    a.rawg.scale_dim = in->scale_dim;
+    const GeomBwdArgs a = geom_bwd_args(opt, d, D, M, scale_modifier, tan_fovx, tan_fovy, pose_only, to_device_view(in, nullptr), in->scale_dim);
     {
         ScopedKernelTimer tm(K_GEOM_BWD, stream);
-        if (in->delta_mode) hipLaunchKernelGGL((geometry_bwd_views_kernel<true, true>), dim3((unsigned)((P + 255) / 256), (unsigned)V), dim3(256), 0, stream, a, t, d);
-        else hipLaunchKernelGGL(geometry_bwd_views_kernel<true>, dim3((unsigned)((P + 255) / 256), (unsigned)V), dim3(256), 0, stream, a, t, d);
+        with_raw_pre<true>(true, in->delta_mode, [&](auto k) {
+            hipLaunchKernelGGL((geometry_bwd_views_kernel<k.raw, k.pre>), dim3((unsigned)((P + 255) / 256), (unsigned)V), dim3(256), 0, stream, a, t, d);
+        });
         hipLaunchKernelGGL(tau_sum_views_kernel, dim3(1, (unsigned)V), dim3(384), 0, stream, t, d);
         if (!pose_only) {
             ReduceTargets r{out->xyz, out->features_dc, out->features_rest, out->logit_opacity, out->log_scales, out->raw_rotations};
@@ -953,69 +961,56 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
     return 0;
 }
 
-static int backward_impl(const Call& c, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D, const float* shs,
-                 const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* projmatrix_raw,
-                 const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer,
-                 char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth, float* dL_dmean2D, float* dL_dconic,
-                 float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                 float* dL_dscale, float* dL_drot, float* dL_dtau, float* dL_dtau_sum, int debug, void* stream_,
-                 const gsr_raw_inputs* raw, const gsr_raw_grads* rawg)
+static int backward_impl(const Call& c, int P, int D, int M, const float* background, int width, int height, const FwdInputs& in, float scale_modifier,
+                         const FwdCamera& cam, const BwdState& st, const BwdCotangents& ct, const BwdGrads& g, const gsr_raw_grads* rawg, int debug, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
+    const gsr_raw_inputs* const raw = in.raw;
     const bool accumulate = (debug & GSR_BACKWARD_ACCUMULATE) != 0;     // include/gs_rasterizer.h
     const bool pose_only = (debug & GSR_BACKWARD_POSE_ONLY) != 0;
     debug &= 1;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) { g_last_error = "gsr_backward: invalid size"; return GSR_ERR_INVALID_ARGUMENT; }
-    if (P == 0) { if (dL_dtau_sum) GSR_HIP_CHECK(hipMemsetAsync(dL_dtau_sum, 0, 6 * sizeof(float), stream)); return 0; }
-    // Intermediate gradients the caller does not want may be NULL (dL_dconic, dL_dcolor, dL_ddepth, dL_dcov3D; dL_dtau when
-    // dL_dtau_sum is given): the kernel then keeps them in registers only. gsr_backward itself requires all of them.
-    if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix || !dL_dpix_depth || !background || (!means3D && !raw) || !viewmatrix ||
-        !projmatrix || !projmatrix_raw || !campos || !dL_dmean2D || (!pose_only && (!dL_dopacity || !dL_dmean3D)) || (!dL_dtau && !dL_dtau_sum) ||
+    if (P < 0 || st.R < 0 || width <= 0 || height <= 0) { g_last_error = "gsr_backward: invalid size"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (P == 0) { if (g.dL_dtau_sum) GSR_HIP_CHECK(hipMemsetAsync(g.dL_dtau_sum, 0, 6 * sizeof(float), stream)); return 0; }
+    if (!st.geom_buffer || !st.binning_buffer || !st.image_buffer || !ct.dL_dpix || !ct.dL_dpix_depth || !background || (!in.means3D && !raw) || !cam.viewmatrix ||
+        !cam.projmatrix || !cam.projmatrix_raw || !cam.cam_pos || !g.dL_dmean2D || (!pose_only && (!g.dL_dopacity || !g.dL_dmean3D)) || (!g.dL_dtau && !g.dL_dtau_sum) ||
         (raw && (!raw_inputs_ok(raw, M) || !rawg ||
-                 (!pose_only && (!dL_dscale || !dL_drot || (!raw->flow_proj1 && (!rawg->features_dc || (M > 1 && !rawg->features_rest)))))))) {
+                 (!pose_only && (!g.dL_dscale || !g.dL_drot || (!raw->flow_proj1 && (!rawg->features_dc || (M > 1 && !rawg->features_rest)))))))) {
         g_last_error = "gsr_backward: null argument"; return GSR_ERR_INVALID_ARGUMENT;
     }
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y, T = gx * gy;
-    char* gp = geom_buffer; char* ip = image_buffer;
+    const ViewDims d = view_dims(P, width, height);
+    char* gp = st.geom_buffer; char* ip = st.image_buffer;
     GeomState geom = GeomState::from(gp, (size_t)P);
-    ImageState img = ImageState::from(ip, (size_t)width * height, (size_t)T, 0);
-    if (!radii) radii = geom.internal_radii;   // rasterizer_impl.cu:387-390
-    if (R > 0) {
+    ImageState img = ImageState::from(ip, (size_t)width * height, (size_t)d.T, 0);
+    if (st.R > 0) {
         // one block per CHUNK entries of a tile list; sum over tiles of ceil(n / CHUNK) <= R / CHUNK + T, surplus blocks exit
         ScopedKernelTimer tm(K_RENDER_BWD, stream);
-        const int grid = R / CHUNK + T;
-        hipLaunchKernelGGL(render_bwd_kernel, dim3(grid), dim3(RB), 0, stream, T, gx, (const char*)binning_buffer,
+        const int grid = st.R / CHUNK + d.T;
+        hipLaunchKernelGGL(render_bwd_kernel, dim3(grid), dim3(RB), 0, stream, d.T, d.gx, (const char*)st.binning_buffer,
                            (const uint32_t*)geom.header, width, height, background, geom.rec,
-                           img.final_T, img.final_C, img.n_contrib, dL_dpix, dL_dpix_depth);
+                           img.final_T, img.final_C, img.n_contrib, ct.dL_dpix, ct.dL_dpix_depth);
     }
     GSR_STAGE("render_bwd");
-    GeomBwdArgs a;
-    a.P = P; a.D = D; a.M = M; a.W = width; a.H = height;
-    a.means3D = means3D; a.radii = radii; a.shs = shs; a.clamped = geom.clamped; a.scales = scales; a.rotations = rotations;
-    a.scale_modifier = scale_modifier; a.cov3Ds = cov3D_precomp ? cov3D_precomp : geom.cov3D;   // rasterizer_impl.cu:429
-    a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.projmatrix_raw = projmatrix_raw; a.campos = campos;
-    a.focal_y = height / (2.0f * tan_fovy); a.focal_x = width / (2.0f * tan_fovx); a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-    a.tiles_touched = geom.tiles_touched; a.point_offsets = geom.point_offsets; a.bin_base = binning_buffer; a.header = geom.header;
-    a.dL_dmean2D = dL_dmean2D; a.dL_dconic = dL_dconic; a.dL_dopacity = dL_dopacity; a.dL_dcolor = dL_dcolor; a.dL_ddepth = dL_ddepth;
-    a.dL_dmean3D = dL_dmean3D; a.dL_dcov3D = dL_dcov3D; a.dL_dsh = dL_dsh; a.dL_dscale = dL_dscale; a.dL_drot = dL_drot; a.dL_dtau = dL_dtau;
+    GeomBwdArgs a = geom_bwd_args(c.opt, d, D, M, scale_modifier, cam.tan_fovx, cam.tan_fovy, pose_only, to_device_view(raw, nullptr), raw ? raw->scale_dim : 0);
+    a.means3D = in.means3D; a.shs = in.shs; a.clamped = geom.clamped; a.scales = in.scales; a.rotations = in.rotations;
+    a.radii = st.radii ? st.radii : geom.internal_radii;                       // rasterizer_impl.cu:387-390
+    a.cov3Ds = in.cov3D_precomp ? in.cov3D_precomp : geom.cov3D;               // rasterizer_impl.cu:429
+    a.viewmatrix = cam.viewmatrix; a.projmatrix = cam.projmatrix; a.projmatrix_raw = cam.projmatrix_raw; a.campos = cam.cam_pos;
+    a.tiles_touched = geom.tiles_touched; a.point_offsets = geom.point_offsets; a.bin_base = st.binning_buffer; a.header = geom.header;
+    a.dL_dmean2D = g.dL_dmean2D; a.dL_dconic = g.dL_dconic; a.dL_dopacity = g.dL_dopacity; a.dL_dcolor = g.dL_dcolor; a.dL_ddepth = g.dL_ddepth;
+    a.dL_dmean3D = g.dL_dmean3D; a.dL_dcov3D = g.dL_dcov3D; a.dL_dsh = g.dL_dsh; a.dL_dscale = g.dL_dscale; a.dL_drot = g.dL_drot; a.dL_dtau = g.dL_dtau;
     a.accumulate = accumulate ? 1 : 0;
-    a.pose_only = pose_only ? 1 : 0;
-    a.sh_rows = c.opt.sh_rows ? 1 : 0;
-    a.tau_partials = dL_dtau_sum ? geom.tau_partials : nullptr;
-    a.raw = to_device_view(raw, nullptr);
-    a.rawg = RawGrads{};
-    if (raw) { a.rawg.f_dc = rawg->features_dc; a.rawg.f_rest = rawg->features_rest; a.rawg.ddx = rawg->dx; a.rawg.dds = rawg->ds; a.rawg.ddr = rawg->dr; a.rawg.scale_dim = raw->scale_dim; a.rawg.ddx2 = rawg->dx2; }
+    a.tau_partials = g.dL_dtau_sum ? geom.tau_partials : nullptr;
+    if (raw) { a.rawg.f_dc = rawg->features_dc; a.rawg.f_rest = rawg->features_rest; a.rawg.ddx = rawg->dx; a.rawg.dds = rawg->ds; a.rawg.ddr = rawg->dr; a.rawg.ddx2 = rawg->dx2; }
     {
         ScopedKernelTimer tm(K_GEOM_BWD, stream);
-        if (raw && raw->delta_mode) hipLaunchKernelGGL((geometry_bwd_kernel<true, true>), dim3((P + 255) / 256), dim3(256), 0, stream, a);
-        else if (raw) hipLaunchKernelGGL(geometry_bwd_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(geometry_bwd_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, a);
-        if (dL_dtau_sum && c.track_tail)     // gsr_track_step: pose-gradient sum + exposure-gradient sum + camera step in one launch
-            hipLaunchKernelGGL(track_tail_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, (const float*)geom.tau_partials, dL_dtau_sum, T,
+        with_raw_pre(raw != nullptr, raw && raw->delta_mode, [&](auto k) {
+            hipLaunchKernelGGL((geometry_bwd_kernel<k.raw, k.pre>), dim3((P + 255) / 256), dim3(256), 0, stream, a);
+        });
+        if (g.dL_dtau_sum && c.track_tail)     // gsr_track_step: pose-gradient sum + exposure-gradient sum + camera step in one launch
+            hipLaunchKernelGGL(track_tail_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, (const float*)geom.tau_partials, g.dL_dtau_sum, d.T,
                                c.track_tail->exposure_partials, c.track_tail->dL_dexposure, c.track_tail->step);
-        else if (dL_dtau_sum)
-            hipLaunchKernelGGL(tau_sum_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, geom.tau_partials, dL_dtau_sum);
+        else if (g.dL_dtau_sum)
+            hipLaunchKernelGGL(tau_sum_kernel, dim3(1), dim3(384), 0, stream, (P + 255) / 256, geom.tau_partials, g.dL_dtau_sum);
     }
     GSR_STAGE("geometry_bwd");
     return 0;
@@ -1089,10 +1084,13 @@ int gsr_backward_fused(int P, int D, int M, int R, const float* background, int 
                  float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscale, float* dL_drot, float* dL_dtau, float* dL_dtau_sum, int debug, void* stream)
 {
-    return backward_impl(Call{read_options()}, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, projmatrix_raw, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer,
-                         dL_dpix, dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                         dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, debug, stream, nullptr, nullptr);
+    FwdInputs in;
+    in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp;
+    BwdGrads g;
+    g.dL_dmean2D = dL_dmean2D; g.dL_dconic = dL_dconic; g.dL_dopacity = dL_dopacity; g.dL_dcolor = dL_dcolor; g.dL_ddepth = dL_ddepth; g.dL_dmean3D = dL_dmean3D;
+    g.dL_dcov3D = dL_dcov3D; g.dL_dsh = dL_dsh; g.dL_dscale = dL_dscale; g.dL_drot = dL_drot; g.dL_dtau = dL_dtau; g.dL_dtau_sum = dL_dtau_sum;
+    return backward_impl(Call{read_options()}, P, D, M, background, width, height, in, scale_modifier, {viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, projmatrix_raw},
+                         {geom_buffer, binning_buffer, image_buffer, radii, R}, {dL_dpix, dL_dpix_depth}, g, nullptr, debug, stream);
 }
 
 int gsr_backward_raw(int P, int D, int M, int R, const float* background, int width, int height, const gsr_raw_inputs* in,
@@ -1102,10 +1100,12 @@ int gsr_backward_raw(int P, int D, int M, int R, const float* background, int wi
                      float* dL_dtau_sum, int debug, void* stream)
 {
     if (!in || !out) { g_last_error = "gsr_backward_raw: null descriptor"; return GSR_ERR_INVALID_ARGUMENT; }
-    return backward_impl(Call{read_options()}, P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
-                         projmatrix, projmatrix_raw, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                         dL_dpix_depth, dL_dmean2D, nullptr, out->logit_opacity, nullptr, nullptr, out->xyz, nullptr, nullptr,
-                         out->log_scales, out->raw_rotations, nullptr, dL_dtau_sum, debug, stream, in, out);
+    FwdInputs fin;
+    fin.raw = in;
+    BwdGrads g;
+    g.dL_dmean2D = dL_dmean2D; g.dL_dopacity = out->logit_opacity; g.dL_dmean3D = out->xyz; g.dL_dscale = out->log_scales; g.dL_drot = out->raw_rotations; g.dL_dtau_sum = dL_dtau_sum;
+    return backward_impl(Call{read_options()}, P, D, M, background, width, height, fin, scale_modifier, {viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, projmatrix_raw},
+                         {geom_buffer, binning_buffer, image_buffer, radii, R}, {dL_dpix, dL_dpix_depth}, g, out, debug, stream);
 }
 
 int gsr_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D, const float* shs,
@@ -2729,12 +2729,11 @@ int gsr_track_step(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_f
     const int R = forward_impl(c, al.fns(), P, D, M, background, width, height, fin, scale_modifier, {step->viewmatrix, step->full_proj, step->campos, tan_fovx, tan_fovy},
                                {out_color, out_depth, out_opacity, radii, n_touched}, 0, stream);
     if (R < 0) return R;
-    gsr_raw_grads none;
-    memset(&none, 0, sizeof(none));
-    const int rc = backward_impl(c, P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, step->viewmatrix,
-                                 step->full_proj, projmatrix_raw, step->campos, tan_fovx, tan_fovy, radii, al.g.got, al.b.got, al.i.got, g_image, g_depth, dL_dmean2D,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tau6, GSR_BACKWARD_POSE_ONLY, stream,
-                                 in, &none);
+    const gsr_raw_grads none{};
+    BwdGrads g;
+    g.dL_dmean2D = dL_dmean2D; g.dL_dtau_sum = tau6;
+    const int rc = backward_impl(c, P, D, M, background, width, height, fin, scale_modifier, {step->viewmatrix, step->full_proj, step->campos, tan_fovx, tan_fovy, projmatrix_raw},
+                                 {al.g.got, al.b.got, al.i.got, radii, R}, {g_image, g_depth}, g, &none, GSR_BACKWARD_POSE_ONLY, stream);
     if (rc < 0) return rc;
     GSR_HIP_CHECK(hipGetLastError());
     return R;

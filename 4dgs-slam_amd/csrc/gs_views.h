@@ -6,7 +6,8 @@
 // ~5 us of every small kernel is outside any wave's lifetime). Here blockIdx.y (blockIdx.z for the long-list sort) selects the view:
 // every view keeps its own geometry / image / binning buffers (the layout of the single-view path, carved on the device from the
 // buffers' base addresses), the per-view pointers travel by value in the kernel arguments (ViewTable, <= 12 views, 2.6 KB), and the
-// kernels are the single-view BODIES of gs_forward.h / gs_render.h / gs_backward.h, unchanged.
+// kernels are the single-view BODIES of gs_forward.h / gs_render.h / gs_backward.h, unchanged. So are the launch shapes: the host takes them from the
+// one FwdPlan / SortTier (below) that the single-view path reads too.
 //
 // Parameter gradients: the views' geometry kernels run concurrently, so they cannot add to one gradient buffer. Each view writes
 // its parameter gradients to a scratch row; views_reduce_kernel then adds them to the target in VIEW ORDER, visible views only, one
@@ -36,6 +37,39 @@ static_assert(sizeof(ViewTable) + sizeof(PreprocessArgs) + 64 <= 4096 && sizeof(
               "the view table travels by value in the kernel arguments (4 KB)");
 
 struct ViewDims { int P, W, H, gx, gy, T, nblocks; };
+inline ViewDims view_dims(int P, int width, int height)
+{
+    ViewDims d;
+    d.P = P; d.W = width; d.H = height; d.gx = (width + TILE_X - 1) / TILE_X; d.gy = (height + TILE_Y - 1) / TILE_Y; d.T = d.gx * d.gy;
+    d.nblocks = (P + GB - 1) / GB;
+    return d;
+}
+
+// ---- host side. How the stages of a forward pass are launched is decided once per call (gs_capi.hip: plan_forward, sort_tier) for the single-view
+// kernels of gs_forward.h / gs_render.h (forward_impl) and for their *_views_kernel wrappers below (gsr_forward_views) alike: both paths read the
+// plan and decide none of it themselves -- a batch equals V single calls bit for bit only while the two agree.
+struct FwdPlan {
+    ViewDims d;                                 // the frame in tiles (gx x gy = T), the blocks of the per-Gaussian kernels (nblocks)
+    int eager;                                  // PreprocessArgs::eager, scatter's argument
+    bool lds_hist; size_t hist_lds_bytes;       // tile histograms in dynamic LDS (scatter's, and the front of preprocess's); else global atomics
+    // render_bwd's work items ranked by one extra block of the scatter launch (it keeps the tiles' list lengths in the histogram's LDS); with it
+    // render_fwd's blocks take the tiles of their XCD band by list length, dealt over the band's CUs (gs_forward.h F3c), DEAL_HEAVY lists per CU
+    // held back for the CUs with one block less. order_fwd: the scatter kernel's argument, 0 = band order, else 1 + DEAL_HEAVY (render_fwd's:
+    // != 0). order_word: both for gs_views.h, bit 0 = ordered work items, bit 1 = ordered render_fwd tiles, bits 2.. = DEAL_HEAVY
+    bool order_items; int order_fwd, order_word;
+    // SH rows through LDS (gs_device.h: stage_rows): one 6.25 KB window per wave behind the tile histogram, reserved only when coefficients above
+    // the DC band are read. (The compiler contracts the two evaluations of the SH polynomial differently: the colours differ in the last bit.)
+    bool sh_win; int sh_win_offset; size_t pre_lds;   // PreprocessArgs::sh_win_offset; preprocess's dynamic LDS
+    bool wide_offsets;                          // tile_offsets: TO_SEGS_BIG segments of 32 rows, not TO_SEGS of 16
+};
+// Where tile lists of up to `longest_list` entries get sorted (gs_capi.hip: sort_tier). NONE: inside render_fwd (up to SORT_SMALL_CAP entries). MID / FULL:
+// by one sort_tiles launch in front of it, of 18 KiB blocks (eight per CU) when no list exceeds SORT_MID_CAP keys, of 36 KiB blocks (four per CU)
+// otherwise -- splitting the tiles between two launches by length was measured: the two tails cost more than the occupancy returns (99 -> 131 us).
+// chunks > 0: lists beyond SORT_LDS_CAP too, by a chunk-wise LDS sort + rank by counting on a (T, chunks) grid (gs_forward.h F4b).
+struct SortTier { enum Kind { NONE, MID, FULL } kind; uint32_t chunks; };
+// the template arguments of a stage's kernel as a type, for a generic lambda that launches it: tile_offsets' <SEGS, RMAX>, preprocess / geometry's <RAW, PRE>
+template <int SEGS, int RMAX> struct OffsetsShape { static constexpr int segs = SEGS, rmax = RMAX; };
+template <bool RAW, bool PRE> struct RawPre { static constexpr bool raw = RAW, pre = PRE; };
 
 __device__ __forceinline__ GeomState view_geom(const ViewSlot& s, int P) { char* p = s.geom; return GeomState::from(p, (size_t)P); }
 __device__ __forceinline__ ImageState view_image(const ViewSlot& s, const ViewDims& d)

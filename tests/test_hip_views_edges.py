@@ -2,7 +2,7 @@
 diff_gaussian_rasterization/views.py) at the sizes, view counts and option values where the batched path has logic of its own: partly
 filled tiles and the last batched frame size, the Gaussian counts at which tile_offsets / the eager scatter change variant, one to twelve
 views with views that see nothing, tile lists exactly at the bounds of the shared sort capacity, overflow inside a batch (by count and by
-list length), the option table, the delta_mode entry point and the view slot groups.
+list length), the option table (and M = 9, which it leaves out), the delta_mode entry point and the view slot groups.
 
 The reference of every case is V single-view calls on the same inputs (raw.rasterize_gaussians_raw), and everything is compared bit for
 bit (torch.equal): per view the five outputs, dL_dmean2D, the delta gradients, theta and rho; the parameter gradients either as the
@@ -90,7 +90,7 @@ def _random_scene(P, V, W, H, D=0, M=None, iso=False, dyn=False, scale_mean=0.02
     """P random Gaussians in (spread times) the frustum of the camera at the origin, seen from keyframe_pose(2 v) or `poses`.
     visible: rows that stay in front of the cameras; every other Gaussian is moved behind them."""
     cam0 = make_camera(W, H)
-    max_deg = {None: D, 1: 0, 4: 1, 16: 3}[M]
+    max_deg = {None: D, 1: 0, 4: 1, 9: 2, 16: 3}[M]
     g = make_gaussians(P, _wide(cam0, spread), seed=seed, sh_degree=D, max_sh_degree=max_deg, scale_mean=scale_mean)
     if P < 16:
         g["means3D"][:, :2] *= 0.5              # a handful of Gaussians: well inside the frustum
@@ -690,6 +690,15 @@ def test_option_table(W, H, row, monkeypatch):
             assert not bool(bucket.flat.any())
     else:
         _check_case(sc, monkeypatch, f"options-{W}x{H}", mode=mode, native=bool(o["native"]), options=opts, lazy=bool(o["lazy"]))
+
+
+@pytest.mark.parametrize("sh_rows", [0, 1])
+@pytest.mark.parametrize("D", [1, 2])
+def test_nine_coefficients_per_gaussian(D, sh_rows, monkeypatch):
+    """M = 9 is the one value at which preprocess takes the SH row windows (sh_rows, D > 0, M = 9 or 16) that the option table does not reach."""
+    sc = _random_scene(2500, 3, 37, 23, D=D, M=9, seed=9 + D)
+    assert sc.M == 9
+    _check_case(sc, monkeypatch, f"m9-D{D}-sh_rows{sh_rows}", mode="bucket", options=dict(sh_rows=sh_rows))
 
 
 @pytest.mark.parametrize("how", ["speculate0", "debug"])
