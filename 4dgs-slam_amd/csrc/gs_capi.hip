@@ -51,6 +51,8 @@
 #include "gs_yolo.h"
 #include "../../include/perceptual.h"
 #include "gs_lpips.h"
+#include "../../include/motion_segmentation.h"
+#include "gs_motion.h"
 
 namespace gsr {
 
@@ -3360,6 +3362,144 @@ int gsr_lpips_distance(int batch, int levels, const int* level_chw, const float*
     hipLaunchKernelGGL(lpips_distance_kernel, dim3((unsigned)L.first[levels]), dim3(LPIPS_BLOCK), 0, stream, L, batch, norm, partial);
     GSR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)batch), dim3(64), 0, stream, L, partial, taps, scores);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_flow_rigid_fit: MotionHead | flags [H, W] bytes | the slab [blocks, 32] doubles; every part starts on a multiple of 16 bytes
+struct MotionFitLayout { size_t head, flags, slab, bytes; unsigned blocks; };
+static bool motion_size_ok(int width, int height)
+{
+    return width >= 1 && height >= 1 && (long long)width * height < 0x80000000LL;
+}
+static bool motion_fit_layout(int width, int height, MotionFitLayout& l)
+{
+    if (!motion_size_ok(width, height)) return false;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n = (size_t)width * height;
+    l.blocks = (unsigned)std::min<size_t>((n + MOTION_BLOCK - 1) / MOTION_BLOCK, MOTION_MAX_BLOCKS);
+    l.head = 0;
+    l.flags = up(sizeof(MotionHead));
+    l.slab = l.flags + up(n);
+    l.bytes = l.slab + up((size_t)l.blocks * MOTION_ROW * sizeof(double));
+    return true;
+}
+
+size_t gsr_flow_rigid_fit_workspace_size(int width, int height)
+{
+    MotionFitLayout l;
+    return motion_fit_layout(width, height, l) ? l.bytes : 0;
+}
+
+int gsr_flow_rigid_fit(int width, int height, float fx, float fy, float cx, float cy, const float* flow_ij, const float* depth_i,
+                       const float* flow_ji, const unsigned char* fit_mask, const float* T_init, int iters, float scale_multiplier,
+                       float c_min, float c_max, float occlusion_px, float residual_px, float* T, float* residual, double* stats,
+                       unsigned char* candidate, double* trace, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_flow_rigid_fit: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    MotionFitLayout l;
+    if (!motion_fit_layout(width, height, l)) return fail("width and height must be positive and width * height below 2^31");
+    if (!(fx > 0.f && fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail("fx and fy must be positive and the intrinsics finite");
+    if (iters < 1 || iters > 64) return fail("iters must be in [1, 64], got " + std::to_string(iters));
+    if (!(scale_multiplier > 0.f) || !(c_min > 0.f) || !(c_max >= c_min) || !std::isfinite(c_max) || !std::isfinite(scale_multiplier))
+        return fail("scale_multiplier must be positive and 0 < c_min <= c_max");
+    if (!(occlusion_px >= 0.f) || !(residual_px >= 0.f)) return fail("occlusion_px and residual_px must not be negative");
+    if (!flow_ij || !depth_i || !T || !residual || !stats || !workspace)
+        return fail("flow_ij, depth_i, T, residual, stats and workspace must not be NULL");
+    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
+        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_flow_rigid_fit_workspace_size), got " +
+                    std::to_string(workspace_bytes));
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = static_cast<char*>(workspace);
+    MotionHead* head = reinterpret_cast<MotionHead*>(ws + l.head);
+    unsigned char* flags = reinterpret_cast<unsigned char*>(ws + l.flags);
+    double* slab = reinterpret_cast<double*>(ws + l.slab);
+    const MotionCam cam{width, height, fx, fy, cx, cy};
+    const size_t n = (size_t)width * height;
+    const unsigned pixel_blocks = (unsigned)((n + MOTION_BLOCK - 1) / MOTION_BLOCK);
+    const float2* f_ij = reinterpret_cast<const float2*>(flow_ij);
+    GSR_HIP_CHECK(hipMemsetAsync(head, 0, l.flags, stream));
+    hipLaunchKernelGGL(motion_prep_kernel, dim3(pixel_blocks), dim3(MOTION_BLOCK), 0, stream, cam, f_ij, depth_i,
+                       reinterpret_cast<const float2*>(flow_ji), fit_mask, T_init, occlusion_px, flags, head);
+    GSR_HIP_CHECK(hipGetLastError());
+    for (int k = 0; k < iters; ++k) {
+        hipLaunchKernelGGL(motion_residual_kernel, dim3(l.blocks), dim3(MOTION_BLOCK), 0, stream, cam, f_ij, depth_i, flags, head, (float*)nullptr);
+        GSR_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(motion_normal_kernel, dim3(l.blocks), dim3(MOTION_BLOCK), 0, stream, cam, f_ij, depth_i, flags, head, scale_multiplier,
+                           c_min, c_max, slab);
+        GSR_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(motion_solve_kernel, dim3(1), dim3(MOTION_BLOCK), 0, stream, (int)l.blocks, slab, head,
+                           trace ? trace + (size_t)k * MOTION_ROW : (double*)nullptr);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(motion_residual_kernel, dim3(l.blocks), dim3(MOTION_BLOCK), 0, stream, cam, f_ij, depth_i, flags, head, residual);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_finish_kernel, dim3(candidate ? pixel_blocks : 1u), dim3(MOTION_BLOCK), 0, stream, (long long)n, head, scale_multiplier,
+                       c_min, c_max, residual_px, flags, residual, T, stats, candidate);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_motion_mask_clean: two byte images [H, W] | parent [H, W] int32 | area [H, W] int32
+struct MotionCleanLayout { size_t a, b, parent, area, bytes; };
+static bool motion_clean_layout(int width, int height, MotionCleanLayout& l)
+{
+    if (!motion_size_ok(width, height)) return false;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n = (size_t)width * height;
+    l.a = 0;
+    l.b = l.a + up(n);
+    l.parent = l.b + up(n);
+    l.area = l.parent + up(n * sizeof(int));
+    l.bytes = l.area + up(n * sizeof(int));
+    return true;
+}
+
+size_t gsr_motion_mask_clean_workspace_size(int width, int height)
+{
+    MotionCleanLayout l;
+    return motion_clean_layout(width, height, l) ? l.bytes : 0;
+}
+
+int gsr_motion_mask_clean(int width, int height, const unsigned char* candidate, int open_radius, int grow_radius, int min_area,
+                          unsigned char* moving, int* labels, int* counts, unsigned char* motion, void* workspace, size_t workspace_bytes,
+                          void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_motion_mask_clean: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    MotionCleanLayout l;
+    if (!motion_clean_layout(width, height, l)) return fail("width and height must be positive and width * height below 2^31");
+    if (open_radius < 0 || open_radius > 8 || grow_radius < 0 || grow_radius > 8)
+        return fail("open_radius and grow_radius must be in [0, 8], got " + std::to_string(open_radius) + " and " + std::to_string(grow_radius));
+    if (min_area < 1) return fail("min_area must be at least 1, got " + std::to_string(min_area));
+    if (!candidate || !moving || !labels || !counts || !workspace) return fail("candidate, moving, labels, counts and workspace must not be NULL");
+    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
+        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_motion_mask_clean_workspace_size), got " +
+                    std::to_string(workspace_bytes));
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = static_cast<char*>(workspace);
+    unsigned char* a = reinterpret_cast<unsigned char*>(ws + l.a);
+    unsigned char* b = reinterpret_cast<unsigned char*>(ws + l.b);
+    int* parent = reinterpret_cast<int*>(ws + l.parent);
+    int* area = reinterpret_cast<int*>(ws + l.area);
+    const long long n = (long long)width * height;
+    const dim3 grid((unsigned)((n + MOTION_BLOCK - 1) / MOTION_BLOCK)), block(MOTION_BLOCK);
+    hipLaunchKernelGGL(motion_morph_kernel, grid, block, 0, stream, width, height, open_radius, 1, candidate, a, (unsigned char*)nullptr, (int*)nullptr);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_morph_kernel, grid, block, 0, stream, width, height, open_radius, 0, (const unsigned char*)a, b, (unsigned char*)nullptr,
+                       (int*)nullptr);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_label_init_kernel, grid, block, 0, stream, width, n, (const unsigned char*)b, parent, area, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_label_merge_kernel, grid, block, 0, stream, width, height, (const unsigned char*)b, parent);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_label_flatten_kernel, grid, block, 0, stream, n, parent, labels);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_label_count_kernel, grid, block, 0, stream, n, (const int*)labels, area, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_label_filter_kernel, grid, block, 0, stream, n, min_area, (const int*)area, labels, a, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(motion_morph_kernel, grid, block, 0, stream, width, height, grow_radius, 0, (const unsigned char*)a, moving, motion, counts + 3);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

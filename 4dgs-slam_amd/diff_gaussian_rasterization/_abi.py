@@ -252,6 +252,11 @@ FUNCTIONS = {
     "gsr_lpips_prepare": (i, [i, i, i, vp, vp, vp, vp]),
     "gsr_lpips_workspace_size": (sz, [i, i, P(i)]),
     "gsr_lpips_distance": (i, [i, i, P(i), P(vp), P(vp), i, vp, vp, vp, vp]),
+    # motion_segmentation.h
+    "gsr_flow_rigid_fit_workspace_size": (sz, [i, i]),
+    "gsr_flow_rigid_fit": (i, [i, i, f, f, f, f] + [vp] * 5 + [i] + [f] * 5 + [vp] * 6 + [sz, vp]),
+    "gsr_motion_mask_clean_workspace_size": (sz, [i, i]),
+    "gsr_motion_mask_clean": (i, [i, i, vp, i, i, i] + [vp] * 5 + [sz, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

@@ -333,6 +333,16 @@ class _Reader:
 
 
 # ---- datasets ----------------------------------------------------------------------------------------------------------------------
+def check_motion_segmenter(motion_segmenter, flow, has_depth):
+    """A flow-and-depth motion segmenter needs both: refuse it, naming what is missing, before anything is read or allocated."""
+    if motion_segmenter is None:
+        return
+    if flow is None:
+        raise ValueError("a motion segmenter needs a flow estimator (flow=): it segments from the optical flow between a frame and its partner")
+    if not has_depth:
+        raise ValueError("a motion segmenter needs sensor depth: a monocular sequence (no depth files) cannot be segmented from flow and depth")
+
+
 class RecordedRGBDDataset:
     """A recorded sequence with the interface of slam/dataset.py's SyntheticRGBDDataset; ``gt_flow`` only with a flow estimator."""
 
@@ -340,7 +350,7 @@ class RecordedRGBDDataset:
     SEG_CACHE_FRAMES = 32          # segmented motion masks kept (0.3 MB each at 640x480): evaluation reads the frames again
 
     def __init__(self, frames, calibration, device="cuda:0", distorted=False, prefetch=4, max_frames=None, flow=None, segmenter=None,
-                 seg_classes=None):
+                 seg_classes=None, motion_segmenter=None):
         import torch
         from .camera import getProjectionMatrix2
         from .pretrained import EventLog
@@ -348,6 +358,7 @@ class RecordedRGBDDataset:
             frames = frames.sliced(0, min(int(max_frames), len(frames)))
         if len(frames) == 0:
             raise ValueError("the sequence has no frames (after Calibration start / end)")
+        check_motion_segmenter(motion_segmenter, flow, not (frames.depth_paths and frames.depth_paths[0] is None))
         self.frames = frames
         self.device = torch.device(device)
         c = calibration
@@ -384,6 +395,7 @@ class RecordedRGBDDataset:
         self.seg_classes = list(seg_classes) if self._segmenter is not None else None
         self._seg_cache = collections.OrderedDict()   # frame -> its motion mask with the instance masks cleared
         self._seg_log = EventLog(self.device)
+        self._motion_segmenter = motion_segmenter     # slam/motion_segmentation.py FlowMotionSegmenter: flow + depth, any class
 
     _decode = staticmethod(frame_decode.decode_frame)     # what the read-ahead thread runs on one entry of _decode_tasks
 
@@ -443,6 +455,31 @@ class RecordedRGBDDataset:
         return {"frames": t["calls"], "classes": self.seg_classes, "ms_per_frame": t["ms_per_item"], "ms_first": t["ms_first"],
                 "ms_rest_mean": t["ms_per_item_rest"]}
 
+    @property
+    def motion_segmentation_stats(self):
+        """Frames segmented from flow and depth, the device ms per frame of the fit and of the cleaning, the mean moving share and the mean
+        final cutoff (None without a motion segmenter). The flow pair each frame needs is counted in flow_stats, not here."""
+        return None if self._motion_segmenter is None else self._motion_segmenter.stats
+
+    def _segment_motion(self, idx, hf, motion):
+        """motion &= ~(what frame idx's flow to its partner frame cannot be explained by one camera motion), in place on the caller's
+        stream. The partner is `gap` frames back, or ahead for the first frames; a one-frame sequence keeps its mask."""
+        import torch
+        gap = self._motion_segmenter.gap
+        j = idx - gap if idx >= gap else min(idx + gap, self.num_imgs - 1)
+        if j == idx:
+            return
+        flow_ij, flow_ji = self._gt_flow(idx, j)[0], self._gt_flow(j, idx)[0]
+        main = torch.cuda.current_stream(self.device)
+        depth_h = torch.from_numpy(np.ascontiguousarray(hf.depth, dtype=np.float32)).pin_memory()
+        with torch.cuda.stream(self._side):
+            depth = depth_h.to(self.device, non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        main.wait_event(ready)
+        depth.record_stream(main)
+        self._motion_segmenter.segment(flow_ij, depth, (self.fx, self.fy, self.cx, self.cy), flow_ji=flow_ji, motion=motion, stream=main)
+
     def _frame_image(self, idx):
         """Frame idx's image [3,H,W] without moving the read-ahead window (a keyframe the flow term needs again); never segmented."""
         if not 0 <= idx < self.num_imgs:
@@ -456,12 +493,14 @@ class RecordedRGBDDataset:
         if not 0 <= idx < self.num_imgs:
             raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
         hf = self._reader.get(idx)
-        if self._segmenter is None:
+        if self._segmenter is None and self._motion_segmenter is None:
             image, motion = self._prepare(hf)
             return image, hf.depth, self.poses[idx].clone(), motion
         hit = self._seg_cache.get(idx)
-        image, motion = self._prepare(hf, segment=hit is None)
+        image, motion = self._prepare(hf, segment=hit is None and self._segmenter is not None)
         if hit is None:
+            if self._motion_segmenter is not None:      # after the file mask and the instance masks: known movers stay out of the fit
+                self._segment_motion(idx, hf, motion)
             self._seg_cache[idx] = motion
             while len(self._seg_cache) > self.SEG_CACHE_FRAMES:
                 self._seg_cache.popitem(last=False)
@@ -499,28 +538,31 @@ class RecordedRGBDDataset:
 class TUMDataset(RecordedRGBDDataset):
     """TUM RGB-D and Bonn (utils/dataset.py:677-696): Dataset.type 'tum'; Bonn calibrations are distorted."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None, motion_segmenter=None):
         from .segmentation import dataset_classes
+        check_motion_segmenter(motion_segmenter, flow, sequence_has_depth(config))
         c = config["Dataset"]["Calibration"]
         frames = tum_frames(config)
         super().__init__(frames, c, device, distorted=bool(c.get("distorted", False)), prefetch=prefetch, max_frames=max_frames, flow=flow,
-                         segmenter=segmenter, seg_classes=dataset_classes("tum", config["Dataset"], bool(frames.mask_paths)))
+                         segmenter=segmenter, seg_classes=dataset_classes("tum", config["Dataset"], bool(frames.mask_paths)),
+                         motion_segmenter=motion_segmenter)
 
 
 class CoFusionDataset(RecordedRGBDDataset):
     """CoFusion (utils/dataset.py:490-660): Dataset.type 'CoFusion'; never undistorted, depth divided in float32."""
 
-    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None, motion_segmenter=None):
         from .segmentation import dataset_classes
         c, d = config["Dataset"]["Calibration"], config["Dataset"]
         has_depth = sequence_has_depth(config)
+        check_motion_segmenter(motion_segmenter, flow, has_depth)
         frames = parse_cofusion(d["dataset_path"], depth=has_depth).sliced(int(c.get("start", 0)), int(c.get("end", -1)))
         if d.get("seg_teddy", False) or d.get("seg_clock", False):           # :545-547, after the slicing
             frames.color_paths = sorted(frames.color_paths, key=extract_number)
             if has_depth:
                 frames.depth_paths = sorted(frames.depth_paths, key=extract_number)
         super().__init__(frames, c, device, distorted=False, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter,
-                         seg_classes=dataset_classes("CoFusion", d, bool(frames.mask_paths)))
+                         seg_classes=dataset_classes("CoFusion", d, bool(frames.mask_paths)), motion_segmenter=motion_segmenter)
 
 
 class EurocDataset(RecordedRGBDDataset):
@@ -609,16 +651,20 @@ class EurocDataset(RecordedRGBDDataset):
 SUPPORTED_TYPES = ("tum", "CoFusion", "euroc")
 
 
-def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None):
+def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None, motion_segmenter=None):
     """utils/dataset.py:962-976 for the recorded types this project reads: 'tum' (TUM, Bonn), 'CoFusion' and 'euroc' (stereo). flow: an optical-flow
     estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None. segmenter: a YOLO instance segmenter
-    (slam/segmentation.py YoloSeg) whose masks of the loader's classes are cleared from the motion masks, or None."""
+    (slam/segmentation.py YoloSeg) whose masks of the loader's classes are cleared from the motion masks, or None. motion_segmenter: a
+    class-agnostic segmenter from flow and depth (slam/motion_segmentation.py FlowMotionSegmenter; needs flow and an RGB-D type), or None."""
     kind = config["Dataset"].get("type")
     if kind == "tum":
-        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
+        return TUMDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter, motion_segmenter=motion_segmenter)
     if kind == "CoFusion":
-        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
+        return CoFusionDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter,
+                               motion_segmenter=motion_segmenter)
     if kind == "euroc":
+        if motion_segmenter is not None:
+            raise ValueError("Dataset.type 'euroc' takes no motion segmenter: segmenting stereo sequences from flow is not supported")
         return EurocDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
     raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn), 'CoFusion' and 'euroc' (stereo)")
 

@@ -8,6 +8,10 @@ dynamic mapping's optical-flow term runs on RAFT's flows (slam/optical_flow.py),
 device ms per pair; --gma-weights PATH (a GMA checkpoint, gma-things.pth and its kind) runs the term on GMA's flows instead (RAFT with global
 motion aggregation, the reference's second estimator), and the `flow` block's `estimator` says which. With --yolo-weights PATH (the reference's pretrained/yolov9e-seg.pt) every frame is segmented as the reference's loaders do
 (slam/segmentation.py), static and dynamic runs alike, and a `segmentation` block reports the frames segmented and the device ms per frame.
+With --flow-masks (needs --dynamic and one of --raft-weights / --gma-weights) every frame's motion mask also loses what its flow to a
+partner frame and its depth cannot explain as one camera motion, whatever its class (slam/motion_segmentation.py), and a
+`motion_segmentation` block reports the frames segmented, the device ms per frame of the fit and of the cleaning, the mean moving share
+and the mean cutoff; the flow pair this adds per frame is the dominant cost and is counted in the `flow` block.
 With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and the LPIPS v0.1 linear layers) the rendering evaluation
 reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair.
 `Dataset.sensor_type: monocular` runs on the images alone (a sequence whose Calibration has no depth_scale is read without depth files; the
@@ -44,11 +48,15 @@ def parse_args(argv=None):
     est.add_argument("--gma-weights", default=None, help="GMA checkpoint (gma-things.pth): the flow term of --dynamic runs, on GMA's flows")
     ap.add_argument("--yolo-weights", default=None, help="YOLO-seg checkpoint (yolov9e-seg.pt): motion masks of people and the "
                                                          "loader's object classes")
+    ap.add_argument("--flow-masks", action="store_true", default=False,
+                    help="segment moving regions of any class from flow and depth (needs --dynamic and --raft-weights or --gma-weights)")
     ap.add_argument("--lpips-weights", nargs=2, default=None, metavar=("ALEXNET", "LIN"),
                     help="torchvision AlexNet state_dict and LPIPS v0.1 linear layers: mean_lpips in the rendering evaluation")
     ap.add_argument("--save-map", nargs="?", const="", default=None, metavar="DIR",
                     help="after the evaluations, save the map for tools/play_map.py (default DIR: <save dir>/map)")
     args = ap.parse_args(argv)
+    if args.flow_masks and not (args.dynamic and (args.raft_weights or args.gma_weights)):
+        ap.error("--flow-masks needs --dynamic and one of --raft-weights / --gma-weights: the masks are segmented from the estimated flow")
     if args.raft_weights and not args.dynamic:
         warnings.warn("--raft-weights only serves the flow term of --dynamic runs; ignored")
         args.raft_weights = None
@@ -99,7 +107,11 @@ def main(argv=None):
     elif args.lpips_weights:
         from slam.perceptual import Lpips
         lpips = Lpips.from_checkpoints(*args.lpips_weights, device="cuda:0")
-    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow, segmenter=segmenter)
+    extra = {}
+    if args.flow_masks:
+        from slam.motion_segmentation import FlowMotionSegmenter
+        extra["motion_segmenter"] = FlowMotionSegmenter(gap=int(config["Training"].get("kf_interval", 5)))
+    ds = load_dataset(config, "cuda:0", prefetch=args.prefetch, max_frames=args.frames, flow=flow, segmenter=segmenter, **extra)
     slam = SLAM(config, ds, save_dir=save_dir, lpips=lpips)
     res = slam.run()
     if args.save_map is not None:
@@ -117,6 +129,8 @@ def main(argv=None):
         res["flow"] = dict(ds.flow_stats, estimator="gma" if args.gma_weights else "raft")
     if segmenter is not None:
         res["segmentation"] = ds.segmentation_stats
+    if args.flow_masks:
+        res["motion_segmentation"] = ds.motion_segmentation_stats
     if lpips is not None:
         res["lpips"] = lpips.stats
     ds.close()
