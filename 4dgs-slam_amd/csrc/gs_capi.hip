@@ -94,6 +94,43 @@ static size_t required(F&& f)
     return reinterpret_cast<size_t>(p) + 256;
 }
 
+// ---- workspaces that only the host carves ------------------------------------------------------------------------------------------
+// One layout function per workspace: it takes the shape arguments and a base and returns typed pointers plus the total bytes. The
+// *_workspace_size entry point runs it on a null base (null pointers, the same offsets), the launching entry point on the caller's pointer;
+// no offset, rounding or slack of such a workspace is written anywhere else. Regions lie in the order they are taken, each starting on a
+// multiple of `unit` bytes from the base. align_base: the entry point accepts any base, the carver rounds it up to `unit` and the size pays
+// one unit for that. Where a layout function returns its struct as a braced list of take() calls, the members' order is the regions' order
+// (a braced list is evaluated left to right). (GeomState / ImageState / carve_binning above are not of this kind: the multi-view kernels
+// carve them on the device.)
+struct Carver {
+    char* base;
+    size_t unit, slack, off = 0;
+    Carver(const void* workspace, size_t unit_, bool align_base = false) : unit(unit_), slack(align_base ? unit_ : 0)
+    {
+        const size_t a = reinterpret_cast<size_t>(workspace);
+        base = reinterpret_cast<char*>(align_base ? up(a) : a);
+    }
+    size_t up(size_t v) const { return (v + unit - 1) & ~(unit - 1); }
+    template <typename T> T* take(size_t count)
+    {
+        off = up(off);
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+    char* nested(size_t bytes) { return take<char>(bytes); }                      // a sub-workspace: another layout function carves it
+    size_t bytes() const { return std::max(off + slack, unit); }                  // the last region ends with its data; never 0
+    size_t bytes_padded() const { return std::max(up(off) + slack, unit); }       // the last region rounded up as well
+};
+// What the entry points that receive the byte count of their workspace ask of it (tests match on the text)
+static bool workspace_fits(const char* who, const char* size_fn, const void* workspace, size_t workspace_bytes, size_t need)
+{
+    if (workspace_bytes >= need && !(reinterpret_cast<size_t>(workspace) & 15)) return true;
+    g_last_error = std::string(who) + ": workspace must be 16-byte aligned and hold " + std::to_string(need) + " bytes (" + size_fn + "), got " +
+                   std::to_string(workspace_bytes);
+    return false;
+}
+
 // ---- per-kernel timing with events on the launch stream ---------------------------------------------------------
 enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"preprocess_fwd", "scan", "scatter_instances", "sort_tiles",
@@ -903,10 +940,16 @@ extern "C" int gsr_forward_views(int V, gsr_view* views, gsr_alloc_fn geometry_a
     return 0;
 }
 
-extern "C" size_t gsr_views_scratch_size(int V, int P, int M, int scale_dim)
+// scratch of gsr_backward_views: per view one row of partial gradients (PartLayout), each row starting on a multiple of 256 bytes
+struct ViewsScratch { float* part; size_t row_floats, bytes; };
+static ViewsScratch views_scratch_layout(int V, int P, int M, int scale_dim, const char* scratch)
 {
-    return (size_t)V * (part_layout((size_t)P, M, scale_dim).total * sizeof(float) + 256) + 256;
+    Carver c(scratch, 256, true);
+    const size_t row_floats = V > 0 && P > 0 ? c.up(part_layout((size_t)P, M, scale_dim).total * sizeof(float)) / sizeof(float) : 0;
+    return {c.take<float>((size_t)std::max(V, 0) * row_floats), row_floats, c.bytes()};
 }
+
+extern "C" size_t gsr_views_scratch_size(int V, int P, int M, int scale_dim) { return views_scratch_layout(V, P, M, scale_dim, nullptr).bytes; }
 
 extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, const float* background, int width, int height, const gsr_raw_inputs* in,
                                   float scale_modifier, float tan_fovx, float tan_fovy, const gsr_raw_grads* out, char* scratch, int debug, void* stream_)
@@ -923,9 +966,7 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
     const ViewDims d = view_dims(P, width, height);
     ViewTable t;
     memset(&t, 0, sizeof(t));
-    const PartLayout L = part_layout((size_t)P, M, in->scale_dim);
-    const size_t row_bytes = (L.total * sizeof(float) + 255) & ~size_t(255);
-    char* sp = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~uintptr_t(255));
+    const ViewsScratch sc = views_scratch_layout(V, P, M, in->scale_dim, scratch);
     int max_R = 0;
     for (int v = 0; v < V; v++) {
         const gsr_view& w = views[v];
@@ -937,7 +978,7 @@ extern "C" int gsr_backward_views(int V, gsr_view* views, int P, int D, int M, c
         fill_view_slot(s, w);
         s.ddx2 = w.ddx2;
         s.dL_dpix = w.dL_dcolor; s.dL_dpix_depth = w.dL_ddepth; s.dL_dmean2D = w.dL_dmean2D; s.ddx = w.ddx; s.dds = w.dds; s.ddr = w.ddr; s.tau_sum = w.dL_dtau_sum;
-        s.part = pose_only ? nullptr : reinterpret_cast<float*>(sp + (size_t)v * row_bytes);
+        s.part = pose_only ? nullptr : sc.part + (size_t)v * sc.row_floats;
         s.cap = (uint32_t)std::max(0, w.num_rendered);
         max_R = std::max(max_R, w.num_rendered);
     }
@@ -1062,19 +1103,6 @@ static void hexplane_launch(const gsr_hexplane_field& f, int64_t n, hipStream_t 
     switch (lpp) { GSR_HEX_CASE(2) GSR_HEX_CASE(4) GSR_HEX_CASE(8) GSR_HEX_CASE(16) }
 #undef GSR_HEX_CASE
 }
-
-// Carves the workspace of the field's sorted backward passes (a member template: outside the C-linkage block). Regions of 256-byte granularity
-// taken in order from the caller's buffer; a null base yields null pointers and the same offsets (size queries).
-struct HexCarver {
-    char* base;
-    size_t off;
-    template <typename T> T* take(size_t count)
-    {
-        char* p = base ? base + off : nullptr;
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return reinterpret_cast<T*>(p);
-    }
-};
 
 extern "C" {
 
@@ -1227,20 +1255,20 @@ int gsr_debug_read_state(int P, int R, int width, int height, const char* geom_b
 // ---- simple_knn.h ---------------------------------------------------------------------------------------------------
 struct KnnWorkspace {
     KnnGrid* grid; uint32_t* cell_of; uint32_t* cell_count; uint32_t* cell_start; uint32_t* cursor; float4* sorted_pts;
-    static KnnWorkspace from(char*& p, size_t P, size_t C)
+    size_t bytes;
+    static KnnWorkspace from(const char* workspace, size_t P, size_t C)
     {
+        Carver c(workspace, 256, true);
         KnnWorkspace w;
-        carve(p, w.grid, 1); carve(p, w.cell_of, P); carve(p, w.cell_count, C); carve(p, w.cell_start, C + 1); carve(p, w.cursor, C);
-        carve(p, w.sorted_pts, P);
+        w.grid = c.take<KnnGrid>(1); w.cell_of = c.take<uint32_t>(P); w.cell_count = c.take<uint32_t>(C); w.cell_start = c.take<uint32_t>(C + 1);
+        w.cursor = c.take<uint32_t>(C); w.sorted_pts = c.take<float4>(P);
+        w.bytes = c.bytes();
         return w;
     }
 };
 static inline size_t knn_max_cells(int P) { return (size_t)(P < 64 ? 64 : P); }
 
-size_t gsr_knn_workspace_size(int P)
-{
-    return required([&](char*& p) { KnnWorkspace::from(p, (size_t)(P > 0 ? P : 1), knn_max_cells(P)); });
-}
+size_t gsr_knn_workspace_size(int P) { return KnnWorkspace::from(nullptr, (size_t)(P > 0 ? P : 1), knn_max_cells(P)).bytes; }
 
 int gsr_knn_mean_dist2(int P, const float* points, float* mean_dists, char* workspace, void* stream_)
 {
@@ -1248,8 +1276,7 @@ int gsr_knn_mean_dist2(int P, const float* points, float* mean_dists, char* work
     if (P < 0 || (P > 0 && (!points || !mean_dists || !workspace))) { g_last_error = "gsr_knn_mean_dist2: null argument"; return GSR_ERR_INVALID_ARGUMENT; }
     if (P == 0) return 0;
     const size_t C = knn_max_cells(P);
-    char* wp = workspace;
-    KnnWorkspace w = KnnWorkspace::from(wp, (size_t)P, C);
+    const KnnWorkspace w = KnnWorkspace::from(workspace, (size_t)P, C);
     ScopedKernelTimer tm(K_KNN, stream);
     GSR_HIP_CHECK(hipMemsetAsync(w.grid, 0xFF, 3 * sizeof(uint32_t), stream));                       // bbox min = ~0
     GSR_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char*>(w.grid) + 12, 0x00, 3 * sizeof(uint32_t), stream));   // bbox max = 0
@@ -1450,11 +1477,17 @@ static inline dim3 ssim_grid(int width, int height, int channels)
 {
     return dim3((width + SSIM_T - 1) / SSIM_T, (height + SSIM_T - 1) / SSIM_T, channels);
 }
-size_t gsr_ssim_workspace_size(int width, int height, int channels)
+// workspace of the SSIM pair: one partial sum per block of the forward launch | the three derivative maps [3, C, H, W] the backward pass reads
+struct SsimWs { int nblocks; float* partials; float* dmaps; size_t bytes; };
+static SsimWs ssim_layout(int width, int height, int channels, const char* workspace)
 {
+    const bool ok = width > 0 && height > 0 && channels > 0;
     const dim3 g = ssim_grid(width, height, channels);
-    return (size_t)g.x * g.y * g.z * sizeof(float) + 256 + (size_t)3 * channels * width * height * sizeof(float);
+    const int nblocks = ok ? (int)(g.x * g.y * g.z) : 0;
+    Carver c(workspace, 256);
+    return {nblocks, c.take<float>((size_t)nblocks), c.take<float>(ok ? (size_t)3 * channels * width * height : 0), c.bytes()};
 }
+size_t gsr_ssim_workspace_size(int width, int height, int channels) { return ssim_layout(width, height, channels, nullptr).bytes; }
 
 int gsr_ssim_forward(int width, int height, int channels, const float* img1, const float* img2, const unsigned char* mask, float* ssim_mean,
                      char* workspace, void* stream_)
@@ -1464,11 +1497,9 @@ int gsr_ssim_forward(int width, int height, int channels, const float* img1, con
         g_last_error = "gsr_ssim_forward: null / invalid argument"; return GSR_ERR_INVALID_ARGUMENT;
     }
     const dim3 g = ssim_grid(width, height, channels);
-    const int nblocks = (int)(g.x * g.y * g.z);
-    float* partials = reinterpret_cast<float*>(workspace);
-    float* dmaps = reinterpret_cast<float*>(workspace + (((size_t)nblocks * sizeof(float) + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(ssim_fwd_kernel, g, dim3(SSIM_T * SSIM_T), 0, stream, width, height, img1, img2, mask, ssim_window(), dmaps, partials);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, nblocks, (const float*)partials,
+    const SsimWs w = ssim_layout(width, height, channels, workspace);
+    hipLaunchKernelGGL(ssim_fwd_kernel, g, dim3(SSIM_T * SSIM_T), 0, stream, width, height, img1, img2, mask, ssim_window(), w.dmaps, w.partials);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, w.nblocks, (const float*)w.partials,
                        1.0f / ((float)channels * (float)width * (float)height), ssim_mean);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1482,8 +1513,7 @@ int gsr_ssim_backward(int width, int height, int channels, const float* img1, co
         g_last_error = "gsr_ssim_backward: null / invalid argument"; return GSR_ERR_INVALID_ARGUMENT;
     }
     const dim3 g = ssim_grid(width, height, channels);
-    const int nblocks = (int)(g.x * g.y * g.z);
-    const float* dmaps = reinterpret_cast<const float*>(workspace + (((size_t)nblocks * sizeof(float) + 255) & ~(size_t)255));
+    const float* dmaps = ssim_layout(width, height, channels, workspace).dmaps;
     hipLaunchKernelGGL(ssim_bwd_kernel, g, dim3(SSIM_T * SSIM_T), 0, stream, width, height, img1, img2, mask, ssim_window(), dmaps, upstream,
                        1.0f / ((float)channels * (float)width * (float)height), dL_dimg1);
     GSR_HIP_CHECK(hipGetLastError());
@@ -1553,7 +1583,7 @@ struct HexBwdWs {
 // The planes the generic walk scatters into: all six, or the three spatial ones of the batched views (their time families keep column sums per view)
 constexpr int HEX_ALL_PLANES = 63, HEX_SPATIAL_PLANES = (1 << 0) | (1 << 1) | (1 << 3);
 
-static void hexsort_carve_head(HexCarver& c, const gsr_hexplane_field& f, int64_t n, HexBwdWs* L)
+static void hexsort_carve_head(Carver& c, const gsr_hexplane_field& f, int64_t n, HexBwdWs* L)
 {
     hexsort_plan(f, &L->P);
     const size_t nb = (size_t)L->P.key_off[6];
@@ -1569,7 +1599,7 @@ static void hexsort_carve_head(HexCarver& c, const gsr_hexplane_field& f, int64_
 
 // Ordered mode (HexOrd): where the fixed-point sums of the planes in `plane_mask` live and, for the V > 0 views of the batched path, the time
 // families' column sums. Closes the carve.
-static void hexord_carve_tail(HexCarver& c, const gsr_hexplane_field& f, int64_t n, int V, int plane_mask, bool ordered, HexBwdWs* L)
+static void hexord_carve_tail(Carver& c, const gsr_hexplane_field& f, int64_t n, int V, int plane_mask, bool ordered, HexBwdWs* L)
 {
     if (ordered) {
         HexOrd& h = L->ord;
@@ -1598,13 +1628,13 @@ static void hexord_carve_tail(HexCarver& c, const gsr_hexplane_field& f, int64_t
         if (V > 0 && h.acc) h.acc_t = h.acc + elems;
         L->ord_bytes = all * sizeof(unsigned long long);
     }
-    L->total = c.off + 256;
+    L->total = c.bytes_padded();
 }
 
 static HexBwdWs hexsort_carve(const gsr_hexplane_field& f, int64_t n, bool ordered, char* base)
 {
     HexBwdWs L{};
-    HexCarver c{base, 0};
+    Carver c(base, 256, true);
     hexsort_carve_head(c, f, n, &L);
     L.ws.gs = c.take<float>((size_t)6 * n * f.num_levels * f.feat_dim);
     hexord_carve_tail(c, f, n, 0, HEX_ALL_PLANES, ordered, &L);
@@ -1750,7 +1780,7 @@ int gsr_hexplane_forward_views(const gsr_hexplane_field* field, int64_t n, const
 static HexBwdWs hexviews_carve(const gsr_hexplane_field& f, int64_t n, int V, bool ordered, char* base)
 {
     HexBwdWs L{};
-    HexCarver c{base, 0};
+    Carver c(base, 256, true);
     hexsort_carve_head(c, f, n, &L);
     const size_t row = (size_t)f.num_levels * f.feat_dim;
     L.vw.gs_sp = c.take<float>((size_t)3 * n * row);
@@ -2092,11 +2122,15 @@ int gsr_dense_backward_input(int M, int N, int K, const float* G, int ldg, const
     return dense_forward_launch("gsr_dense_backward_input", M, N, K, G, ldg, nullptr, 0, planes_t, nullptr, 0, dX, lddx, mask, ldmask, dbias, workspace, stream_);
 }
 
-size_t gsr_dense_chain_workspace_size(int M, int N, int count)
+// workspace of gsr_dense_chain: per product the column sums of its row bands [ceil(M / 32), N], each product's starting on a multiple of 256 bytes
+struct DenseChainWs { float* partial; size_t per_op_floats, bytes; };
+static DenseChainWs dense_chain_layout(int M, int N, int count, const char* workspace)
 {
-    if (M < 1 || N < 1 || count < 1) return 256;
-    return (size_t)count * ((size_t)((M + 31) / 32) * (size_t)N * sizeof(float) + 256) + 256;
+    Carver c(workspace, 256);
+    const size_t per_op_floats = M < 1 || N < 1 || count < 1 ? 0 : c.up((size_t)((M + 31) / 32) * (size_t)N * sizeof(float)) / sizeof(float);
+    return {c.take<float>((size_t)std::max(count, 0) * per_op_floats), per_op_floats, c.bytes()};
 }
+size_t gsr_dense_chain_workspace_size(int M, int N, int count) { return dense_chain_layout(M, N, count, nullptr).bytes; }
 
 int gsr_dense_chain(int M, int N, int count, const gsr_dense_chain_op* ops, char* workspace, void* stream_)
 {
@@ -2121,14 +2155,14 @@ int gsr_dense_chain(int M, int N, int count, const gsr_dense_chain_op* ops, char
     }
     const int bt = dense8_row_tiles(M, 1);
     const unsigned blocks = (unsigned)((M + 16 * bt - 1) / (16 * bt));
-    const size_t per_op = ((size_t)((M + 31) / 32) * (size_t)N * sizeof(float) + 255) & ~size_t(255);
+    const DenseChainWs w = dense_chain_layout(M, N, count, workspace);
     Dense8Chain c;
     c.M = M; c.count = count;
     float* partial[DENSE8_CHAIN_MAX];
     for (int l = 0; l < count; l++) {
         const gsr_dense_chain_op& q = ops[l];
         Dense8Layer& L = c.layer[l];
-        partial[l] = q.dbias ? reinterpret_cast<float*>(workspace + (size_t)l * per_op) : nullptr;
+        partial[l] = q.dbias ? w.partial + (size_t)l * w.per_op_floats : nullptr;
         L.X = q.X; L.gate = nullptr; L.planes = reinterpret_cast<const unsigned short*>(q.planes); L.bias = q.bias; L.Y = q.Y; L.mask = q.mask; L.colsum = partial[l];
         L.N = N; L.K = q.K; L.ldx = q.ldx; L.ldgate = 0; L.Npad = round_up_int(N, DENSE_BN); L.Kpad = round_up_int(q.K, DENSE_BK); L.relu = q.relu ? 1 : 0;
         L.ldy = q.ldy; L.vec = 1; L.ldmask = q.ldmask;
@@ -2181,12 +2215,22 @@ static void dense_wgrad_plan(int M, int N, int K, int* slices, int* rows_per_sli
     *slices = std::max(1, (M + *rows_per_slice - 1) / *rows_per_slice);
 }
 
+// workspace of gsr_dense_wgrad and gsr_dense_wgrad_many: the slices' partial products, `floats` of them, at a base the call aligns to 256 bytes
+struct WgradWs { float* partial; size_t bytes; };
+static WgradWs wgrad_layout(size_t floats, const char* workspace)
+{
+    Carver c(workspace, 256, true);
+    return {c.take<float>(floats), c.bytes()};
+}
+static WgradWs dense_wgrad_layout(int M, int N, int K, int slices, const char* workspace)         // slices: of dense_wgrad_plan
+{
+    return wgrad_layout(M < 1 || N < 1 || K < 1 ? 0 : (size_t)slices * N * K, workspace);
+}
 size_t gsr_dense_wgrad_workspace_size(int M, int N, int K)
 {
-    if (M < 1 || N < 1 || K < 1) return 256;
     int slices, rps;
     dense_wgrad_plan(M, N, K, &slices, &rps);
-    return (size_t)slices * N * K * sizeof(float) + 256;
+    return dense_wgrad_layout(M, N, K, slices, nullptr).bytes;
 }
 
 int gsr_dense_wgrad(int M, int N, int K, const float* G, int ldg, const float* gate, int ldgate, const float* X, int ldx, float* dW, int lddw,
@@ -2199,7 +2243,7 @@ int gsr_dense_wgrad(int M, int N, int K, const float* G, int ldg, const float* g
     if (M == 0) { GSR_HIP_CHECK(hipMemset2DAsync(dW, (size_t)lddw * sizeof(float), 0, (size_t)K * sizeof(float), (size_t)N, stream)); return 0; }
     int slices, rps;
     dense_wgrad_plan(M, N, K, &slices, &rps);
-    float* partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    float* partial = dense_wgrad_layout(M, N, K, slices, workspace).partial;
     const dim3 grid((unsigned)((N + DENSE_BM - 1) / DENSE_BM), (unsigned)((K + DENSE_BN - 1) / DENSE_BN), (unsigned)slices);
     hipLaunchKernelGGL(dense_wgrad_kernel, grid, dim3(DENSE_THREADS), 0, stream, M, N, K, G, ldg, gate, ldgate, X, ldx, rps, partial);
     hipLaunchKernelGGL(dense_wgrad_sum_kernel, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, stream, slices, N * K, (const float*)partial, K, dW, lddw);
@@ -2233,12 +2277,15 @@ static int dense_wgrad_many_plan(int M, int count, const gsr_dense_wgrad_item* i
     return tiles;
 }
 
+static WgradWs dense_wgrad_many_layout(int M, int tiles, int slices, const char* workspace)      // tiles, slices: of dense_wgrad_many_plan
+{
+    return wgrad_layout(tiles < 0 || M < 1 ? 0 : (size_t)slices * tiles * (DENSE_BM * DENSE_BN), workspace);
+}
 size_t gsr_dense_wgrad_many_workspace_size(int M, int count, const gsr_dense_wgrad_item* items)
 {
-    int slices, rps;
+    int slices = 0, rps = 0;
     const int tiles = dense_wgrad_many_plan(M, count, items, nullptr, &slices, &rps);
-    if (tiles < 0 || M < 1) return 256;
-    return (size_t)slices * tiles * (DENSE_BM * DENSE_BN) * sizeof(float) + 256;
+    return dense_wgrad_many_layout(M, tiles, slices, nullptr).bytes;
 }
 
 int gsr_dense_wgrad_many(int M, int count, const gsr_dense_wgrad_item* items, char* workspace, void* stream_)
@@ -2258,7 +2305,7 @@ int gsr_dense_wgrad_many(int M, int count, const gsr_dense_wgrad_item* items, ch
             GSR_HIP_CHECK(hipMemset2DAsync(items[i].dW, (size_t)items[i].lddw * sizeof(float), 0, (size_t)items[i].K * sizeof(float), (size_t)items[i].N, stream));
         return 0;
     }
-    float* partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    float* partial = dense_wgrad_many_layout(M, tiles, slices, workspace).partial;
     hipLaunchKernelGGL(dense_wgrad_many_kernel, dim3((unsigned)tiles, (unsigned)slices), dim3(DENSE_THREADS), 0, stream, M, t, rps, partial);
     hipLaunchKernelGGL(dense_wgrad_many_sum_kernel, dim3((unsigned)tiles, 16), dim3(256), 0, stream, t, slices, (const float*)partial);
     GSR_HIP_CHECK(hipGetLastError());
@@ -2395,47 +2442,49 @@ static size_t node_ws_floats(int64_t n, int32_t m)      // per batch element: bl
     const size_t ordered_route = ((size_t)n * NODE_DET_MAX_K + (size_t)m) * NODE_GRAD;        // per-(Gaussian, k) contributions + the summed row
     return (std::max(atomics_route, ordered_route) + 63) & ~size_t(63);
 }
-static size_t index_csr_ints(int S, int E, int Nv) { return (((size_t)S * ((size_t)E + 2 * (size_t)Nv + 1) + 64) * sizeof(int) + 255) & ~size_t(255); }
 static int index_csr_epad(int E) { return round_up_int(E, CSR_REG_TRIP); }
-static size_t node_ws_shared_bytes(int64_t n, int32_t m)  // once per call (any batch size): the reverse lists of nn_idx (gsr_index_csr's workspace for one set)
-{
-    const int E = (int)std::min<int64_t>(n * NODE_DET_MAX_K, INT32_MAX / 2);
-    return index_csr_ints(1, E, m) + (size_t)index_csr_epad(E > 0 ? E : 1) * sizeof(unsigned short) + 512;
-}
-
-size_t gsr_node_blend_workspace_size(int64_t n, int32_t m)
-{
-    return gsr_node_blend_workspace_size_batch(n, m, 1);
-}
-
-size_t gsr_node_blend_workspace_size_batch(int64_t n, int32_t m, int B)
-{
-    if (m < 1 || B < 1) return 256;
-    return (size_t)B * node_ws_floats(n, m) * sizeof(float) + node_ws_shared_bytes(n, m) + 512;
-}
 
 /* ---- deterministic scatter-add through an index array (include/control_nodes.h) ------------------------------------------------------ */
-size_t gsr_index_csr_workspace_size(int S, int E, int Nv)
+// workspace of gsr_index_csr, read again by gsr_segment_sum: cursor [S] | order [S, E] with seg [S, Nv] {begin, count} right behind it | the
+// sets packed to 16 bits [S, Epad] (small sets only)
+struct IndexCsrWs { int *cursor, *order, *seg; unsigned short* packed; size_t bytes; };
+static IndexCsrWs index_csr_layout(int S, int E, int Nv, const char* workspace)
 {
-    return index_csr_ints(S, E, Nv) + (size_t)S * index_csr_epad(E > 0 ? E : 1) * sizeof(unsigned short) + 512;      // the lists + the set packed to 16 bits
+    const size_t s = (size_t)std::max(S, 0), e = (size_t)std::max(E, 0), nv = (size_t)std::max(Nv, 0);
+    Carver c(workspace, 256, true);
+    int* const cursor = c.take<int>(s), * const order = c.take<int>(s * e + 2 * s * nv);
+    return {cursor, order, order ? order + s * e : nullptr, c.take<unsigned short>(s * (size_t)index_csr_epad(E > 0 ? E : 1)), c.bytes()};
+}
+size_t gsr_index_csr_workspace_size(int S, int E, int Nv) { return index_csr_layout(S, E, Nv, nullptr).bytes; }
+
+// workspace of the blend's backward pass: per batch element the block partials and the summed row | once per call (any batch size) the
+// reverse lists of nn_idx, gsr_index_csr's workspace for one set
+struct NodeBlendWs { float* partial; size_t stride; char* csr; size_t bytes; };
+static NodeBlendWs node_blend_layout(int64_t n, int32_t m, int B, const char* workspace)
+{
+    Carver c(workspace, 256, true);
+    NodeBlendWs w{};
+    if (m >= 1 && B >= 1) {
+        const int E = (int)std::min<int64_t>(n * NODE_DET_MAX_K, INT32_MAX / 2);
+        w.stride = node_ws_floats(n, m);
+        w.partial = c.take<float>((size_t)B * w.stride);
+        w.csr = c.nested(index_csr_layout(1, E, m, nullptr).bytes);
+    }
+    w.bytes = c.bytes();
+    return w;
 }
 
-static void index_csr_carve(char* workspace, int S, int E, int Nv, int*& order, int*& seg, int*& cursor)
-{
-    int* p = reinterpret_cast<int*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-    cursor = p; order = p + ((S + 63) & ~63); seg = order + (size_t)S * E;
-}
+size_t gsr_node_blend_workspace_size(int64_t n, int32_t m) { return node_blend_layout(n, m, 1, nullptr).bytes; }
+size_t gsr_node_blend_workspace_size_batch(int64_t n, int32_t m, int B) { return node_blend_layout(n, m, B, nullptr).bytes; }
 
 int gsr_index_csr(int S, int E, int Nv, const int64_t* idx, char* workspace, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (S < 1 || S > 65535 || E < 0 || Nv < 1 || !workspace || (E > 0 && !idx)) { g_last_error = "gsr_index_csr: invalid argument"; return GSR_ERR_INVALID_ARGUMENT; }
-    int *order, *seg, *cursor;
-    index_csr_carve(workspace, S, E, Nv, order, seg, cursor);
+    const auto [cursor, order, seg, packed, ws_bytes] = index_csr_layout(S, E, Nv, workspace);
     GSR_HIP_CHECK(hipMemsetAsync(cursor, 0, (size_t)S * sizeof(int), stream));
     if (E >= 1 && E <= 20 * CSR_REG_TRIP && Nv < 65535) {          // small sets: packed to 16 bits, a wave holds the whole set in registers
         const int Epad = index_csr_epad(E);
-        unsigned short* packed = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(cursor) + index_csr_ints(S, E, Nv));
         hipLaunchKernelGGL(index_csr_pack_kernel, dim3((unsigned)((Epad + 255) / 256), (unsigned)S), dim3(256), 0, stream, E, Epad, idx, packed);
         const dim3 grid((unsigned)((Nv + 3) / 4), (unsigned)S);
         if (Epad <= 10 * CSR_REG_TRIP) hipLaunchKernelGGL(index_csr_reg_kernel<10>, grid, dim3(256), 0, stream, E, Epad, Nv, (const unsigned short*)packed, order, seg, cursor);
@@ -2514,10 +2563,9 @@ int gsr_segment_sum(int B, int S, int E, int C, int Nv, const float* g, const ch
     hipStream_t stream = (hipStream_t)stream_;
     if (B < 0 || S < 1 || E < 0 || C < 1 || Nv < 1 || !csr_workspace || (B > 0 && (!out || (E > 0 && !g)))) { g_last_error = "gsr_segment_sum: invalid argument"; return GSR_ERR_INVALID_ARGUMENT; }
     if (B == 0) return 0;
-    int *order, *seg, *cursor;
-    index_csr_carve(const_cast<char*>(csr_workspace), S, E, Nv, order, seg, cursor);
+    const IndexCsrWs w = index_csr_layout(S, E, Nv, csr_workspace);
     const size_t total = (size_t)B * Nv * C * SEG_LANES;
-    hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, B, E, C, Nv, g, (size_t)E * C, (const int*)order, (const int*)seg,
+    hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, B, E, C, Nv, g, (size_t)E * C, (const int*)w.order, (const int*)w.seg,
                        set_of_b, out, (size_t)Nv * C);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
@@ -2543,10 +2591,11 @@ int gsr_node_blend_backward_batch(const gsr_node_blend* a, int B, const float* n
         g_last_error = "gsr_node_blend_backward_batch: 1 <= B <= 65535; B > 1 needs node attributes and takes no direct cotangent of nn_weight"; return GSR_ERR_INVALID_ARGUMENT;
     }
     if (!workspace || (a->n > 0 && (!nn_weight || !nn_dist || !nn_idx))) { g_last_error = "gsr_node_blend_backward: null workspace / saved tensors"; return GSR_ERR_INVALID_ARGUMENT; }
-    float* partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    const NodeBlendWs ws = node_blend_layout(a->n, a->m, B, workspace);
+    float* const partial = ws.partial;
     const int total = a->m * NODE_GRAD;
     const bool use_lds = a->m <= NODE_LDS_MAX;
-    const size_t stride = node_ws_floats(a->n, a->m);
+    const size_t stride = ws.stride;
     // K <= 4 (every shipped call): the ordered route -- contributions written per (Gaussian, k), summed per node in the order of the Gaussians
     // (index_csr_kernel + segment_sum_kernel above): bit-reproducible. K > 4: round 3's LDS-atomic accumulation.
     const bool ordered = a->K <= NODE_DET_MAX_K && a->n > 0;
@@ -2555,15 +2604,13 @@ int gsr_node_blend_backward_batch(const gsr_node_blend* a, int B, const float* n
         const int E = (int)(a->n * a->K);
         float* contrib = partial;                                  // [B][E][21], batch stride `stride`
         summed = partial + (size_t)E * NODE_GRAD;
-        char* shared = reinterpret_cast<char*>(partial + (size_t)B * stride);
         hipLaunchKernelGGL(node_blend_bwd_kernel, dim3((unsigned)node_bwd_blocks(a->n), (unsigned)B), dim3(NODE_BLOCK), 0, stream, *a, nn_weight,
                            nn_dist, nn_idx, g_xyz, g_rotation, g_scaling, g_nn_weight, partial, 0, stride, contrib, stride);
-        if (int rc = gsr_index_csr(1, E, a->m, nn_idx, shared, stream_)) return rc;
-        int *order, *seg, *cursor;
-        index_csr_carve(shared, 1, E, a->m, order, seg, cursor);
+        if (int rc = gsr_index_csr(1, E, a->m, nn_idx, ws.csr, stream_)) return rc;
+        const IndexCsrWs csr = index_csr_layout(1, E, a->m, ws.csr);
         const size_t nthreads = (size_t)B * a->m * NODE_GRAD * SEG_LANES;
         hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, B, E, NODE_GRAD, a->m, (const float*)contrib, stride,
-                           (const int*)order, (const int*)seg, (const int*)nullptr, summed, stride);
+                           (const int*)csr.order, (const int*)csr.seg, (const int*)nullptr, summed, stride);
     } else {
         const int G = use_lds ? node_bwd_blocks(a->n) : 1;
         if (!use_lds || a->n == 0) {
@@ -2588,11 +2635,14 @@ int gsr_node_blend_backward_batch(const gsr_node_blend* a, int B, const float* n
 // ---- map maintenance + camera step (include/slam_map.h) -----------------------------------------------------------------------
 extern "C" {
 
-size_t gsr_seed_workspace_size(int n)
+// workspace of gsr_seed_from_rgbd: the mean squared distances [n] | gsr_knn_mean_dist2's workspace
+struct SeedWs { float* dist2; char* knn; size_t bytes; };
+static SeedWs seed_layout(int n, const char* workspace)
 {
-    const size_t N = (size_t)(n > 0 ? n : 1);
-    return gsr_knn_workspace_size(n) + N * sizeof(float) + 512;      // k-NN scratch + the mean squared distances
+    Carver c(workspace, 256, true);
+    return {c.take<float>((size_t)(n > 0 ? n : 1)), c.nested(gsr_knn_workspace_size(n)), c.bytes()};
 }
+size_t gsr_seed_workspace_size(int n) { return seed_layout(n, nullptr).bytes; }
 
 int gsr_seed_from_rgbd(int n, const int* pix, int width, int height, const float* depth, const float* image, const float* exposure_a,
                        const float* exposure_b, float fx, float fy, float cx, float cy, const float* R, const float* T, float point_size,
@@ -2609,11 +2659,9 @@ int gsr_seed_from_rgbd(int n, const int* pix, int width, int height, const float
     }
     hipLaunchKernelGGL(seed_backproject_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, pix, width, height, depth, image, exposure_a,
                        exposure_b, fx, fy, cx, cy, R, T, xyz, features_dc, rotations, logit_opacity);
-    uintptr_t a = (reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255);
-    float* dist2 = reinterpret_cast<float*>(a);
-    char* knn_ws = reinterpret_cast<char*>((a + (size_t)n * sizeof(float) + 255) & ~uintptr_t(255));
-    if (int rc = gsr_knn_mean_dist2(n, xyz, dist2, knn_ws, stream_)) return rc;
-    hipLaunchKernelGGL(seed_scales_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const float*)dist2, point_size, scale_dim, log_scales);
+    const SeedWs w = seed_layout(n, workspace);
+    if (int rc = gsr_knn_mean_dist2(n, xyz, w.dist2, w.knn, stream_)) return rc;
+    hipLaunchKernelGGL(seed_scales_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const float*)w.dist2, point_size, scale_dim, log_scales);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -2688,12 +2736,16 @@ int gsr_camera_step_launch(const gsr_camera_step* s, void* stream_)
     return 0;
 }
 
-size_t gsr_track_workspace_size(int width, int height)
+// workspace of gsr_track_step, packed floats (include/slam_map.h): dL/dimage [3, N] | dL/ddepth [N] | the exposure gradient's partials [T, 2] |
+// the pose gradient {trans, rot} [6] | the exposure gradient [2]
+struct TrackWs { float *g_image, *g_depth, *partials, *tau6, *g_exp; size_t bytes; };
+static TrackWs track_layout(int width, int height, const char* workspace)
 {
-    if (width <= 0 || height <= 0) return 0;
     const size_t N = (size_t)width * height, T = (size_t)((width + TILE_X - 1) / TILE_X) * ((height + TILE_Y - 1) / TILE_Y);
-    return (4 * N + 2 * T + 8) * sizeof(float);
+    Carver c(workspace, sizeof(float));
+    return {c.take<float>(3 * N), c.take<float>(N), c.take<float>(2 * T), c.take<float>(6), c.take<float>(2), c.bytes()};
 }
+size_t gsr_track_workspace_size(int width, int height) { return width > 0 && height > 0 ? track_layout(width, height, nullptr).bytes : 0; }
 
 int gsr_track_step(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_fn binning_alloc, void* binning_user, gsr_alloc_fn image_alloc,
                    void* image_user, int P, int D, int M, const float* background, int width, int height, const gsr_raw_inputs* in,
@@ -2707,9 +2759,8 @@ int gsr_track_step(gsr_alloc_fn geometry_alloc, void* geometry_user, gsr_alloc_f
         g_last_error = "gsr_track_step: null / invalid argument (P > 0; loss targets, pose deltas, full_proj, campos, a 16-byte aligned workspace of gsr_track_workspace_size bytes)";
         return GSR_ERR_INVALID_ARGUMENT;
     }
-    const size_t N = (size_t)width * height, T = (size_t)((width + TILE_X - 1) / TILE_X) * ((height + TILE_Y - 1) / TILE_Y);
-    float* const ws = reinterpret_cast<float*>(workspace);
-    float* const g_image = ws, * const g_depth = ws + 3 * N, * const partials = ws + 4 * N, * const tau6 = partials + 2 * T, * const g_exp = tau6 + 6;
+    const size_t N = (size_t)width * height;
+    const auto [g_image, g_depth, partials, tau6, g_exp, ws_bytes] = track_layout(width, height, workspace);
     gsr_camera_step st = *step;                   // which tensors are stepped: the pose always, the exposure pair when it is given
     st.g_rot_delta = tau6 + 3; st.g_trans_delta = tau6;
     st.g_exposure_a = st.exposure_a ? g_exp : nullptr; st.g_exposure_b = st.exposure_b ? g_exp + 1 : nullptr;
@@ -2800,10 +2851,17 @@ int gsr_edge_mask(const float* image, int height, int width, float edge_threshol
     return 0;
 }
 
-size_t gsr_mono_keyframe_depth_workspace_size(int height, int width)
+// workspace of gsr_mono_keyframe_depth (the byte offsets: gs_map.h): the select's state, 260 words | {n_valid, the select's output} |
+// 64 x {s1, s2} doubles | the keys [n]
+struct MonoWs { uint32_t* state; uint32_t* n_valid; float* median; double* partial; uint32_t* keys; size_t bytes; };
+static MonoWs mono_layout(int height, int width, const char* workspace)
 {
-    return height > 0 && width > 0 ? MONO_WS_KEYS + (size_t)height * (size_t)width * sizeof(uint32_t) : MONO_WS_KEYS;
+    Carver c(workspace, 16);
+    uint32_t* const state = c.take<uint32_t>(260), * const n_valid = c.take<uint32_t>(2);
+    return {state, n_valid, reinterpret_cast<float*>(n_valid ? n_valid + 1 : nullptr), c.take<double>(2 * SELECT_BLOCKS),
+            c.take<uint32_t>(height > 0 && width > 0 ? (size_t)height * (size_t)width : 0), c.bytes()};
 }
+size_t gsr_mono_keyframe_depth_workspace_size(int height, int width) { return mono_layout(height, width, nullptr).bytes; }
 
 int gsr_mono_keyframe_depth(const float* depth, const float* opacity, const float* gt_image, int height, int width, float rgb_boundary_threshold,
                             const float* noise, float* out, float* stats, char* workspace, void* stream_)
@@ -2814,13 +2872,9 @@ int gsr_mono_keyframe_depth(const float* depth, const float* opacity, const floa
     if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) { g_last_error = "gsr_mono_keyframe_depth: the workspace must be 16-byte aligned"; return GSR_ERR_INVALID_ARGUMENT; }
     hipStream_t stream = (hipStream_t)stream_;
     const int n = height * width;
-    uint32_t* state = reinterpret_cast<uint32_t*>(workspace);
-    uint32_t* n_valid = reinterpret_cast<uint32_t*>(workspace + MONO_WS_COUNT);
-    float* median = reinterpret_cast<float*>(workspace + MONO_WS_MEDIAN);
-    double* partial = reinterpret_cast<double*>(workspace + MONO_WS_PARTIAL);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(workspace + MONO_WS_KEYS);
+    const auto [state, n_valid, median, partial, keys, ws_bytes] = mono_layout(height, width, workspace);
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    GSR_HIP_CHECK(hipMemsetAsync(workspace, 0, MONO_WS_PARTIAL, stream));            // select state, n_valid, the select's output
+    GSR_HIP_CHECK(hipMemsetAsync(workspace, 0, reinterpret_cast<char*>(partial) - workspace, stream));   // select state, n_valid, the select's output
     hipLaunchKernelGGL(mono_keys_kernel, dim3(blocks), dim3(256), 0, stream, depth, opacity, gt_image, n, rgb_boundary_threshold, keys, n_valid);
     for (int shift = 24; shift >= 0; shift -= 8)
         hipLaunchKernelGGL(radix_select_counted_pass_kernel, dim3(SELECT_BLOCKS), dim3(1024), 0, stream, reinterpret_cast<const float*>(keys), n,
@@ -2959,34 +3013,30 @@ int gsr_frame_export(int views, int width, int height, const float* colour, int6
 
 // workspace of gsr_jpeg_encode: coefficients [V, blocks, 64] int16 | bit lengths, then offsets [V, blocks] u32 | total bits [V] u32 | the bit
 // buffers [V, raw_words] u32; every part starts on a multiple of 16 bytes
-struct JpegLayout { JpegShape shape; size_t coef, lengths, totals, raw, bytes; };
-static bool jpeg_layout(int views, int width, int height, JpegLayout& l)
+struct JpegLayout { JpegShape shape; short* coef; uint32_t *lengths, *totals, *raw; size_t bytes; };
+static bool jpeg_layout(int views, int width, int height, const void* workspace, JpegLayout& l)
 {
     if (views <= 0 || views > 65535 || width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
     const long long cols = (width + 15) / 16, rows = (height + 15) / 16, blocks = cols * rows * 6;
     if (blocks > 1290000) return false;                              // blocks * 1664 bits stay below 2^31
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     l.shape.W = width; l.shape.H = height; l.shape.mcu_cols = (int)cols; l.shape.blocks = (int)blocks;
     l.shape.raw_words = (size_t)blocks * JPEG_BLOCK_WORDS + JPEG_TAIL_WORDS;
-    l.coef = 0;
-    l.lengths = l.coef + up((size_t)views * blocks * 64 * sizeof(short));
-    l.totals = l.lengths + up((size_t)views * blocks * sizeof(uint32_t));
-    l.raw = l.totals + up((size_t)views * sizeof(uint32_t));
-    l.bytes = l.raw + (size_t)views * l.shape.raw_words * sizeof(uint32_t);
+    Carver c(workspace, 16);
+    l.coef = c.take<short>((size_t)views * blocks * 64);
+    l.lengths = c.take<uint32_t>((size_t)views * blocks);
+    l.totals = c.take<uint32_t>((size_t)views);
+    l.raw = c.take<uint32_t>((size_t)views * l.shape.raw_words);
+    l.bytes = c.bytes();
     return true;
 }
 
-size_t gsr_jpeg_workspace_size(int views, int width, int height)
-{
-    JpegLayout l;
-    return jpeg_layout(views, width, height, l) ? l.bytes : 0;
-}
+size_t gsr_jpeg_workspace_size(int views, int width, int height) { JpegLayout l; return jpeg_layout(views, width, height, nullptr, l) ? l.bytes : 0; }
 
 int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8, const unsigned short* qtables, unsigned char* scan,
                     int64_t scan_stride, int* sizes, short* coefficients, void* workspace, size_t workspace_bytes, void* stream_)
 {
     JpegLayout l;
-    if (!jpeg_layout(views, width, height, l)) {
+    if (!jpeg_layout(views, width, height, workspace, l)) {
         g_last_error = "gsr_jpeg_encode: views, width and height must be in [1, 65535], with at most 1290000 8x8 blocks per view";
         return GSR_ERR_INVALID_ARGUMENT;
     }
@@ -2995,17 +3045,10 @@ int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8,
         return GSR_ERR_INVALID_ARGUMENT;
     }
     if (scan_stride <= 0) { g_last_error = "gsr_jpeg_encode: scan_stride must be positive"; return GSR_ERR_INVALID_ARGUMENT; }
-    if (workspace_bytes < l.bytes || ((size_t)workspace & 15)) {
-        g_last_error = "gsr_jpeg_encode: workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_jpeg_workspace_size), got " +
-                       std::to_string(workspace_bytes);
-        return GSR_ERR_INVALID_ARGUMENT;
-    }
+    if (!workspace_fits("gsr_jpeg_encode", "gsr_jpeg_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
     hipStream_t stream = (hipStream_t)stream_;
-    char* ws = static_cast<char*>(workspace);
-    short* coef = reinterpret_cast<short*>(ws + l.coef);
-    uint32_t* lengths = reinterpret_cast<uint32_t*>(ws + l.lengths);
-    uint32_t* totals = reinterpret_cast<uint32_t*>(ws + l.totals);
-    uint32_t* raw = reinterpret_cast<uint32_t*>(ws + l.raw);
+    short* const coef = l.coef;
+    uint32_t* const lengths = l.lengths, * const totals = l.totals, * const raw = l.raw;
     const dim3 per_block((unsigned)((l.shape.blocks + JPEG_WAVES - 1) / JPEG_WAVES), (unsigned)views);
     hipLaunchKernelGGL(jpeg_transform_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, rgb8, qtables, coef, coefficients, lengths, raw);
     GSR_HIP_CHECK(hipGetLastError());
@@ -3020,24 +3063,20 @@ int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8,
 
 // workspace of gsr_stereo_depth: census codes of the left and of the right image [H, W] u64 | S [H, W, D] u16 (unused when the caller
 // gives cost_sum); every part starts on a multiple of 16 bytes
-struct StereoLayout { size_t code_l, code_r, cost, bytes; };
-static bool stereo_layout(int width, int height, int D, StereoLayout& l)
+struct StereoLayout { uint64_t *code_l, *code_r; unsigned short* cost; size_t bytes; };
+static bool stereo_layout(int width, int height, int D, const void* workspace, StereoLayout& l)
 {
     if (width < 1 || height < 1 || (D != 64 && D != 128) || (long long)width * height * D > 0x7fffffffLL) return false;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t n = (size_t)width * height;
-    l.code_l = 0;
-    l.code_r = l.code_l + up(n * sizeof(uint64_t));
-    l.cost = l.code_r + up(n * sizeof(uint64_t));
-    l.bytes = l.cost + up(n * D * sizeof(unsigned short));
+    Carver c(workspace, 16);
+    l.code_l = c.take<uint64_t>(n);
+    l.code_r = c.take<uint64_t>(n);
+    l.cost = c.take<unsigned short>(n * D);
+    l.bytes = c.bytes_padded();
     return true;
 }
 
-size_t gsr_stereo_workspace_size(int width, int height, int num_disparities)
-{
-    StereoLayout l;
-    return stereo_layout(width, height, num_disparities, l) ? l.bytes : 0;
-}
+size_t gsr_stereo_workspace_size(int width, int height, int D) { StereoLayout l; return stereo_layout(width, height, D, nullptr, l) ? l.bytes : 0; }
 
 int gsr_stereo_depth(int width, int height, int num_disparities, int p1, int p2, int uniqueness_ratio, int disp12_max_diff, float bf,
                      const unsigned char* left_raw, const unsigned char* right_raw, const float* map_left, const float* map_right,
@@ -3046,7 +3085,7 @@ int gsr_stereo_depth(int width, int height, int num_disparities, int p1, int p2,
 {
     auto fail = [&](const std::string& what) { g_last_error = "gsr_stereo_depth: " + what; return GSR_ERR_INVALID_ARGUMENT; };
     StereoLayout l;
-    if (!stereo_layout(width, height, num_disparities, l))
+    if (!stereo_layout(width, height, num_disparities, workspace, l))
         return fail("width and height must be positive, num_disparities 64 or 128 (got " + std::to_string(num_disparities) +
                     ") and width * height * num_disparities below 2^31");
     if (!(p1 > 0 && p1 < p2 && p2 <= 2047)) return fail("the penalties must satisfy 0 < p1 < p2 <= 2047, got p1 " + std::to_string(p1) + ", p2 " + std::to_string(p2));
@@ -3056,15 +3095,11 @@ int gsr_stereo_depth(int width, int height, int num_disparities, int p1, int p2,
     if ((map_left != nullptr) != (map_right != nullptr)) return fail("map_left and map_right go together: both or neither");
     if (map_left && (!left_rect || !right_rect)) return fail("left_rect and right_rect must not be NULL when maps are given");
     if (image && !lut) return fail("image needs lut");
-    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
-        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_stereo_workspace_size), got " +
-                    std::to_string(workspace_bytes));
+    if (!workspace_fits("gsr_stereo_depth", "gsr_stereo_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
     if ((num_disparities == 128 && cost_sum && ((size_t)cost_sum & 3))) return fail("cost_sum must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    char* ws = static_cast<char*>(workspace);
-    uint64_t* code_l = reinterpret_cast<uint64_t*>(ws + l.code_l);
-    uint64_t* code_r = reinterpret_cast<uint64_t*>(ws + l.code_r);
-    unsigned short* S = cost_sum ? cost_sum : reinterpret_cast<unsigned short*>(ws + l.cost);
+    uint64_t* const code_l = l.code_l, * const code_r = l.code_r;
+    unsigned short* S = cost_sum ? cost_sum : l.cost;
     const size_t n = (size_t)width * height;
     const unsigned pixel_blocks = (unsigned)((n + STEREO_BLOCK - 1) / STEREO_BLOCK);
     if (map_left || left_rect || right_rect || image) {
@@ -3205,15 +3240,15 @@ int gsr_gma_aggregate(int batch, int dim, int h, int w, const float* attn, const
     return 0;
 }
 
-static size_t yolo_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// workspace: score [A] | cls [A] | box float4 [A] | order [A] | obox float4 [A] | n | mask u64 [A, words]
-size_t gsr_yolo_workspace_size(int anchors)
+// workspace of gsr_yolo_detect: score [A] | cls [A] | box float4 [A] | order [A] | obox float4 [A] | n | mask u64 [A, words]
+struct YoloWs { float* score; int* cls; float4* box; int* order; float4* obox; int* n; unsigned long long* mask; size_t bytes; };
+static YoloWs yolo_layout(size_t A, const void* workspace)
 {
-    if (anchors <= 0 || anchors > YOLO_MAX_ANCHORS) return 0;
-    const size_t A = (size_t)anchors, words = (A + 63) / 64;
-    return yolo_align(A * 4) * 2 + yolo_align(A * 16) * 2 + yolo_align(A * 4) + yolo_align(4) + A * words * 8;
+    Carver c(workspace, 256);
+    return {c.take<float>(A), c.take<int>(A), c.take<float4>(A), c.take<int>(A), c.take<float4>(A), c.take<int>(1),
+            c.take<unsigned long long>(A * ((A + 63) / 64)), c.bytes()};
 }
+size_t gsr_yolo_workspace_size(int anchors) { return anchors > 0 && anchors <= YOLO_MAX_ANCHORS ? yolo_layout((size_t)anchors, nullptr).bytes : 0; }
 
 int gsr_yolo_detect(int levels, const int* level_hw, const float* level_stride, const float* const* head, const float* const* coef, int nc,
                     int nm, const int* classes, int n_classes, float conf, float iou, int max_det, void* workspace, float* dets, int max_dets,
@@ -3255,14 +3290,7 @@ int gsr_yolo_detect(int levels, const int* level_hw, const float* level_stride, 
         cs.bits[classes[k] >> 5] |= 1u << (classes[k] & 31);
     }
     const int words = (int)((A + 63) / 64);
-    char* ws = (char*)workspace;
-    float* score = (float*)ws;                     ws += yolo_align(A * 4);
-    int* cls = (int*)ws;                           ws += yolo_align(A * 4);
-    float4* box = (float4*)ws;                     ws += yolo_align(A * 16);
-    int* order = (int*)ws;                         ws += yolo_align(A * 4);
-    float4* obox = (float4*)ws;                    ws += yolo_align(A * 16);
-    int* n = (int*)ws;                             ws += yolo_align(4);
-    unsigned long long* mask = (unsigned long long*)ws;
+    const auto [score, cls, box, order, obox, n, mask, ws_bytes] = yolo_layout((size_t)A, workspace);
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(yolo_decode_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, stream, L, (int)A, nc, cs, conf, score, cls, box);
     GSR_HIP_CHECK(hipGetLastError());
@@ -3367,29 +3395,25 @@ int gsr_lpips_distance(int batch, int levels, const int* level_chw, const float*
 }
 
 // workspace of gsr_flow_rigid_fit: MotionHead | flags [H, W] bytes | the slab [blocks, 32] doubles; every part starts on a multiple of 16 bytes
-struct MotionFitLayout { size_t head, flags, slab, bytes; unsigned blocks; };
+struct MotionFitLayout { MotionHead* head; unsigned char* flags; double* slab; size_t bytes; unsigned blocks; };
 static bool motion_size_ok(int width, int height)
 {
     return width >= 1 && height >= 1 && (long long)width * height < 0x80000000LL;
 }
-static bool motion_fit_layout(int width, int height, MotionFitLayout& l)
+static bool motion_fit_layout(int width, int height, const void* workspace, MotionFitLayout& l)
 {
     if (!motion_size_ok(width, height)) return false;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t n = (size_t)width * height;
     l.blocks = (unsigned)std::min<size_t>((n + MOTION_BLOCK - 1) / MOTION_BLOCK, MOTION_MAX_BLOCKS);
-    l.head = 0;
-    l.flags = up(sizeof(MotionHead));
-    l.slab = l.flags + up(n);
-    l.bytes = l.slab + up((size_t)l.blocks * MOTION_ROW * sizeof(double));
+    Carver c(workspace, 16);
+    l.head = c.take<MotionHead>(1);
+    l.flags = c.take<unsigned char>(n);
+    l.slab = c.take<double>((size_t)l.blocks * MOTION_ROW);
+    l.bytes = c.bytes_padded();
     return true;
 }
 
-size_t gsr_flow_rigid_fit_workspace_size(int width, int height)
-{
-    MotionFitLayout l;
-    return motion_fit_layout(width, height, l) ? l.bytes : 0;
-}
+size_t gsr_flow_rigid_fit_workspace_size(int width, int height) { MotionFitLayout l; return motion_fit_layout(width, height, nullptr, l) ? l.bytes : 0; }
 
 int gsr_flow_rigid_fit(int width, int height, float fx, float fy, float cx, float cy, const float* flow_ij, const float* depth_i,
                        const float* flow_ji, const unsigned char* fit_mask, const float* T_init, int iters, float scale_multiplier,
@@ -3398,7 +3422,7 @@ int gsr_flow_rigid_fit(int width, int height, float fx, float fy, float cx, floa
 {
     auto fail = [&](const std::string& what) { g_last_error = "gsr_flow_rigid_fit: " + what; return GSR_ERR_INVALID_ARGUMENT; };
     MotionFitLayout l;
-    if (!motion_fit_layout(width, height, l)) return fail("width and height must be positive and width * height below 2^31");
+    if (!motion_fit_layout(width, height, workspace, l)) return fail("width and height must be positive and width * height below 2^31");
     if (!(fx > 0.f && fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
         return fail("fx and fy must be positive and the intrinsics finite");
     if (iters < 1 || iters > 64) return fail("iters must be in [1, 64], got " + std::to_string(iters));
@@ -3407,19 +3431,16 @@ int gsr_flow_rigid_fit(int width, int height, float fx, float fy, float cx, floa
     if (!(occlusion_px >= 0.f) || !(residual_px >= 0.f)) return fail("occlusion_px and residual_px must not be negative");
     if (!flow_ij || !depth_i || !T || !residual || !stats || !workspace)
         return fail("flow_ij, depth_i, T, residual, stats and workspace must not be NULL");
-    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
-        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_flow_rigid_fit_workspace_size), got " +
-                    std::to_string(workspace_bytes));
+    if (!workspace_fits("gsr_flow_rigid_fit", "gsr_flow_rigid_fit_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
     hipStream_t stream = (hipStream_t)stream_;
-    char* ws = static_cast<char*>(workspace);
-    MotionHead* head = reinterpret_cast<MotionHead*>(ws + l.head);
-    unsigned char* flags = reinterpret_cast<unsigned char*>(ws + l.flags);
-    double* slab = reinterpret_cast<double*>(ws + l.slab);
+    MotionHead* const head = l.head;
+    unsigned char* const flags = l.flags;
+    double* const slab = l.slab;
     const MotionCam cam{width, height, fx, fy, cx, cy};
     const size_t n = (size_t)width * height;
     const unsigned pixel_blocks = (unsigned)((n + MOTION_BLOCK - 1) / MOTION_BLOCK);
     const float2* f_ij = reinterpret_cast<const float2*>(flow_ij);
-    GSR_HIP_CHECK(hipMemsetAsync(head, 0, l.flags, stream));
+    GSR_HIP_CHECK(hipMemsetAsync(head, 0, flags - reinterpret_cast<unsigned char*>(head), stream));
     hipLaunchKernelGGL(motion_prep_kernel, dim3(pixel_blocks), dim3(MOTION_BLOCK), 0, stream, cam, f_ij, depth_i,
                        reinterpret_cast<const float2*>(flow_ji), fit_mask, T_init, occlusion_px, flags, head);
     GSR_HIP_CHECK(hipGetLastError());
@@ -3442,25 +3463,21 @@ int gsr_flow_rigid_fit(int width, int height, float fx, float fy, float cx, floa
 }
 
 // workspace of gsr_motion_mask_clean: two byte images [H, W] | parent [H, W] int32 | area [H, W] int32
-struct MotionCleanLayout { size_t a, b, parent, area, bytes; };
-static bool motion_clean_layout(int width, int height, MotionCleanLayout& l)
+struct MotionCleanLayout { unsigned char *a, *b; int *parent, *area; size_t bytes; };
+static bool motion_clean_layout(int width, int height, const void* workspace, MotionCleanLayout& l)
 {
     if (!motion_size_ok(width, height)) return false;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t n = (size_t)width * height;
-    l.a = 0;
-    l.b = l.a + up(n);
-    l.parent = l.b + up(n);
-    l.area = l.parent + up(n * sizeof(int));
-    l.bytes = l.area + up(n * sizeof(int));
+    Carver c(workspace, 16);
+    l.a = c.take<unsigned char>(n);
+    l.b = c.take<unsigned char>(n);
+    l.parent = c.take<int>(n);
+    l.area = c.take<int>(n);
+    l.bytes = c.bytes_padded();
     return true;
 }
 
-size_t gsr_motion_mask_clean_workspace_size(int width, int height)
-{
-    MotionCleanLayout l;
-    return motion_clean_layout(width, height, l) ? l.bytes : 0;
-}
+size_t gsr_motion_mask_clean_workspace_size(int width, int height) { MotionCleanLayout l; return motion_clean_layout(width, height, nullptr, l) ? l.bytes : 0; }
 
 int gsr_motion_mask_clean(int width, int height, const unsigned char* candidate, int open_radius, int grow_radius, int min_area,
                           unsigned char* moving, int* labels, int* counts, unsigned char* motion, void* workspace, size_t workspace_bytes,
@@ -3468,20 +3485,15 @@ int gsr_motion_mask_clean(int width, int height, const unsigned char* candidate,
 {
     auto fail = [&](const std::string& what) { g_last_error = "gsr_motion_mask_clean: " + what; return GSR_ERR_INVALID_ARGUMENT; };
     MotionCleanLayout l;
-    if (!motion_clean_layout(width, height, l)) return fail("width and height must be positive and width * height below 2^31");
+    if (!motion_clean_layout(width, height, workspace, l)) return fail("width and height must be positive and width * height below 2^31");
     if (open_radius < 0 || open_radius > 8 || grow_radius < 0 || grow_radius > 8)
         return fail("open_radius and grow_radius must be in [0, 8], got " + std::to_string(open_radius) + " and " + std::to_string(grow_radius));
     if (min_area < 1) return fail("min_area must be at least 1, got " + std::to_string(min_area));
     if (!candidate || !moving || !labels || !counts || !workspace) return fail("candidate, moving, labels, counts and workspace must not be NULL");
-    if (workspace_bytes < l.bytes || ((size_t)workspace & 15))
-        return fail("workspace must be 16-byte aligned and hold " + std::to_string(l.bytes) + " bytes (gsr_motion_mask_clean_workspace_size), got " +
-                    std::to_string(workspace_bytes));
+    if (!workspace_fits("gsr_motion_mask_clean", "gsr_motion_mask_clean_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
     hipStream_t stream = (hipStream_t)stream_;
-    char* ws = static_cast<char*>(workspace);
-    unsigned char* a = reinterpret_cast<unsigned char*>(ws + l.a);
-    unsigned char* b = reinterpret_cast<unsigned char*>(ws + l.b);
-    int* parent = reinterpret_cast<int*>(ws + l.parent);
-    int* area = reinterpret_cast<int*>(ws + l.area);
+    unsigned char* const a = l.a, * const b = l.b;
+    int* const parent = l.parent, * const area = l.area;
     const long long n = (long long)width * height;
     const dim3 grid((unsigned)((n + MOTION_BLOCK - 1) / MOTION_BLOCK)), block(MOTION_BLOCK);
     hipLaunchKernelGGL(motion_morph_kernel, grid, block, 0, stream, width, height, open_radius, 1, candidate, a, (unsigned char*)nullptr, (int*)nullptr);

@@ -482,8 +482,7 @@ __global__ void __launch_bounds__(1024) radix_select_pass_kernel(const float* __
 //   (4) mono_depth_kernel      the unbiased std from the 64 partial pairs in a fixed order (shifted by the median the difference of the two
 //                              sums does not cancel; a constant depth gives exactly 0), then the per-pixel rule and the stats block
 // workspace (bytes): [0, 1040) select state, 260 words | [1040] n_valid | [1044] the select's output | [1056, 2080) 64 x {s1, s2} doubles |
-// [2080, + 4 n) keys.
-constexpr size_t MONO_WS_COUNT = 1040, MONO_WS_MEDIAN = 1044, MONO_WS_PARTIAL = 1056, MONO_WS_KEYS = 2080;
+// [2080, + 4 n) keys (carved by mono_layout, gs_capi.hip).
 
 __global__ void __launch_bounds__(1024) radix_select_counted_pass_kernel(const float* __restrict__ x, int n, const uint32_t* __restrict__ n_selected,
                                                                          int shift, uint32_t* __restrict__ state, float* __restrict__ out)

@@ -48,8 +48,13 @@ def binding() -> str:
     return "native" if _glue is not None else "ctypes"
 
 
+def stream_handle(stream, device) -> int:
+    """The HIP stream a C entry point takes: of `stream` (a torch stream), or of the current stream of `device` when it is None."""
+    return (stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream
+
+
 def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
+    return stream_handle(None, dev)
 
 
 def load_library():
@@ -109,13 +114,32 @@ def _require_device(t: torch.Tensor, name: str):
         )
 
 
-def dev_f32(t, name, shape=None):
-    """Device pointer of a contiguous float32 device tensor, of the given shape if any (no copy: anything else is rejected)."""
+F32 = (torch.float32,)
+
+
+def dev_ptr(t, name, dtypes, shape=None):
+    """Device pointer of an operand of a C entry point: a contiguous device tensor of one of `dtypes` and, if given, of `shape`; None for
+    None. No copy: anything else is rejected."""
+    if t is None:
+        return None
     _require_device(t, name)
-    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise RuntimeError(f"{name} must be a contiguous float32 device tensor" + (f" of shape {tuple(shape)}" if shape else "") +
-                           f", got {t.dtype} {tuple(t.shape)}")
+    if t.dtype not in dtypes or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        # (callers and tests know both spellings of the text: "contiguous float32 ..." and "contiguous torch.uint8 ...")
+        raise RuntimeError(f"{name} must be a contiguous {' or '.join('float32' if d is torch.float32 else str(d) for d in dtypes)} device tensor" +
+                           (f" of shape {tuple(shape)}" if shape is not None else "") + f", got {t.dtype} {tuple(t.shape)}")
     return t.data_ptr()
+
+
+def workspace(ws, need, device, name="workspace"):
+    """The workspace of a C entry point that needs `need` bytes (its *_workspace_size): allocated on `device` when `ws` is None, otherwise
+    `ws` itself, which must be a contiguous one-dimensional uint8 device tensor of at least `need` bytes. (The library checks the alignment of
+    its base.)"""
+    if ws is None:
+        return torch.empty(int(need), dtype=torch.uint8, device=device)
+    _require_device(ws, name)
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"{name} must be a contiguous uint8 device tensor of at least {need} bytes, got {ws.dtype} {tuple(ws.shape)}")
+    return ws
 
 
 def _ptr(t):

@@ -58,7 +58,7 @@ def kabsch_rotations(S):
     n = Sc.numel() // 9
     if n:
         with torch.cuda.device(Sc.device):
-            _C.load_library().gsr_kabsch_rotations(n, _C.dev_f32(Sc, "S"), R.data_ptr(), _C._stream(Sc.device))
+            _C.load_library().gsr_kabsch_rotations(n, _C.dev_ptr(Sc, "S", _C.F32), R.data_ptr(), _C._stream(Sc.device))
     return R
 
 

@@ -7,13 +7,7 @@ import torch
 from diff_gaussian_rasterization import _C
 
 
-def _dev(t, name, dtype, shape):
-    if t is None:
-        return None
-    _C._require_device(t, name)
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be a contiguous {dtype} device tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    return t.data_ptr()
+_U8, _F32 = (torch.uint8,), _C.F32
 
 
 def frame_prepare(rgb, map_xy, lut, mask_l, mask_threshold, image, motion, stream=None):
@@ -23,11 +17,11 @@ def frame_prepare(rgb, map_xy, lut, mask_l, mask_threshold, image, motion, strea
     if rgb.dim() != 3 or rgb.shape[2] != 3:
         raise RuntimeError(f"rgb must be [H, W, 3], got {tuple(rgb.shape)}")
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    args = (_dev(rgb, "rgb", torch.uint8, (H, W, 3)), _dev(map_xy, "map_xy", torch.float32, (H, W, 2)), _dev(lut, "lut", torch.float32, (256,)),
-            _dev(mask_l, "mask_l", torch.uint8, (H, W)), float(mask_threshold), _dev(image, "image", torch.float32, (3, H, W)),
-            None if motion is None else _dev(motion, "motion", torch.uint8 if motion.dtype == torch.uint8 else torch.bool, (H, W)))
-    s = (stream if stream is not None else torch.cuda.current_stream(rgb.device)).cuda_stream
-    _C.load_library().gsr_frame_prepare(W, H, *args, s)
+    dev = _C.dev_ptr
+    args = (dev(rgb, "rgb", _U8, (H, W, 3)), dev(map_xy, "map_xy", _F32, (H, W, 2)), dev(lut, "lut", _F32, (256,)),
+            dev(mask_l, "mask_l", _U8, (H, W)), float(mask_threshold), dev(image, "image", _F32, (3, H, W)),
+            dev(motion, "motion", (torch.uint8, torch.bool), (H, W)))
+    _C.load_library().gsr_frame_prepare(W, H, *args, _C.stream_handle(stream, rgb.device))
 
 
 # matplotlib's "jet" as data: (x, y) knots of its three piecewise-linear segments (_cm.py _jet_data; y0 == y1 at every knot)
@@ -74,13 +68,11 @@ def frame_export(colour, depth, lut, depth_vmax, depth_scale, rgb8, depth_rgb8=N
         raise RuntimeError("a depth output was asked for without depth")
     c_ptr, c_stride = _views(colour, "colour", 3, V, H, W)
     d_ptr, d_stride = _views(depth, "depth", 1, V, H, W) if depth is not None else (None, 0)
-    u16 = None
-    if depth_u16 is not None:
-        if depth_u16.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
-            raise RuntimeError(f"depth_u16 must be a 16-bit integer tensor, got {depth_u16.dtype}")
-        u16 = _dev(depth_u16, "depth_u16", depth_u16.dtype, (V, H, W))
-    args = (c_ptr, c_stride, d_ptr, d_stride, _dev(lut, "lut", torch.uint8, (256, 3)), float(depth_vmax), float(depth_scale),
-            _dev(rgb8, "rgb8", torch.uint8, (V, H, W, 3)), _dev(depth_rgb8, "depth_rgb8", torch.uint8, (V, H, W, 3)), u16)
-    s = (stream if stream is not None else torch.cuda.current_stream(colour.device)).cuda_stream
+    if depth_u16 is not None and depth_u16.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        raise RuntimeError(f"depth_u16 must be a 16-bit integer tensor, got {depth_u16.dtype}")
+    dev = _C.dev_ptr
+    args = (c_ptr, c_stride, d_ptr, d_stride, dev(lut, "lut", _U8, (256, 3)), float(depth_vmax), float(depth_scale),
+            dev(rgb8, "rgb8", _U8, (V, H, W, 3)), dev(depth_rgb8, "depth_rgb8", _U8, (V, H, W, 3)),
+            dev(depth_u16, "depth_u16", (torch.int16, getattr(torch, "uint16", torch.int16)), (V, H, W)))
     with torch.cuda.device(colour.device):
-        _C.load_library().gsr_frame_export(V, W, H, *args, s)
+        _C.load_library().gsr_frame_export(V, W, H, *args, _C.stream_handle(stream, colour.device))

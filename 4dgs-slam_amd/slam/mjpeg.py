@@ -97,15 +97,7 @@ def jpeg_workspace_size(views, width, height):
     return int(_C.load_library().gsr_jpeg_workspace_size(views, width, height))
 
 
-def _dev(t, name, dtypes, shape):
-    _C._require_device(t, name)
-    if t.dtype not in dtypes or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be a contiguous {' or '.join(str(d) for d in dtypes)} device tensor of shape {tuple(shape)}, got {t.dtype} "
-                           f"{tuple(t.shape)}")
-    return t.data_ptr()
-
-
-_U16 = (torch.int16, getattr(torch, "uint16", torch.int16))
+_U16 =(torch.int16, getattr(torch, "uint16", torch.int16))
 
 
 def jpeg_encode(rgb8, qtables, scan, sizes, coefficients=None, workspace=None, stream=None):
@@ -123,21 +115,17 @@ def jpeg_encode(rgb8, qtables, scan, sizes, coefficients=None, workspace=None, s
     if scan.dim() != 2:
         raise RuntimeError(f"scan must be [V, capacity], got {tuple(scan.shape)}")
     rows, cols = mcu_grid(W, H)
-    args = [_dev(rgb8, "rgb8", (torch.uint8,), (V, H, W, 3)), _dev(qtables, "qtables", _U16, (2, 64)),
+    _dev = _C.dev_ptr
+    args = [_dev(rgb8,"rgb8", (torch.uint8,), (V, H, W, 3)), _dev(qtables, "qtables", _U16, (2, 64)),
             _dev(scan, "scan", (torch.uint8,), (V, scan.shape[1])), int(scan.shape[1]), _dev(sizes, "sizes", (torch.int32,), (V,)),
             None if coefficients is None else _dev(coefficients, "coefficients", (torch.int16,), (V, rows, cols, 6, 64))]
     lib = _C.load_library()
     need = int(lib.gsr_jpeg_workspace_size(V, W, H))
     if need == 0:
         raise RuntimeError(f"rgb8: {V} views of {W} x {H} are outside what gsr_jpeg_encode takes")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rgb8.device)
-    _C._require_device(workspace, "workspace")
-    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise RuntimeError(f"workspace must be a contiguous uint8 device tensor of at least {need} bytes, got {workspace.dtype} {tuple(workspace.shape)}")
-    s = (stream if stream is not None else torch.cuda.current_stream(rgb8.device)).cuda_stream
+    workspace = _C.workspace(workspace, need, rgb8.device)
     with torch.cuda.device(rgb8.device):
-        lib.gsr_jpeg_encode(V, W, H, *args, workspace.data_ptr(), int(workspace.numel()), s)
+        lib.gsr_jpeg_encode(V, W, H, *args, workspace.data_ptr(), int(workspace.numel()), _C.stream_handle(stream, rgb8.device))
 
 
 # ---- container ---------------------------------------------------------------------------------------------------------------------

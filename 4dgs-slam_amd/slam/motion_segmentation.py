@@ -16,22 +16,9 @@ from . import pretrained
 TRACE_ROW = 32          # doubles per pass of gsr_flow_rigid_fit's trace: 21 of H, 6 of g, sum w, sum w e^2, pixels with w > 0, median bin, c
 
 
-def _dev(t, name, dtypes, shape):
-    if t is None:
-        return None
-    _C._require_device(t, name)
-    if t.dtype not in dtypes or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be a contiguous {' or '.join(str(d) for d in dtypes)} device tensor of shape {tuple(shape)}, got {t.dtype} "
-                           f"{tuple(t.shape)}")
-    return t.data_ptr()
-
-
+_dev, _stream = _C.dev_ptr, _C.stream_handle
 _BYTES = (torch.uint8, torch.bool)
-_F32 = (torch.float32,)
-
-
-def _stream(stream, device):
-    return (stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream
+_F32 = _C.F32
 
 
 def _size_refused(what, W, H):
@@ -54,9 +41,7 @@ def flow_rigid_fit(flow_ij, depth_i, intrinsics, flow_ji=None, fit_mask=None, T_
     need = int(lib.gsr_flow_rigid_fit_workspace_size(W, H))
     if need == 0:
         raise _size_refused("gsr_flow_rigid_fit", W, H)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    _dev(workspace, "workspace", (torch.uint8,), (int(workspace.numel()),))
+    workspace = _C.workspace(workspace, need, dev)
     out = {"T": torch.empty((4, 4), dtype=torch.float32, device=dev), "residual": torch.empty((H, W), dtype=torch.float32, device=dev),
            "stats": torch.empty(4, dtype=torch.float64, device=dev),
            "candidate": torch.empty((H, W), dtype=torch.uint8, device=dev) if candidate else None,
@@ -84,9 +69,7 @@ def motion_mask_clean(candidate, open_radius=1, grow_radius=2, min_area=64, moti
     need = int(lib.gsr_motion_mask_clean_workspace_size(W, H))
     if need == 0:
         raise _size_refused("gsr_motion_mask_clean", W, H)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    _dev(workspace, "workspace", (torch.uint8,), (int(workspace.numel()),))
+    workspace = _C.workspace(workspace, need, dev)
     moving = torch.empty((H, W), dtype=torch.uint8, device=dev)
     labels = torch.empty((H, W), dtype=torch.int32, device=dev)
     counts = torch.empty(4, dtype=torch.int32, device=dev)

@@ -204,8 +204,8 @@ def corr_pyramid(fmap1, fmap2, both=True):
     """The correlation pyramid of fmaps [D, h, w]: a list of LEVELS tensors [2 (or 1), h*w, h_l, w_l]; index 0 is 1->2 (row: a pixel of
     image 1, grid: image 2), index 1 is 2->1. One launch of the product for both directions, one per pooled level."""
     D, h, w = (int(s) for s in fmap1.shape)
-    _C.dev_f32(fmap1, "fmap1", (D, h, w))
-    _C.dev_f32(fmap2, "fmap2", (D, h, w))
+    _C.dev_ptr(fmap1, "fmap1", _C.F32, (D, h, w))
+    _C.dev_ptr(fmap2, "fmap2", _C.F32, (D, h, w))
     nd = 2 if both else 1
     levels = [torch.empty((nd, h * w, hl, wl), dtype=torch.float32, device=fmap1.device) for hl, wl in level_sizes(h, w)]
     p12 = (C.c_void_p * LEVELS)(*[t[0].data_ptr() for t in levels])
@@ -220,12 +220,12 @@ def corr_lookup(levels, coords, out=None):
     B, _, h, w = (int(s) for s in coords.shape)
     if B != int(levels[0].shape[0]) or tuple(levels[0].shape[1:]) != (h * w, h, w):
         raise RuntimeError(f"coords {tuple(coords.shape)} do not match the pyramid {tuple(levels[0].shape)}")
-    _C.dev_f32(coords, "coords", (B, 2, h, w))
+    _C.dev_ptr(coords, "coords", _C.F32, (B, 2, h, w))
     for t in levels:
-        _C.dev_f32(t, "pyramid level")
+        _C.dev_ptr(t, "pyramid level", _C.F32)
     if out is None:
         out = torch.empty((B, CORR_CHANNELS, h, w), dtype=torch.float32, device=coords.device)
-    _C.dev_f32(out, "out", (B, CORR_CHANNELS, h, w))
+    _C.dev_ptr(out, "out", _C.F32, (B, CORR_CHANNELS, h, w))
     ptrs = (C.c_void_p * (B * LEVELS))(*[levels[l][b].data_ptr() for b in range(B) for l in range(LEVELS)])
     with torch.cuda.device(coords.device):
         _C.load_library().gsr_raft_corr_lookup(B, h, w, ptrs, coords.data_ptr(), out.data_ptr(), _C._stream(coords.device))
@@ -237,8 +237,8 @@ def upsample(flow, mask, pad, out_hw, ndc=True):
     top, bottom), out_hw = (H, W) unpadded -> [B, H, W, 2]."""
     B, _, h, w = (int(s) for s in flow.shape)
     H, W = (int(s) for s in out_hw)
-    _C.dev_f32(flow, "flow", (B, 2, h, w))
-    _C.dev_f32(mask, "mask", (B, MASK_CHANNELS, h, w))
+    _C.dev_ptr(flow, "flow", _C.F32, (B, 2, h, w))
+    _C.dev_ptr(mask, "mask", _C.F32, (B, MASK_CHANNELS, h, w))
     out = torch.empty((B, H, W, 2), dtype=torch.float32, device=flow.device)
     with torch.cuda.device(flow.device):
         _C.load_library().gsr_raft_upsample(B, h, w, flow.data_ptr(), mask.data_ptr(), int(pad[0]), int(pad[2]), W, H, int(bool(ndc)),
@@ -249,12 +249,12 @@ def upsample(flow, mask, pad, out_hw, ndc=True):
 def gma_attention(q, k, scale, out=None):
     """GMA's attention: q, k [B, D, h, w] (B = 1 or 2) -> softmax_j(sum_c (scale q[b, c, i]) k[b, c, j]) as [B, N, N], N = h * w."""
     B, D, h, w = (int(s) for s in q.shape)
-    _C.dev_f32(q, "q", (B, D, h, w))
-    _C.dev_f32(k, "k", (B, D, h, w))
+    _C.dev_ptr(q, "q", _C.F32, (B, D, h, w))
+    _C.dev_ptr(k, "k", _C.F32, (B, D, h, w))
     N = h * w
     if out is None:
         out = torch.empty((B, N, N), dtype=torch.float32, device=q.device)
-    _C.dev_f32(out, "attn", (B, N, N))
+    _C.dev_ptr(out, "attn", _C.F32, (B, N, N))
     with torch.cuda.device(q.device):
         _C.load_library().gsr_gma_attention(B, D, h, w, q.data_ptr(), k.data_ptr(), float(scale), out.data_ptr(), _C._stream(q.device))
     return out
@@ -263,12 +263,12 @@ def gma_attention(q, k, scale, out=None):
 def gma_aggregate(attn, v, x, gamma, out=None):
     """GMA's aggregation: x + gamma * (attn @ v over the pixels); attn [B, N, N], v and x [B, D, h, w] -> [B, D, h, w]."""
     B, D, h, w = (int(s) for s in x.shape)
-    _C.dev_f32(attn, "attn", (B, h * w, h * w))
-    _C.dev_f32(v, "v", (B, D, h, w))
-    _C.dev_f32(x, "x", (B, D, h, w))
+    _C.dev_ptr(attn, "attn", _C.F32, (B, h * w, h * w))
+    _C.dev_ptr(v, "v", _C.F32, (B, D, h, w))
+    _C.dev_ptr(x, "x", _C.F32, (B, D, h, w))
     if out is None:
         out = torch.empty_like(x)
-    _C.dev_f32(out, "out", (B, D, h, w))
+    _C.dev_ptr(out, "out", _C.F32, (B, D, h, w))
     with torch.cuda.device(x.device):
         _C.load_library().gsr_gma_aggregate(B, D, h, w, attn.data_ptr(), v.data_ptr(), x.data_ptr(), float(gamma), out.data_ptr(),
                                             _C._stream(x.device))

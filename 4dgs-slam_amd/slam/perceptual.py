@@ -100,8 +100,8 @@ def check_size(height, width):
 def prepare(x, y):
     """gsr_lpips_prepare: x, y [B, 3, H, W] in [0, 1] -> the network batch [2B, 3, H, W] (x's rows, then y's), scaled. One launch."""
     B, _, H, W = (int(s) for s in x.shape)
-    _C.dev_f32(x, "x", (B, 3, H, W))
-    _C.dev_f32(y, "y", (B, 3, H, W))
+    _C.dev_ptr(x, "x", _C.F32, (B, 3, H, W))
+    _C.dev_ptr(y, "y", _C.F32, (B, 3, H, W))
     out = torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _C.load_library().gsr_lpips_prepare(B, H, W, x.data_ptr(), y.data_ptr(), out.data_ptr(), _C._stream(x.device))
@@ -119,8 +119,8 @@ def distance(feats, lins, norm="torchmetrics", workspaces=None):
     chw = []
     for l, (f, w) in enumerate(zip(feats, lins)):
         n, c, h, wd = (int(s) for s in f.shape)
-        _C.dev_f32(f, f"feats[{l}]", (2 * B, c, h, wd))
-        _C.dev_f32(w, f"lins[{l}]", (c,))
+        _C.dev_ptr(f, f"feats[{l}]", _C.F32, (2 * B, c, h, wd))
+        _C.dev_ptr(w, f"lins[{l}]", _C.F32, (c,))
         chw += [c, h, wd]
     nl, dev = len(feats), feats[0].device
     L = _C.load_library()

@@ -372,13 +372,13 @@ def postprocess(head_outputs, proto, classes, strides, motion=None, conf=CONF, i
     nm, ph, pw = (int(s) for s in proto.shape)
     H, W = 4 * ph, 4 * pw
     check_size(H, W)
-    _C.dev_f32(proto, "proto")
+    _C.dev_ptr(proto, "proto", _C.F32)
     nc = int(head_outputs[0][0].shape[0]) - 4 * GSR_YOLO_REG_MAX
     hw, heads, coefs = [], [], []
     for l, (h, c) in enumerate(head_outputs):
         _, lh, lw = (int(s) for s in h.shape)
-        heads.append(_C.dev_f32(h, f"head[{l}]", (4 * GSR_YOLO_REG_MAX + nc, lh, lw)))
-        coefs.append(_C.dev_f32(c, f"coef[{l}]", (nm, lh, lw)))
+        heads.append(_C.dev_ptr(h, f"head[{l}]", _C.F32, (4 * GSR_YOLO_REG_MAX + nc, lh, lw)))
+        coefs.append(_C.dev_ptr(c, f"coef[{l}]", _C.F32, (nm, lh, lw)))
         hw += [lh, lw]
     anchors = sum(hw[2 * l] * hw[2 * l + 1] for l in range(nl))
     if anchors > GSR_YOLO_MAX_ANCHORS:
@@ -409,8 +409,8 @@ def masks_from_dets(dets, counts, proto, motion=None):
     nm, ph, pw = (int(s) for s in proto.shape)
     H, W = 4 * ph, 4 * pw
     check_size(H, W)
-    _C.dev_f32(proto, "proto")
-    _C.dev_f32(dets, "dets", (int(dets.shape[0]), GSR_YOLO_DET_HEAD + nm))
+    _C.dev_ptr(proto, "proto", _C.F32)
+    _C.dev_ptr(dets, "dets", _C.F32, (int(dets.shape[0]), GSR_YOLO_DET_HEAD + nm))
     mask = torch.empty((H, W), dtype=torch.uint8, device=proto.device)
     with torch.cuda.device(proto.device):
         _C.load_library().gsr_yolo_masks(int(dets.shape[0]), dets.data_ptr(), counts.data_ptr(), nm, proto.data_ptr(), ph, pw, H, W,

@@ -34,17 +34,7 @@ def stereo_workspace_size(width, height, num_disparities):
     return int(_C.load_library().gsr_stereo_workspace_size(int(width), int(height), int(num_disparities)))
 
 
-def _dev(t, name, dtypes, shape):
-    if t is None:
-        return None
-    _C._require_device(t, name)
-    if t.dtype not in dtypes or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be a contiguous {' or '.join(str(d) for d in dtypes)} device tensor of shape {tuple(shape)}, got {t.dtype} "
-                           f"{tuple(t.shape)}")
-    return t.data_ptr()
-
-
-_U16 = (torch.int16, getattr(torch, "uint16", torch.int16))
+_U16 =(torch.int16, getattr(torch, "uint16", torch.int16))
 
 
 def stereo_depth(left, right, disparity16, depth=None, image=None, lut=None, maps=None, left_rect=None, right_rect=None, cost_sum=None,
@@ -59,24 +49,19 @@ def stereo_depth(left, right, disparity16, depth=None, image=None, lut=None, map
         raise RuntimeError(f"left must be [H, W], got {tuple(left.shape)}")
     H, W, D = int(left.shape[0]), int(left.shape[1]), int(num_disparities)
     map_l, map_r = maps if maps is not None else (None, None)
-    u8, f32 = (torch.uint8,), (torch.float32,)
+    u8, f32, _dev = (torch.uint8,), _C.F32, _C.dev_ptr
     args = [_dev(left, "left", u8, (H, W)), _dev(right, "right", u8, (H, W)), _dev(map_l, "map_left", f32, (H, W, 2)),
             _dev(map_r, "map_right", f32, (H, W, 2)), _dev(lut, "lut", f32, (256,)), _dev(left_rect, "left_rect", u8, (H, W)),
             _dev(right_rect, "right_rect", u8, (H, W)), _dev(image, "image", f32, (3, H, W)),
             _dev(disparity16, "disparity16", (torch.int16,), (H, W)), _dev(depth, "depth", f32, (H, W)),
             _dev(cost_sum, "cost_sum", _U16, (H, W, D))]
     lib = _C.load_library()
-    need = int(lib.gsr_stereo_workspace_size(W, H, D))
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=left.device)
-    if workspace is not None:
-        _C._require_device(workspace, "workspace")
-        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
-            raise RuntimeError(f"workspace must be a contiguous uint8 device tensor, got {workspace.dtype} {tuple(workspace.shape)}")
-    s = (stream if stream is not None else torch.cuda.current_stream(left.device)).cuda_stream
+    # a size the library refuses asks for 0 bytes, and the byte count of a given workspace is left to the library as well: the call below
+    # raises with the library's text, which names the size query
+    workspace = _C.workspace(workspace, int(lib.gsr_stereo_workspace_size(W, H, D)) if workspace is None else 0, left.device)
     with torch.cuda.device(left.device):
         lib.gsr_stereo_depth(W, H, D, int(p1), int(p2), int(uniqueness_ratio), int(disp12_max_diff), float(bf), *args,
-                             None if workspace is None else workspace.data_ptr(), 0 if workspace is None else int(workspace.numel()), s)
+                             workspace.data_ptr() or None, int(workspace.numel()), _C.stream_handle(stream, left.device))
 
 
 class StereoMatcher:
