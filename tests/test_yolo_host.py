@@ -1,6 +1,7 @@
 """Host-side checks of the YOLO segmenter (slam/segmentation.py): loading an ultralytics-style checkpoint without ultralytics (fp16 to fp32,
 the layer graph from `f`), refusing foreign globals and unknown module types, the size rule, the loaders' class sets, the fp64 reference
-(tests/yolo_reference.py) on hand-made NMS cases, and tools/run_slam.py's --yolo-weights. No GPU needed."""
+(tests/yolo_reference.py) on hand-made NMS cases, its vectorised NMS against the scalar statement, its max_dets rule and its two
+input-quality measures, and tools/run_slam.py's --yolo-weights. No GPU needed."""
 import io
 import os
 import pickle
@@ -164,6 +165,107 @@ def test_reference_max_det_and_score_ties():
     scores = [[0.5, 0.0] for _ in range(320)]                                           # all tied
     rows, _ = ref.non_max_suppression(*_case(boxes, scores), cls_id=0)
     assert rows[:, 6].tolist() == [float(k) for k in range(300)]                        # ties by anchor, cut at max_det
+
+
+def _nms_inputs():
+    """name -> (xyxy boxes [n, 4], scores [n]) with n <= 300, so that the scalar nms() stays fast."""
+    g = torch.Generator().manual_seed(0)
+    out = {}
+    xy = torch.rand((300, 2), generator=g, dtype=torch.float64) * 100
+    wh = torch.rand((300, 2), generator=g, dtype=torch.float64) * 40 + 5
+    out["random"] = (torch.cat((xy, xy + wh), 1), torch.rand(300, generator=g, dtype=torch.float64))
+    # dense: jittered copies of 12 boxes, so that most IoUs are high and survivors suppress in long runs
+    base = out["random"][0][:12].repeat(25, 1) + torch.rand((300, 4), generator=g, dtype=torch.float64) * 4
+    out["random dense"] = (base, torch.rand(300, generator=g, dtype=torch.float64))
+    out["identical"] = (torch.tensor([[10.0, 20.0, 50.0, 70.0]], dtype=torch.float64).repeat(200, 1),
+                        torch.rand(200, generator=g, dtype=torch.float64))
+    k = torch.arange(256, dtype=torch.float64)
+    x, y = (k % 16) * 20, (k // 16) * 20
+    out["disjoint"] = (torch.stack((x, y, x + 20, y + 20), 1), torch.rand(256, generator=g, dtype=torch.float64))     # edges touch: IoU 0
+    for d in (2, 6):                                       # 1-cell shifts of a box of half-width d cells: IoU 0.6 and 0.846 next door
+        x = torch.arange(300, dtype=torch.float64) * 8
+        b = torch.stack((x - 8 * d, torch.zeros(300, dtype=torch.float64), x + 8 * d, torch.full((300,), 16.0 * d, dtype=torch.float64)), 1)
+        out[f"chain d={d} descending"] = (b, torch.linspace(0.9, 0.3, 300, dtype=torch.float64))
+        out[f"chain d={d} random"] = (b, torch.rand(300, generator=g, dtype=torch.float64))
+    out["tied scores"] = (out["random dense"][0], torch.randint(0, 4, (300,), generator=g).double() / 8 + 0.3)
+    out["all tied"] = (out["chain d=6 random"][0], torch.full((300,), 0.5, dtype=torch.float64))
+    out["empty"] = (torch.zeros((0, 4), dtype=torch.float64), torch.zeros(0, dtype=torch.float64))
+    out["one"] = (out["random"][0][:1], out["random"][1][:1])
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(_nms_inputs()))
+def test_reference_vectorised_nms_equals_the_scalar_statement(name):
+    boxes, scores = _nms_inputs()[name]
+    for thr in (0.7, 0.45):
+        want = ref.nms(boxes, scores, thr)
+        assert ref.nms_vectorised(boxes, scores, thr) == want
+        if name == "identical":
+            assert len(want) == 1
+        if name == "disjoint":
+            assert len(want) == len(boxes)
+        if name == "chain d=6 descending" and thr == 0.7:
+            assert want == list(range(0, 300, 3))          # shifts 1 and 2 (IoU 0.846, 0.714) go, shift 3 (0.6) stays
+        if name == "all tied" and thr == 0.7:
+            assert want == list(range(0, 300, 3))          # ties are visited by lower index
+
+
+def _tiny_heads(cands, nc=2, width=8):
+    """One level of 1 x width anchors (stride 8), background class logits -6; cands: anchor -> (class, logit). Every box is its own
+    cell (l, t, r, b = 0, 0, 1, 1 by near one-hot DFL bins), so nothing is suppressed."""
+    h = torch.zeros((64 + nc, 1, width))
+    h[64:] = -6.0
+    for k, d in enumerate((0, 0, 1, 1)):
+        h[k * 16 + d] = 12.0
+    for a, (c, logit) in cands.items():
+        h[64 + c, 0, a] = logit
+    return [(h, torch.arange(3.0 * width).reshape(3, 1, width))]
+
+
+def test_reference_max_dets_rule():
+    # global order: a0 (class 0) a5 (1) a1 (0) a6 (1) a2 (0) a3 (0) a7 (1) a4 (0)
+    heads = _tiny_heads({0: (0, 3.0), 1: (0, 2.0), 2: (0, 1.0), 3: (0, 0.5), 4: (0, 0.0), 5: (1, 2.5), 6: (1, 1.5), 7: (1, 0.2)})
+
+    def anchors(**kw):
+        rows, coef, counts = ref.detections(heads, [8.0], [0, 1], counts=True, **kw)
+        assert counts == (len(rows), 8, 8) and torch.equal(coef[:, 0], rows[:, 6])      # coefficient 0 of anchor a is a
+        return [int(a) for a in rows[:, 6]]
+
+    assert anchors() == [0, 1, 2, 3, 4, 5, 6, 7]                                        # per class, concatenated
+    assert anchors(max_det=3) == [0, 1, 2, 5, 6, 7]
+    assert anchors(max_det=3, max_dets=6) == [0, 1, 2, 5, 6, 7]                         # max_dets not binding: as without it
+    assert anchors(max_det=3, max_dets=4) == [0, 1, 5, 6]                               # the first four of the global order
+    assert anchors(max_det=3, max_dets=5) == [0, 1, 2, 5, 6]
+    assert anchors(max_det=2, max_dets=5) == [0, 1, 5, 6]                               # a2 is over its class's max_det: never counted
+    assert anchors(max_det=1, max_dets=2) == [0, 5]
+    assert anchors(max_det=5, max_dets=1) == [0]
+    rows, _ = ref.detections(heads, [8.0], [1], max_dets=2)
+    assert [int(a) for a in rows[:, 6]] == [5, 6]
+
+
+def test_reference_input_quality_measures():
+    a, b = [0.0, 0.0, 10.0, 10.0], [5.0, 0.0, 15.0, 10.0]                               # IoU 50 / 150
+    assert ref.min_iou_margin([a, b], [0, 0], 0.7) == pytest.approx(0.7 - 1 / 3, abs=1e-15)
+    assert ref.min_iou_margin([a, b], [0, 0], 0.3) == pytest.approx(1 / 3 - 0.3, abs=1e-15)
+    assert ref.min_iou_margin([a, b], [0, 1], 0.7) == float("inf")                      # no pair of equal class
+    assert ref.min_iou_margin([a], [0], 0.7) == float("inf") and ref.min_iou_margin([], [], 0.7) == float("inf")
+    c = [0.0, 0.0, 10.0, 10.5]                                                          # IoU with a: 100 / 105; with b: 50 / 155
+    assert ref.min_iou_margin([a, b, c], [0, 0, 0], 0.7) == pytest.approx(100 / 105 - 0.7, abs=1e-15)
+    assert ref.min_iou_margin([a, b, c], [0, 0, 1], 0.7) == pytest.approx(0.7 - 1 / 3, abs=1e-15)
+    assert ref.min_iou_margin([a, b, a], [0, 1, 1], 0.7) == pytest.approx(0.7 - 1 / 3, abs=1e-15)      # a and a differ in class
+    assert ref.min_iou_margin([a, a], [3, 3], 0.7) == pytest.approx(0.3, abs=1e-15)
+    z = [3.0, 3.0, 3.0, 9.0]                                                            # zero area: IoU 0 with everything, itself included
+    assert ref.min_iou_margin([z, z], [0, 0], 0.7) == pytest.approx(0.7, abs=1e-15)
+    many = torch.tensor([a, b, c] * 400, dtype=torch.float64)                           # more than one block of rows
+    many[1100] = torch.tensor([0.0, 0.0, 10.0, 14.0])                                   # IoU with a: 100 / 140 = 0.714
+    assert ref.min_iou_margin(many, torch.zeros(1200), 0.7) == pytest.approx(100 / 140 - 0.7, abs=1e-15)
+
+    assert ref.min_score_gap([0.9, 0.5, 0.5, 0.26]) == pytest.approx(0.01, abs=1e-15)   # to conf; the tie is no gap
+    assert ref.min_score_gap([0.9, 0.5, 0.5, 0.6, 0.26], conf=0.1) == pytest.approx(0.1, abs=1e-15)
+    assert ref.min_score_gap([0.9, 0.9 - 1e-6, 0.5]) == pytest.approx(1e-6, abs=1e-15)
+    assert ref.min_score_gap([0.5, 0.5]) == pytest.approx(0.25, abs=1e-15)
+    assert ref.min_score_gap([0.2], conf=0.25) == pytest.approx(0.05, abs=1e-15)
+    assert ref.min_score_gap([]) == float("inf")
 
 
 def test_run_slam_yolo_flag(tmp_path):

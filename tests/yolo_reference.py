@@ -1,7 +1,9 @@
 """The YOLO-seg contract restated plainly in torch float64, for the tests: the unfused modules (convolution, then BatchNorm with its
 running statistics, then the activation), ultralytics' Detect / Segment inference decode, ops.non_max_suppression with the greedy NMS
-written out (torchvision is not installed here), and ops.process_mask in its logit form. Runs over the stub modules that
-slam.segmentation.load_checkpoint returns, on any device."""
+written out (torchvision is not installed here; nms() is the statement, nms_vectorised() what thousands of candidates need), and
+ops.process_mask in its logit form; and two measures of an input's quality, min_iou_margin() and min_score_gap(). Runs over the stub
+modules that slam.segmentation.load_checkpoint returns, on any device."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -151,25 +153,111 @@ def nms(boxes, scores, iou_thres):
     return kept
 
 
-def non_max_suppression(boxes_xywh, scores, coefs, cls_id, conf=0.25, iou=0.7, max_det=300):
-    """One predict(classes=[cls_id]) call: rows (x1, y1, x2, y2, score, class, anchor) [n, 7] and coefficients [n, nm]."""
+def _np64(t):
+    return t.detach().to("cpu", D).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+
+
+def nms_vectorised(boxes, scores, iou_thres):
+    """nms() with the inner loop as array arithmetic in float64: one visited box at a time against all boxes behind it in the visiting
+    order (score descending, ties by lower index). The same expressions as nms(), so the same decisions. Kept indices, visiting order."""
+    b, s = _np64(boxes).reshape(-1, 4), _np64(scores).reshape(-1)
+    order = np.argsort(-s, kind="stable")
+    b = b[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    alive = np.ones(len(b), dtype=bool)
+    kept = []
+    for i in range(len(b)):
+        if not alive[i]:
+            continue
+        kept.append(int(order[i]))
+        r = b[i + 1:]
+        iw = np.maximum(np.minimum(b[i, 2], r[:, 2]) - np.maximum(b[i, 0], r[:, 0]), 0.0)
+        ih = np.maximum(np.minimum(b[i, 3], r[:, 3]) - np.maximum(b[i, 1], r[:, 1]), 0.0)
+        inter = iw * ih
+        with np.errstate(divide="ignore", invalid="ignore"):
+            alive[i + 1:] &= ~(inter / (area[i] + area[i + 1:] - inter) > iou_thres)
+    return kept
+
+
+def survivors(boxes_xywh, scores, cls_id, conf=0.25, iou=0.7):
+    """(the anchors of class cls_id that NMS keeps, in visiting order and before max_det; the number of candidates of the class)."""
     best, j = scores.max(1)
-    keep = (scores.amax(1) > conf) & (best > conf) & (j == cls_id)
-    idx = torch.nonzero(keep).flatten().tolist()
+    idx = torch.nonzero((best > conf) & (j == cls_id)).flatten()
     xy, wh = boxes_xywh[:, :2], boxes_xywh[:, 2:]
     xyxy = torch.cat((xy - wh / 2, xy + wh / 2), 1)
-    idx = sorted(idx, key=lambda a: (-float(best[a]), a))[:MAX_NMS]
+    idx = idx[torch.sort(best[idx], descending=True, stable=True).indices][:MAX_NMS]     # score descending, anchor ascending
     off = xyxy[idx] + float(cls_id) * MAX_WH
-    kept = [idx[k] for k in nms(off, best[idx], iou)][:max_det]
-    rows = torch.tensor([[*xyxy[a].tolist(), float(best[a]), float(cls_id), float(a)] for a in kept], dtype=D).reshape(-1, 7)
-    return rows, coefs[kept]
+    kept = idx[torch.as_tensor(nms_vectorised(off, best[idx], iou), dtype=torch.long, device=idx.device)]
+    return kept, len(idx)
 
 
-def detections(heads, strides, classes, conf=0.25, iou=0.7, max_det=300, fp32_scores=False):
-    """The reference's one predict per class, concatenated: rows [n, 7] and coefficients [n, nm]."""
+def _rows(boxes_xywh, scores, coefs, cls_id, kept):
+    xy, wh = boxes_xywh[kept, :2], boxes_xywh[kept, 2:]
+    rows = torch.cat((xy - wh / 2, xy + wh / 2, scores[kept, cls_id, None], torch.full((len(kept), 1), float(cls_id), dtype=D,
+                      device=kept.device), kept.to(D)[:, None]), 1)
+    return rows.cpu().reshape(-1, 7), coefs[kept]
+
+
+def non_max_suppression(boxes_xywh, scores, coefs, cls_id, conf=0.25, iou=0.7, max_det=300):
+    """One predict(classes=[cls_id]) call: rows (x1, y1, x2, y2, score, class, anchor) [n, 7] and coefficients [n, nm]."""
+    kept, _ = survivors(boxes_xywh, scores, cls_id, conf, iou)
+    return _rows(boxes_xywh, scores, coefs, cls_id, kept[:max_det])
+
+
+def detections(heads, strides, classes, conf=0.25, iou=0.7, max_det=300, fp32_scores=False, max_dets=None, counts=False):
+    """The reference's one predict per class, concatenated: rows [n, 7] and coefficients [n, nm]. max_dets (gsr_yolo_detect's row
+    capacity): the survivors are visited in global order (score descending, then anchor ascending) and one is emitted while its class
+    has fewer than max_det and fewer than max_dets are emitted in all; the rows stay per class, concatenated. counts: also return
+    (emitted, candidates, NMS survivors before max_det), as gsr_yolo_detect reports them."""
     boxes, scores, coefs = decode(heads, strides, fp32_scores)
-    out = [non_max_suppression(boxes, scores, coefs, c, conf, iou, max_det) for c in sorted(set(classes))]
-    return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+    classes = sorted(set(classes))
+    kept, cand = zip(*(survivors(boxes, scores, c, conf, iou) for c in classes))
+    cut = [k[:max_det] for k in kept]
+    if max_dets is not None:
+        first = sorted((-s, a, q) for q, (k, c) in enumerate(zip(cut, classes)) for s, a in zip(scores[k, c].tolist(), k.tolist()))
+        cut = [torch.tensor([a for _, a, q in first[:max_dets] if q == p], dtype=torch.long, device=boxes.device)
+               for p in range(len(classes))]
+    out = [_rows(boxes, scores, coefs, c, k) for c, k in zip(classes, cut)]
+    rows, co = torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+    return (rows, co, (len(rows), sum(cand), sum(len(k) for k in kept))) if counts else (rows, co)
+
+
+def _t64(x):
+    return x.to(D) if isinstance(x, torch.Tensor) else torch.tensor(x, dtype=D)
+
+
+def _pair_iou(a, b):
+    """IoU [len(a), len(b)] of xyxy boxes in float64; 0 where the union is empty."""
+    iw = (torch.minimum(a[:, None, 2], b[None, :, 2]) - torch.maximum(a[:, None, 0], b[None, :, 0])).clamp_(min=0)
+    ih = (torch.minimum(a[:, None, 3], b[None, :, 3]) - torch.maximum(a[:, None, 1], b[None, :, 1])).clamp_(min=0)
+    inter = iw * ih
+    union = ((a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1]))[:, None] + ((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]))[None, :] - inter
+    return torch.where(union > 0, inter / union.clamp(min=1e-300), torch.zeros_like(inter))
+
+
+def min_iou_margin(boxes_xyxy, cls, iou=0.7, block=512):
+    """Input quality: the smallest |IoU - iou| over all pairs of candidates of equal class (float64, in blocks of rows); inf without
+    such a pair. Far from 0, no NMS decision can turn on float32 rounding."""
+    b = _t64(boxes_xyxy).reshape(-1, 4)
+    cls = torch.as_tensor(cls, device=b.device).reshape(-1)
+    best = float("inf")
+    for i0 in range(0, len(b), block):
+        m = (_pair_iou(b[i0:i0 + block], b) - iou).abs()
+        rows = torch.arange(i0, min(i0 + block, len(b)), device=b.device)
+        pair = (cls[i0:i0 + block, None] == cls[None, :]) & (rows[:, None] != torch.arange(len(b), device=b.device)[None, :])
+        if bool(pair.any()):
+            best = min(best, float(m[pair].min()))
+    return best
+
+
+def min_score_gap(scores, conf=0.25):
+    """Input quality: the smallest difference between two distinct candidate scores, and between any candidate score and conf
+    (float64); inf without scores. Above float32's rounding, neither the sort nor the conf test can turn on it; equal scores are ties."""
+    s = torch.unique(_t64(scores).reshape(-1))                 # sorted ascending, distinct
+    if len(s) == 0:
+        return float("inf")
+    gap = float((s - conf).abs().min())
+    return min(gap, float((s[1:] - s[:-1]).min())) if len(s) > 1 else gap
 
 
 def mask_logits(rows, coefs, proto, shape):
