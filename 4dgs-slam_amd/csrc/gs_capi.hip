@@ -44,6 +44,8 @@
 #include "gs_jpeg.h"
 #include "../../include/stereo_depth.h"
 #include "gs_stereo.h"
+#include "../../include/multiview_depth.h"
+#include "gs_sweep.h"
 #include "../../include/optical_flow.h"
 #include "gs_raft.h"
 #include "gs_gma.h"
@@ -132,9 +134,11 @@ static bool workspace_fits(const char* who, const char* size_fn, const void* wor
 }
 
 // ---- per-kernel timing with events on the launch stream ---------------------------------------------------------
-enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE, K_COUNT };
+enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE,
+                K_SWEEP_CENSUS, K_SWEEP_COST, K_SWEEP_PATHS, K_SWEEP_SELECT, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"preprocess_fwd", "scan", "scatter_instances", "sort_tiles",
-                                                  "render_fwd", "render_bwd", "geometry_bwd", "knn_total", "frame_prepare"};
+                                                  "render_fwd", "render_bwd", "geometry_bwd", "knn_total", "frame_prepare",
+                                                  "sweep_census", "sweep_cost", "sweep_paths", "sweep_select"};
 struct Profiler {
     unsigned mask = 0;   // bit i set => kernel id i is timed
     struct Rec { hipEvent_t a, b; int id; };
@@ -3129,6 +3133,81 @@ int gsr_stereo_depth(int width, int height, int num_disparities, int p1, int p2,
     else
         hipLaunchKernelGGL(stereo_select_kernel<2>, dim3(select_blocks), dim3(STEREO_BLOCK), 0, stream, width, height, uniqueness_ratio, disp12_max_diff,
                            bf16, S, disparity16, depth);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_sweep_depth: census codes of the reference and of the partners [1 + J, H, W] u64 | C [H, W, 64] u8 (unused when the
+// caller gives cost) | S [H, W, 64] u16 (unused when the caller gives cost_sum) | the observability flags [H, W] u8; every part starts on
+// a multiple of 16 bytes
+struct SweepLayout { uint64_t* codes; unsigned char* cost; unsigned short* cost_sum; unsigned char* observable; size_t bytes; };
+static bool sweep_layout(int width, int height, int partners, const void* workspace, SweepLayout& l)
+{
+    if (width < 1 || height < 1 || partners < 1 || partners > SWEEP_MAX_PARTNERS || (long long)width * height * SWEEP_D > 0x7fffffffLL) return false;
+    const size_t n = (size_t)width * height;
+    Carver c(workspace, 16);
+    l.codes = c.take<uint64_t>(n * (size_t)(1 + partners));
+    l.cost = c.take<unsigned char>(n * SWEEP_D);
+    l.cost_sum = c.take<unsigned short>(n * SWEEP_D);
+    l.observable = c.take<unsigned char>(n);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_sweep_workspace_size(int width, int height, int partners) { SweepLayout l; return sweep_layout(width, height, partners, nullptr, l) ? l.bytes : 0; }
+
+int gsr_sweep_depth(int width, int height, int partners, float fx, float fy, float cx, float cy, float w_min, float w_step, int p1, int p2,
+                    int uniqueness_ratio, int min_span_px, const unsigned char* ref_grey, const unsigned char* partner_grey,
+                    const float* transforms, short* index16, float* depth, unsigned char* cost, unsigned short* cost_sum, void* workspace,
+                    size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_sweep_depth: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    SweepLayout l;
+    if (!sweep_layout(width, height, partners, workspace, l))
+        return fail("width and height must be positive, partners in [1, 4] (got " + std::to_string(partners) + ") and width * height * 64 below 2^31");
+    if (!(p1 > 0 && p1 < p2 && p2 <= 2047)) return fail("the penalties must satisfy 0 < p1 < p2 <= 2047, got p1 " + std::to_string(p1) + ", p2 " + std::to_string(p2));
+    if (uniqueness_ratio < 0 || uniqueness_ratio > 99) return fail("uniqueness_ratio must be in [0, 99], got " + std::to_string(uniqueness_ratio));
+    if (min_span_px < 0) return fail("min_span_px must not be negative, got " + std::to_string(min_span_px));
+    if (!(std::isfinite(w_min) && std::isfinite(w_step) && w_min >= 0.0f && w_step > 0.0f))
+        return fail("w_min must be finite and >= 0 and w_step finite and > 0, got w_min " + std::to_string(w_min) + ", w_step " + std::to_string(w_step));
+    if (!ref_grey || !partner_grey || !transforms || !index16 || !depth || !workspace)
+        return fail("ref_grey, partner_grey, transforms, index16, depth and workspace must not be NULL");
+    if (!workspace_fits("gsr_sweep_depth", "gsr_sweep_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    if (cost_sum && ((size_t)cost_sum & 1)) return fail("cost_sum must be 2-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)width * height;
+    unsigned char* const C = cost ? cost : l.cost;
+    unsigned short* const S = cost_sum ? cost_sum : l.cost_sum;
+    const unsigned pixel_blocks = (unsigned)((n + STEREO_BLOCK - 1) / STEREO_BLOCK);
+    // the census of image i (0: the reference, 1 + j: partner j) goes to codes[i]; stereo_census_kernel takes two images per launch
+    auto image = [&](int i) { return i == 0 ? ref_grey : partner_grey + (size_t)(i - 1) * n; };
+    for (int i = 0; i <= partners; i += 2) {
+        ScopedKernelTimer tm(K_SWEEP_CENSUS, stream);
+        const int pair = i + 1 <= partners ? 2 : 1;                      // an odd image out: one side, blockIdx.y stays 0
+        hipLaunchKernelGGL(stereo_census_kernel, dim3(pixel_blocks, pair), dim3(STEREO_BLOCK), 0, stream, width, height, image(i),
+                           pair == 2 ? image(i + 1) : nullptr, l.codes + (size_t)i * n, pair == 2 ? l.codes + (size_t)(i + 1) * n : nullptr);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    const unsigned wave_blocks = (unsigned)((n + STEREO_BLOCK / 64 - 1) / (STEREO_BLOCK / 64));
+    {
+        ScopedKernelTimer tm(K_SWEEP_COST, stream);
+        hipLaunchKernelGGL(sweep_cost_kernel, dim3(wave_blocks), dim3(STEREO_BLOCK), 0, stream, width, height, partners,
+                           SweepCamera{fx, fy, cx, cy, w_min, w_step}, min_span_px, l.codes, transforms, C, l.observable);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
+    {
+        ScopedKernelTimer tm(K_SWEEP_PATHS, stream);                     // the eight launches as one stage
+        for (int r = 0; r < 8; ++r) {
+            const int dx = dirs[r][0], dy = dirs[r][1];
+            const unsigned paths = (unsigned)(dy == 0 ? height : dx == 0 ? width : width + height - 1);
+            hipLaunchKernelGGL(sweep_path_kernel, dim3(paths), dim3(64), 0, stream, width, height, dx, dy, p1, p2, C, S, (int)(r == 0));
+            GSR_HIP_CHECK(hipGetLastError());
+        }
+    }
+    ScopedKernelTimer tm(K_SWEEP_SELECT, stream);
+    hipLaunchKernelGGL(sweep_select_kernel, dim3(wave_blocks), dim3(STEREO_BLOCK), 0, stream, width, height, uniqueness_ratio, w_min, w_step, S,
+                       l.observable, index16, depth);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

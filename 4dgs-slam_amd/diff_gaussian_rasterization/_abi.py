@@ -238,6 +238,9 @@ FUNCTIONS = {
     # stereo_depth.h
     "gsr_stereo_workspace_size": (sz, [i, i, i]),
     "gsr_stereo_depth": (i, [i] * 7 + [f] + [vp] * 12 + [sz, vp]),
+    # multiview_depth.h
+    "gsr_sweep_workspace_size": (sz, [i, i, i]),
+    "gsr_sweep_depth": (i, [i] * 3 + [f] * 6 + [i] * 4 + [vp] * 8 + [sz, vp]),
     # optical_flow.h
     "gsr_raft_corr_pyramid": (i, [i, i, i, vp, vp, P(vp), P(vp), vp]),
     "gsr_raft_corr_lookup": (i, [i, i, i, P(vp), vp, vp, vp]),

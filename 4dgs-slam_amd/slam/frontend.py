@@ -15,6 +15,7 @@ How a frame is processed:
              whether the frame becomes a keyframe (``slam/keyframes.py``; ONE host transfer per frame);
   insert     the window update is computed on the device and read back as two indices; the back-end maps the new keyframe.
 """
+import struct
 import time
 
 import torch
@@ -54,6 +55,36 @@ def get_median_depth(depth, opacity=None, mask=None, return_std=False):
     return lower_median(valid_depth)
 
 
+MONO_SWEEP_DEFAULTS = {"enabled": False, "partners": 3, "near": 0.25, "p1": 10, "p2": 120, "uniqueness_ratio": 40, "min_span_px": 8}
+
+
+def mono_sweep_options(training):
+    """The ``Training.mono_sweep`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
+    sweep cannot take are refused here, before the run starts."""
+    block = training.get("mono_sweep")
+    if not block or not block.get("enabled", False):
+        return None
+    unknown = sorted(set(block) - set(MONO_SWEEP_DEFAULTS))
+    if unknown:
+        raise ValueError(f"Training.mono_sweep: unknown keys {unknown} (known: {sorted(MONO_SWEEP_DEFAULTS)})")
+    opt = dict(MONO_SWEEP_DEFAULTS, **block)
+    opt = {"enabled": True, "near": float(opt["near"]), **{k: int(opt[k]) for k in ("partners", "p1", "p2", "uniqueness_ratio", "min_span_px")}}
+    if not 1 <= opt["partners"] <= 4:
+        raise ValueError(f"Training.mono_sweep.partners must be 1 to 4, got {opt['partners']}")
+    if not (0.0 < opt["near"] <= 1.0):
+        raise ValueError(f"Training.mono_sweep.near must be in (0, 1] (the nearest swept depth as a share of the median), got {opt['near']}")
+    if not (0 < opt["p1"] < opt["p2"] <= 2047) or not 0 <= opt["uniqueness_ratio"] <= 99 or opt["min_span_px"] < 0:
+        raise ValueError("Training.mono_sweep needs 0 < p1 < p2 <= 2047, 0 <= uniqueness_ratio <= 99 and min_span_px >= 0, got "
+                         f"p1 {opt['p1']}, p2 {opt['p2']}, uniqueness_ratio {opt['uniqueness_ratio']}, min_span_px {opt['min_span_px']}")
+    return opt
+
+
+def merge_sweep_depth(sweep_depth, sweep_valid, gt_img, rgb_boundary_threshold, fallback):
+    """The seed depth of a swept keyframe: the sweep's where it is valid and the pixel passes the RGB boundary threshold, else the fallback."""
+    use = sweep_valid & (gt_img.sum(dim=0) > rgb_boundary_threshold)
+    return torch.where(use, sweep_depth, fallback)
+
+
 class FrontEnd:
     MIN_KEYFRAME_GAP = 5          # a keyframe at the latest every five frames (utils/slam_frontend.py:739)
 
@@ -76,6 +107,8 @@ class FrontEnd:
         self.log = []
         self.init_done_at = None
         self.resets = 0                    # monocular input: how often the map was started over (a failed initialisation)
+        self.mono_sweep = mono_sweep_options(training)      # None: a monocular keyframe is seeded the reference's way alone
+        self._sweeper, self._sweep_events, self._sweep_shares = None, [], []
 
     def set_hyperparams(self):
         """:115-126."""
@@ -113,10 +146,52 @@ class FrontEnd:
         if depth is None:
             return (2.0 + 0.3 * noise) * (gt_img.sum(dim=0) > threshold)
         seed_depth, stats = kf.mono_keyframe_depth(depth, opacity, gt_img, threshold, noise)
-        if int(stats.view(torch.int32)[2]) < 2:
+        if self.mono_sweep is None:
+            n_valid = int(stats.view(torch.int32)[2])
+        else:                                                 # the same one host read, all three words of it
+            median, _, n_valid = stats.view(torch.int32).tolist()
+            median = struct.unpack("<f", struct.pack("<i", median))[0]
+        if n_valid < 2:
             self.reset = True
             self.log.append(("reset", "no valid depth to seed a keyframe from"))
+        elif self.mono_sweep is not None:
+            seed_depth = self._sweep_seed_depth(gt_img, seed_depth, median, threshold)
         return seed_depth
+
+    def _sweep_seed_depth(self, gt_img, fallback, median, threshold):
+        """``Training.mono_sweep``: the new keyframe's depth from a plane sweep (slam/sweep.py, include/multiview_depth.h) against the most
+        recent `partners` keyframes of the window under their tracked poses, inverse depth 0 .. 1 / (near * median) in 63 steps. Where the
+        sweep is valid and the pixel passes the RGB boundary threshold its depth is the seed; everywhere else the fallback stands. Nothing
+        is read by the host: the valid share is kept on the device and the time in events until the run's summary asks (sweep_summary)."""
+        opt = self.mono_sweep
+        newest = self.cameras[self.current_window[0]]
+        partners = [self.cameras[k] for k in self.current_window[1:1 + opt["partners"]] if self.cameras[k].original_image is not None]
+        if not partners or not (median > 0.0 and median < float("inf")):
+            return fallback
+        if self._sweeper is None:
+            from .sweep import PlaneSweep, relative_transforms
+            self._sweeper = PlaneSweep(p1=opt["p1"], p2=opt["p2"], uniqueness_ratio=opt["uniqueness_ratio"], min_span_px=opt["min_span_px"],
+                                       device=gt_img.device)
+            self._relative_transforms = relative_transforms
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        begin.record()
+        swept = self._sweeper.sweep(gt_img, [cam.original_image for cam in partners], (newest.fx, newest.fy, newest.cx, newest.cy),
+                                    self._relative_transforms(newest, partners), 0.0, 1.0 / (opt["near"] * median * 63.0))
+        end.record()
+        self._sweep_events.append((begin, end))
+        self._sweep_shares.append(swept["valid"].float().mean())
+        return merge_sweep_depth(swept["depth"], swept["valid"], gt_img, threshold, fallback)
+
+    def sweep_summary(self):
+        """The `sweep` block of the run result (None with the option off): keyframes swept, their mean valid share, device ms per keyframe."""
+        if self.mono_sweep is None:
+            return None
+        n = len(self._sweep_events)
+        if n == 0:
+            return {"keyframes": 0, "valid_share": 0.0, "device_ms_per_keyframe": 0.0}
+        torch.cuda.synchronize(self.device)
+        ms = sum(a.elapsed_time(b) for a, b in self._sweep_events)
+        return {"keyframes": n, "valid_share": float(torch.stack(self._sweep_shares).mean()), "device_ms_per_keyframe": ms / n}
 
     def initialize(self, frame_idx, viewpoint):
         """:189-207."""

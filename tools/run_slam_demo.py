@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """BASELINE config #4 in its asset-free form: the whole SLAM system (slam/system.py) on the synthetic RGB-D sequence (slam/dataset.py),
 static and dynamic, eager tracking and hipGraph tracking; prints ATE / PSNR / fps as one JSON document. With --monocular the static
-sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every frame's depth is None; the ATE is scale-aligned)."""
+sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every frame's depth is None; the ATE is scale-aligned); with
+--mono-sweep as well, new keyframes are seeded from a plane sweep over the window (Training.mono_sweep, slam/sweep.py) and the result has a
+`sweep` block."""
 import json
 import os
 import sys
@@ -20,12 +22,13 @@ save_map = sys.argv[sys.argv.index("--save-map") + 1] if "--save-map" in sys.arg
 only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
 profile = "--profile" in sys.argv
 monocular = "--monocular" in sys.argv
+mono_sweep = "--mono-sweep" in sys.argv
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
              ("dynamic_320x240_eager", True, False, 36, (320, 240)), ("dynamic_320x240_graph", True, True, 36, (320, 240)),
              ("dynamic_640x480_graph", True, True, 36, (640, 480)))
 if monocular:
-    scenarios = (("monocular_320x240_graph", False, True, 40, (320, 240)),)
+    scenarios = (("monocular_sweep_320x240_graph" if mono_sweep else "monocular_320x240_graph", False, True, 40, (320, 240)),)
 for name, dyn, graph, frames, wh in scenarios:
     if only not in name:
         continue
@@ -41,6 +44,8 @@ for name, dyn, graph, frames, wh in scenarios:
                                           "model_params": {"dynamic_model": dyn}})
     if monocular:      # (kf_interval 2, window 4: the window fills -- and the map counts as initialised -- within the 40 frames)
         cfg = merge_config(cfg, {"Dataset": {"sensor_type": "monocular"}, "Training": {"kf_interval": 2, "window_size": 4}})
+        if mono_sweep:
+            cfg = merge_config(cfg, {"Training": {"mono_sweep": {"enabled": True}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
