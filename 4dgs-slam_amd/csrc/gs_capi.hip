@@ -55,6 +55,8 @@
 #include "gs_lpips.h"
 #include "../../include/motion_segmentation.h"
 #include "gs_motion.h"
+#include "../../include/visual_odometry.h"
+#include "gs_odometry.h"
 
 namespace gsr {
 
@@ -135,10 +137,11 @@ static bool workspace_fits(const char* who, const char* size_fn, const void* wor
 
 // ---- per-kernel timing with events on the launch stream ---------------------------------------------------------
 enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE,
-                K_SWEEP_CENSUS, K_SWEEP_COST, K_SWEEP_PATHS, K_SWEEP_SELECT, K_COUNT };
+                K_SWEEP_CENSUS, K_SWEEP_COST, K_SWEEP_PATHS, K_SWEEP_SELECT, K_ODO_PYRAMID, K_ODO_SUMS, K_ODO_SOLVE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"preprocess_fwd", "scan", "scatter_instances", "sort_tiles",
                                                   "render_fwd", "render_bwd", "geometry_bwd", "knn_total", "frame_prepare",
-                                                  "sweep_census", "sweep_cost", "sweep_paths", "sweep_select"};
+                                                  "sweep_census", "sweep_cost", "sweep_paths", "sweep_select",
+                                                  "odometry_pyramid", "odometry_sums", "odometry_solve"};
 struct Profiler {
     unsigned mask = 0;   // bit i set => kernel id i is timed
     struct Rec { hipEvent_t a, b; int id; };
@@ -3591,6 +3594,128 @@ int gsr_motion_mask_clean(int width, int height, const unsigned char* candidate,
     hipLaunchKernelGGL(motion_label_filter_kernel, grid, block, 0, stream, n, min_area, (const int*)area, labels, a, counts);
     GSR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(motion_morph_kernel, grid, block, 0, stream, width, height, grow_radius, 0, (const unsigned char*)a, moving, motion, counts + 3);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// a pyramid buffer of gsr_odometry_pyramid: OdoPyramidHead | per level I [h, w] floats | D [h, w] floats; every part starts on a multiple of 16 bytes
+struct OdoPyramidLayout { OdoPyramidHead* head; int w[ODO_MAX_LEVELS], h[ODO_MAX_LEVELS]; float* I[ODO_MAX_LEVELS]; float* D[ODO_MAX_LEVELS]; size_t bytes; };
+static bool odo_pyramid_layout(int width, int height, int levels, const void* buffer, OdoPyramidLayout& l)
+{
+    if (width < 1 || height < 1 || levels < 1 || levels > ODO_MAX_LEVELS || (long long)width * height >= 0x80000000LL) return false;
+    if ((width >> (levels - 1)) < ODO_MIN_COARSEST || (height >> (levels - 1)) < ODO_MIN_COARSEST) return false;
+    Carver c(buffer, 16);
+    l.head = c.take<OdoPyramidHead>(1);
+    for (int k = 0; k < levels; ++k) {
+        l.w[k] = width >> k;
+        l.h[k] = height >> k;
+        l.I[k] = c.take<float>((size_t)l.w[k] * l.h[k]);
+        l.D[k] = c.take<float>((size_t)l.w[k] * l.h[k]);
+    }
+    l.bytes = c.bytes_padded();
+    return true;
+}
+static const char* const kOdoSizeText = "levels must be in [1, 6], the coarsest level at least 8 x 8 and width * height below 2^31";
+
+size_t gsr_odometry_pyramid_size(int width, int height, int levels)
+{
+    OdoPyramidLayout l;
+    return odo_pyramid_layout(width, height, levels, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_odometry_pyramid(int width, int height, int levels, const float* image, const float* depth, const unsigned char* mask,
+                         float depth_min, float depth_max, void* pyramid, size_t pyramid_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_odometry_pyramid: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    OdoPyramidLayout l;
+    if (!odo_pyramid_layout(width, height, levels, pyramid, l)) return fail(kOdoSizeText);
+    if (!(depth_min >= 0.f) || !(depth_max >= depth_min)) return fail("0 <= depth_min <= depth_max must hold");
+    if (!image || !pyramid) return fail("image and pyramid must not be NULL");
+    if (!workspace_fits("gsr_odometry_pyramid", "gsr_odometry_pyramid_size", pyramid, pyramid_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    ScopedKernelTimer tm(K_ODO_PYRAMID, stream);
+    GSR_HIP_CHECK(hipMemsetAsync(l.head, 0, sizeof(OdoPyramidHead), stream));
+    auto blocks = [](int w, int h) { return dim3((unsigned)(((size_t)w * h + ODO_BLOCK - 1) / ODO_BLOCK)); };
+    hipLaunchKernelGGL(odo_level0_kernel, blocks(width, height), dim3(ODO_BLOCK), 0, stream, width, height, image, depth, mask, depth_min,
+                       depth_max, l.I[0], l.D[0], l.head);
+    GSR_HIP_CHECK(hipGetLastError());
+    for (int k = 1; k < levels; ++k) {
+        hipLaunchKernelGGL(odo_down_kernel, blocks(l.w[k], l.h[k]), dim3(ODO_BLOCK), 0, stream, l.w[k], l.h[k], l.w[k - 1], (const float*)l.I[k - 1],
+                           (const float*)l.D[k - 1], l.I[k], l.D[k]);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// workspace of gsr_odometry_align: OdoHead | the slab [blocks of level 0, 32] doubles
+struct OdoAlignLayout { OdoHead* head; double* slab; size_t bytes; };
+static unsigned odo_blocks(int w, int h) { return (unsigned)std::min<size_t>(((size_t)w * h + ODO_BLOCK - 1) / ODO_BLOCK, ODO_MAX_BLOCKS); }
+static bool odo_align_layout(int width, int height, int levels, const void* workspace, OdoAlignLayout& l)
+{
+    OdoPyramidLayout p;
+    if (!odo_pyramid_layout(width, height, levels, nullptr, p)) return false;
+    Carver c(workspace, 16);
+    l.head = c.take<OdoHead>(1);
+    l.slab = c.take<double>((size_t)odo_blocks(width, height) * MOTION_ROW);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_odometry_align_workspace_size(int width, int height, int levels)
+{
+    OdoAlignLayout l;
+    return odo_align_layout(width, height, levels, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_odometry_align(int width, int height, int levels, float fx, float fy, float cx, float cy, const void* previous, const void* current,
+                       const float* T_init, const int* iters, float nu, float sigma_init, float sigma_min, float min_share, float max_last_step,
+                       float max_translation, float max_rotation, float* T, double* stats, double* trace, void* workspace,
+                       size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_odometry_align: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    OdoAlignLayout l;
+    OdoPyramidLayout P, C;
+    if (!odo_align_layout(width, height, levels, workspace, l) || !odo_pyramid_layout(width, height, levels, previous, P) ||
+        !odo_pyramid_layout(width, height, levels, current, C))
+        return fail(kOdoSizeText);
+    if (!(fx > 0.f && fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail("fx and fy must be positive and the intrinsics finite");
+    if (!iters) return fail("iters must not be NULL");
+    for (int k = 0; k < levels; ++k)
+        if (iters[k] < 0 || iters[k] > 64) return fail("iters[" + std::to_string(k) + "] must be in [0, 64], got " + std::to_string(iters[k]));
+    if (!(nu > 0.f) || !std::isfinite(nu) || !(sigma_init > 0.f) || !std::isfinite(sigma_init) || !(sigma_min > 0.f) || !std::isfinite(sigma_min))
+        return fail("nu, sigma_init and sigma_min must be positive and finite");
+    if (!(min_share >= 0.f && min_share <= 1.f) || !(max_last_step >= 0.f) || !(max_translation >= 0.f) || !(max_rotation >= 0.f))
+        return fail("min_share must be in [0, 1] and max_last_step, max_translation, max_rotation must not be negative");
+    if (!previous || !current || !T || !stats || !workspace) return fail("previous, current, T, stats and workspace must not be NULL");
+    if (!workspace_fits("gsr_odometry_align", "gsr_odometry_align_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+        hipLaunchKernelGGL(odo_init_kernel, dim3(1), dim3(64), 0, stream, T_init, sigma_init, l.head);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    int pass = 0;
+    for (int k = levels - 1; k >= 0; --k) {
+        const float scale = 1.f / (float)(1 << k);                                  // a power of two: the products below are exact
+        const OdoLevel L{P.w[k], P.h[k], fx * scale, fy * scale, (float)(((double)cx + 0.5) * scale - 0.5), (float)(((double)cy + 0.5) * scale - 0.5),
+                         P.I[k], P.D[k], C.I[k]};
+        const unsigned blocks = odo_blocks(L.w, L.h);
+        for (int it = 0; it < iters[k]; ++it, ++pass) {
+            {
+                ScopedKernelTimer tm(K_ODO_SUMS, stream);
+                hipLaunchKernelGGL(odo_sums_kernel, dim3(blocks), dim3(ODO_BLOCK), 0, stream, L, nu, (const OdoHead*)l.head, l.slab);
+                GSR_HIP_CHECK(hipGetLastError());
+            }
+            ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+            hipLaunchKernelGGL(odo_solve_kernel, dim3(1), dim3(ODO_BLOCK), 0, stream, (int)blocks, (const double*)l.slab, l.head, sigma_min, k,
+                               trace ? trace + (size_t)pass * MOTION_ROW : (double*)nullptr);
+            GSR_HIP_CHECK(hipGetLastError());
+        }
+    }
+    ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+    hipLaunchKernelGGL(odo_finish_kernel, dim3(1), dim3(64), 0, stream, (const OdoHead*)l.head, (const OdoPyramidHead*)P.head, min_share, max_last_step,
+                       max_translation, max_rotation, T, stats);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -283,23 +283,80 @@ __device__ inline void motion_se3_exp(const double xi[6], double E[16])
     E[15] = 1.0;
 }
 
-// One block. Adds the slab's rows in index order (column k by thread k), solves (H + 1e-9 tr(H) / 6 I) xi = -g by Cholesky, T <- exp(xi) T;
-// a matrix that is not positive definite (an empty fit set) leaves T as it is. Zeroes the histogram for the next pass.
-__global__ void __launch_bounds__(MOTION_BLOCK) motion_solve_kernel(int rows, const double* __restrict__ slab, MotionHead* head, double* __restrict__ trace_row)
+// Shared with gs_odometry.h: the slab sum, the regularised 6 x 6 solve and the pose update of one Gauss-Newton pass.
+constexpr int MOTION_SLAB_TILE = 128;                           // rows staged in LDS at a time: the loads run in parallel, the adds in row order
+struct MotionSolveLds { double A[6][6], g[6], xi[6], E[16], Tn[16]; };     // thread 0's own: indexed by loop variables, and LDS is nearer than scratch
+
+// Every thread of the block calls it. Adds the slab's rows in index order, column k by thread k; threads k < MOTION_ROW return column k's sum.
+// tile: MOTION_SLAB_TILE * MOTION_ROW doubles of LDS.
+__device__ __forceinline__ double motion_slab_sum(int rows, const double* __restrict__ slab, double* tile)
 {
-    constexpr int TILE = 128;                                   // rows staged in LDS at a time: the loads run in parallel, the adds in row order
-    __shared__ double tile[TILE * MOTION_ROW];
-    __shared__ double sums[MOTION_ROW];
-    __shared__ double A[6][6], g[6], xi[6], E[16], Tn[16];      // thread 0's own: indexed by loop variables, and LDS is nearer than scratch
     double s = 0.0;
-    for (int r0 = 0; r0 < rows; r0 += TILE) {
-        const int count = min(TILE, rows - r0) * MOTION_ROW;
+    for (int r0 = 0; r0 < rows; r0 += MOTION_SLAB_TILE) {
+        const int count = min(MOTION_SLAB_TILE, rows - r0) * MOTION_ROW;
         for (int k = threadIdx.x; k < count; k += MOTION_BLOCK) tile[k] = slab[(size_t)r0 * MOTION_ROW + k];
         __syncthreads();
         if (threadIdx.x < MOTION_ROW)
             for (int k = threadIdx.x; k < count; k += MOTION_ROW) s += tile[k];
         __syncthreads();
     }
+    return s;
+}
+
+// One thread. sums: the 21 entries of H (upper triangle, row-major), then the 6 of g. Solves (H + 1e-9 tr(H) / 6 I) xi = -g by Cholesky and
+// sets T <- exp(xi) T; xi stays in L.xi. False, and T as it was, where the matrix is not positive definite or xi is not finite.
+__device__ inline bool motion_gauss_newton_step(const double* sums, double* T, MotionSolveLds& L)
+{
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) { L.A[i][j] = sums[k]; L.A[j][i] = sums[k]; ++k; }
+    double tr = 0.0;
+    for (int i = 0; i < 6; ++i) { tr += L.A[i][i]; L.g[i] = -sums[21 + i]; }
+    for (int i = 0; i < 6; ++i) L.A[i][i] += 1e-9 * tr / 6.0;
+    bool ok = true;                                             // A = L L^T, L in the lower triangle
+    for (int j = 0; j < 6 && ok; ++j) {
+        double d = L.A[j][j];
+        for (int m = 0; m < j; ++m) d -= L.A[j][m] * L.A[j][m];
+        if (!(d > 0.0)) { ok = false; break; }
+        L.A[j][j] = sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double s = L.A[i][j];
+            for (int m = 0; m < j; ++m) s -= L.A[i][m] * L.A[j][m];
+            L.A[i][j] = s / L.A[j][j];
+        }
+    }
+    if (!ok) return false;
+    for (int i = 0; i < 6; ++i) {
+        double s = L.g[i];
+        for (int m = 0; m < i; ++m) s -= L.A[i][m] * L.xi[m];
+        L.xi[i] = s / L.A[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double s = L.xi[i];
+        for (int m = i + 1; m < 6; ++m) s -= L.A[m][i] * L.xi[m];
+        L.xi[i] = s / L.A[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!isfinite(L.xi[i])) return false;
+    motion_se3_exp(L.xi, L.E);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+            for (int m = 0; m < 4; ++m) s += L.E[4 * i + m] * T[4 * m + j];
+            L.Tn[4 * i + j] = s;
+        }
+    for (int i = 0; i < 16; ++i) T[i] = L.Tn[i];
+    return true;
+}
+
+// One block. Adds the slab's rows in index order (column k by thread k), solves (H + 1e-9 tr(H) / 6 I) xi = -g by Cholesky, T <- exp(xi) T;
+// a matrix that is not positive definite (an empty fit set) leaves T as it is. Zeroes the histogram for the next pass.
+__global__ void __launch_bounds__(MOTION_BLOCK) motion_solve_kernel(int rows, const double* __restrict__ slab, MotionHead* head, double* __restrict__ trace_row)
+{
+    __shared__ double tile[MOTION_SLAB_TILE * MOTION_ROW];
+    __shared__ double sums[MOTION_ROW];
+    __shared__ MotionSolveLds L;
+    const double s = motion_slab_sum(rows, slab, tile);
     if (threadIdx.x < MOTION_ROW) sums[threadIdx.x] = s;
     for (int k = threadIdx.x; k < MOTION_BINS; k += MOTION_BLOCK) head->hist[k] = 0;
     __syncthreads();
@@ -309,45 +366,7 @@ __global__ void __launch_bounds__(MOTION_BLOCK) motion_solve_kernel(int rows, co
     if (trace_row)
         for (int k = 0; k < MOTION_ROW; ++k) trace_row[k] = sums[k];
     head->sum_w = sums[27];
-    int k = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) { A[i][j] = sums[k]; A[j][i] = sums[k]; ++k; }
-    double tr = 0.0;
-    for (int i = 0; i < 6; ++i) { tr += A[i][i]; g[i] = -sums[21 + i]; }
-    for (int i = 0; i < 6; ++i) A[i][i] += 1e-9 * tr / 6.0;
-    bool ok = true;                                             // A = L L^T, L in the lower triangle
-    for (int j = 0; j < 6 && ok; ++j) {
-        double d = A[j][j];
-        for (int m = 0; m < j; ++m) d -= A[j][m] * A[j][m];
-        if (!(d > 0.0)) { ok = false; break; }
-        A[j][j] = sqrt(d);
-        for (int i = j + 1; i < 6; ++i) {
-            double s = A[i][j];
-            for (int m = 0; m < j; ++m) s -= A[i][m] * A[j][m];
-            A[i][j] = s / A[j][j];
-        }
-    }
-    if (!ok) return;
-    for (int i = 0; i < 6; ++i) {
-        double s = g[i];
-        for (int m = 0; m < i; ++m) s -= A[i][m] * xi[m];
-        xi[i] = s / A[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double s = xi[i];
-        for (int m = i + 1; m < 6; ++m) s -= A[m][i] * xi[m];
-        xi[i] = s / A[i][i];
-    }
-    for (int i = 0; i < 6; ++i)
-        if (!isfinite(xi[i])) return;
-    motion_se3_exp(xi, E);
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-            for (int m = 0; m < 4; ++m) s += E[4 * i + m] * head->T[4 * m + j];
-            Tn[4 * i + j] = s;
-        }
-    for (int i = 0; i < 16; ++i) head->T[i] = Tn[i];
+    motion_gauss_newton_step(sums, head->T, L);
 }
 
 // After the residual pass under the final T: c from its histogram, the outputs T and stats, and candidate = usable and residual > max(residual_px, c).

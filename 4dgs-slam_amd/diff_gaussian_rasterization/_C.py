@@ -345,7 +345,8 @@ def debug_read_state(P, R, W, H, geomBuffer, binningBuffer, imageBuffer):
 
 
 KERNEL_IDS = {"preprocess_fwd": 0, "scan": 1, "scatter_instances": 2, "sort_tiles": 3, "render_fwd": 4, "render_bwd": 5,
-              "geometry_bwd": 6, "frame_prepare": 8, "sweep_census": 9, "sweep_cost": 10, "sweep_paths": 11, "sweep_select": 12}
+              "geometry_bwd": 6, "frame_prepare": 8, "sweep_census": 9, "sweep_cost": 10, "sweep_paths": 11, "sweep_select": 12,
+              "odometry_pyramid": 13, "odometry_sums": 14, "odometry_solve": 15}
 
 
 def profile_enable(kernels=True):
@@ -367,7 +368,7 @@ def profile_reset():
 
 def profile_read():
     lib = load_library()
-    cap = 16
+    cap = 32
     names = (C.c_char_p * cap)()
     ms = (C.c_float * cap)()
     calls = (C.c_int * cap)()

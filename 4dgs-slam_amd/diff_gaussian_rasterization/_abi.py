@@ -260,6 +260,11 @@ FUNCTIONS = {
     "gsr_flow_rigid_fit": (i, [i, i, f, f, f, f] + [vp] * 5 + [i] + [f] * 5 + [vp] * 6 + [sz, vp]),
     "gsr_motion_mask_clean_workspace_size": (sz, [i, i]),
     "gsr_motion_mask_clean": (i, [i, i, vp, i, i, i] + [vp] * 5 + [sz, vp]),
+    # visual_odometry.h
+    "gsr_odometry_pyramid_size": (sz, [i, i, i]),
+    "gsr_odometry_pyramid": (i, [i, i, i, vp, vp, vp, f, f, vp, sz, vp]),
+    "gsr_odometry_align_workspace_size": (sz, [i, i, i]),
+    "gsr_odometry_align": (i, [i, i, i, f, f, f, f, vp, vp, vp, P(i)] + [f] * 7 + [vp] * 4 + [sz, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

@@ -15,6 +15,7 @@ How a frame is processed:
              whether the frame becomes a keyframe (``slam/keyframes.py``; ONE host transfer per frame);
   insert     the window update is computed on the device and read back as two indices; the back-end maps the new keyframe.
 """
+import math
 import struct
 import time
 
@@ -85,6 +86,58 @@ def merge_sweep_depth(sweep_depth, sweep_valid, gt_img, rgb_boundary_threshold, 
     return torch.where(use, sweep_depth, fallback)
 
 
+POSE_PRIOR_DEFAULTS = {"enabled": False, "levels": 3, "iters": [5, 7, 10], "nu": 5.0, "sigma_init": 0.1, "sigma_min": 1e-3, "min_share": 0.3,
+                       "max_last_step": 1e-2, "max_translation": 0.5, "max_rotation": 20.0, "depth_min": 0.0, "depth_max": 1e6,
+                       "constant_velocity": False}
+
+
+def pose_prior_options(training):
+    """The ``Training.pose_prior`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
+    alignment cannot take are refused here, before the run starts. max_translation is in metres (monocular input: map units), max_rotation
+    in degrees; iters lists the passes per level, finest first."""
+    block = training.get("pose_prior")
+    if not block or not block.get("enabled", False):
+        return None
+    unknown = sorted(set(block) - set(POSE_PRIOR_DEFAULTS))
+    if unknown:
+        raise ValueError(f"Training.pose_prior: unknown keys {unknown} (known: {sorted(POSE_PRIOR_DEFAULTS)})")
+    opt = dict(POSE_PRIOR_DEFAULTS, **block)
+    opt["enabled"], opt["constant_velocity"], opt["levels"] = True, bool(opt["constant_velocity"]), int(opt["levels"])
+    if not 1 <= opt["levels"] <= 6:
+        raise ValueError(f"Training.pose_prior.levels must be 1 to 6, got {opt['levels']}")
+    if "iters" not in block and opt["levels"] != POSE_PRIOR_DEFAULTS["levels"]:
+        raise ValueError(f"Training.pose_prior.iters must be given with levels = {opt['levels']}: one count per level, finest first")
+    if isinstance(opt["iters"], (str, bytes)) or not hasattr(opt["iters"], "__len__"):
+        raise ValueError(f"Training.pose_prior.iters must be a list of {opt['levels']} pass counts, finest first, got {opt['iters']!r}")
+    opt["iters"] = [int(v) for v in opt["iters"]]
+    if len(opt["iters"]) != opt["levels"] or not all(0 <= v <= 64 for v in opt["iters"]):
+        raise ValueError(f"Training.pose_prior.iters must hold {opt['levels']} pass counts in [0, 64], finest first, got {opt['iters']}")
+    for key in ("nu", "sigma_init", "sigma_min", "min_share", "max_last_step", "max_translation", "max_rotation", "depth_min", "depth_max"):
+        opt[key] = float(opt[key])
+        if math.isnan(opt[key]):
+            raise ValueError(f"Training.pose_prior.{key} must be a number, got nan")
+    for key in ("nu", "sigma_init", "sigma_min"):
+        if not (0.0 < opt[key] < math.inf):
+            raise ValueError(f"Training.pose_prior.{key} must be positive and finite, got {opt[key]}")
+    if not 0.0 <= opt["min_share"] <= 1.0:
+        raise ValueError(f"Training.pose_prior.min_share must be in [0, 1], got {opt['min_share']}")
+    for key in ("max_last_step", "max_translation", "max_rotation"):
+        if opt[key] < 0.0:
+            raise ValueError(f"Training.pose_prior.{key} must not be negative, got {opt[key]}")
+    if opt["max_rotation"] > 180.0:
+        raise ValueError(f"Training.pose_prior.max_rotation is in degrees and must not exceed 180, got {opt['max_rotation']}")
+    if not 0.0 <= opt["depth_min"] <= opt["depth_max"]:
+        raise ValueError(f"Training.pose_prior needs 0 <= depth_min <= depth_max, got {opt['depth_min']} and {opt['depth_max']}")
+    return opt
+
+
+def compose_pose(T, R_prev, t_prev):
+    """The world-to-camera pose T W2C_prev of the current frame from the relative motion T [4, 4] (previous camera -> current camera) and the
+    previous frame's world-to-camera R [3, 3], t [3]: R = T_R R_prev, t = T_R t_prev + T_t. Tensor operations only."""
+    T_R = T[:3, :3].to(R_prev.dtype)
+    return T_R @ R_prev, T_R @ t_prev + T[:3, 3].to(t_prev.dtype)
+
+
 class FrontEnd:
     MIN_KEYFRAME_GAP = 5          # a keyframe at the latest every five frames (utils/slam_frontend.py:739)
 
@@ -109,6 +162,8 @@ class FrontEnd:
         self.resets = 0                    # monocular input: how often the map was started over (a failed initialisation)
         self.mono_sweep = mono_sweep_options(training)      # None: a monocular keyframe is seeded the reference's way alone
         self._sweeper, self._sweep_events, self._sweep_shares = None, [], []
+        self.pose_prior = pose_prior_options(training)      # None: a frame's tracking starts at the previous frame's pose, as in the reference
+        self._odometry = self._prior_motion = None
 
     def set_hyperparams(self):
         """:115-126."""
@@ -193,11 +248,50 @@ class FrontEnd:
         ms = sum(a.elapsed_time(b) for a, b in self._sweep_events)
         return {"keyframes": n, "valid_share": float(torch.stack(self._sweep_shares).mean()), "device_ms_per_keyframe": ms / n}
 
+    # ---- Training.pose_prior: the start of a frame's tracking from dense frame-to-frame alignment (slam/odometry.py) -------------------
+    def _prior_keep(self, viewpoint, render_pkg=None):
+        """Keep `viewpoint` as the frame the next one is aligned against. Its depth: the sensor's (RGB-D) or the matcher's (stereo); for
+        monocular input the depth of `render_pkg` where its opacity is above 0.5 (None: the map does not exist yet, nothing is kept)."""
+        if self._odometry is None:
+            from .odometry import DenseOdometry
+            options = {k: v for k, v in self.pose_prior.items() if k not in ("enabled", "constant_velocity")}
+            self._odometry = DenseOdometry(viewpoint.image_width, viewpoint.image_height, (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
+                                           device=self.device, **options)
+        if self.monocular:
+            depth = None if render_pkg is None else render_pkg["depth"].detach() * (render_pkg["opacity"].detach() > 0.5)
+        else:
+            depth = viewpoint.depth_device()
+        if depth is None:
+            self._odometry.drop()
+            return
+        mask = viewpoint.motion_mask if self.dynamic_model else None
+        self._odometry.keep(viewpoint.original_image, depth, mask)
+
+    def _prior_start(self, viewpoint, previous):
+        """Move `viewpoint` from the previous frame's pose W2C_prev to T W2C_prev, T the aligned motion (identity where the gate refused it:
+        the reference's start). Device tensors throughout; the host reads nothing."""
+        T_init = self._prior_motion if self.pose_prior["constant_velocity"] else None
+        T, _ = self._odometry.align(viewpoint.original_image, T_init)
+        self._prior_motion = T
+        viewpoint.update_RT(*compose_pose(T, previous.R, previous.T))
+
+    def odometry_summary(self):
+        """The `odometry` block of the run result (None with the option off): frames aligned, the accepted share, the mean inlier share,
+        device ms per frame."""
+        if self.pose_prior is None:
+            return None
+        if self._odometry is None:
+            return {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
+        return self._odometry.summary()
+
     def initialize(self, frame_idx, viewpoint):
         """:189-207."""
         self.kf_indices, self.iteration_count, self.occ_aware_visibility, self.current_window = [], 0, {}, []
         self.initialized, self.reset = not self.monocular, False
         viewpoint.update_RT(viewpoint.R_gt, viewpoint.T_gt)               # first frame at the ground-truth pose
+        if self.pose_prior is not None:                                   # a map that starts (over) drops the kept frame
+            self._prior_motion = None
+            self._prior_keep(viewpoint)
         seed_depth = self.add_new_keyframe(frame_idx, init=True)
         self.sync_backend(self.backend.handle_init(frame_idx, viewpoint, seed_depth))
 
@@ -217,6 +311,8 @@ class FrontEnd:
     def tracking(self, frame_idx, viewpoint, last_keyframe_idx=None):
         previous = self.cameras[frame_idx - self.use_every_n_frames]
         viewpoint.update_RT(previous.R, previous.T)
+        if self._odometry is not None and self._odometry.has_previous:
+            self._prior_start(viewpoint, previous)
         tracker = self._tracker_for_current_map(viewpoint)
         tracker.load(viewpoint)
         replayed = False
@@ -235,7 +331,10 @@ class FrontEnd:
                     break
         tracker.store(viewpoint)
         self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])        # :461
-        return render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
+        render_pkg = render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
+        if self.pose_prior is not None:
+            self._prior_keep(viewpoint, render_pkg)
+        return render_pkg
 
     # ---- keyframe management (:472-562): the decisions of the reference, computed by slam/keyframes.py -------------------------
     def is_keyframe(self, cur_frame_idx, last_keyframe_idx, cur_frame_visibility_filter, occ_aware_visibility):

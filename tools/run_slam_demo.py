@@ -3,7 +3,9 @@
 static and dynamic, eager tracking and hipGraph tracking; prints ATE / PSNR / fps as one JSON document. With --monocular the static
 sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every frame's depth is None; the ATE is scale-aligned); with
 --mono-sweep as well, new keyframes are seeded from a plane sweep over the window (Training.mono_sweep, slam/sweep.py) and the result has a
-`sweep` block."""
+`sweep` block. With --pose-prior every frame's tracking starts from the dense frame-to-frame alignment (Training.pose_prior,
+slam/odometry.py) and the result has an `odometry` block; --tracking-itr N sets Training.tracking_itr_num (default 60): a prior is worth
+most where the tracker is given few iterations."""
 import json
 import os
 import sys
@@ -23,6 +25,8 @@ only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
 profile = "--profile" in sys.argv
 monocular = "--monocular" in sys.argv
 mono_sweep = "--mono-sweep" in sys.argv
+pose_prior = "--pose-prior" in sys.argv
+tracking_itr = int(sys.argv[sys.argv.index("--tracking-itr") + 1]) if "--tracking-itr" in sys.argv else 60
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
              ("dynamic_320x240_eager", True, False, 36, (320, 240)), ("dynamic_320x240_graph", True, True, 36, (320, 240)),
@@ -35,7 +39,7 @@ for name, dyn, graph, frames, wh in scenarios:
     torch.manual_seed(0)
     ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=0.025 if wh[0] > 320 else 0.03,
                               sensor_depth=not monocular)
-    cfg = merge_config(default_config(), {"Training": {"init_itr_num": 400, "init_gaussian_update": 100, "init_gaussian_reset": 200, "tracking_itr_num": 60,
+    cfg = merge_config(default_config(), {"Training": {"init_itr_num": 400, "init_gaussian_update": 100, "init_gaussian_reset": 200, "tracking_itr_num": tracking_itr,
                                                        "static_map_iters": 30, "dynamic_map_iters": 80, "network_init_iters": 50, "gaussian_update_every": 60,
                                                        "gaussian_update_offset": 20, "tracking_graph": graph,
                                                        "fused_grad_accumulation": os.environ.get("GSR_FUSED_ACC", "1") == "1",
@@ -46,6 +50,8 @@ for name, dyn, graph, frames, wh in scenarios:
         cfg = merge_config(cfg, {"Dataset": {"sensor_type": "monocular"}, "Training": {"kf_interval": 2, "window_size": 4}})
         if mono_sweep:
             cfg = merge_config(cfg, {"Training": {"mono_sweep": {"enabled": True}}})
+    if pose_prior:
+        cfg = merge_config(cfg, {"Training": {"pose_prior": {"enabled": True}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
