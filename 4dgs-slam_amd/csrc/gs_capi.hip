@@ -42,6 +42,7 @@
 #include "gs_frame.h"
 #include "../../include/video_io.h"
 #include "gs_jpeg.h"
+#include "gs_png.h"
 #include "../../include/stereo_depth.h"
 #include "gs_stereo.h"
 #include "../../include/multiview_depth.h"
@@ -3064,6 +3065,72 @@ int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8,
     hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, coef, lengths, raw);
     GSR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)views), dim3(JPEG_SCAN_BLOCK), 0, stream, l.shape, raw, totals, scan, (long long)scan_stride, sizes);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_png_encode: the segments' staging slots [V, nseg, PNG_SLOT] bytes | their sizes [V, nseg] u32 | their Adler sums
+// [V, nseg, 2] u32 | their offsets in the stream [V, nseg] u32; every part starts on a multiple of 16 bytes
+struct PngLayout { PngShape shape; unsigned char* staging; uint32_t *seg_bytes, *seg_sums, *offsets; size_t bytes; long long bound; };
+static bool png_layout(int views, int width, int height, int kind, const void* workspace, PngLayout& l)
+{
+    if (views <= 0 || views > 65535 || width <= 0 || height <= 0 || (kind != 0 && kind != 1)) return false;
+    const long long D = kind == 0 ? 3 : 2, row = (long long)width * D + 1;
+    if (row > 0x7fffffffLL / height) return false;
+    const long long n = row * height, nseg = (n + PNG_SEG - 1) / PNG_SEG;
+    l.bound = PNG_HEAD + n + PNG_SEG_EXTRA * nseg + PNG_TAIL;
+    if (l.bound > 0x7fffffffLL) return false;                        // offsets and sizes are 32-bit
+    l.shape.W = width; l.shape.H = height; l.shape.D = (int)D; l.shape.kind = kind; l.shape.filter = 0;
+    l.shape.row = (int)row; l.shape.n = (int)n; l.shape.nseg = (int)nseg;
+    const size_t segments = (size_t)views * (size_t)nseg;
+    Carver c(workspace, 16);
+    l.staging = c.take<unsigned char>(segments * PNG_SLOT);
+    l.seg_bytes = c.take<uint32_t>(segments);
+    l.seg_sums = c.take<uint32_t>(segments * 2);
+    l.offsets = c.take<uint32_t>(segments);
+    l.bytes = c.bytes();
+    return true;
+}
+
+size_t gsr_png_workspace_size(int views, int width, int height, int kind)
+{
+    PngLayout l;
+    return png_layout(views, width, height, kind, nullptr, l) ? l.bytes : 0;
+}
+
+size_t gsr_png_stream_bound(int width, int height, int kind)
+{
+    PngLayout l;
+    return png_layout(1, width, height, kind, nullptr, l) ? (size_t)l.bound : 0;
+}
+
+int gsr_png_encode(int views, int width, int height, int kind, int filter, const void* pixels, unsigned char* out, int64_t out_stride, int* sizes,
+                   void* workspace, size_t workspace_bytes, void* stream_)
+{
+    if (kind != 0 && kind != 1) { g_last_error = "gsr_png_encode: kind must be 0 (8-bit RGB) or 1 (16-bit grey)"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (filter != 0 && filter != 2) { g_last_error = "gsr_png_encode: filter must be 0 (None) or 2 (Up)"; return GSR_ERR_INVALID_ARGUMENT; }
+    PngLayout l;
+    if (!png_layout(views, width, height, kind, workspace, l)) {
+        g_last_error = "gsr_png_encode: views must be in [1, 65535], width and height positive, and a view's stream bound (gsr_png_stream_bound) below 2^31";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    const char* const null_name = !pixels ? "pixels" : !out ? "out" : !sizes ? "sizes" : !workspace ? "workspace" : nullptr;
+    if (null_name) { g_last_error = std::string("gsr_png_encode: ") + null_name + " must not be NULL"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (out_stride < l.bound) {
+        g_last_error = "gsr_png_encode: out_stride must be at least gsr_png_stream_bound = " + std::to_string(l.bound) + " bytes, got " + std::to_string(out_stride);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!workspace_fits("gsr_png_encode", "gsr_png_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    l.shape.filter = filter;
+    hipStream_t stream = (hipStream_t)stream_;
+    const dim3 per_segment((unsigned)l.shape.nseg, (unsigned)views);
+    hipLaunchKernelGGL(png_segment_kernel, per_segment, dim3(PNG_BLOCK), 0, stream, l.shape, static_cast<const unsigned char*>(pixels), l.staging,
+                       l.seg_bytes, l.seg_sums);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(png_offsets_kernel, dim3((unsigned)views), dim3(PNG_SCAN_BLOCK), 0, stream, l.shape, l.seg_bytes, l.seg_sums, l.offsets, out,
+                       (long long)out_stride, sizes);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(png_gather_kernel, per_segment, dim3(PNG_BLOCK), 0, stream, l.shape, l.staging, l.seg_bytes, l.offsets, out, (long long)out_stride);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

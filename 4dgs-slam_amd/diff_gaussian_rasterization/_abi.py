@@ -20,6 +20,7 @@ GSR_KNN_MAX_K, GSR_KNN_MAX_DIM, GSR_BLEND_MAX_K = 32, 32, 8                     
 GSR_NODE_RADIUS_IS_LOG, GSR_NODE_WEIGHT_IS_LOGIT = 1, 2
 GSR_YOLO_MAX_LEVELS, GSR_YOLO_MAX_ANCHORS, GSR_YOLO_REG_MAX, GSR_YOLO_DET_HEAD = 4, 8192, 16, 7  # segmentation.h
 GSR_LPIPS_MAX_LEVELS, GSR_LPIPS_NORM_TORCHMETRICS, GSR_LPIPS_NORM_LPIPS = 8, 0, 1  # perceptual.h
+GSR_PNG_SEGMENT = 16384                                                           # video_io.h
 
 # ---- types (field names and order as in the headers; every pointer field is a plain address) -----------------------------------
 gsr_alloc_fn = C.CFUNCTYPE(vp, vp, sz)
@@ -235,6 +236,9 @@ FUNCTIONS = {
     # video_io.h
     "gsr_jpeg_workspace_size": (sz, [i, i, i]),
     "gsr_jpeg_encode": (i, [i, i, i, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "gsr_png_workspace_size": (sz, [i, i, i, i]),
+    "gsr_png_stream_bound": (sz, [i, i, i]),
+    "gsr_png_encode": (i, [i, i, i, i, i, vp, vp, i64, vp, vp, sz, vp]),
     # stereo_depth.h
     "gsr_stereo_workspace_size": (sz, [i, i, i]),
     "gsr_stereo_depth": (i, [i] * 7 + [f] + [vp] * 12 + [sz, vp]),

@@ -6,6 +6,8 @@ launch for the distinct times of a chunk (ControlNodes.begin_iteration(blend=...
 launch, copies the bytes into pinned ring buffers on a side stream and hands them to one writer thread (slam/png.py); the loop waits only
 when it must reuse a ring slot, and once at the end. write_video(...) sends the same exported bytes through the device's JPEG encoder
 (slam/mjpeg.py, gsr_jpeg_encode) instead and writes one Motion-JPEG AVI file per image kind; the host copies only the compressed bytes.
+write(..., device_png=True) does the same for the lossless files: the device's deflate encoder (slam/png_device.py, gsr_png_encode) makes
+each picture's zlib stream and the writer thread only frames and writes it.
 
 Camera paths are plain functions that return (poses, times): poses float32 [N, 4, 4] world-to-camera matrices on the host, times a list of
 floats in the map's normalised time. The reference's `novel=` argument of render() is dead code there and has no counterpart."""
@@ -255,14 +257,23 @@ class Playback:
     # -- files ----------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def write(self, poses, times, out_dir, depth16=False, depth_colour=True, depth_vmax=DEPTH_VMAX, depth_scale=DEPTH_SCALE, png_filter="up",
-              png_level=1, files=True):
+              png_level=1, files=True, device_png=False):
         """Render and write rgb/<stamp>.png, depth_vis/<stamp>.png (jet, 0 .. depth_vmax; depth_colour=False: not written) and, with
         depth16, depth/<stamp>.png (16 bit, depth * depth_scale) plus rgb.txt, depth.txt and groundtruth.txt, so that the folder is a TUM
         sequence; <stamp> as recorded.write_tum_sequence names frames. files=False runs everything but the encoding and the disk (for
-        measurements). Returns {"frames", "seconds", "fps", "writer_wait_s", "export_ms", "calibration"}."""
+        measurements). Returns {"frames", "seconds", "fps", "writer_wait_s", "export_ms", "calibration"}. device_png=True compresses on
+        the device instead (slam/png_device.py, one gsr_png_encode per chunk and image kind): the host copies only the compressed bytes and
+        the writer thread only frames them (png.assemble) and writes; the same file names, pixels and lists; the dict gains "encode_ms" and
+        "bytes" (the PNG bytes of all frames); files=False then still encodes. png_level has no meaning there and must be left alone."""
         from . import recorded
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("Playback.write allocates pinned buffers and synchronises with its writer: not while a graph is being captured")
+        if device_png:
+            if png_level != 1:
+                raise ValueError(f"png_level has no meaning with device_png (the device's encoder has one setting), got {png_level!r}")
+            if png_filter not in png.FILTERS:
+                raise ValueError(f"png_filter must be one of {sorted(png.FILTERS)}, got {png_filter!r}")
+            return self._write_device_png(poses, times, out_dir, depth16, depth_colour, depth_vmax, depth_scale, png_filter, files)
         dev, H, W = self.device, self.height, self.width
         t0 = _time.perf_counter()                                    # (the cameras and the buffers are part of the time reported)
         cams = self._cameras(poses, times)
@@ -345,6 +356,142 @@ class Playback:
                 "calibration": {"fx": float(k.fx), "fy": float(k.fy), "cx": float(k.cx), "cy": float(k.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
                                 "p2": 0.0, "k3": 0.0, "distorted": False, "width": W, "height": H, "depth_scale": float(depth_scale)}}
 
+    def _compressed(self, cams, kinds, shapes, cap, depth_vmax, depth_scale, encode, emit, check=None, name="playback-writer"):
+        """The loop write_video and write(device_png=True) share. Per chunk: one gsr_frame_export, then encode(kind, pixels [n, ...], out
+        [n, cap[kind]], sizes [n], stream) per image kind on the main stream; the chunk's sizes are copied on a side stream, and the ONE writer
+        thread, once they are on the host, runs check(sizes [kinds, n], first frame) (it may raise), copies just the used bytes and calls
+        emit(kind, frame, bytes) per picture. The loop waits only for a free slot and once at the end. Returns (writer_wait_s,
+        writer_wait_at_end_s, export_ms, encode_ms); the writer's first error is raised after the loop."""
+        dev = self.device
+        # a slot owns the exported bytes, the compressed bytes and their sizes on the device, and the pinned copies of the last two
+        slots = [{"dev": {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in kinds},
+                  "scan": {k: torch.empty((CHUNK, cap[k]), dtype=torch.uint8, device=dev) for k in kinds},
+                  "sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32, device=dev),
+                  "host": {k: torch.empty((CHUNK, cap[k]), dtype=torch.uint8).pin_memory() for k in kinds},
+                  "host_sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32).pin_memory()}
+                 for _ in range(min(RING, max(1, -(-len(cams) // CHUNK))))]
+        lut = torch.from_numpy(frame_io.jet_lut().copy()).to(dev)
+        free, jobs, errors = queue.Queue(), queue.Queue(), []
+        for s in slots:
+            free.put(s)
+        main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+
+        def writer():
+            while True:
+                job = jobs.get()
+                if job is None:
+                    return
+                slot, lo, n, sized = job
+                try:
+                    sized.synchronize()                              # the sizes are on the host: copy just the bytes that were used
+                    sizes = slot["host_sizes"].numpy()[:, :n].copy()
+                    if check is not None:
+                        check(sizes, lo)
+                    if errors:
+                        continue
+                    with torch.cuda.stream(side):
+                        for ki, k in enumerate(kinds):
+                            for v in range(n):
+                                slot["host"][k][v, :int(sizes[ki, v])].copy_(slot["scan"][k][v, :int(sizes[ki, v])], non_blocking=True)
+                        done = torch.cuda.Event()
+                        done.record(side)
+                    done.synchronize()
+                    for ki, k in enumerate(kinds):
+                        a = slot["host"][k].numpy()
+                        for v in range(n):
+                            emit(k, lo + v, a[v, :int(sizes[ki, v])].tobytes())
+                except BaseException as e:                           # surfaced by the caller after the loop
+                    errors.append(e)
+                finally:
+                    free.put(slot)
+
+        thread = threading.Thread(target=writer, name=name, daemon=True)
+        thread.start()
+        timing, export_timing = [], []
+        wait = 0.0
+        try:
+            for lo, colour, depth, _ in self._chunks(cams):
+                n = int(colour.shape[0])
+                w0 = _time.perf_counter()
+                slot = free.get()                                    # the only wait inside the loop: every slot is still with the writer
+                wait += _time.perf_counter() - w0
+                if errors:
+                    break
+                out = {k: t[:n] for k, t in slot["dev"].items()}
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record(main)
+                frame_io.frame_export(colour, depth, lut, depth_vmax, depth_scale, out["rgb"], out.get("depth_vis"), out.get("depth"), main)
+                ev[1].record(main)
+                for ki, k in enumerate(kinds):
+                    encode(k, out[k], slot["scan"][k][:n], slot["sizes"][ki, :n], main)
+                ev[2].record(main)
+                export_timing.append((ev[0], ev[1]))
+                timing.append((ev[1], ev[2]))
+                side.wait_event(ev[2])
+                with torch.cuda.stream(side):
+                    slot["host_sizes"].copy_(slot["sizes"], non_blocking=True)
+                    sized = torch.cuda.Event()
+                    sized.record(side)
+                jobs.put((slot, lo, n, sized))
+        finally:
+            jobs.put(None)
+            w0 = _time.perf_counter()
+            thread.join()                                            # the one wait at the end
+            wait_end = _time.perf_counter() - w0
+        if errors:
+            raise errors[0]
+        torch.cuda.synchronize(dev)
+        return wait, wait_end, sum(a.elapsed_time(b) for a, b in export_timing), sum(a.elapsed_time(b) for a, b in timing)
+
+    def _result(self, N, t0, wait, wait_end, export_ms, encode_ms, total, depth_scale, **more):
+        seconds = _time.perf_counter() - t0
+        k = self._like
+        return {"frames": N, "seconds": seconds, "fps": N / seconds if seconds > 0 else float("inf"), "writer_wait_s": wait,
+                "writer_wait_at_end_s": wait_end, "export_ms": export_ms, "export_ms_per_view": export_ms / max(N, 1), **more,
+                "bytes": total, "encode_ms": encode_ms, "encode_ms_per_view": encode_ms / max(N, 1),
+                "calibration": {"fx": float(k.fx), "fy": float(k.fy), "cx": float(k.cx), "cy": float(k.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
+                                "p2": 0.0, "k3": 0.0, "distorted": False, "width": self.width, "height": self.height,
+                                "depth_scale": float(depth_scale)}}
+
+    def _write_device_png(self, poses, times, out_dir, depth16, depth_colour, depth_vmax, depth_scale, png_filter, files):
+        """write(device_png=True): gsr_png_encode per chunk and image kind; the writer thread frames each stream as a file and writes it."""
+        from . import png_device, recorded
+        dev, H, W = self.device, self.height, self.width
+        t0 = _time.perf_counter()
+        cams = self._cameras(poses, times)
+        N = len(cams)
+        stamps = [recorded.tum_stamp(i) for i in range(N)]
+        kinds = ["rgb"] + (["depth_vis"] if depth_colour else []) + (["depth"] if depth16 else [])
+        if files:
+            for k in kinds:
+                os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+        u16 = getattr(torch, "uint16", torch.int16)
+        shapes = {"rgb": ((CHUNK, H, W, 3), torch.uint8), "depth_vis": ((CHUNK, H, W, 3), torch.uint8), "depth": ((CHUNK, H, W), u16)}
+        code = {k: 1 if k == "depth" else 0 for k in kinds}                       # the encoder's picture kind
+        cap = {k: png_device.png_stream_bound(W, H, code[k]) for k in kinds}      # the worst case: no picture can fail to fit
+        if min(cap.values()) == 0:
+            raise ValueError(f"Playback.write: {W} x {H} pictures are outside what the device's PNG encoder takes")
+        workspace = torch.empty(max(png_device.png_workspace_size(CHUNK, W, H, c) for c in set(code.values())), dtype=torch.uint8,
+                                device=dev)                                      # shared: the encodes run in stream order
+        total = [0]
+
+        def encode(k, pixels, out, sizes, main):
+            png_device.png_encode(pixels, out, sizes, png_filter, workspace, main)
+
+        def emit(k, i, stream):
+            data = png.assemble(W, H, code[k], stream)
+            total[0] += len(data)
+            if files:
+                with open(os.path.join(out_dir, k, stamps[i] + ".png"), "wb") as f:
+                    f.write(data)
+
+        timings = self._compressed(cams, kinds, shapes, cap, depth_vmax, depth_scale, encode, emit, name="playback-png-writer")
+        result = self._result(N, t0, *timings, total[0], depth_scale)                 # (the lists stay out of the time, as in write())
+        if files and depth16:
+            c2w = [np.linalg.inv(p) for p in torch.as_tensor(poses, dtype=torch.float32).numpy().astype(np.float64)]
+            recorded.write_tum_lists(out_dir, stamps, c2w, origin="played back from a saved map")
+        return result
+
     @torch.no_grad()
     def write_video(self, poses, times, out_dir, fps=30.0, quality=90, depth_colour=True, depth_vmax=DEPTH_VMAX, files=True, capacity=None):
         """Render and write rgb.avi and depth_vis.avi (jet, 0 .. depth_vmax; depth_colour=False: not written): Motion-JPEG in AVI 1.0
@@ -370,100 +517,28 @@ class Playback:
         if files:
             os.makedirs(out_dir, exist_ok=True)
             writers = {k: mjpeg.AviWriter(paths[k], W, H, fps) for k in kinds}
-        # a slot owns the exported bytes, the compressed bytes and their sizes on the device, and the pinned copies of the last two
-        slots = [{"dev": {k: torch.empty((CHUNK, H, W, 3), dtype=torch.uint8, device=dev) for k in kinds},
-                  "scan": {k: torch.empty((CHUNK, cap), dtype=torch.uint8, device=dev) for k in kinds},
-                  "sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32, device=dev),
-                  "host": {k: torch.empty((CHUNK, cap), dtype=torch.uint8).pin_memory() for k in kinds},
-                  "host_sizes": torch.empty((len(kinds), CHUNK), dtype=torch.int32).pin_memory()}
-                 for _ in range(min(RING, max(1, -(-N // CHUNK))))]
-        lut = torch.from_numpy(frame_io.jet_lut().copy()).to(dev)
         q_dev = torch.from_numpy(qtables.astype(np.int16)).to(dev)
         workspace = torch.empty(mjpeg.jpeg_workspace_size(CHUNK, W, H), dtype=torch.uint8, device=dev)   # shared: the encodes run in stream order
-        free, jobs, errors = queue.Queue(), queue.Queue(), []
         total = [0]
-        for s in slots:
-            free.put(s)
-        main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
 
-        def writer():
-            while True:
-                job = jobs.get()
-                if job is None:
-                    return
-                slot, lo, n, sized = job
-                try:
-                    sized.synchronize()                              # the sizes are on the host: copy just the bytes that were used
-                    sizes = slot["host_sizes"].numpy()[:, :n].copy()
-                    if (sizes < 0).any():
-                        ki, v = (int(a[0]) for a in np.nonzero(sizes < 0))
-                        raise RuntimeError(f"frame {lo + v} ({kinds[ki]}) needs {-int(sizes[ki, v])} bytes as a JPEG, its capacity is {cap}: "
-                                           f"pass a larger capacity or a lower quality")
-                    if errors:
-                        continue
-                    with torch.cuda.stream(side):
-                        for ki, k in enumerate(kinds):
-                            for v in range(n):
-                                slot["host"][k][v, :int(sizes[ki, v])].copy_(slot["scan"][k][v, :int(sizes[ki, v])], non_blocking=True)
-                        done = torch.cuda.Event()
-                        done.record(side)
-                    done.synchronize()
-                    for ki, k in enumerate(kinds):
-                        a = slot["host"][k].numpy()
-                        for v in range(n):
-                            total[0] += len(header) + int(sizes[ki, v]) + 2
-                            if files:
-                                writers[k].add(header + a[v, :int(sizes[ki, v])].tobytes() + mjpeg.EOI)
-                except BaseException as e:                           # surfaced by the caller after the loop
-                    errors.append(e)
-                finally:
-                    free.put(slot)
+        def encode(k, pixels, out, sizes, main):
+            mjpeg.jpeg_encode(pixels, q_dev, out, sizes, None, workspace, main)
 
-        thread = threading.Thread(target=writer, name="playback-video-writer", daemon=True)
-        thread.start()
-        timing, export_timing = [], []
-        wait = 0.0
+        def check(sizes, lo):
+            if (sizes < 0).any():
+                ki, v = (int(a[0]) for a in np.nonzero(sizes < 0))
+                raise RuntimeError(f"frame {lo + v} ({kinds[ki]}) needs {-int(sizes[ki, v])} bytes as a JPEG, its capacity is {cap}: "
+                                   f"pass a larger capacity or a lower quality")
+
+        def emit(k, i, scan):
+            total[0] += len(header) + len(scan) + 2
+            if files:
+                writers[k].add(header + scan + mjpeg.EOI)
+
         try:
-            for lo, colour, depth, _ in self._chunks(cams):
-                n = int(colour.shape[0])
-                w0 = _time.perf_counter()
-                slot = free.get()                                    # the only wait inside the loop: every slot is still with the writer
-                wait += _time.perf_counter() - w0
-                if errors:
-                    break
-                out = {k: t[:n] for k, t in slot["dev"].items()}
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                ev[0].record(main)
-                frame_io.frame_export(colour, depth, lut, depth_vmax, DEPTH_SCALE, out["rgb"], out.get("depth_vis"), None, main)
-                ev[1].record(main)
-                for ki, k in enumerate(kinds):
-                    mjpeg.jpeg_encode(out[k], q_dev, slot["scan"][k][:n], slot["sizes"][ki, :n], None, workspace, main)
-                ev[2].record(main)
-                export_timing.append((ev[0], ev[1]))
-                timing.append((ev[1], ev[2]))
-                side.wait_event(ev[2])
-                with torch.cuda.stream(side):
-                    slot["host_sizes"].copy_(slot["sizes"], non_blocking=True)
-                    sized = torch.cuda.Event()
-                    sized.record(side)
-                jobs.put((slot, lo, n, sized))
+            timings = self._compressed(cams, kinds, {k: ((CHUNK, H, W, 3), torch.uint8) for k in kinds}, {k: cap for k in kinds}, depth_vmax,
+                                       DEPTH_SCALE, encode, emit, check, name="playback-video-writer")
         finally:
-            jobs.put(None)
-            w0 = _time.perf_counter()
-            thread.join()                                            # the one wait at the end
-            wait_end = _time.perf_counter() - w0
             for w in writers.values():
                 w.close()
-        if errors:
-            raise errors[0]
-        torch.cuda.synchronize(dev)
-        seconds = _time.perf_counter() - t0
-        export_ms = sum(a.elapsed_time(b) for a, b in export_timing)
-        encode_ms = sum(a.elapsed_time(b) for a, b in timing)
-        k = self._like
-        return {"frames": N, "seconds": seconds, "fps": N / seconds if seconds > 0 else float("inf"), "writer_wait_s": wait,
-                "writer_wait_at_end_s": wait_end, "export_ms": export_ms, "export_ms_per_view": export_ms / max(N, 1),
-                "files": [paths[k] for k in kinds] if files else [], "bytes": total[0], "encode_ms": encode_ms,
-                "encode_ms_per_view": encode_ms / max(N, 1),
-                "calibration": {"fx": float(k.fx), "fy": float(k.fy), "cx": float(k.cx), "cy": float(k.cy), "k1": 0.0, "k2": 0.0, "p1": 0.0,
-                                "p2": 0.0, "k3": 0.0, "distorted": False, "width": W, "height": H, "depth_scale": float(DEPTH_SCALE)}}
+        return self._result(N, t0, *timings, total[0], DEPTH_SCALE, files=[paths[k] for k in kinds] if files else [])

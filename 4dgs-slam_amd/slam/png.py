@@ -1,6 +1,7 @@
 """A PNG writer for the two image kinds a playback produces: 8-bit RGB [H, W, 3] and 16-bit grey [H, W] (big-endian on disk). One IDAT chunk
 from a single zlib.compress call (which releases the GIL, so a writer thread does not hold up the loop that feeds it), every scanline
-with filter 0 (None) or filter 2 (Up, computed for the whole image with one numpy subtraction). numpy and zlib only."""
+with filter 0 (None) or filter 2 (Up, computed for the whole image with one numpy subtraction). assemble() frames a zlib stream that was
+made elsewhere (slam/png_device.py: on the device) as the same kind of file. numpy and zlib only."""
 import struct
 import zlib
 
@@ -39,6 +40,18 @@ def encode(image, filter="up", level=1):
         raw[:, 1:] = rows
     header = struct.pack(">IIBBBBB", W, H, depth, colour, 0, 0, 0)
     return SIGNATURE + _chunk(b"IHDR", header) + _chunk(b"IDAT", zlib.compress(raw, level)) + _chunk(b"IEND", b"")
+
+
+def assemble(width, height, kind, stream_bytes):
+    """The bytes of a PNG file whose one IDAT chunk is `stream_bytes`, a complete zlib stream of the filtered scanlines: kind 0 is 8-bit
+    RGB (colour type 2), kind 1 16-bit grey (colour type 0). Signature, IHDR, IDAT, IEND; the CRCs by zlib.crc32."""
+    if kind not in (0, 1):
+        raise ValueError(f"png.assemble: kind must be 0 (8-bit RGB) or 1 (16-bit grey), got {kind!r}")
+    if width < 1 or height < 1:
+        raise ValueError(f"png.assemble: empty image ({width} x {height})")
+    depth, colour = ((8, 2), (16, 0))[kind]
+    header = struct.pack(">IIBBBBB", width, height, depth, colour, 0, 0, 0)
+    return SIGNATURE + _chunk(b"IHDR", header) + _chunk(b"IDAT", bytes(stream_bytes)) + _chunk(b"IEND", b"")
 
 
 def write(path, image, filter="up", level=1):

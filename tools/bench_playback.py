@@ -8,7 +8,10 @@
 --video [--repeats R] [--quality Q]: the video mode instead. On the same map and path it alternates Playback.write (PNG files of rgb and
 depth_vis) and Playback.write_video (Motion-JPEG AVI, compressed on the device), each with files and with files=False, R times each, and
 times gsr_jpeg_encode by device events at V = 1 and 12; writes profiles/playback_video.json. --encode-only: only that last timing (the
-form to run under a kernel profiler)."""
+form to run under a kernel profiler).
+--device-png [--repeats R]: the lossless mode. On the same map and path it alternates Playback.write with the host's zlib and with
+device_png=True (gsr_png_encode), each without and with the 16-bit depth, R times each, and times gsr_png_encode by device events at V = 1
+and 12 for both picture kinds, with the bytes per picture beside zlib level 1's; writes profiles/playback_device_png.json."""
 import argparse
 import json
 import os
@@ -108,6 +111,60 @@ def video_mode(pb, poses, times, tmp, repeats, quality):
     return {"runs": runs, "summary": summary}
 
 
+def time_png_encode(colour, depth, repeats=20):
+    """Per picture kind: ms per call of gsr_png_encode (filter Up) on the exported bytes of the given views, by device events around `repeats`
+    back-to-back calls, and the stream bytes per view beside zlib level 1 on the same filtered bytes."""
+    import zlib
+    from slam import png, png_device
+    V, _, H, W = colour.shape
+    dev = colour.device
+    lut = torch.from_numpy(frame_io.jet_lut().copy()).to(dev)
+    rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+    vis, u16 = torch.empty_like(rgb), torch.empty((V, H, W), dtype=torch.int16, device=dev)
+    frame_io.frame_export(colour, depth, lut, DEPTH_VMAX, DEPTH_SCALE, rgb, vis, u16)
+    out = []
+    for name, pixels, kind in (("rgb", rgb, 0), ("depth_vis", vis, 0), ("depth", u16, 1)):
+        stream = torch.empty((V, png_device.png_stream_bound(W, H, kind)), dtype=torch.uint8, device=dev)
+        sizes = torch.empty((V,), dtype=torch.int32, device=dev)
+        ws = torch.empty(png_device.png_workspace_size(V, W, H, kind), dtype=torch.uint8, device=dev)
+        for _ in range(3):
+            png_device.png_encode(pixels, stream, sizes, "up", ws)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(repeats):
+            png_device.png_encode(pixels, stream, sizes, "up", ws)
+        b.record()
+        b.synchronize()
+        ms = a.elapsed_time(b) / repeats
+        host = pixels.cpu().numpy()
+        host = host.view(np.uint16) if kind == 1 else host
+        zl = [len(png.encode(host[v], "up", 1)) - 57 for v in range(V)]                  # the file less signature, IHDR, IEND and chunk framing
+        got = [int(v) for v in sizes.cpu()]
+        out.append({"picture": name, "views": V, "ms_per_call": ms, "us_per_view": ms * 1e3 / V, "stream_bytes_per_view": sum(got) / V,
+                    "zlib_level1_bytes_per_view": sum(zl) / V, "ratio": sum(got) / sum(zl), "raw_bytes_per_view": int(pixels[0].numel()) * pixels.element_size(),
+                    "workspace_bytes": int(ws.numel())})
+    return out
+
+
+def device_png_mode(pb, poses, times, tmp, repeats):
+    keep = ("frames", "seconds", "fps", "writer_wait_s", "writer_wait_at_end_s", "export_ms_per_view")
+    dkeep = keep + ("encode_ms_per_view", "bytes")
+    pb.write(poses[:24], times[:24], os.path.join(tmp, "warm_host"), depth16=True)       # first-use costs stay out of every figure
+    pb.write(poses[:24], times[:24], os.path.join(tmp, "warm_device"), depth16=True, device_png=True)
+    runs = {"host": [], "device": [], "host_depth16": [], "device_depth16": [], "device_no_files": []}
+    for r in range(repeats):
+        for d16 in (False, True):
+            tag = "_depth16" if d16 else ""
+            a = pb.write(poses, times, os.path.join(tmp, f"host{tag}{r}"), depth16=d16)
+            runs["host" + tag].append({k: a[k] for k in keep})
+            b = pb.write(poses, times, os.path.join(tmp, f"device{tag}{r}"), depth16=d16, device_png=True)
+            runs["device" + tag].append({k: b[k] for k in dkeep})
+        c = pb.write(poses, times, os.path.join(tmp, f"device_none{r}"), files=False, device_png=True)
+        runs["device_no_files"].append({k: c[k] for k in dkeep})
+    summary = {k: {"fps_min": min(x["fps"] for x in v), "fps_max": max(x["fps"] for x in v)} for k, v in runs.items()}
+    return {"runs": runs, "summary": summary}
+
+
 def yardstick(pb, poses, times, out_dir):
     """The frames as the code before this module could produce them: one render() per frame, torch's clamp / scale / permute / .cpu(), PIL's
     encoder, matplotlib's colormap for the depth picture."""
@@ -152,10 +209,14 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="default: profiles/playback.json, or profiles/playback_video.json with --video")
     ap.add_argument("--video", action="store_true", help="the video mode: PNG files and Motion-JPEG AVI files alternated on the same path")
     ap.add_argument("--encode-only", action="store_true", help="with --video: only the gsr_jpeg_encode timing")
+    ap.add_argument("--device-png", action="store_true", help="the lossless mode: PNG files by the host's zlib and by the device's encoder, alternated")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--quality", type=int, default=90)
     args = ap.parse_args(argv)
-    args.out = args.out or os.path.join(REPO, "profiles", "playback_video.json" if args.video else "playback.json")
+    if args.video and args.device_png:
+        ap.error("--video and --device-png are two modes: pick one")
+    args.out = args.out or os.path.join(REPO, "profiles", "playback_video.json" if args.video else
+                                        "playback_device_png.json" if args.device_png else "playback.json")
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         directory = args.map or build_map(os.path.join(tmp, "map"))
@@ -170,6 +231,16 @@ def main(argv=None):
                    "gsr_jpeg_encode": [time_encode(pb, colour[:1], depth[:1], args.quality), time_encode(pb, colour, depth, args.quality)]}
             if not args.encode_only:
                 out.update(video_mode(pb, poses, times, tmp, args.repeats, args.quality))
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+            print(json.dumps(out))
+            return
+        if args.device_png:
+            out = {"device": torch.cuda.get_device_name(0), "resolution": [pb.width, pb.height], "frames": args.frames,
+                   "gaussians": int(loaded.gaussians.get_xyz.shape[0]),
+                   "gsr_png_encode": [time_png_encode(colour[:1], depth[:1]), time_png_encode(colour, depth)]}
+            out.update(device_png_mode(pb, poses, times, tmp, args.repeats))
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
                 json.dump(out, f, indent=1)

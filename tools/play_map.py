@@ -5,7 +5,10 @@ writes rgb/*.png, depth_vis/*.png (jet, 0-6 m) and, with --depth16, depth/*.png 
 the frames written, the seconds, frames per second and the time the loop waited for the writer thread.
   play_map.py --map DIR --path ... --out DIR --video [--fps F] [--quality Q] [--no-depth-vis]
 writes rgb.avi and depth_vis.avi instead: Motion-JPEG in AVI, compressed on the device (slam/mjpeg.py); the JSON line gains "video": true,
-"bytes" and "encode_ms"."""
+"bytes" and "encode_ms".
+  play_map.py --map DIR --path ... --out DIR --device-png [--depth16] [--no-depth-vis]
+writes the same PNG files and lists as the first form, compressed on the device (slam/png_device.py); the JSON line gains
+"device_png": true, "bytes" and "encode_ms"."""
 import argparse
 import json
 import os
@@ -24,6 +27,7 @@ def main(argv=None):
     ap.add_argument("--depth16", action="store_true", help="also write 16-bit depth and the TUM lists")
     ap.add_argument("--no-depth-vis", action="store_true", help="do not write the jet-coloured depth pictures")
     ap.add_argument("--video", action="store_true", help="write Motion-JPEG AVI files (rgb.avi, depth_vis.avi) instead of PNG folders")
+    ap.add_argument("--device-png", action="store_true", help="compress the PNG files on the device instead of with the host's zlib")
     ap.add_argument("--fps", type=float, default=30.0, help="frame rate of the video files")
     ap.add_argument("--quality", type=int, default=90, help="JPEG quality of the video frames, 1 .. 100")
     ap.add_argument("--device", default="cuda:0")
@@ -34,12 +38,16 @@ def main(argv=None):
     poses, times = parse_path(loaded, args.path)
     if args.video and args.depth16:
         ap.error("--depth16 has no video form: the 16-bit depth is written as PNG files only")
+    if args.video and args.device_png:
+        ap.error("--device-png compresses PNG files: it does not go with --video")
     extra = {}
     if args.video:
         res = Playback(loaded).write_video(poses, times, args.out, fps=args.fps, quality=args.quality, depth_colour=not args.no_depth_vis)
         extra = {"video": True, "bytes": res["bytes"], "encode_ms": res["encode_ms"]}
     else:
-        res = Playback(loaded).write(poses, times, args.out, depth16=args.depth16, depth_colour=not args.no_depth_vis)
+        res = Playback(loaded).write(poses, times, args.out, depth16=args.depth16, depth_colour=not args.no_depth_vis, device_png=args.device_png)
+        if args.device_png:
+            extra = {"device_png": True, "bytes": res["bytes"], "encode_ms": res["encode_ms"]}
     print(json.dumps({"map": args.map, "path": args.path, "out": args.out, "frames": res["frames"], "seconds": res["seconds"],
                       "fps": res["fps"], "writer_wait_s": res["writer_wait_s"], "gaussians": int(loaded.gaussians.get_xyz.shape[0]),
                       "dynamic": loaded.dynamic, **extra}))
