@@ -58,6 +58,8 @@
 #include "gs_motion.h"
 #include "../../include/visual_odometry.h"
 #include "gs_odometry.h"
+#include "../../include/relocalisation.h"
+#include "gs_reloc.h"
 
 namespace gsr {
 
@@ -3783,6 +3785,93 @@ int gsr_odometry_align(int width, int height, int levels, float fx, float fy, fl
     ScopedKernelTimer tm(K_ODO_SOLVE, stream);
     hipLaunchKernelGGL(odo_finish_kernel, dim3(1), dim3(64), 0, stream, (const OdoHead*)l.head, (const OdoPyramidHead*)P.head, min_share, max_last_step,
                        max_translation, max_rotation, T, stats);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_reloc_encode: the sums of every cell, [grid_w * grid_h, 6] words
+struct RelocEncodeLayout { unsigned* cells; size_t bytes; };
+static bool reloc_encode_layout(int grid_w, int grid_h, const void* workspace, RelocEncodeLayout& l)
+{
+    if (grid_w < 1 || grid_h < 1 || (long long)grid_w * grid_h > RELOC_MAX_CELLS) return false;
+    Carver c(workspace, 16);
+    l.cells = c.take<unsigned>((size_t)grid_w * grid_h * RELOC_CELL_WORDS);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+static bool reloc_ferns_ok(int ferns) { return ferns >= 8 && ferns <= RELOC_MAX_FERNS && ferns % 8 == 0; }
+
+size_t gsr_reloc_encode_workspace_size(int grid_w, int grid_h)
+{
+    RelocEncodeLayout l;
+    return reloc_encode_layout(grid_w, grid_h, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_reloc_encode(int width, int height, const float* image, const float* depth, const unsigned char* mask, int grid_w, int grid_h,
+                     int ferns, const int* fern_table, float depth_scale, unsigned int* code, void* workspace, size_t workspace_bytes,
+                     void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_reloc_encode: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    RelocEncodeLayout l;
+    if (width < 1 || height < 1 || (long long)width * height >= (1LL << 23))
+        return fail("width and height must be at least 1 and width * height below 2^23, got " + std::to_string(width) + " x " + std::to_string(height));
+    if (!reloc_encode_layout(grid_w, grid_h, workspace, l) || grid_w > width || grid_h > height)
+        return fail("1 <= grid_w <= width, 1 <= grid_h <= height and grid_w * grid_h <= 4096 must hold, got " + std::to_string(grid_w) + " x " +
+                    std::to_string(grid_h));
+    if (!reloc_ferns_ok(ferns)) return fail("ferns must be a multiple of 8 in [8, 2048], got " + std::to_string(ferns));
+    if (!(depth_scale > 0.f) || !std::isfinite(depth_scale)) return fail("depth_scale must be positive and finite");
+    if (!image || !fern_table || !code || !workspace) return fail("image, fern_table, code and workspace must not be NULL");
+    if (!workspace_fits("gsr_reloc_encode", "gsr_reloc_encode_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int cells = grid_w * grid_h;
+    hipLaunchKernelGGL(reloc_cells_kernel, dim3((unsigned)cells), dim3(RELOC_BLOCK), 0, stream, width, height, image, depth, mask, grid_w, grid_h,
+                       depth_scale, l.cells);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(reloc_ferns_kernel, dim3(1), dim3(RELOC_BLOCK), 0, stream, ferns, cells, fern_table, (const unsigned*)l.cells, code);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_reloc_search(int rows, int ferns, const unsigned int* database, const unsigned int* query, int nibble_mask, int topk, int* distance,
+                     int* best, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_reloc_search: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    if (rows < 0 || rows > RELOC_MAX_ROWS) return fail("rows must be in [0, 2^20], got " + std::to_string(rows));
+    if (!reloc_ferns_ok(ferns)) return fail("ferns must be a multiple of 8 in [8, 2048], got " + std::to_string(ferns));
+    if (nibble_mask < 1 || nibble_mask > 15) return fail("nibble_mask must be in [1, 15], got " + std::to_string(nibble_mask));
+    if (topk < 1 || topk > RELOC_MAX_TOPK) return fail("topk must be in [1, 16], got " + std::to_string(topk));
+    if (!best) return fail("best must not be NULL");
+    if (rows > 0 && (!database || !query || !distance)) return fail("database, query and distance must not be NULL when rows > 0");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (rows > 0) {
+        const int words = ferns / 8;
+        int lanes = 1;
+        while (lanes < words && lanes < 64) lanes <<= 1;
+        const size_t threads = (size_t)rows * lanes;
+        hipLaunchKernelGGL(reloc_distance_kernel, dim3((unsigned)((threads + RELOC_BLOCK - 1) / RELOC_BLOCK)), dim3(RELOC_BLOCK), 0, stream, rows,
+                           words, lanes, database, query, (unsigned)nibble_mask * 0x11111111u, distance);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(reloc_select_kernel, dim3(1), dim3(RELOC_SELECT_BLOCK), 0, stream, rows, ferns, topk, (const int*)distance, best);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_reloc_score(int width, int height, const float* render, const float* render_depth, const float* opacity, const float* image,
+                    const float* depth, const unsigned char* mask, int tau_colour, float tau_depth, int* counts, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_reloc_score: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    if (width < 1 || height < 1 || (long long)width * height >= 0x80000000LL)
+        return fail("width and height must be at least 1 and width * height below 2^31, got " + std::to_string(width) + " x " + std::to_string(height));
+    if (tau_colour < 0 || tau_colour > 765) return fail("tau_colour must be in [0, 765], got " + std::to_string(tau_colour));
+    if (!(tau_depth >= 0.f) || !std::isfinite(tau_depth)) return fail("tau_depth must be finite and not negative");
+    if (!render || !render_depth || !opacity || !image || !counts) return fail("render, render_depth, opacity, image and counts must not be NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)width * height;
+    GSR_HIP_CHECK(hipMemsetAsync(counts, 0, RELOC_COUNTS * sizeof(int), stream));
+    const unsigned blocks = (unsigned)std::min<size_t>((n + RELOC_BLOCK - 1) / RELOC_BLOCK, RELOC_SCORE_MAX_BLOCKS);
+    hipLaunchKernelGGL(reloc_score_kernel, dim3(blocks), dim3(RELOC_BLOCK), 0, stream, n, render, render_depth, opacity, image, depth, mask, tau_colour,
+                       tau_depth, counts);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -11,7 +11,10 @@ How a frame is processed:
              loss -> backward -> ONE camera-step launch (Adam on pose + exposure, update_pose, matrices) -- either replayed as a
              captured hipGraph (``Training.tracking_graph``) or called eagerly; the host only polls the convergence latch every
              ``converge_check_every`` iterations (the reference synchronises every iteration, :440);
-  decide     one device-side statistics vector per frame (visibility overlap with the newest keyframe, distance to it) decides
+  judge      only with ``Training.relocalisation``: the rendering at the tracked pose is scored against the frame (one launch, ONE host
+             transfer of eight ints); a refused frame is lost and is looked for among the keyframes (``slam/relocalise.py``); one that is
+             not found keeps the previous pose and is passed over;
+  decide    one device-side statistics vector per frame (visibility overlap with the newest keyframe, distance to it) decides
              whether the frame becomes a keyframe (``slam/keyframes.py``; ONE host transfer per frame);
   insert     the window update is computed on the device and read back as two indices; the back-end maps the new keyframe.
 """
@@ -26,6 +29,7 @@ from gaussian_renderer import render
 from . import keyframes as kf
 from .camera import Camera
 from .eval_utils import eval_ate, save_gaussians
+from .relocalise import KeyframeIndex, Relocaliser, relocalisation_options, score, verdict
 
 
 @torch.no_grad()
@@ -164,6 +168,9 @@ class FrontEnd:
         self._sweeper, self._sweep_events, self._sweep_shares = None, [], []
         self.pose_prior = pose_prior_options(training)      # None: a frame's tracking starts at the previous frame's pose, as in the reference
         self._odometry = self._prior_motion = None
+        self.relocalisation = relocalisation_options(training)      # None: a frame is never judged lost, as in the reference
+        self._reloc_index = self._relocaliser = None
+        self._reloc_events, self._reloc_stats = [], {"scored": 0, "lost": 0, "relocalised": 0}
 
     def set_hyperparams(self):
         """:115-126."""
@@ -292,6 +299,11 @@ class FrontEnd:
         if self.pose_prior is not None:                                   # a map that starts (over) drops the kept frame
             self._prior_motion = None
             self._prior_keep(viewpoint)
+        if self.relocalisation is not None:                               # a map that starts (over) forgets the places of the old one
+            if self._reloc_index is None:
+                self._reloc_index = KeyframeIndex.from_options(self.relocalisation, self.device)
+            self._reloc_index.clear()
+            self._reloc_add(frame_idx, viewpoint)
         seed_depth = self.add_new_keyframe(frame_idx, init=True)
         self.sync_backend(self.backend.handle_init(frame_idx, viewpoint, seed_depth))
 
@@ -313,6 +325,15 @@ class FrontEnd:
         viewpoint.update_RT(previous.R, previous.T)
         if self._odometry is not None and self._odometry.has_previous:
             self._prior_start(viewpoint, previous)
+        pkg = self._optimise_pose(viewpoint)
+        self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])        # :461
+        render_pkg = render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
+        if self.pose_prior is not None:
+            self._prior_keep(viewpoint, render_pkg)
+        return render_pkg
+
+    def _optimise_pose(self, viewpoint):
+        """The pose (and exposure) of `viewpoint` optimised against the map from where it stands; returns the last iteration's render."""
         tracker = self._tracker_for_current_map(viewpoint)
         tracker.load(viewpoint)
         replayed = False
@@ -330,11 +351,67 @@ class FrontEnd:
                 if (it + 1) % self.converge_check_every == 0 and tracker.cam.converged():
                     break
         tracker.store(viewpoint)
-        self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])        # :461
+        return pkg
+
+    # ---- Training.relocalisation: is the tracked frame lost, and if so where is it (slam/relocalise.py) -------------------------------
+    def _reloc_mask(self, viewpoint):
+        return viewpoint.motion_mask if self.dynamic_model else None
+
+    def _reloc_add(self, frame_idx, viewpoint):
+        """The new keyframe's real frame into the place index: one encode into the next row of the device database."""
+        self._reloc_index.add(frame_idx, viewpoint.original_image, viewpoint.depth_device(), self._reloc_mask(viewpoint))
+
+    def _reloc_track_from(self, viewpoint):
+        pkg = self._optimise_pose(viewpoint)
+        self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])
+        return render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
+
+    def _found(self, frame_idx, viewpoint, render_pkg):
+        """Judge the tracked frame by the rendering tracking() returned: one gsr_reloc_score launch and ONE host read, its eight counts.
+        Accepted: (True, render_pkg), nothing else happens. Refused: the frame is lost and Relocaliser.localise looks for it among the
+        keyframes; found there: ("relocalised", frame, keyframe, candidates tried) is logged and the rendering at the new pose returned.
+        Not found: ("lost", frame) is logged, the frame gets the previous frame's pose and (False, None) tells run() to pass it over."""
+        opt = self.relocalisation
+        mask = self._reloc_mask(viewpoint)
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        begin.record()
+        counts = score(render_pkg, viewpoint, opt["tau_colour"], opt["tau_depth"], mask)
+        end.record()
+        self._reloc_events.append((begin, end))
+        self._reloc_stats["scored"] += 1
+        if verdict(counts.tolist(), opt)["accepted"]:
+            return True, render_pkg
+        if self._relocaliser is None:
+            render_at = lambda camera: render_without_grad(camera, self.gaussians, self.pipeline_params, self.background)
+            self._relocaliser = Relocaliser(self._reloc_index, self.cameras, render_at, self._reloc_track_from,
+                                            (viewpoint.image_width, viewpoint.image_height), (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
+                                            opt)
+        previous = self.cameras[frame_idx - self.use_every_n_frames]
+        viewpoint.update_RT(previous.R, previous.T)                        # what a refusal leaves the frame with
+        found = self._relocaliser.localise(viewpoint, mask)
+        if not found["accepted"]:
+            self._reloc_stats["lost"] += 1
+            self.log.append(("lost", frame_idx))
+            if self._odometry is not None:
+                self._odometry.drop()                                         # the next frame is not aligned against a frame without a pose
+            return False, None
+        self._reloc_stats["relocalised"] += 1
+        self.log.append(("relocalised", frame_idx, found["keyframe"], found["candidates_tried"]))
         render_pkg = render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
         if self.pose_prior is not None:
             self._prior_keep(viewpoint, render_pkg)
-        return render_pkg
+        return True, render_pkg
+
+    def relocalisation_summary(self):
+        """The `relocalisation` block of the run result (None with the option off): frames scored, lost, relocalised, device ms per score."""
+        if self.relocalisation is None:
+            return None
+        n = len(self._reloc_events)
+        ms = 0.0
+        if n:
+            torch.cuda.synchronize(self.device)
+            ms = sum(a.elapsed_time(b) for a, b in self._reloc_events) / n
+        return {**self._reloc_stats, "device_ms_per_score": ms}
 
     # ---- keyframe management (:472-562): the decisions of the reference, computed by slam/keyframes.py -------------------------
     def is_keyframe(self, cur_frame_idx, last_keyframe_idx, cur_frame_visibility_filter, occ_aware_visibility):
@@ -390,6 +467,8 @@ class FrontEnd:
         depth_map = self.add_new_keyframe(cur_frame_idx, depth=render_pkg["depth"], opacity=render_pkg["opacity"], init=False)
         if self.reset:                                                            # no valid depth to seed from (_monocular_seed_depth)
             return
+        if self.relocalisation is not None:
+            self._reloc_add(cur_frame_idx, viewpoint)
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))
         self.log.append(("keyframe", cur_frame_idx, overlap))
         viewpoint.clean_key()
@@ -413,6 +492,12 @@ class FrontEnd:
                 continue
             self.initialized = self.initialized or len(self.current_window) == self.window_size
             render_pkg = self.tracking(cur_frame_idx, viewpoint, previous_kf)
+            if self.relocalisation is not None and self.initialized:
+                found, render_pkg = self._found(cur_frame_idx, viewpoint, render_pkg)
+                if not found:                             # lost: it keeps the previous frame's pose and is no keyframe
+                    self.cleanup(cur_frame_idx)
+                    self.dynamic_objects = self.dataset.dynamic_objects
+                    continue
             frames_since_kf = cur_frame_idx - previous_kf
             previous_kf = newest_kf = self.current_window[0]
             visibility = (render_pkg["n_touched"] > 0).long()

@@ -102,6 +102,8 @@ class SLAM:
                 self.result["sweep"] = fe.sweep_summary()
         if fe.pose_prior is not None:
             self.result["odometry"] = fe.odometry_summary()
+        if fe.relocalisation is not None:
+            self.result["relocalisation"] = fe.relocalisation_summary()
         if fe.init_done_at is not None and len(fe.cameras) > 1:          # frames per second once the map exists (tracking + keyframe mapping)
             self.result["seconds_init"] = fe.init_done_at - t0
             self.result["fps_after_init"] = (len(fe.cameras) - 1) / max(1e-9, t0 + dt - fe.init_done_at)
