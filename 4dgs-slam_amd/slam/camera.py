@@ -312,3 +312,29 @@ def update_pose(camera, converged_threshold=1e-4):
 
 def fov_from_focal(f, size):
     return 2 * math.atan(size / (2 * f))
+
+
+# ---- small conversions the front-end's stages, the odometry and the relocaliser share ----------------------------------------------
+def compose_pose(T, R_prev, t_prev):
+    """The world-to-camera pose T W2C_prev of the current frame from the relative motion T [4, 4] (previous camera -> current camera) and the
+    previous frame's world-to-camera R [3, 3], t [3]: R = T_R R_prev, t = T_R t_prev + T_t. Tensor operations only."""
+    T_R = T[:3, :3].to(R_prev.dtype)
+    return T_R @ R_prev, T_R @ t_prev + T[:3, 3].to(t_prev.dtype)
+
+
+def opaque_depth(depth, opacity):
+    """A rendered depth where the map covers the pixel (opacity above 0.5), zero elsewhere."""
+    return depth.detach() * (opacity.detach() > 0.5)
+
+
+def frame_tensors(image, depth, mask, device):
+    """(image [3, H, W] float32, depth [H, W] float32 or None, mask [H, W] uint8 / bool or None), contiguous on `device`."""
+    image = image.detach().to(device=device, dtype=torch.float32).contiguous()
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    if depth is not None:
+        depth = torch.as_tensor(depth).detach().to(device=device, dtype=torch.float32).reshape(H, W).contiguous()
+    if mask is not None:
+        mask = mask.detach().to(device).reshape(H, W).contiguous()
+        if mask.dtype not in (torch.uint8, torch.bool):
+            mask = mask != 0
+    return image, depth, mask

@@ -17,10 +17,14 @@ How a frame is processed:
   decide    one device-side statistics vector per frame (visibility overlap with the newest keyframe, distance to it) decides
              whether the frame becomes a keyframe (``slam/keyframes.py``; ONE host transfer per frame);
   insert     the window update is computed on the device and read back as two indices; the back-end maps the new keyframe.
+
+What the reference does not have is one object of ``slam/stages.py`` per option, None when its ``Training`` block is absent or off:
+``mono_sweep`` (a monocular keyframe's seed depth), ``pose_prior`` (where tracking starts) and ``relocalisation`` (the judge step). This
+file calls them by name and keeps what couples them: the log, and the prior's kept frame when a frame is lost or relocalised.
 """
-import math
 import struct
 import time
+import weakref
 
 import torch
 
@@ -29,12 +33,8 @@ from gaussian_renderer import render
 from . import keyframes as kf
 from .camera import Camera
 from .eval_utils import eval_ate, save_gaussians
-from .relocalise import KeyframeIndex, Relocaliser, relocalisation_options, score, verdict
-
-
-@torch.no_grad()
-def render_without_grad(viewpoint, gaussians, pipe, background):
-    return render(viewpoint, gaussians, pipe, background, dynamic=False)
+from .relocalise import relocalisation_options
+from .stages import PosePrior, Relocalisation, SweepSeeding, mono_sweep_options, pose_prior_options
 
 
 def lower_median(x):
@@ -60,88 +60,6 @@ def get_median_depth(depth, opacity=None, mask=None, return_std=False):
     return lower_median(valid_depth)
 
 
-MONO_SWEEP_DEFAULTS = {"enabled": False, "partners": 3, "near": 0.25, "p1": 10, "p2": 120, "uniqueness_ratio": 40, "min_span_px": 8}
-
-
-def mono_sweep_options(training):
-    """The ``Training.mono_sweep`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
-    sweep cannot take are refused here, before the run starts."""
-    block = training.get("mono_sweep")
-    if not block or not block.get("enabled", False):
-        return None
-    unknown = sorted(set(block) - set(MONO_SWEEP_DEFAULTS))
-    if unknown:
-        raise ValueError(f"Training.mono_sweep: unknown keys {unknown} (known: {sorted(MONO_SWEEP_DEFAULTS)})")
-    opt = dict(MONO_SWEEP_DEFAULTS, **block)
-    opt = {"enabled": True, "near": float(opt["near"]), **{k: int(opt[k]) for k in ("partners", "p1", "p2", "uniqueness_ratio", "min_span_px")}}
-    if not 1 <= opt["partners"] <= 4:
-        raise ValueError(f"Training.mono_sweep.partners must be 1 to 4, got {opt['partners']}")
-    if not (0.0 < opt["near"] <= 1.0):
-        raise ValueError(f"Training.mono_sweep.near must be in (0, 1] (the nearest swept depth as a share of the median), got {opt['near']}")
-    if not (0 < opt["p1"] < opt["p2"] <= 2047) or not 0 <= opt["uniqueness_ratio"] <= 99 or opt["min_span_px"] < 0:
-        raise ValueError("Training.mono_sweep needs 0 < p1 < p2 <= 2047, 0 <= uniqueness_ratio <= 99 and min_span_px >= 0, got "
-                         f"p1 {opt['p1']}, p2 {opt['p2']}, uniqueness_ratio {opt['uniqueness_ratio']}, min_span_px {opt['min_span_px']}")
-    return opt
-
-
-def merge_sweep_depth(sweep_depth, sweep_valid, gt_img, rgb_boundary_threshold, fallback):
-    """The seed depth of a swept keyframe: the sweep's where it is valid and the pixel passes the RGB boundary threshold, else the fallback."""
-    use = sweep_valid & (gt_img.sum(dim=0) > rgb_boundary_threshold)
-    return torch.where(use, sweep_depth, fallback)
-
-
-POSE_PRIOR_DEFAULTS = {"enabled": False, "levels": 3, "iters": [5, 7, 10], "nu": 5.0, "sigma_init": 0.1, "sigma_min": 1e-3, "min_share": 0.3,
-                       "max_last_step": 1e-2, "max_translation": 0.5, "max_rotation": 20.0, "depth_min": 0.0, "depth_max": 1e6,
-                       "constant_velocity": False}
-
-
-def pose_prior_options(training):
-    """The ``Training.pose_prior`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
-    alignment cannot take are refused here, before the run starts. max_translation is in metres (monocular input: map units), max_rotation
-    in degrees; iters lists the passes per level, finest first."""
-    block = training.get("pose_prior")
-    if not block or not block.get("enabled", False):
-        return None
-    unknown = sorted(set(block) - set(POSE_PRIOR_DEFAULTS))
-    if unknown:
-        raise ValueError(f"Training.pose_prior: unknown keys {unknown} (known: {sorted(POSE_PRIOR_DEFAULTS)})")
-    opt = dict(POSE_PRIOR_DEFAULTS, **block)
-    opt["enabled"], opt["constant_velocity"], opt["levels"] = True, bool(opt["constant_velocity"]), int(opt["levels"])
-    if not 1 <= opt["levels"] <= 6:
-        raise ValueError(f"Training.pose_prior.levels must be 1 to 6, got {opt['levels']}")
-    if "iters" not in block and opt["levels"] != POSE_PRIOR_DEFAULTS["levels"]:
-        raise ValueError(f"Training.pose_prior.iters must be given with levels = {opt['levels']}: one count per level, finest first")
-    if isinstance(opt["iters"], (str, bytes)) or not hasattr(opt["iters"], "__len__"):
-        raise ValueError(f"Training.pose_prior.iters must be a list of {opt['levels']} pass counts, finest first, got {opt['iters']!r}")
-    opt["iters"] = [int(v) for v in opt["iters"]]
-    if len(opt["iters"]) != opt["levels"] or not all(0 <= v <= 64 for v in opt["iters"]):
-        raise ValueError(f"Training.pose_prior.iters must hold {opt['levels']} pass counts in [0, 64], finest first, got {opt['iters']}")
-    for key in ("nu", "sigma_init", "sigma_min", "min_share", "max_last_step", "max_translation", "max_rotation", "depth_min", "depth_max"):
-        opt[key] = float(opt[key])
-        if math.isnan(opt[key]):
-            raise ValueError(f"Training.pose_prior.{key} must be a number, got nan")
-    for key in ("nu", "sigma_init", "sigma_min"):
-        if not (0.0 < opt[key] < math.inf):
-            raise ValueError(f"Training.pose_prior.{key} must be positive and finite, got {opt[key]}")
-    if not 0.0 <= opt["min_share"] <= 1.0:
-        raise ValueError(f"Training.pose_prior.min_share must be in [0, 1], got {opt['min_share']}")
-    for key in ("max_last_step", "max_translation", "max_rotation"):
-        if opt[key] < 0.0:
-            raise ValueError(f"Training.pose_prior.{key} must not be negative, got {opt[key]}")
-    if opt["max_rotation"] > 180.0:
-        raise ValueError(f"Training.pose_prior.max_rotation is in degrees and must not exceed 180, got {opt['max_rotation']}")
-    if not 0.0 <= opt["depth_min"] <= opt["depth_max"]:
-        raise ValueError(f"Training.pose_prior needs 0 <= depth_min <= depth_max, got {opt['depth_min']} and {opt['depth_max']}")
-    return opt
-
-
-def compose_pose(T, R_prev, t_prev):
-    """The world-to-camera pose T W2C_prev of the current frame from the relative motion T [4, 4] (previous camera -> current camera) and the
-    previous frame's world-to-camera R [3, 3], t [3]: R = T_R R_prev, t = T_R t_prev + T_t. Tensor operations only."""
-    T_R = T[:3, :3].to(R_prev.dtype)
-    return T_R @ R_prev, T_R @ t_prev + T[:3, 3].to(t_prev.dtype)
-
-
 class FrontEnd:
     MIN_KEYFRAME_GAP = 5          # a keyframe at the latest every five frames (utils/slam_frontend.py:739)
 
@@ -164,13 +82,12 @@ class FrontEnd:
         self.log = []
         self.init_done_at = None
         self.resets = 0                    # monocular input: how often the map was started over (a failed initialisation)
-        self.mono_sweep = mono_sweep_options(training)      # None: a monocular keyframe is seeded the reference's way alone
-        self._sweeper, self._sweep_events, self._sweep_shares = None, [], []
-        self.pose_prior = pose_prior_options(training)      # None: a frame's tracking starts at the previous frame's pose, as in the reference
-        self._odometry = self._prior_motion = None
-        self.relocalisation = relocalisation_options(training)      # None: a frame is never judged lost, as in the reference
-        self._reloc_index = self._relocaliser = None
-        self._reloc_events, self._reloc_stats = [], {"scored": 0, "lost": 0, "relocalised": 0}
+        # the optional stages (slam/stages.py), each None when its block is absent or off: a monocular keyframe is then seeded the reference's
+        # way alone, a frame's tracking starts at the previous frame's pose and no frame is ever judged lost, as in the reference
+        sweep, prior, reloc = mono_sweep_options(training), pose_prior_options(training), relocalisation_options(training)
+        self.mono_sweep = sweep and SweepSeeding(sweep)
+        self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model)
+        self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model)
 
     def set_hyperparams(self):
         """:115-126."""
@@ -217,79 +134,8 @@ class FrontEnd:
             self.reset = True
             self.log.append(("reset", "no valid depth to seed a keyframe from"))
         elif self.mono_sweep is not None:
-            seed_depth = self._sweep_seed_depth(gt_img, seed_depth, median, threshold)
+            seed_depth = self.mono_sweep.seed_depth(gt_img, seed_depth, median, threshold, [self.cameras[k] for k in self.current_window])
         return seed_depth
-
-    def _sweep_seed_depth(self, gt_img, fallback, median, threshold):
-        """``Training.mono_sweep``: the new keyframe's depth from a plane sweep (slam/sweep.py, include/multiview_depth.h) against the most
-        recent `partners` keyframes of the window under their tracked poses, inverse depth 0 .. 1 / (near * median) in 63 steps. Where the
-        sweep is valid and the pixel passes the RGB boundary threshold its depth is the seed; everywhere else the fallback stands. Nothing
-        is read by the host: the valid share is kept on the device and the time in events until the run's summary asks (sweep_summary)."""
-        opt = self.mono_sweep
-        newest = self.cameras[self.current_window[0]]
-        partners = [self.cameras[k] for k in self.current_window[1:1 + opt["partners"]] if self.cameras[k].original_image is not None]
-        if not partners or not (median > 0.0 and median < float("inf")):
-            return fallback
-        if self._sweeper is None:
-            from .sweep import PlaneSweep, relative_transforms
-            self._sweeper = PlaneSweep(p1=opt["p1"], p2=opt["p2"], uniqueness_ratio=opt["uniqueness_ratio"], min_span_px=opt["min_span_px"],
-                                       device=gt_img.device)
-            self._relative_transforms = relative_transforms
-        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        begin.record()
-        swept = self._sweeper.sweep(gt_img, [cam.original_image for cam in partners], (newest.fx, newest.fy, newest.cx, newest.cy),
-                                    self._relative_transforms(newest, partners), 0.0, 1.0 / (opt["near"] * median * 63.0))
-        end.record()
-        self._sweep_events.append((begin, end))
-        self._sweep_shares.append(swept["valid"].float().mean())
-        return merge_sweep_depth(swept["depth"], swept["valid"], gt_img, threshold, fallback)
-
-    def sweep_summary(self):
-        """The `sweep` block of the run result (None with the option off): keyframes swept, their mean valid share, device ms per keyframe."""
-        if self.mono_sweep is None:
-            return None
-        n = len(self._sweep_events)
-        if n == 0:
-            return {"keyframes": 0, "valid_share": 0.0, "device_ms_per_keyframe": 0.0}
-        torch.cuda.synchronize(self.device)
-        ms = sum(a.elapsed_time(b) for a, b in self._sweep_events)
-        return {"keyframes": n, "valid_share": float(torch.stack(self._sweep_shares).mean()), "device_ms_per_keyframe": ms / n}
-
-    # ---- Training.pose_prior: the start of a frame's tracking from dense frame-to-frame alignment (slam/odometry.py) -------------------
-    def _prior_keep(self, viewpoint, render_pkg=None):
-        """Keep `viewpoint` as the frame the next one is aligned against. Its depth: the sensor's (RGB-D) or the matcher's (stereo); for
-        monocular input the depth of `render_pkg` where its opacity is above 0.5 (None: the map does not exist yet, nothing is kept)."""
-        if self._odometry is None:
-            from .odometry import DenseOdometry
-            options = {k: v for k, v in self.pose_prior.items() if k not in ("enabled", "constant_velocity")}
-            self._odometry = DenseOdometry(viewpoint.image_width, viewpoint.image_height, (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
-                                           device=self.device, **options)
-        if self.monocular:
-            depth = None if render_pkg is None else render_pkg["depth"].detach() * (render_pkg["opacity"].detach() > 0.5)
-        else:
-            depth = viewpoint.depth_device()
-        if depth is None:
-            self._odometry.drop()
-            return
-        mask = viewpoint.motion_mask if self.dynamic_model else None
-        self._odometry.keep(viewpoint.original_image, depth, mask)
-
-    def _prior_start(self, viewpoint, previous):
-        """Move `viewpoint` from the previous frame's pose W2C_prev to T W2C_prev, T the aligned motion (identity where the gate refused it:
-        the reference's start). Device tensors throughout; the host reads nothing."""
-        T_init = self._prior_motion if self.pose_prior["constant_velocity"] else None
-        T, _ = self._odometry.align(viewpoint.original_image, T_init)
-        self._prior_motion = T
-        viewpoint.update_RT(*compose_pose(T, previous.R, previous.T))
-
-    def odometry_summary(self):
-        """The `odometry` block of the run result (None with the option off): frames aligned, the accepted share, the mean inlier share,
-        device ms per frame."""
-        if self.pose_prior is None:
-            return None
-        if self._odometry is None:
-            return {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
-        return self._odometry.summary()
 
     def initialize(self, frame_idx, viewpoint):
         """:189-207."""
@@ -297,13 +143,12 @@ class FrontEnd:
         self.initialized, self.reset = not self.monocular, False
         viewpoint.update_RT(viewpoint.R_gt, viewpoint.T_gt)               # first frame at the ground-truth pose
         if self.pose_prior is not None:                                   # a map that starts (over) drops the kept frame
-            self._prior_motion = None
-            self._prior_keep(viewpoint)
+            self.pose_prior.restart(viewpoint)
         if self.relocalisation is not None:                               # a map that starts (over) forgets the places of the old one
-            if self._reloc_index is None:
-                self._reloc_index = KeyframeIndex.from_options(self.relocalisation, self.device)
-            self._reloc_index.clear()
-            self._reloc_add(frame_idx, viewpoint)
+            # (the stage keeps the two calls for the run: through a weak reference, or this object -- streams, events and captured graphs --
+            # would be freed by the cycle collector alone, whenever it next runs, be that in the middle of a later run's graph capture)
+            me = weakref.proxy(self)
+            self.relocalisation.restart(frame_idx, viewpoint, self.cameras, lambda c: me._render_at(c), lambda v: me._track_and_render(v))
         seed_depth = self.add_new_keyframe(frame_idx, init=True)
         self.sync_backend(self.backend.handle_init(frame_idx, viewpoint, seed_depth))
 
@@ -323,13 +168,11 @@ class FrontEnd:
     def tracking(self, frame_idx, viewpoint, last_keyframe_idx=None):
         previous = self.cameras[frame_idx - self.use_every_n_frames]
         viewpoint.update_RT(previous.R, previous.T)
-        if self._odometry is not None and self._odometry.has_previous:
-            self._prior_start(viewpoint, previous)
-        pkg = self._optimise_pose(viewpoint)
-        self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])        # :461
-        render_pkg = render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
         if self.pose_prior is not None:
-            self._prior_keep(viewpoint, render_pkg)
+            self.pose_prior.start(viewpoint, previous)
+        render_pkg = self._track_and_render(viewpoint)
+        if self.pose_prior is not None:
+            self.pose_prior.keep(viewpoint, render_pkg)
         return render_pkg
 
     def _optimise_pose(self, viewpoint):
@@ -346,72 +189,37 @@ class FrontEnd:
             pkg = tracker.pkg                    # the captured iteration's static outputs: the last replay's render
         else:                                    # eager: the same iteration, launch by launch
             self.graph_stats["eager_frames"] += 1
-            for it in range(self.tracking_itr_num):
-                pkg = tracker.iteration()
-                if (it + 1) % self.converge_check_every == 0 and tracker.cam.converged():
-                    break
+            pkg = tracker.run_eager(self.tracking_itr_num, self.converge_check_every)
         tracker.store(viewpoint)
         return pkg
 
-    # ---- Training.relocalisation: is the tracked frame lost, and if so where is it (slam/relocalise.py) -------------------------------
-    def _reloc_mask(self, viewpoint):
-        return viewpoint.motion_mask if self.dynamic_model else None
+    @torch.no_grad()
+    def _render_at(self, camera):
+        return render(camera, self.gaussians, self.pipeline_params, self.background, dynamic=False)
 
-    def _reloc_add(self, frame_idx, viewpoint):
-        """The new keyframe's real frame into the place index: one encode into the next row of the device database."""
-        self._reloc_index.add(frame_idx, viewpoint.original_image, viewpoint.depth_device(), self._reloc_mask(viewpoint))
-
-    def _reloc_track_from(self, viewpoint):
+    def _track_and_render(self, viewpoint):
+        """Track `viewpoint` from where it stands (the median depth is the last tracking iteration's, :461) and render the map there."""
         pkg = self._optimise_pose(viewpoint)
         self.median_depth = get_median_depth(pkg["depth"], pkg["opacity"])
-        return render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
+        return self._render_at(viewpoint)
 
     def _found(self, frame_idx, viewpoint, render_pkg):
-        """Judge the tracked frame by the rendering tracking() returned: one gsr_reloc_score launch and ONE host read, its eight counts.
-        Accepted: (True, render_pkg), nothing else happens. Refused: the frame is lost and Relocaliser.localise looks for it among the
-        keyframes; found there: ("relocalised", frame, keyframe, candidates tried) is logged and the rendering at the new pose returned.
-        Not found: ("lost", frame) is logged, the frame gets the previous frame's pose and (False, None) tells run() to pass it over."""
-        opt = self.relocalisation
-        mask = self._reloc_mask(viewpoint)
-        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        begin.record()
-        counts = score(render_pkg, viewpoint, opt["tau_colour"], opt["tau_depth"], mask)
-        end.record()
-        self._reloc_events.append((begin, end))
-        self._reloc_stats["scored"] += 1
-        if verdict(counts.tolist(), opt)["accepted"]:
-            return True, render_pkg
-        if self._relocaliser is None:
-            render_at = lambda camera: render_without_grad(camera, self.gaussians, self.pipeline_params, self.background)
-            self._relocaliser = Relocaliser(self._reloc_index, self.cameras, render_at, self._reloc_track_from,
-                                            (viewpoint.image_width, viewpoint.image_height), (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
-                                            opt)
+        """Judge the tracked frame by the rendering tracking() returned (Relocaliser.judge: ONE host read, the eight counts). Accepted:
+        (True, render_pkg). Found again among the keyframes: ("relocalised", frame, keyframe, candidates tried) is logged and the rendering
+        at the new pose returned. Not found: ("lost", frame) is logged, the frame has the previous one's pose and run() passes it over."""
         previous = self.cameras[frame_idx - self.use_every_n_frames]
-        viewpoint.update_RT(previous.R, previous.T)                        # what a refusal leaves the frame with
-        found = self._relocaliser.localise(viewpoint, mask)
+        found = self.relocalisation.judge(viewpoint, render_pkg, (previous.R, previous.T))
         if not found["accepted"]:
-            self._reloc_stats["lost"] += 1
             self.log.append(("lost", frame_idx))
-            if self._odometry is not None:
-                self._odometry.drop()                                         # the next frame is not aligned against a frame without a pose
+            if self.pose_prior is not None:
+                self.pose_prior.drop()                                        # the next frame is not aligned against a frame without a pose
             return False, None
-        self._reloc_stats["relocalised"] += 1
-        self.log.append(("relocalised", frame_idx, found["keyframe"], found["candidates_tried"]))
-        render_pkg = render_without_grad(viewpoint, self.gaussians, self.pipeline_params, self.background)
-        if self.pose_prior is not None:
-            self._prior_keep(viewpoint, render_pkg)
+        if found["keyframe"] is not None:
+            self.log.append(("relocalised", frame_idx, found["keyframe"], found["candidates_tried"]))
+            render_pkg = self._render_at(viewpoint)
+            if self.pose_prior is not None:
+                self.pose_prior.keep(viewpoint, render_pkg)
         return True, render_pkg
-
-    def relocalisation_summary(self):
-        """The `relocalisation` block of the run result (None with the option off): frames scored, lost, relocalised, device ms per score."""
-        if self.relocalisation is None:
-            return None
-        n = len(self._reloc_events)
-        ms = 0.0
-        if n:
-            torch.cuda.synchronize(self.device)
-            ms = sum(a.elapsed_time(b) for a, b in self._reloc_events) / n
-        return {**self._reloc_stats, "device_ms_per_score": ms}
 
     # ---- keyframe management (:472-562): the decisions of the reference, computed by slam/keyframes.py -------------------------
     def is_keyframe(self, cur_frame_idx, last_keyframe_idx, cur_frame_visibility_filter, occ_aware_visibility):
@@ -468,7 +276,7 @@ class FrontEnd:
         if self.reset:                                                            # no valid depth to seed from (_monocular_seed_depth)
             return
         if self.relocalisation is not None:
-            self._reloc_add(cur_frame_idx, viewpoint)
+            self.relocalisation.add(cur_frame_idx, viewpoint)
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))
         self.log.append(("keyframe", cur_frame_idx, overlap))
         viewpoint.clean_key()

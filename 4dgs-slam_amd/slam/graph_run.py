@@ -16,6 +16,7 @@ Statistics per kind of run in ``backend.<kind>_stats`` (runs, replays, direct, r
 failed capture sets ``backend._<kind>_broken`` and switches that kind's graphs off (a failed static capture also switches off every other
 kind: BackEnd._graphs_enabled reads ``_graph_broken``)."""
 import contextlib
+import gc
 import time
 
 import torch
@@ -43,8 +44,10 @@ def note_failure(backend, kind, error):
 @contextlib.contextmanager
 def capture_options(**opts):
     """The rasterizer options (gsr_set_option) of a capture, put back however the block is left: they only matter while host code runs --
-    replays never consult them."""
-    before = {}
+    replays never consult them. The cycle collector is held off meanwhile: destroying what it finds (an earlier run's streams, events,
+    graphs) takes calls that a process must not make while a stream captures, and the runtime aborts on them."""
+    before, collecting = {}, gc.isenabled()
+    gc.disable()
     try:
         for name, value in opts.items():
             before[name] = _C.set_option(name, value)
@@ -52,6 +55,8 @@ def capture_options(**opts):
     finally:
         for name, value in before.items():
             _C.set_option(name, value)
+        if collecting:
+            gc.enable()
 
 
 def capture(backend, runner, options):

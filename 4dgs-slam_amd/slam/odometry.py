@@ -1,7 +1,7 @@
 """Dense frame-to-frame visual odometry: the checked ctypes binding of include/visual_odometry.h (gsr_odometry_pyramid: an intensity / depth
 pyramid of a frame; gsr_odometry_align: coarse-to-fine photometric Gauss-Newton on SE(3) with Student-t weights and an acceptance gate on the
 device, csrc/gs_odometry.h) and ``DenseOdometry``, which keeps the previous frame's pyramid. The front-end starts a frame's tracking from its
-result (slam/frontend.py, ``Training.pose_prior``); the reference starts at the previous pose and has no counterpart.
+result (slam/stages.py, ``Training.pose_prior``); the reference starts at the previous pose and has no counterpart.
 tests/odometry_reference.py restates the contract in numpy. No CPU path.
 
 Limits: brightness changes between the two frames are not modelled (the tracker's exposure terms come after this step); a mover that is not
@@ -12,6 +12,9 @@ import math
 import torch
 
 from diff_gaussian_rasterization import _C
+
+from .camera import frame_tensors
+from .pretrained import EventLog
 
 STATS = ("accepted", "inlier_share", "sigma", "last_step", "pixels_in", "translation", "angle", "valid_depths")
 TRACE_ROW = 32
@@ -94,20 +97,11 @@ class DenseOdometry:
         self._current = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._workspace = torch.empty(align_workspace_size(self.width, self.height, self.levels), dtype=torch.uint8, device=self.device)
         self.has_previous = False
-        self._events, self._stats = [], []
-
-    def _image(self, image):
-        return image.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.log, self._stats = EventLog(self.device), []
 
     def keep(self, image, depth=None, mask=None):
         """Build the frame's pyramid (depth None: no pixel can be aligned from it) and make it the previous frame."""
-        if depth is not None:
-            depth = depth.detach().to(device=self.device, dtype=torch.float32).reshape(self.height, self.width).contiguous()
-        if mask is not None:
-            mask = mask.detach().to(self.device).reshape(self.height, self.width).contiguous()
-            if mask.dtype not in (torch.uint8, torch.bool):
-                mask = mask != 0
-        build_pyramid(self._image(image), depth, mask, self.levels, self._current, *self.depth_range)
+        build_pyramid(*frame_tensors(image, depth, mask, self.device), self.levels, self._current, *self.depth_range)
         self._previous, self._current = self._current, self._previous
         self.has_previous = depth is not None
 
@@ -118,26 +112,19 @@ class DenseOdometry:
         """T [4, 4] float32 and stats float64 [8] (STATS) of `image` against the kept frame, both on the device."""
         if not self.has_previous:
             raise RuntimeError("DenseOdometry.align: no previous frame is kept (keep() with a depth comes first)")
-        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        begin.record()
-        build_pyramid(self._image(image), None, None, self.levels, self._current)
-        T = torch.empty((4, 4), dtype=torch.float32, device=self.device)
-        stats = torch.empty(len(STATS), dtype=torch.float64, device=self.device)
-        if T_init is not None:
-            T_init = T_init.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        align_pyramids(self.width, self.height, self.levels, self.K, self._previous, self._current, self.iters, T, stats, T_init=T_init,
-                       trace=trace, workspace=self._workspace, **self.params)
-        end.record()
-        self._events.append((begin, end))
+        with self.log.timed():
+            build_pyramid(*frame_tensors(image, None, None, self.device), self.levels, self._current)
+            T = torch.empty((4, 4), dtype=torch.float32, device=self.device)
+            stats = torch.empty(len(STATS), dtype=torch.float64, device=self.device)
+            if T_init is not None:
+                T_init = T_init.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            align_pyramids(self.width, self.height, self.levels, self.K, self._previous, self._current, self.iters, T, stats, T_init=T_init,
+                           trace=trace, workspace=self._workspace, **self.params)
         self._stats.append(stats)
         return T, stats
 
     def summary(self):
         """Frames aligned, the share the gate accepted, their mean inlier share, device ms per frame: the one host read, at the end of a run."""
-        n = len(self._events)
-        if n == 0:
-            return {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
-        torch.cuda.synchronize(self.device)
-        ms = sum(a.elapsed_time(b) for a, b in self._events)
-        accepted, share = torch.stack(self._stats)[:, :2].mean(dim=0).tolist()
-        return {"frames": n, "accepted_share": accepted, "inlier_share": share, "device_ms_per_frame": ms / n}
+        accepted, share = torch.stack(self._stats)[:, :2].mean(dim=0).tolist() if self._stats else (0.0, 0.0)
+        return {"frames": len(self._stats), "accepted_share": accepted, "inlier_share": share,
+                "device_ms_per_frame": self.log.summary()["ms_per_item"] or 0.0}

@@ -3,9 +3,10 @@ include/relocalisation.h (gsr_reloc_encode: the randomised-fern code of a frame,
 of keyframe codes; gsr_reloc_score: the counts by which a rendering is judged against a frame; csrc/gs_reloc.h) and what is built from them:
 
   KeyframeIndex   the fern table, a growable device database of keyframe codes and the keyframe ids: place recognition
-  score, verdict  does the map rendered at a pose agree with the frame? -- also the "am I lost?" test of a run (slam/frontend.py)
-  Relocaliser     candidates of the index in order: render the map at the candidate keyframe, align the frame against that rendering
-                  (slam/odometry.py), track from there, accept the first pose the verdict agrees with
+  score, verdict  does the map rendered at a pose agree with the frame?
+  Relocaliser     localise(): candidates of the index in order: render the map at the candidate keyframe, align the frame against that
+                  rendering (slam/odometry.py), track from there, accept the first pose the verdict agrees with; judge(): the "am I lost?"
+                  test of a tracked frame and, if it is, localise() -- one path for a run (slam/stages.py Relocalisation) and for follow()
   MapLocaliser    the same against a map_io.LoadedMap, whose index is built from renderings at the keyframe poses; follow() tracks a sequence
 
 The reference has no counterpart. tests/reloc_reference.py restates the three kernels in integer numpy. No CPU path.
@@ -18,6 +19,10 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _C
+
+from .camera import Camera, compose_pose, frame_tensors, opaque_depth
+from .options import check_gate, check_pass_counts, read_block, to_floats
+from .pretrained import EventLog
 
 I32 = (torch.int32,)
 MASK = (torch.uint8, torch.bool)
@@ -118,14 +123,9 @@ def relocalisation_options(training):
     metres; iters lists the alignment's passes per level, finest first (default: one count per level); max_translation in metres,
     max_rotation in degrees: the gate of the alignment against a keyframe's rendering, wider than the frame-to-frame one."""
     name = "Training.relocalisation"
-    block = training.get("relocalisation")
-    if not block or not block.get("enabled", False):
+    opt = read_block(training, "relocalisation", RELOCALISATION_DEFAULTS)
+    if opt is None:
         return None
-    unknown = sorted(set(block) - set(RELOCALISATION_DEFAULTS))
-    if unknown:
-        raise ValueError(f"{name}: unknown keys {unknown} (known: {sorted(RELOCALISATION_DEFAULTS)})")
-    opt = dict(RELOCALISATION_DEFAULTS, **block)
-    opt["enabled"] = True
     for key in ("ferns", "seed", "topk", "tau_colour", "levels"):
         if isinstance(opt[key], float) and not opt[key].is_integer():
             raise ValueError(f"{name}.{key} must be an integer, got {opt[key]!r}")
@@ -143,10 +143,7 @@ def relocalisation_options(training):
         raise ValueError(f"{name}.topk must be 1 to {MAX_TOPK}, got {opt['topk']}")
     if not 0 <= opt["tau_colour"] <= 765:
         raise ValueError(f"{name}.tau_colour must be in [0, 765], got {opt['tau_colour']}")
-    for key in ("depth_scale", "depth_lo", "depth_hi", "tau_depth", "min_score", "min_coverage", "max_translation", "max_rotation"):
-        opt[key] = float(opt[key])
-        if math.isnan(opt[key]):
-            raise ValueError(f"{name}.{key} must be a number, got nan")
+    to_floats(opt, name, ("depth_scale", "depth_lo", "depth_hi", "tau_depth", "min_score", "min_coverage", "max_translation", "max_rotation"))
     if not (0.0 < opt["depth_scale"] < math.inf):
         raise ValueError(f"{name}.depth_scale must be positive and finite, got {opt['depth_scale']}")
     if not (0.0 < opt["depth_lo"] < opt["depth_hi"] < math.inf):
@@ -160,16 +157,8 @@ def relocalisation_options(training):
         raise ValueError(f"{name}.levels must be 1 to 6, got {opt['levels']}")
     if opt["iters"] is None:
         opt["iters"] = list(DEFAULT_ITERS[:opt["levels"]])
-    if isinstance(opt["iters"], (str, bytes)) or not hasattr(opt["iters"], "__len__"):
-        raise ValueError(f"{name}.iters must be a list of {opt['levels']} pass counts, finest first, got {opt['iters']!r}")
-    opt["iters"] = [int(v) for v in opt["iters"]]
-    if len(opt["iters"]) != opt["levels"] or not all(0 <= v <= 64 for v in opt["iters"]):
-        raise ValueError(f"{name}.iters must hold {opt['levels']} pass counts in [0, 64], finest first, got {opt['iters']}")
-    for key in ("max_translation", "max_rotation"):
-        if opt[key] < 0.0:
-            raise ValueError(f"{name}.{key} must not be negative, got {opt[key]}")
-    if opt["max_rotation"] > 180.0:
-        raise ValueError(f"{name}.max_rotation is in degrees and must not exceed 180, got {opt['max_rotation']}")
+    check_pass_counts(opt, name)
+    check_gate(opt, name, ("max_translation", "max_rotation"))
     return opt
 
 
@@ -179,19 +168,6 @@ def default_options(**overrides):
 
 
 # ---- place recognition -------------------------------------------------------------------------------------------------------------
-def _frame_tensors(image, depth, mask, device):
-    """(image [3, H, W] float32, depth [H, W] float32 or None, mask [H, W] uint8 / bool or None), contiguous on `device`."""
-    image = image.detach().to(device=device, dtype=torch.float32).contiguous()
-    H, W = int(image.shape[-2]), int(image.shape[-1])
-    if depth is not None:
-        depth = torch.as_tensor(depth).detach().to(device=device, dtype=torch.float32).reshape(H, W).contiguous()
-    if mask is not None:
-        mask = mask.detach().to(device).reshape(H, W).contiguous()
-        if mask.dtype not in MASK:
-            mask = mask != 0
-    return image, depth, mask
-
-
 class KeyframeIndex:
     """The fern table, the codes of the keyframes added so far (a device database that doubles when it is full) and their ids.
 
@@ -228,14 +204,14 @@ class KeyframeIndex:
             grown = torch.zeros((2 * row, self.words), dtype=torch.int32, device=self.device)
             grown[:row] = self.database
             self.database = grown
-        image, depth, mask = _frame_tensors(image, depth, mask, self.device)
+        image, depth, mask = frame_tensors(image, depth, mask, self.device)
         encode(image, depth, mask, self.grid, self.table, self.depth_scale, self.database[row], self._workspace)
         self.ids.append(frame_id)
 
     def query(self, image, depth=None, mask=None, topk=4, nibble_mask=None):
         """(best int32 [topk, 2], distance int32 [len(self)]) on the device. nibble_mask None: 0xF with a depth, 0x7 without (a frame that
         has no depth is compared on its colour bits alone)."""
-        image, depth, mask = _frame_tensors(image, depth, mask, self.device)
+        image, depth, mask = frame_tensors(image, depth, mask, self.device)
         encode(image, depth, mask, self.grid, self.table, self.depth_scale, self._query, self._workspace)
         rows = len(self.ids)
         best = torch.empty((int(topk), 2), dtype=torch.int32, device=self.device)
@@ -258,7 +234,7 @@ def score(render_pkg, viewpoint, tau_colour=48, tau_depth=0.05, mask=None):
         render = torch.exp(a.detach()) * render + b.detach()
     dev = render.device
     H, W = int(render.shape[-2]), int(render.shape[-1])
-    image, depth, mask = _frame_tensors(viewpoint.original_image, viewpoint.depth_device(), mask, dev)
+    image, depth, mask = frame_tensors(viewpoint.original_image, viewpoint.depth_device(), mask, dev)
     counts = torch.empty(len(COUNTS), dtype=torch.int32, device=dev)
     score_counts(render.to(torch.float32).contiguous(), render_pkg["depth"].detach().reshape(H, W).contiguous(),
                  render_pkg["opacity"].detach().reshape(H, W).contiguous(), image, depth, mask, tau_colour, tau_depth, counts)
@@ -285,11 +261,12 @@ class Relocaliser:
     keyframes: {id: camera} -- pose (R, T) and time of every id the index holds; render_at(camera) -> render package of the map at that
     camera; track_from(viewpoint) -> render package: refines viewpoint's pose against the map from where it stands and renders there.
     The two callables keep the class ignorant of whether it serves a live run or a loaded map. size = (width, height), K = (fx, fy, cx,
-    cy), opt = relocalisation_options(...)."""
+    cy), opt = relocalisation_options(...); log: an EventLog that times every judge()'s score (default: none is kept)."""
 
-    def __init__(self, index, keyframes, render_at, track_from, size, K, opt):
+    def __init__(self, index, keyframes, render_at, track_from, size, K, opt, log=None):
         from .odometry import DenseOdometry
         self.index, self.keyframes, self.render_at, self.track_from, self.opt = index, keyframes, render_at, track_from, opt
+        self.log = EventLog("cpu") if log is None else log
         self.odometry = DenseOdometry(size[0], size[1], K, levels=opt["levels"], iters=opt["iters"], max_translation=opt["max_translation"],
                                       max_rotation=opt["max_rotation"], device=index.device)
 
@@ -297,12 +274,23 @@ class Relocaliser:
     def _seed(self, viewpoint, keyframe):
         """Place `viewpoint` at the keyframe's pose moved by the alignment of its image against the map rendered there; where the
         alignment's gate refuses, T is the identity and the pose is the keyframe's. Device tensors throughout."""
-        from .frontend import compose_pose
         pkg = self.render_at(keyframe)
-        depth = pkg["depth"].detach() * (pkg["opacity"].detach() > 0.5)
-        self.odometry.keep(pkg["render"], depth, None)
+        self.odometry.keep(pkg["render"], opaque_depth(pkg["depth"], pkg["opacity"]), None)
         T, _ = self.odometry.align(viewpoint.original_image)
         viewpoint.update_RT(*compose_pose(T, keyframe.R, keyframe.T))
+
+    def judge(self, viewpoint, render_pkg, fallback, mask=None):
+        """Is the tracked frame where `render_pkg` shows the map? One gsr_reloc_score launch and ONE host read, its eight counts. Accepted:
+        nothing else happens. Refused: the frame gets the pose `fallback` = (R, T) and localise() looks for it among the keyframes. Returns
+        localise()'s dictionary: accepted with "keyframe" None: tracked; with a keyframe: relocalised there; not accepted: lost."""
+        opt = self.opt
+        with self.log.timed():
+            counts = score(render_pkg, viewpoint, opt["tau_colour"], opt["tau_depth"], mask)
+        counts = counts.tolist()
+        if verdict(counts, opt)["accepted"]:
+            return {"accepted": True, "keyframe": None, "candidates_tried": 0, "counts": counts, "distance": None}
+        viewpoint.update_RT(*fallback)
+        return self.localise(viewpoint, mask)
 
     def localise(self, viewpoint, mask=None):
         """Encode the frame, search the index, and try the candidates in the order of `best`: seed the pose at the candidate (_seed),
@@ -362,7 +350,7 @@ class MapLocaliser:
         cams = [self.keyframes[k] for k in loaded_map.kf_indices]
         colour, depth, opacity = Playback(loaded_map).render(_w2c(cams), [float(c.time) for c in cams])
         for i, k in enumerate(loaded_map.kf_indices):
-            self.index.add(k, colour[i], depth[i, 0] * (opacity[i, 0] > 0.5), None)
+            self.index.add(k, colour[i], opaque_depth(depth[i, 0], opacity[i, 0]), None)
         self._tracker = None
         self.relocaliser = Relocaliser(self.index, self.keyframes, self._render_at, self._track_from, self.size, self.K, self.opt)
 
@@ -372,24 +360,18 @@ class MapLocaliser:
         return render(camera, self.map.gaussians, self.map.pipeline_params, self.map.background, dynamic=False)
 
     def _track_from(self, viewpoint):
-        """The front-end's tracking of one frame (eager TrackingGraph iterations with its convergence poll) on the loaded Gaussians."""
+        """The front-end's tracking of one frame (TrackingGraph.run_eager) on the loaded Gaussians."""
         from .tracking_graph import TrackingGraph
         training = self.config["Training"]
         if self._tracker is None:
             self._tracker = TrackingGraph(self.map.gaussians, self.map.pipeline_params, self.map.background, self.config, viewpoint)
-        tracker = self._tracker
-        tracker.load(viewpoint)
-        every = int(training.get("converge_check_every", 5))
-        for it in range(int(training["tracking_itr_num"])):
-            tracker.iteration()
-            if (it + 1) % every == 0 and tracker.cam.converged():
-                break
-        tracker.store(viewpoint)
+        self._tracker.load(viewpoint)
+        self._tracker.run_eager(int(training["tracking_itr_num"]), int(training.get("converge_check_every", 5)))
+        self._tracker.store(viewpoint)
         return self._render_at(viewpoint)
 
     def camera(self, dataset, idx):
         """The frame `idx` of a dataset as a Camera ready to be localised (its pose is the identity until localise() sets it)."""
-        from .camera import Camera
         viewpoint = Camera.init_from_dataset(dataset, idx, dataset.projection_matrix)
         viewpoint.compute_grad_mask(self.config)
         return viewpoint
@@ -404,25 +386,20 @@ class MapLocaliser:
         {"poses": float32 [N, 4, 4] world-to-camera, "status": per frame "localised" | "tracked" | "relocalised" | "lost", "frames",
         "ate_rmse": against the dataset's ground truth over the frames that are not lost, None without one or with fewer than three}."""
         from .eval_utils import ate_rmse
-        opt = self.opt
         poses, status, gts = [], [], []
         previous = None
         for idx in frames:
             viewpoint = self.camera(dataset, idx)
             if previous is None:
-                found = self.localise(viewpoint)["accepted"]
-                state = "localised" if found else "lost"
+                found, state = self.localise(viewpoint), "localised"
             else:
                 viewpoint.update_RT(*previous)
-                pkg = self._track_from(viewpoint)
-                found = verdict(score(pkg, viewpoint, opt["tau_colour"], opt["tau_depth"]).tolist(), opt)["accepted"]
-                state = "tracked"
-                if not found:
-                    viewpoint.update_RT(*previous)
-                    found = self.localise(viewpoint)["accepted"]
-                    state = "relocalised" if found else "lost"
-            if found:
+                found = self.relocaliser.judge(viewpoint, self._track_from(viewpoint), previous)
+                state = "tracked" if found["keyframe"] is None else "relocalised"
+            if found["accepted"]:
                 previous = (viewpoint.R.detach().clone(), viewpoint.T.detach().clone())
+            else:
+                state = "lost"
             pose = torch.eye(4)
             pose[:3, :3], pose[:3, 3] = viewpoint.R.detach().cpu(), viewpoint.T.detach().cpu()
             gt = torch.eye(4)

@@ -1,0 +1,183 @@
+"""The optional stages of the front-end, one object each: ``SweepSeeding`` (``Training.mono_sweep``), ``PosePrior`` (``Training.pose_prior``)
+and ``Relocalisation`` (``Training.relocalisation``). Each owns its checked options (``.options``), the device object it builds at its first
+use (slam/sweep.py and slam/odometry.py are not imported before that), the device time of its calls and the ``summary()`` a run reports.
+What couples two stages (a lost frame drops the prior's kept frame) is left to ``FrontEnd``. Imports without a GPU."""
+import torch
+
+from .camera import compose_pose, opaque_depth
+from .options import check_gate, check_pass_counts, read_block, to_floats
+from .pretrained import EventLog
+from .relocalise import KeyframeIndex, Relocaliser
+
+
+# ---- Training.mono_sweep: a monocular keyframe's seed depth from a plane sweep over the window ---------------------------------------------
+MONO_SWEEP_DEFAULTS = {"enabled": False, "partners": 3, "near": 0.25, "p1": 10, "p2": 120, "uniqueness_ratio": 40, "min_span_px": 8}
+
+
+def mono_sweep_options(training):
+    """The ``Training.mono_sweep`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
+    sweep cannot take are refused here, before the run starts."""
+    opt = read_block(training, "mono_sweep", MONO_SWEEP_DEFAULTS)
+    if opt is None:
+        return None
+    opt = {"enabled": True, "near": float(opt["near"]), **{k: int(opt[k]) for k in ("partners", "p1", "p2", "uniqueness_ratio", "min_span_px")}}
+    if not 1 <= opt["partners"] <= 4:
+        raise ValueError(f"Training.mono_sweep.partners must be 1 to 4, got {opt['partners']}")
+    if not (0.0 < opt["near"] <= 1.0):
+        raise ValueError(f"Training.mono_sweep.near must be in (0, 1] (the nearest swept depth as a share of the median), got {opt['near']}")
+    if not (0 < opt["p1"] < opt["p2"] <= 2047) or not 0 <= opt["uniqueness_ratio"] <= 99 or opt["min_span_px"] < 0:
+        raise ValueError("Training.mono_sweep needs 0 < p1 < p2 <= 2047, 0 <= uniqueness_ratio <= 99 and min_span_px >= 0, got "
+                         f"p1 {opt['p1']}, p2 {opt['p2']}, uniqueness_ratio {opt['uniqueness_ratio']}, min_span_px {opt['min_span_px']}")
+    return opt
+
+
+def merge_sweep_depth(sweep_depth, sweep_valid, gt_img, rgb_boundary_threshold, fallback):
+    """The seed depth of a swept keyframe: the sweep's where it is valid and the pixel passes the RGB boundary threshold, else the fallback."""
+    use = sweep_valid & (gt_img.sum(dim=0) > rgb_boundary_threshold)
+    return torch.where(use, sweep_depth, fallback)
+
+
+class SweepSeeding:
+    def __init__(self, options):
+        self.options = options
+        self.sweeper = None                   # slam.sweep.PlaneSweep, built at the first keyframe swept
+        self.shares, self.log = [], EventLog("cuda")      # per swept keyframe its valid share, a device scalar, and its device time
+
+    def seed_depth(self, gt_img, fallback, median, threshold, window):
+        """The new keyframe's depth from a plane sweep (slam/sweep.py, include/multiview_depth.h) against the most recent `partners`
+        keyframes of `window` (its cameras, the new keyframe first) under their tracked poses, inverse depth 0 .. 1 / (near * median) in 63
+        steps, merged with `fallback` (merge_sweep_depth). Nothing is read by the host: the valid share stays on the device until summary()."""
+        opt = self.options
+        newest = window[0]
+        partners = [cam for cam in window[1:1 + opt["partners"]] if cam.original_image is not None]
+        if not partners or not (median > 0.0 and median < float("inf")):
+            return fallback
+        if self.sweeper is None:
+            from .sweep import PlaneSweep
+            self.sweeper = PlaneSweep(p1=opt["p1"], p2=opt["p2"], uniqueness_ratio=opt["uniqueness_ratio"], min_span_px=opt["min_span_px"],
+                                      device=gt_img.device)
+        with self.log.timed():
+            swept = self.sweeper.sweep(gt_img, [cam.original_image for cam in partners], (newest.fx, newest.fy, newest.cx, newest.cy),
+                                       self.sweeper.relative_transforms(newest, partners), 0.0, 1.0 / (opt["near"] * median * 63.0))
+        self.shares.append(swept["valid"].float().mean())
+        return merge_sweep_depth(swept["depth"], swept["valid"], gt_img, threshold, fallback)
+
+    def summary(self):
+        """The `sweep` block of the run result: keyframes swept, their mean valid share, device ms per keyframe."""
+        share = float(torch.stack(self.shares).mean()) if self.shares else 0.0
+        return {"keyframes": len(self.shares), "valid_share": share, "device_ms_per_keyframe": self.log.summary()["ms_per_item"] or 0.0}
+
+
+# ---- Training.pose_prior: the start of a frame's tracking from dense frame-to-frame alignment ----------------------------------------------
+POSE_PRIOR_DEFAULTS = {"enabled": False, "levels": 3, "iters": [5, 7, 10], "nu": 5.0, "sigma_init": 0.1, "sigma_min": 1e-3, "min_share": 0.3,
+                       "max_last_step": 1e-2, "max_translation": 0.5, "max_rotation": 20.0, "depth_min": 0.0, "depth_max": 1e6,
+                       "constant_velocity": False}
+
+
+def pose_prior_options(training):
+    """The ``Training.pose_prior`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys and values the
+    alignment cannot take are refused here, before the run starts. max_translation is in metres (monocular input: map units), max_rotation
+    in degrees; iters lists the passes per level, finest first."""
+    name = "Training.pose_prior"
+    opt = read_block(training, "pose_prior", POSE_PRIOR_DEFAULTS)
+    if opt is None:
+        return None
+    opt["constant_velocity"], opt["levels"] = bool(opt["constant_velocity"]), int(opt["levels"])
+    if not 1 <= opt["levels"] <= 6:
+        raise ValueError(f"{name}.levels must be 1 to 6, got {opt['levels']}")
+    if "iters" not in training["pose_prior"] and opt["levels"] != POSE_PRIOR_DEFAULTS["levels"]:
+        raise ValueError(f"{name}.iters must be given with levels = {opt['levels']}: one count per level, finest first")
+    check_pass_counts(opt, name)
+    to_floats(opt, name, ("nu", "sigma_init", "sigma_min", "min_share", "max_last_step", "max_translation", "max_rotation", "depth_min", "depth_max"))
+    for key in ("nu", "sigma_init", "sigma_min"):
+        if not (0.0 < opt[key] < float("inf")):
+            raise ValueError(f"{name}.{key} must be positive and finite, got {opt[key]}")
+    if not 0.0 <= opt["min_share"] <= 1.0:
+        raise ValueError(f"{name}.min_share must be in [0, 1], got {opt['min_share']}")
+    check_gate(opt, name, ("max_last_step", "max_translation", "max_rotation"))
+    if not 0.0 <= opt["depth_min"] <= opt["depth_max"]:
+        raise ValueError(f"{name} needs 0 <= depth_min <= depth_max, got {opt['depth_min']} and {opt['depth_max']}")
+    return opt
+
+
+class PosePrior:
+    def __init__(self, options, monocular, dynamic_model):
+        self.options, self.monocular, self.dynamic_model = options, monocular, dynamic_model
+        # slam.odometry.DenseOdometry, built with the first frame that is kept; the last aligned motion, where the next alignment starts
+        # with constant_velocity
+        self.odometry = self.motion = None
+
+    def keep(self, viewpoint, render_pkg=None):
+        """Keep `viewpoint` as the frame the next one is aligned against. Its depth: the sensor's (RGB-D) or the matcher's (stereo); for
+        monocular input the depth of `render_pkg` where its opacity is above 0.5 (None: the map does not exist yet, nothing is kept)."""
+        if self.odometry is None:
+            from .odometry import DenseOdometry
+            options = {k: v for k, v in self.options.items() if k not in ("enabled", "constant_velocity")}
+            self.odometry = DenseOdometry(viewpoint.image_width, viewpoint.image_height, (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
+                                          device=viewpoint.device, **options)
+        depth = viewpoint.depth_device()
+        if self.monocular:
+            depth = None if render_pkg is None else opaque_depth(render_pkg["depth"], render_pkg["opacity"])
+        if depth is None:
+            self.odometry.drop()
+            return
+        self.odometry.keep(viewpoint.original_image, depth, viewpoint.motion_mask if self.dynamic_model else None)
+
+    def restart(self, viewpoint):
+        """A map that starts (over): the last motion is forgotten and `viewpoint`, its first frame, replaces the kept frame."""
+        self.motion = None
+        self.keep(viewpoint)
+
+    def drop(self):
+        """The next frame is not aligned against the kept one (a lost frame: it has no pose of its own)."""
+        if self.odometry is not None:
+            self.odometry.drop()
+
+    def start(self, viewpoint, previous):
+        """Move `viewpoint` from the previous frame's pose W2C_prev to T W2C_prev, T the aligned motion (identity where the gate refused it:
+        the reference's start); with no frame kept it stays where it is. Device tensors throughout; the host reads nothing."""
+        if self.odometry is None or not self.odometry.has_previous:
+            return
+        self.motion, _ = self.odometry.align(viewpoint.original_image, self.motion if self.options["constant_velocity"] else None)
+        viewpoint.update_RT(*compose_pose(self.motion, previous.R, previous.T))
+
+    def summary(self):
+        """The `odometry` block of the run result: frames aligned, the accepted share, the mean inlier share, device ms per frame."""
+        if self.odometry is None:
+            return {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
+        return self.odometry.summary()
+
+
+# ---- Training.relocalisation: is the tracked frame lost, and if so where is it ------------------------------------------------------------
+class Relocalisation:
+    def __init__(self, options, dynamic_model):
+        self.options, self.dynamic_model = options, dynamic_model
+        self.index = self.relocaliser = None                  # built with the first map, on the device
+        self.stats, self.log = {"scored": 0, "lost": 0, "relocalised": 0}, EventLog("cuda")
+
+    def restart(self, frame_idx, viewpoint, cameras, render_at, track_from):
+        """A map that starts (over) with the keyframe `viewpoint` forgets the places of the old one. The rest is what Relocaliser works with."""
+        if self.index is None:
+            self.index = KeyframeIndex.from_options(self.options, viewpoint.device)
+            self.relocaliser = Relocaliser(self.index, cameras, render_at, track_from, (viewpoint.image_width, viewpoint.image_height),
+                                           (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), self.options, self.log)
+        self.index.clear()
+        self.add(frame_idx, viewpoint)
+
+    def add(self, frame_idx, viewpoint):
+        """The new keyframe's real frame into the place index: one encode into the next row of the device database."""
+        self.index.add(frame_idx, viewpoint.original_image, viewpoint.depth_device(), viewpoint.motion_mask if self.dynamic_model else None)
+
+    def judge(self, viewpoint, render_pkg, fallback):
+        """Relocaliser.judge of the tracked frame, counted: its result tells accepted, relocalised and lost apart."""
+        found = self.relocaliser.judge(viewpoint, render_pkg, fallback, viewpoint.motion_mask if self.dynamic_model else None)
+        self.stats["scored"] += 1
+        if not found["accepted"]:
+            self.stats["lost"] += 1
+        elif found["keyframe"] is not None:
+            self.stats["relocalised"] += 1
+        return found
+
+    def summary(self):
+        """The `relocalisation` block of the run result: frames scored, lost, relocalised, device ms per score."""
+        return {**self.stats, "device_ms_per_score": self.log.summary()["ms_per_item"] or 0.0}

@@ -1,7 +1,7 @@
 """Plane-sweep depth of one view from up to four others with known relative poses: the checked ctypes binding of include/multiview_depth.h
 (gsr_sweep_depth: census, a cost over 64 inverse-depth hypotheses, eight-path semi-global aggregation, selection and depth on the device,
 csrc/gs_sweep.h) and ``PlaneSweep`` with its cached workspaces. The monocular front-end seeds a new keyframe with it from the window's
-keyframes (slam/frontend.py, ``Training.mono_sweep``); the reference has no counterpart. tests/sweep_reference.py restates the contract in
+keyframes (slam/stages.py, ``Training.mono_sweep``); the reference has no counterpart. tests/sweep_reference.py restates the contract in
 numpy and the kernels equal that bit for bit. No CPU path.
 
 Limits: census windows are compared fronto-parallel, so strong rotation or forward motion between the views weakens the cost; the depth is

@@ -98,12 +98,9 @@ class SLAM:
                        "gaussians": int(self.gaussians.get_xyz.shape[0]), "sensor_type": self.config["Dataset"]["sensor_type"]}
         if self.monocular:
             self.result["resets"] = fe.resets
-            if fe.mono_sweep is not None:
-                self.result["sweep"] = fe.sweep_summary()
-        if fe.pose_prior is not None:
-            self.result["odometry"] = fe.odometry_summary()
-        if fe.relocalisation is not None:
-            self.result["relocalisation"] = fe.relocalisation_summary()
+        for key, stage in (("sweep", fe.mono_sweep if self.monocular else None), ("odometry", fe.pose_prior), ("relocalisation", fe.relocalisation)):
+            if stage is not None:
+                self.result[key] = stage.summary()
         if fe.init_done_at is not None and len(fe.cameras) > 1:          # frames per second once the map exists (tracking + keyframe mapping)
             self.result["seconds_init"] = fe.init_done_at - t0
             self.result["fps_after_init"] = (len(fe.cameras) - 1) / max(1e-9, t0 + dt - fe.init_done_at)

@@ -170,19 +170,27 @@ class TrackingGraph:
             c.refresh_matrices()
         return self
 
+    def _until_converged(self, step, iters, check_every):
+        """step() up to `iters` times, until a convergence poll (one every `check_every` calls) succeeds: (calls, the last one's result)."""
+        done, out = 0, None
+        for done in range(1, iters + 1):
+            out = step()
+            if done % check_every == 0 and self.cam.converged():
+                break
+        return done, out
+
     def run(self, iters, check_every=5):
         """Replay up to `iters` iterations; stops at the first convergence poll that succeeds. Returns (iterations run, ok) where
         ok = False means a replayed forward pass outgrew its binning buffer and the frame must be redone eagerly."""
-        done = 0
         torch.cuda.current_stream(self.cam.device).synchronize()     # eager work queued before (mapping, evaluation renders) may still bump the counter
         self.overflow0 = _C.forward_status()[0]
-        for it in range(iters):
-            self.graph.replay()
-            done += 1
-            if (it + 1) % check_every == 0 and self.cam.converged():
-                break
+        done, _ = self._until_converged(self.graph.replay, iters, check_every)
         torch.cuda.current_stream(self.cam.device).synchronize()
         return done, _C.forward_status()[0] == self.overflow0
+
+    def run_eager(self, iters, check_every=5):
+        """The same iterations launch by launch, with the same convergence poll; returns the last iteration's render package."""
+        return self._until_converged(self.iteration, iters, check_every)[1]
 
     def release(self):
         self.graph = None

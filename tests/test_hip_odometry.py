@@ -283,7 +283,7 @@ def test_slam_run_with_the_prior_on_and_off():
     on, slam_on = _run({"pose_prior": {"enabled": True}})
     off, slam_off = _run({})
     print("prior on:", {k: on[k] for k in ("frames", "keyframes", "ate_rmse", "odometry")}, "| off:", {k: off[k] for k in ("frames", "keyframes", "ate_rmse")})
-    assert "odometry" not in off and slam_off.frontend.pose_prior is None and slam_off.frontend._odometry is None
+    assert "odometry" not in off and slam_off.frontend.pose_prior is None
     assert on["frames"] == off["frames"] == 20
     block = on["odometry"]
     assert block["frames"] == 19 and block["accepted_share"] >= 0.8 and block["inlier_share"] > 0.3 and block["device_ms_per_frame"] > 0.0
@@ -296,4 +296,4 @@ def test_monocular_slam_run_with_the_prior_on():
     print("prior on:", {k: on[k] for k in ("frames", "keyframes", "ate_rmse", "resets", "odometry")}, "| off:", {k: off[k] for k in ("frames", "keyframes", "ate_rmse", "resets")})
     assert on["frames"] == 20 and "odometry" in on and on["odometry"]["frames"] >= 1
     assert on["resets"] <= off["resets"]                                  # the prior causes no reset
-    assert "odometry" not in off and slam_off.frontend._odometry is None
+    assert "odometry" not in off and slam_off.frontend.pose_prior is None

@@ -484,11 +484,11 @@ def test_end_to_end_the_option_on_changes_no_pose_when_nothing_is_lost(plain_run
     on, slam_on = _slam(_dataset(), {"relocalisation": {"enabled": True}})
     events = [e[0] for e in slam_on.frontend.log]
     print("option on:", on["relocalisation"], "keyframes", on["keyframes"])
-    assert "relocalisation" not in off and slam_off.frontend._reloc_index is None
+    assert "relocalisation" not in off and slam_off.frontend.relocalisation is None
     assert "lost" not in events and "relocalised" not in events
     assert on["keyframes"] == off["keyframes"] and on["relocalisation"]["scored"] == FRAMES - 1
     assert on["relocalisation"]["lost"] == on["relocalisation"]["relocalised"] == 0 and on["relocalisation"]["device_ms_per_score"] > 0.0        # measured: 0.15 ms
-    assert len(slam_on.frontend._reloc_index) == len(on["keyframes"])
+    assert len(slam_on.frontend.relocalisation.index) == len(on["keyframes"])
     for i in sorted(slam_off.frontend.cameras):
         a, b = slam_off.frontend.cameras[i], slam_on.frontend.cameras[i]
         assert torch.equal(a.R, b.R) and torch.equal(a.T, b.T), i

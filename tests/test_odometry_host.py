@@ -123,7 +123,8 @@ def _config(pose_prior=None, monocular=False):
 
 
 def test_pose_prior_block_parses_with_defaults_and_is_off_unless_enabled():
-    from slam.frontend import POSE_PRIOR_DEFAULTS, FrontEnd, pose_prior_options
+    from slam.frontend import FrontEnd
+    from slam.stages import POSE_PRIOR_DEFAULTS, pose_prior_options
     assert pose_prior_options({}) is None and pose_prior_options({"pose_prior": {}}) is None
     assert pose_prior_options({"pose_prior": {"enabled": False, "levels": 99}}) is None
     assert FrontEnd(_config()).pose_prior is None
@@ -134,7 +135,7 @@ def test_pose_prior_block_parses_with_defaults_and_is_off_unless_enabled():
     assert set(got) == {"enabled", "levels", "iters", "nu", "sigma_init", "sigma_min", "min_share", "max_last_step", "max_translation",
                         "max_rotation", "depth_min", "depth_max", "constant_velocity"}
     got = FrontEnd(_config({"enabled": True, "levels": 2, "iters": (8, 10), "nu": 4, "max_translation": 0.2, "max_rotation": 10,
-                            "depth_min": 0.1, "depth_max": 8, "constant_velocity": 1})).pose_prior
+                            "depth_min": 0.1, "depth_max": 8, "constant_velocity": 1})).pose_prior.options
     assert (got["levels"], got["iters"], got["nu"], got["max_translation"], got["max_rotation"], got["depth_min"], got["depth_max"],
             got["constant_velocity"]) == (2, [8, 10], 4.0, 0.2, 10.0, 0.1, 8.0, True)
 
@@ -147,13 +148,13 @@ def test_pose_prior_block_parses_with_defaults_and_is_off_unless_enabled():
     ({"max_rotation": 200}, "max_rotation"), ({"max_rotation": float("nan")}, "max_rotation"), ({"depth_min": -1}, "depth_min"),
     ({"depth_min": 3, "depth_max": 2}, "depth_min")])
 def test_pose_prior_refusals_name_what_is_wrong(block, names):
-    from slam.frontend import pose_prior_options
+    from slam.stages import pose_prior_options
     with pytest.raises(ValueError, match="Training.pose_prior.*" + names):
         pose_prior_options({"pose_prior": dict(block, enabled=True)})
 
 
 def test_pose_composition_is_T_times_the_previous_world_to_camera():
-    from slam.frontend import compose_pose
+    from slam.camera import compose_pose
     rng = np.random.default_rng(3)
     for _ in range(8):
         W2C_prev, W2C_cur = (ref.se3_exp(rng.uniform(-1, 1, 6)) for _ in range(2))
@@ -174,11 +175,11 @@ def test_frontend_without_the_option_never_meets_the_odometry():
             "from slam.frontend import FrontEnd\n"
             "cfg = lambda t: {'Training': dict({'monocular': False}, **t), 'Results': {}, 'model_params': {'dynamic_model': False}}\n"
             "off = FrontEnd(cfg({}))\n"
-            "assert off.pose_prior is None and off._odometry is None and off.odometry_summary() is None\n"
+            "assert off.pose_prior is None\n"
             "assert 'slam.odometry' not in sys.modules\n"
             "on = FrontEnd(cfg({'pose_prior': {'enabled': True}}))\n"
-            "assert on.pose_prior['enabled'] and on._odometry is None and 'slam.odometry' not in sys.modules\n"
-            "assert on.odometry_summary() == {'frames': 0, 'accepted_share': 0.0, 'inlier_share': 0.0, 'device_ms_per_frame': 0.0}\n"
+            "assert on.pose_prior.options['enabled'] and on.pose_prior.odometry is None and 'slam.odometry' not in sys.modules\n"
+            "assert on.pose_prior.summary() == {'frames': 0, 'accepted_share': 0.0, 'inlier_share': 0.0, 'device_ms_per_frame': 0.0}\n"
             "print('ok')\n")
     done = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert done.returncode == 0 and done.stdout.strip().endswith("ok"), done.stderr
@@ -217,27 +218,27 @@ def test_the_prior_moves_the_start_and_keeps_the_right_depth():
     previous = _camera(W2C[:3, :3], W2C[:3, 3], torch.ones(2, 2))
     # RGB-D, constant velocity: the first alignment starts at identity, the second at the first one's result
     fe = FrontEnd(_config({"enabled": True, "constant_velocity": True}))
-    fe._odometry = odo = _Odometry(T)
-    fe._prior_keep(previous)
+    fe.pose_prior.odometry = odo = _Odometry(T)
+    fe.pose_prior.keep(previous)
     assert odo.calls == [("keep", previous.depth, None)] and odo.has_previous
     cam = _camera(previous.R, previous.T, 2 * torch.ones(2, 2))
-    fe._prior_start(cam, previous)
+    fe.pose_prior.start(cam, previous)
     want = T.double() @ W2C.double()
     assert odo.calls[-1] == ("align", None)
     assert (cam.R.double() - want[:3, :3]).abs().max() < 1e-6 and (cam.T.double() - want[:3, 3]).abs().max() < 1e-6
-    fe._prior_start(cam, previous)
+    fe.pose_prior.start(cam, previous)
     assert odo.calls[-1][0] == "align" and odo.calls[-1][1] is T
     # monocular: the rendered depth where the opacity is above one half; no rendering yet, nothing kept
     fe = FrontEnd(_config({"enabled": True}, monocular=True))
-    fe._odometry = odo = _Odometry(T)
-    fe._prior_keep(cam)
+    fe.pose_prior.odometry = odo = _Odometry(T)
+    fe.pose_prior.keep(cam)
     assert odo.calls == [("drop",)] and not odo.has_previous
     pkg = {"depth": torch.tensor([[[1.0, 2.0], [3.0, 4.0]]]), "opacity": torch.tensor([[[0.9, 0.5], [0.51, 0.0]]])}
-    fe._prior_keep(cam, pkg)
+    fe.pose_prior.keep(cam, pkg)
     assert torch.equal(odo.calls[-1][1], torch.tensor([[[1.0, 0.0], [3.0, 0.0]]])) and odo.calls[-1][2] is None
     # a dynamic model hands the motion mask on
     fe = FrontEnd(_config({"enabled": True}))
-    fe.dynamic_model, fe._odometry = True, _Odometry(T)
+    fe.pose_prior.dynamic_model, fe.pose_prior.odometry = True, _Odometry(T)
     masked = _camera(previous.R, previous.T, torch.ones(2, 2), mask=torch.tensor([[True, False], [True, True]]))
-    fe._prior_keep(masked)
-    assert fe._odometry.calls[-1][2] is masked.motion_mask
+    fe.pose_prior.keep(masked)
+    assert fe.pose_prior.odometry.calls[-1][2] is masked.motion_mask

@@ -4,9 +4,11 @@ verdict. No GPU needed."""
 import math
 import os
 import sys
+import types
 
 import numpy as np
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (REPO, os.path.join(REPO, "4dgs-slam_amd"), os.path.join(REPO, "tests")):
@@ -169,11 +171,43 @@ def test_the_front_end_reads_the_block_once_and_is_inert_without_it():
     from slam.frontend import FrontEnd
     from slam.system import default_config, merge_config
     off = FrontEnd(default_config())
-    assert off.relocalisation is None and off._reloc_index is None and off.relocalisation_summary() is None
+    assert off.relocalisation is None
     on = FrontEnd(merge_config(default_config(), {"Training": {"relocalisation": {"enabled": True, "topk": 2}}}))
-    assert on.relocalisation["topk"] == 2 and on._reloc_index is None              # the index is built with the map, on the device
+    assert on.relocalisation.options["topk"] == 2 and on.relocalisation.index is None              # the index is built with the map, on the device
+    assert on.relocalisation.summary() == {"scored": 0, "lost": 0, "relocalised": 0, "device_ms_per_score": 0.0}
     with pytest.raises(ValueError, match="relocalisation.topk"):
         FrontEnd(merge_config(default_config(), {"Training": {"relocalisation": {"enabled": True, "topk": 17}}}))
+
+
+def test_a_front_end_whose_stage_has_started_is_freed_without_the_cycle_collector(monkeypatch):
+    """The relocaliser is handed two calls into the front-end. A front-end that could only be freed by the cycle collector would have its
+    streams, events and captured graphs destroyed whenever that next runs -- in the middle of a later run's graph capture, for instance."""
+    import gc
+    import weakref
+    from slam import stages
+    from slam.frontend import FrontEnd
+    from slam.system import default_config, merge_config
+    built = []
+    monkeypatch.setattr(stages, "Relocaliser", lambda *args: built.append(args) or types.SimpleNamespace())
+    monkeypatch.setattr(stages.KeyframeIndex, "from_options", lambda opt, device: types.SimpleNamespace(clear=lambda: None, add=lambda *a: None))
+    frame = types.SimpleNamespace(R_gt=torch.eye(3), T_gt=torch.zeros(3), original_image=torch.ones(3, 2, 2), motion_mask=None, device="cpu",
+                                  image_width=2, image_height=2, fx=1.0, fy=1.0, cx=1.0, cy=1.0, update_RT=lambda R, T: None,
+                                  depth_device=lambda: torch.ones(2, 2))
+    gc.disable()
+    try:
+        fe = FrontEnd(merge_config(default_config(), {"Training": {"relocalisation": {"enabled": True}}}))
+        fe.device, fe.cameras[0] = "cpu", frame
+        fe.backend = types.SimpleNamespace(handle_init=lambda *a: (None, None, {}, []))
+        fe._render_at, fe._track_and_render = (lambda camera: ("rendered at", camera)), (lambda viewpoint: ("tracked", viewpoint))
+        fe.initialize(0, frame)
+        (index, cameras, render_at, track_from, size, K, options, log), = built
+        assert cameras is fe.cameras and render_at(frame) == ("rendered at", frame) and track_from(frame) == ("tracked", frame)
+        assert size == (2, 2) and K == (1.0, 1.0, 1.0, 1.0) and options is fe.relocalisation.options and log is fe.relocalisation.log
+        gone = weakref.ref(fe)
+        del fe
+        assert gone() is None
+    finally:
+        gc.enable()
 
 
 # ---- the verdict ----------------------------------------------------------------------------------------------------------------------------
@@ -195,3 +229,91 @@ def test_verdict_shares_and_every_zero_denominator():
     assert not relocalise.verdict([0, 0, 0, 0, 0, 0, 0, 0], lenient)["accepted"]                        # refused, never a division error
     assert not relocalise.verdict([100, 0, 0, 0, 0, 0, 0, 0], lenient)["accepted"]
     assert relocalise.verdict([100, 1, 0, 1, 0, 0, 0, 0], lenient)["accepted"]
+
+
+# ---- judge and recover: the one path of a live run and of a saved map ---------------------------------------------------------------------------
+ACCEPT, REFUSE = [100, 80, 80, 0, 0, 0, 0, 0], [100, 0, 0, 0, 0, 0, 0, 0]
+NUDGE = 0.125                          # what the tracking double adds to the translation and to the exposure gain
+
+
+class _Index:
+    """Stands in for KeyframeIndex: three keyframes, a fixed answer, and a count of the queries."""
+    device = "cpu"
+
+    def __init__(self, best):
+        self.ids, self.best, self.queries = [10, 20, 30], best, 0
+
+    def query(self, image, depth=None, mask=None, topk=4):
+        self.queries += 1
+        return torch.tensor(self.best, dtype=torch.int32), None
+
+
+class _Aligner:
+    """Stands in for DenseOdometry: every alignment is refused, so a seeded pose is the candidate keyframe's."""
+
+    def __init__(self, *args, **kwargs):
+        pass
+
+    def keep(self, image, depth=None, mask=None):
+        pass
+
+    def align(self, image, T_init=None):
+        return torch.eye(4), None
+
+
+def _frame(seed):
+    g = torch.Generator().manual_seed(seed)
+    cam = types.SimpleNamespace(R=torch.linalg.qr(torch.randn(3, 3, generator=g))[0], T=torch.randn(3, generator=g), original_image=torch.zeros(3, 2, 2),
+                                exposure_a=torch.tensor([0.25]), exposure_b=torch.tensor([-0.5]), depth_device=lambda: None)
+    cam.update_RT = lambda R, T: (setattr(cam, "R", R.clone()), setattr(cam, "T", T.clone()))
+    return cam
+
+
+def _judge(monkeypatch, verdicts, best, fallback_is_entry=False):
+    """Relocaliser.judge of a tracked frame among doubles; the scores are `verdicts` in order. Returns (result, frame, what it was on entry,
+    fallback pose, keyframes, index)."""
+    from slam import odometry
+    monkeypatch.setattr(odometry, "DenseOdometry", _Aligner)
+    script = [torch.tensor(c, dtype=torch.int32) for c in verdicts]
+    monkeypatch.setattr(relocalise, "score", lambda pkg, viewpoint, tau_colour, tau_depth, mask=None: script.pop(0))
+    keyframes, index = {k: _frame(k) for k in (10, 20, 30)}, _Index(best)
+    blank = {"render": torch.zeros(3, 2, 2), "depth": torch.ones(1, 2, 2), "opacity": torch.ones(1, 2, 2)}
+
+    def track_from(viewpoint):
+        viewpoint.update_RT(viewpoint.R, viewpoint.T + NUDGE)
+        viewpoint.exposure_a += NUDGE
+        return blank
+
+    reloc = relocalise.Relocaliser(index, keyframes, lambda camera: blank, track_from, (2, 2), (1.0, 1.0, 1.0, 1.0), relocalise.default_options())
+    frame = _frame(1)
+    fallback = (frame.R.clone(), frame.T.clone()) if fallback_is_entry else (_frame(2).R, _frame(2).T)
+    entry = tuple(t.clone() for t in (frame.R, frame.T, frame.exposure_a, frame.exposure_b))
+    out = reloc.judge(frame, blank, fallback)
+    assert not script                                                         # one score per verdict: nothing is judged twice or skipped
+    return out, frame, entry, fallback, keyframes, index
+
+
+def test_judge_accepts_a_tracked_frame_without_asking_the_index(monkeypatch):
+    out, frame, entry, _, _, index = _judge(monkeypatch, [ACCEPT], [[0, 1], [-1, 9]])
+    assert out["accepted"] and out["keyframe"] is None and out["candidates_tried"] == 0 and out["counts"] == ACCEPT
+    assert index.queries == 0
+    assert all(torch.equal(a, b) for a, b in zip((frame.R, frame.T, frame.exposure_a, frame.exposure_b), entry))     # it stays where tracking put it
+
+
+def test_judge_finds_a_refused_frame_at_the_second_candidate(monkeypatch):
+    out, frame, _, _, keyframes, index = _judge(monkeypatch, [REFUSE, REFUSE, ACCEPT], [[2, 3], [0, 5], [1, 7], [-1, 9]])
+    assert out["accepted"] and out["keyframe"] == 10 and out["candidates_tried"] == 2 and out["distance"] == 5 and index.queries == 1
+    # the pose is the second candidate's (row 0, keyframe 10), tracked once from there -- not the first candidate's, not the fallback
+    assert torch.equal(frame.R, keyframes[10].R) and torch.equal(frame.T, keyframes[10].T + NUDGE)
+
+
+@pytest.mark.parametrize("fallback_is_entry", [True, False])
+def test_judge_leaves_a_frame_that_is_not_found_as_it_came(monkeypatch, fallback_is_entry):
+    """Refused at the tracked pose and at both candidates: the frame has the fallback pose (here once the pose it came with, once another)
+    and the exposure it came with, bit for bit, although the tracking double moved both at every candidate."""
+    out, frame, entry, fallback, _, index = _judge(monkeypatch, [REFUSE, REFUSE, REFUSE], [[2, 3], [0, 5], [-1, 9], [-1, 9]], fallback_is_entry)
+    assert not out["accepted"] and out["keyframe"] is None and out["candidates_tried"] == 2 and index.queries == 1
+    assert torch.equal(frame.R, fallback[0]) and torch.equal(frame.T, fallback[1])
+    assert torch.equal(frame.exposure_a, entry[2]) and torch.equal(frame.exposure_b, entry[3])
+    if fallback_is_entry:
+        assert torch.equal(frame.R, entry[0]) and torch.equal(frame.T, entry[1])

@@ -106,18 +106,11 @@ def _config(mono_sweep=None):
     return {"Training": training, "Results": {}, "model_params": {"dynamic_model": False}}
 
 
-class _Event:
-    def __init__(self, enable_timing=False):
-        pass
-
-    def record(self):
-        pass
-
-
 def _frontend(monkeypatch, mono_sweep, n_valid=50, H=6, W=8):
     """A FrontEnd on the CPU whose device calls are doubles: mono_keyframe_depth returns 3 + noise and a stats word triple, the sweep
     returns depth 7 with a checkerboard of valid pixels."""
     from slam import frontend
+    from slam.pretrained import EventLog
     fe = frontend.FrontEnd(_config(mono_sweep))
     fe.backend = types.SimpleNamespace(gaussians=types.SimpleNamespace(generator=torch.Generator().manual_seed(5)))
     seen = {}
@@ -133,9 +126,9 @@ def _frontend(monkeypatch, mono_sweep, n_valid=50, H=6, W=8):
         return {"depth": torch.where(valid, 7.0, 0.0), "index16": torch.where(valid, 160, -16).to(torch.int16), "valid": valid}
 
     monkeypatch.setattr(frontend.kf, "mono_keyframe_depth", mono_keyframe_depth)
-    monkeypatch.setattr(torch.cuda, "Event", _Event)
-    fe._sweeper = types.SimpleNamespace(sweep=sweep)
-    fe._relative_transforms = lambda newest, partners: ("transforms of", newest.uid, [c.uid for c in partners])
+    if fe.mono_sweep is not None:
+        relative_transforms = lambda newest, partners: ("transforms of", newest.uid, [c.uid for c in partners])
+        fe.mono_sweep.sweeper, fe.mono_sweep.log = types.SimpleNamespace(sweep=sweep, relative_transforms=relative_transforms), EventLog("cpu")
     image = torch.full((3, H, W), 0.5)
     image[:, 0, :] = 0.0                                                                       # the first row fails the RGB boundary threshold
     cam = lambda uid, img=image: types.SimpleNamespace(uid=uid, original_image=img, fx=8.0, fy=9.0, cx=4.0, cy=3.0)
@@ -164,7 +157,7 @@ def test_merge_takes_the_sweep_where_valid_and_coloured_and_keeps_the_noise_draw
     call = seen_on["sweep"]
     assert call["partners"] == 2 and call["transforms"] == ("transforms of", 9, [7, 2]) and call["K"] == (8.0, 9.0, 4.0, 3.0)
     assert call["w_min"] == 0.0 and call["w_step"] == pytest.approx(1.0 / (0.5 * 2.5 * 63.0), rel=1e-12)
-    assert not on.reset and len(on._sweep_shares) == 1 and float(on._sweep_shares[0]) == 0.5
+    assert not on.reset and len(on.mono_sweep.shares) == 1 and float(on.mono_sweep.shares[0]) == 0.5
 
 
 def test_reset_rule_and_first_keyframe_are_unchanged_with_the_option_on(monkeypatch):
@@ -176,11 +169,11 @@ def test_reset_rule_and_first_keyframe_are_unchanged_with_the_option_on(monkeypa
     off, _, _ = _frontend(monkeypatch, None)
     first_on, first_off = on._monocular_seed_depth(image, None, None), off._monocular_seed_depth(image, None, None)
     assert torch.equal(first_on, first_off) and "sweep" not in seen and "noise" not in seen      # the first keyframe has nothing to sweep against
-    assert on.sweep_summary() == {"keyframes": 0, "valid_share": 0.0, "device_ms_per_keyframe": 0.0} and off.sweep_summary() is None
+    assert on.mono_sweep.summary() == {"keyframes": 0, "valid_share": 0.0, "device_ms_per_keyframe": 0.0} and off.mono_sweep is None
 
 
 def test_merge_rule():
-    from slam.frontend import merge_sweep_depth
+    from slam.stages import merge_sweep_depth
     image = torch.tensor([[[0.2, 0.0, 0.2, 0.004]]]).repeat(3, 1, 1)                              # channel sums 0.6, 0, 0.6, 0.012
     got = merge_sweep_depth(torch.tensor([[5.0, 5.0, 0.0, 5.0]]), torch.tensor([[True, True, False, True]]), image, 0.01,
                             torch.tensor([[1.0, 2.0, 3.0, 4.0]]))
@@ -189,7 +182,8 @@ def test_merge_rule():
 
 # ---- configuration ---------------------------------------------------------------------------------------------------------------------
 def test_mono_sweep_block_parses_with_defaults_and_is_off_unless_enabled(tmp_path):
-    from slam.frontend import FrontEnd, mono_sweep_options
+    from slam.frontend import FrontEnd
+    from slam.stages import mono_sweep_options
     from slam.system import default_config
     assert "mono_sweep" not in default_config()["Training"]
     for training in ({}, {"mono_sweep": {}}, {"mono_sweep": {"enabled": False, "partners": 2}}, {"mono_sweep": None}):
@@ -197,7 +191,7 @@ def test_mono_sweep_block_parses_with_defaults_and_is_off_unless_enabled(tmp_pat
     assert FrontEnd(_config()).mono_sweep is None
     assert mono_sweep_options({"mono_sweep": {"enabled": True}}) == {"enabled": True, "partners": 3, "near": 0.25, "p1": 10, "p2": 120,
                                                                      "uniqueness_ratio": 40, "min_span_px": 8}
-    got = FrontEnd(_config({"enabled": True, "partners": 4, "near": 0.5, "p1": 7, "p2": 90, "uniqueness_ratio": 15, "min_span_px": 3})).mono_sweep
+    got = FrontEnd(_config({"enabled": True, "partners": 4, "near": 0.5, "p1": 7, "p2": 90, "uniqueness_ratio": 15, "min_span_px": 3})).mono_sweep.options
     assert got == {"enabled": True, "partners": 4, "near": 0.5, "p1": 7, "p2": 90, "uniqueness_ratio": 15, "min_span_px": 3}
     for block, text in (({"partners": 5}, "partners must be 1 to 4"), ({"partners": 0}, "partners must be 1 to 4"), ({"near": 0.0}, "near must be"),
                         ({"p1": 120}, "0 < p1 < p2"), ({"uniqueness_ratio": 100}, "uniqueness_ratio"), ({"min_span_px": -1}, "min_span_px"),
