@@ -3789,6 +3789,95 @@ int gsr_odometry_align(int width, int height, int levels, float fx, float fy, fl
     return 0;
 }
 
+// workspace of gsr_odometry_align_rgbd: OdoRgbdHead | the slab [blocks of level 0, 64] doubles
+struct OdoRgbdLayout { OdoRgbdHead* head; double* slab; size_t bytes; };
+static bool odo_rgbd_layout(int width, int height, int levels, const void* workspace, OdoRgbdLayout& l)
+{
+    OdoPyramidLayout p;
+    if (!odo_pyramid_layout(width, height, levels, nullptr, p)) return false;
+    Carver c(workspace, 16);
+    l.head = c.take<OdoRgbdHead>(1);
+    l.slab = c.take<double>((size_t)odo_blocks(width, height) * ODO_RGBD_ROW);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_odometry_align_rgbd_workspace_size(int width, int height, int levels)
+{
+    OdoRgbdLayout l;
+    return odo_rgbd_layout(width, height, levels, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_odometry_align_rgbd(int width, int height, int levels, float fx, float fy, float cx, float cy, const void* previous, const void* current,
+                            const float* T_init, const int* iters, int affine, float geometric_weight, float edge_ratio, float nu, float sigma_init,
+                            float sigma_min, float sigma_depth_init, float sigma_depth_min, float min_share, float max_last_step,
+                            float max_translation, float max_rotation, float max_gain, float max_offset, float* T, double* stats, double* trace,
+                            void* workspace, size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_odometry_align_rgbd: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    OdoRgbdLayout l;
+    OdoPyramidLayout P, C;
+    if (!odo_rgbd_layout(width, height, levels, workspace, l) || !odo_pyramid_layout(width, height, levels, previous, P) ||
+        !odo_pyramid_layout(width, height, levels, current, C))
+        return fail(kOdoSizeText);
+    if (!(fx > 0.f && fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail("fx and fy must be positive and the intrinsics finite");
+    if (!iters) return fail("iters must not be NULL");
+    for (int k = 0; k < levels; ++k)
+        if (iters[k] < 0 || iters[k] > 64) return fail("iters[" + std::to_string(k) + "] must be in [0, 64], got " + std::to_string(iters[k]));
+    if (affine != 0 && affine != 1) return fail("affine must be 0 or 1, got " + std::to_string(affine));
+    if (!(geometric_weight >= 0.f) || !std::isfinite(geometric_weight) || !(edge_ratio >= 0.f) || !std::isfinite(edge_ratio))
+        return fail("geometric_weight and edge_ratio must be finite and not negative");
+    if (!(nu > 0.f) || !std::isfinite(nu) || !(sigma_init > 0.f) || !std::isfinite(sigma_init) || !(sigma_min > 0.f) || !std::isfinite(sigma_min))
+        return fail("nu, sigma_init and sigma_min must be positive and finite");
+    if (!(sigma_depth_init > 0.f) || !std::isfinite(sigma_depth_init) || !(sigma_depth_min > 0.f) || !std::isfinite(sigma_depth_min))
+        return fail("sigma_depth_init and sigma_depth_min must be positive and finite");
+    if (!(min_share >= 0.f && min_share <= 1.f) || !(max_last_step >= 0.f) || !(max_translation >= 0.f) || !(max_rotation >= 0.f))
+        return fail("min_share must be in [0, 1] and max_last_step, max_translation, max_rotation must not be negative");
+    if (!(max_gain >= 0.f) || !(max_offset >= 0.f)) return fail("max_gain and max_offset must not be negative");
+    if (!previous || !current || !T || !stats || !workspace) return fail("previous, current, T, stats and workspace must not be NULL");
+    if (!workspace_fits("gsr_odometry_align_rgbd", "gsr_odometry_align_rgbd_workspace_size", workspace, workspace_bytes, l.bytes))
+        return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+        hipLaunchKernelGGL(odo_rgbd_init_kernel, dim3(1), dim3(64), 0, stream, T_init, sigma_init, sigma_depth_init, l.head);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    const bool depth_term = geometric_weight > 0.f;
+    int pass = 0;
+    for (int k = levels - 1; k >= 0; --k) {
+        const float scale = 1.f / (float)(1 << k);                                  // a power of two: the products below are exact
+        const OdoRgbdLevel L{P.w[k], P.h[k], fx * scale, fy * scale, (float)(((double)cx + 0.5) * scale - 0.5),
+                             (float)(((double)cy + 0.5) * scale - 0.5), P.I[k], P.D[k], C.I[k], C.D[k]};
+        const unsigned blocks = odo_blocks(L.w, L.h);
+        for (int it = 0; it < iters[k]; ++it, ++pass) {
+            double* const row = trace ? trace + (size_t)pass * ODO_RGBD_ROW : (double*)nullptr;
+            auto launch = [&](auto A, auto D) {                                     // the instantiation without the terms that are off
+                constexpr bool AFFINE = decltype(A)::value, DEPTH = decltype(D)::value;
+                {
+                    ScopedKernelTimer tm(K_ODO_SUMS, stream);
+                    hipLaunchKernelGGL((odo_rgbd_sums_kernel<AFFINE, DEPTH>), dim3(blocks), dim3(ODO_BLOCK), 0, stream, L, nu, geometric_weight,
+                                       edge_ratio, (const OdoRgbdHead*)l.head, l.slab);
+                }
+                ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+                hipLaunchKernelGGL((odo_rgbd_solve_kernel<AFFINE ? 8 : 6>), dim3(1), dim3(ODO_BLOCK), 0, stream, (int)blocks, (const double*)l.slab,
+                                   l.head, sigma_min, sigma_depth_min, k, row);
+            };
+            if (affine && depth_term) launch(std::true_type{}, std::true_type{});
+            else if (affine) launch(std::true_type{}, std::false_type{});
+            else if (depth_term) launch(std::false_type{}, std::true_type{});
+            else launch(std::false_type{}, std::false_type{});
+            GSR_HIP_CHECK(hipGetLastError());
+        }
+    }
+    ScopedKernelTimer tm(K_ODO_SOLVE, stream);
+    hipLaunchKernelGGL(odo_rgbd_finish_kernel, dim3(1), dim3(64), 0, stream, (const OdoRgbdHead*)l.head, (const OdoPyramidHead*)P.head, affine,
+                       min_share, max_last_step, max_translation, max_rotation, max_gain, max_offset, T, stats);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // workspace of gsr_reloc_encode: the sums of every cell, [grid_w * grid_h, 6] words
 struct RelocEncodeLayout { unsigned* cells; size_t bytes; };
 static bool reloc_encode_layout(int grid_w, int grid_h, const void* workspace, RelocEncodeLayout& l)

@@ -269,6 +269,8 @@ FUNCTIONS = {
     "gsr_odometry_pyramid": (i, [i, i, i, vp, vp, vp, f, f, vp, sz, vp]),
     "gsr_odometry_align_workspace_size": (sz, [i, i, i]),
     "gsr_odometry_align": (i, [i, i, i, f, f, f, f, vp, vp, vp, P(i)] + [f] * 7 + [vp] * 4 + [sz, vp]),
+    "gsr_odometry_align_rgbd_workspace_size": (sz, [i, i, i]),
+    "gsr_odometry_align_rgbd": (i, [i, i, i, f, f, f, f, vp, vp, vp, P(i), i] + [f] * 13 + [vp] * 4 + [sz, vp]),
     # relocalisation.h
     "gsr_reloc_encode_workspace_size": (sz, [i, i]),
     "gsr_reloc_encode": (i, [i, i, vp, vp, vp, i, i, i, vp, f, vp, vp, sz, vp]),

@@ -34,7 +34,7 @@ from . import keyframes as kf
 from .camera import Camera
 from .eval_utils import eval_ate, save_gaussians
 from .relocalise import relocalisation_options
-from .stages import PosePrior, Relocalisation, SweepSeeding, mono_sweep_options, pose_prior_options
+from .stages import PosePrior, Relocalisation, SweepSeeding, mono_sweep_options, pose_prior_options, pose_prior_terms_options
 
 
 def lower_median(x):
@@ -86,7 +86,8 @@ class FrontEnd:
         # way alone, a frame's tracking starts at the previous frame's pose and no frame is ever judged lost, as in the reference
         sweep, prior, reloc = mono_sweep_options(training), pose_prior_options(training), relocalisation_options(training)
         self.mono_sweep = sweep and SweepSeeding(sweep)
-        self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model)
+        terms = pose_prior_terms_options(training)                         # refused without pose_prior
+        self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model, terms)
         self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model)
 
     def set_hyperparams(self):
@@ -277,6 +278,8 @@ class FrontEnd:
             return
         if self.relocalisation is not None:
             self.relocalisation.add(cur_frame_idx, viewpoint)
+        if self.pose_prior is not None:                                           # (aligning against keyframes: this one from now on)
+            self.pose_prior.keyframe(viewpoint, render_pkg)
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))
         self.log.append(("keyframe", cur_frame_idx, overlap))
         viewpoint.clean_key()

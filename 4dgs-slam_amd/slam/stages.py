@@ -1,5 +1,5 @@
-"""The optional stages of the front-end, one object each: ``SweepSeeding`` (``Training.mono_sweep``), ``PosePrior`` (``Training.pose_prior``)
-and ``Relocalisation`` (``Training.relocalisation``). Each owns its checked options (``.options``), the device object it builds at its first
+"""The optional stages of the front-end, one object each: ``SweepSeeding`` (``Training.mono_sweep``), ``PosePrior`` (``Training.pose_prior``
+with ``Training.pose_prior_terms``) and ``Relocalisation`` (``Training.relocalisation``). Each owns its checked options (``.options``), the device object it builds at its first
 use (slam/sweep.py and slam/odometry.py are not imported before that), the device time of its calls and the ``summary()`` a run reports.
 What couples two stages (a lost frame drops the prior's kept frame) is left to ``FrontEnd``. Imports without a GPU."""
 import torch
@@ -100,19 +100,64 @@ def pose_prior_options(training):
     return opt
 
 
+# ---- Training.pose_prior_terms: what the alignment of Training.pose_prior models besides brightness constancy ------------------------------
+POSE_PRIOR_TERMS_DEFAULTS = {"enabled": False, "affine": True, "geometric_weight": 1.0, "edge_ratio": 0.05, "sigma_depth_init": 0.02,
+                             "sigma_depth_min": 1e-4, "max_gain": 0.5, "max_offset": 0.3, "against": "previous"}
+
+
+def pose_prior_terms_options(training):
+    """The ``Training.pose_prior_terms`` block with its defaults filled in, or None when it is absent or not enabled: an affine brightness
+    between the two frames (affine), an inverse-depth term against the current frame's depth (geometric_weight > 0; sigma_depth_* in
+    1 / metres) and the frame aligned against (against: previous or keyframe). It needs ``Training.pose_prior`` enabled."""
+    name = "Training.pose_prior_terms"
+    opt = read_block(training, "pose_prior_terms", POSE_PRIOR_TERMS_DEFAULTS)
+    if opt is None:
+        return None
+    if not (training.get("pose_prior") or {}).get("enabled", False):
+        raise ValueError(f"{name} is enabled but Training.pose_prior is not: the terms belong to its alignment")
+    opt["affine"] = bool(opt["affine"])
+    to_floats(opt, name, ("geometric_weight", "edge_ratio", "sigma_depth_init", "sigma_depth_min", "max_gain", "max_offset"))
+    for key in ("geometric_weight", "edge_ratio"):
+        if not (0.0 <= opt[key] < float("inf")):
+            raise ValueError(f"{name}.{key} must be finite and not negative, got {opt[key]}")
+    for key in ("sigma_depth_init", "sigma_depth_min"):
+        if not (0.0 < opt[key] < float("inf")):
+            raise ValueError(f"{name}.{key} must be positive and finite, got {opt[key]}")
+    for key in ("max_gain", "max_offset"):
+        if opt[key] < 0.0:
+            raise ValueError(f"{name}.{key} must not be negative, got {opt[key]}")
+    if opt["against"] not in ("previous", "keyframe"):
+        raise ValueError(f"{name}.against must be 'previous' or 'keyframe', got {opt['against']!r}")
+    if not opt["affine"] and opt["geometric_weight"] == 0.0 and opt["against"] == "previous":
+        raise ValueError(f"{name} is enabled with affine off, geometric_weight 0 and against = previous: it would change nothing")
+    return opt
+
+
 class PosePrior:
-    def __init__(self, options, monocular, dynamic_model):
-        self.options, self.monocular, self.dynamic_model = options, monocular, dynamic_model
+    def __init__(self, options, monocular, dynamic_model, terms=None):
+        self.options, self.monocular, self.dynamic_model, self.terms = options, monocular, dynamic_model, terms
         # slam.odometry.DenseOdometry, built with the first frame that is kept; the last aligned motion, where the next alignment starts
         # with constant_velocity
         self.odometry = self.motion = None
+        # terms.against = keyframe: the camera of the kept frame (its pose is read when a frame is aligned, after the back-end moved it)
+        self.anchor = None
+
+    @property
+    def against_keyframe(self):
+        return self.terms is not None and self.terms["against"] == "keyframe"
 
     def keep(self, viewpoint, render_pkg=None):
         """Keep `viewpoint` as the frame the next one is aligned against. Its depth: the sensor's (RGB-D) or the matcher's (stereo); for
-        monocular input the depth of `render_pkg` where its opacity is above 0.5 (None: the map does not exist yet, nothing is kept)."""
+        monocular input the depth of `render_pkg` where its opacity is above 0.5 (None: the map does not exist yet, nothing is kept).
+        Against keyframes a frame is kept only while none is: keyframe() and restart() replace the kept one."""
+        if self.against_keyframe and self.anchor is not None and self.odometry is not None and self.odometry.has_previous:
+            return
         if self.odometry is None:
             from .odometry import DenseOdometry
             options = {k: v for k, v in self.options.items() if k not in ("enabled", "constant_velocity")}
+            if self.terms is not None:            # a monocular frame has no depth when it is aligned: photometric and affine alone
+                options.update({k: v for k, v in self.terms.items() if k not in ("enabled", "against")})
+                options["geometric_weight"] = 0.0 if self.monocular else options["geometric_weight"]
             self.odometry = DenseOdometry(viewpoint.image_width, viewpoint.image_height, (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy),
                                           device=viewpoint.device, **options)
         depth = viewpoint.depth_device()
@@ -120,32 +165,65 @@ class PosePrior:
             depth = None if render_pkg is None else opaque_depth(render_pkg["depth"], render_pkg["opacity"])
         if depth is None:
             self.odometry.drop()
+            self.anchor = None
             return
         self.odometry.keep(viewpoint.original_image, depth, viewpoint.motion_mask if self.dynamic_model else None)
+        if self.against_keyframe:
+            self.anchor, self.motion = viewpoint, None
+
+    def keyframe(self, viewpoint, render_pkg=None):
+        """The front-end made `viewpoint` a keyframe: against keyframes it replaces the kept frame, and the next alignment starts at identity."""
+        if self.against_keyframe:
+            self.anchor = None
+            self.keep(viewpoint, render_pkg)
 
     def restart(self, viewpoint):
         """A map that starts (over): the last motion is forgotten and `viewpoint`, its first frame, replaces the kept frame."""
-        self.motion = None
+        self.motion = self.anchor = None
         self.keep(viewpoint)
 
     def drop(self):
-        """The next frame is not aligned against the kept one (a lost frame: it has no pose of its own)."""
-        if self.odometry is not None:
+        """The next frame is not aligned against the kept one (a lost frame: it has no pose of its own). A kept keyframe has a pose: it stays."""
+        if self.odometry is not None and not self.against_keyframe:
             self.odometry.drop()
 
     def start(self, viewpoint, previous):
         """Move `viewpoint` from the previous frame's pose W2C_prev to T W2C_prev, T the aligned motion (identity where the gate refused it:
-        the reference's start); with no frame kept it stays where it is. Device tensors throughout; the host reads nothing."""
+        the reference's start); with no frame kept it stays where it is. Device tensors throughout; the host reads nothing. Against a
+        keyframe the alignment starts at the last accepted motion against it and an accepted T moves `viewpoint` to T W2C_keyframe."""
         if self.odometry is None or not self.odometry.has_previous:
             return
-        self.motion, _ = self.odometry.align(viewpoint.original_image, self.motion if self.options["constant_velocity"] else None)
-        viewpoint.update_RT(*compose_pose(self.motion, previous.R, previous.T))
+        if self.terms is None:
+            self.motion, _ = self.odometry.align(viewpoint.original_image, self.motion if self.options["constant_velocity"] else None)
+            viewpoint.update_RT(*compose_pose(self.motion, previous.R, previous.T))
+            return
+        depth = None if self.monocular else viewpoint.depth_device()
+        mask = viewpoint.motion_mask if self.dynamic_model and depth is not None else None
+        if not self.against_keyframe:
+            start = self.motion if self.options["constant_velocity"] else None
+            self.motion, _ = self.odometry.align(viewpoint.original_image, start, depth=depth, mask=mask)
+            viewpoint.update_RT(*compose_pose(self.motion, previous.R, previous.T))
+            return
+        T, stats = self.odometry.align(viewpoint.original_image, self.motion, depth=depth, mask=mask)
+        accepted = stats[0] > 0.5                                            # stays on the device
+        R, t = compose_pose(T, self.anchor.R, self.anchor.T)
+        viewpoint.update_RT(torch.where(accepted, R, previous.R.to(R)), torch.where(accepted, t, previous.T.to(t)))
+        self.motion = T if self.motion is None else torch.where(accepted, T, self.motion)
 
     def summary(self):
-        """The `odometry` block of the run result: frames aligned, the accepted share, the mean inlier share, device ms per frame."""
+        """The `odometry` block of the run result: frames aligned, the accepted share, the mean inlier share, device ms per frame. With
+        Training.pose_prior_terms on also the mean |alpha| and |beta|, the share of aligned pixels with a depth term, and `against`."""
         if self.odometry is None:
-            return {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
-        return self.odometry.summary()
+            out = {"frames": 0, "accepted_share": 0.0, "inlier_share": 0.0, "device_ms_per_frame": 0.0}
+            if self.terms is not None:
+                out.update(mean_abs_alpha=0.0, mean_abs_beta=0.0, depth_term_share=0.0)
+        else:
+            out = self.odometry.summary()
+        if self.terms is not None:
+            out["against"] = self.terms["against"]
+            if self.monocular:
+                out["depth_term"] = "off: a monocular frame has no depth when it is aligned"
+        return out
 
 
 # ---- Training.relocalisation: is the tracked frame lost, and if so where is it ------------------------------------------------------------

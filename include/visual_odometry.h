@@ -5,7 +5,8 @@
  * (gsr_odometry_align) and an acceptance gate decided on the device. The front-end uses the result as the start of a frame's tracking
  * (slam/frontend.py, Training.pose_prior); the reference starts every frame at the previous pose and has no counterpart. It is specified
  * HERE and restated in float64 numpy in tests/odometry_reference.py: the pyramid equals its float32 restatement bit for bit, the sums of a
- * pass agree within the float32 rounding of their per-pixel terms. Brightness changes between the frames are not modelled. All pointers are
+ * pass agree within the float32 rounding of their per-pixel terms. gsr_odometry_align models no brightness change between the frames and uses
+ * no depth of the current one; gsr_odometry_align_rgbd (restated in tests/odometry_rgbd_reference.py) adds both. All pointers are
  * DEVICE pointers unless said otherwise. Returns 0 or a negative GSR_ERR_* code (gs_rasterizer.h); gsr_last_error() has the text. Nothing is
  * enqueued on a bad argument.
  */
@@ -71,6 +72,50 @@ int gsr_odometry_align(int width, int height, int levels, float fx, float fy, fl
                        const float* T_init, const int* iters, float nu, float sigma_init, float sigma_min, float min_share, float max_last_step,
                        float max_translation, float max_rotation, float* T, double* stats, double* trace, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace gsr_odometry_align_rgbd needs; 0 for a size gsr_odometry_pyramid_size refuses. */
+size_t gsr_odometry_align_rgbd_workspace_size(int width, int height, int levels);
+
+/* gsr_odometry_align_rgbd: gsr_odometry_align with two more terms, each switched by an argument: an affine brightness (alpha, beta) between the
+ * frames (affine = 1) and an inverse-depth residual against the CURRENT frame's depth (geometric_weight = lambda > 0; the current pyramid is then
+ * built with its depth). P, C, T, T_init, the levels, iters and the order of the passes are gsr_odometry_align's. n = 8 unknowns with affine,
+ * xi = [rho | theta | d alpha | d beta], else n = 6. alpha = beta = 0 at the start of every call; both carry across passes and levels. One
+ * pass, for every pixel (u, v) of P_l with depth d > 0:
+ *   X, Y, (x, y), in   exactly as in gsr_odometry_align; (x0, y0) = floor(x, y), (a_x, a_y) = (x, y) - (x0, y0)
+ *   photometric  r_I = (bilinear(C_l, x, y) - (1 + alpha) P_l(u, v)) - beta, with 1 + alpha rounded to float32 (affine = 0: as gsr_odometry_align)
+ *                J_I = [G d pi / d Y [I | -[Y]x], -P_l(u, v), -1], 1 x 8 (affine = 0: the first six)
+ *   depth        taken only where lambda > 0 and the four neighbours D00 = D(y0, x0), D01 = D(y0, x0 + 1), D10 = D(y0 + 1, x0), D11 of C_l's
+ *                depth are all > 0 and max - min <= edge_ratio * min; elsewhere the pixel adds its photometric term alone
+ *                W.. = 1 / D..,  r_D = bilinear(W, a_x, a_y) - 1 / Y_z
+ *                grad W = ((1 - a_y) (W01 - W00) + a_y (W11 - W10), (1 - a_x) (W10 - W00) + a_x (W11 - W01))
+ *                J_D = grad W d pi / d Y [I | -[Y]x] + (1 / Y_z^2) e_z^T [I | -[Y]x], 1 x 6; zero in the columns of alpha and beta
+ *   weights      w_I = (nu + 1) / (nu + (r_I / sigma_I)^2), w_D likewise with sigma_D; both scales LAGGED as sigma is in gsr_odometry_align,
+ *                each from its own sums: sigma_I from sigma_init, max(sigma_min, sqrt(sum w_I r_I^2 / n_I)); sigma_D from sigma_depth_init,
+ *                max(sigma_depth_min, sqrt(sum w_D r_D^2 / n_D)) of the latest earlier pass with n_D > 0 (in 1 / metres)
+ *   H = sum (w_I / sigma_I^2) J_I^T J_I + sum (lambda w_D / sigma_D^2) J_D^T J_D, g likewise with r_I and r_D; n_I the pixels in, n_D the depth
+ *   terms taken. A pixel's photometric term is added to a sum before its depth term.
+ *   A = H + 1e-9 tr(H) / n I, A xi = -g by Cholesky in double; T <- exp(xi[0..5]) T, alpha += xi[6], beta += xi[7]. A counts as not positive
+ *   definite where a pivot of the factorisation is not above 0 or not above 1e-6 of its diagonal entry A_jj (two columns collinear: the
+ *   small multiple of I would otherwise carry them). With n_I < n, such a matrix or a step that is not finite, T, alpha and beta are left
+ *   unchanged and the pass's |xi| counts as infinite. |xi| is the norm of all n entries.
+ * The gate: gsr_odometry_align's tests with n_I for n, and with affine also |alpha| <= max_gain and |beta| <= max_offset (a value that is not
+ * finite fails them). Refused: T is identity.
+ *   stats  12 doubles   the 8 of gsr_odometry_align (sigma is sigma_I, n is n_I), then alpha, beta, the final sigma_D, n_D of the last pass
+ *   trace  [sum of iters, 64] doubles or NULL (tests): per pass the n (n + 1) / 2 entries of H (upper triangle, row-major), the n of g, then
+ *          sum w_I, sum w_I r_I^2, n_I, sum w_D, sum w_D r_D^2, n_D, the sigma_I, sigma_D, alpha and beta the pass used, the level; zeros after
+ * A known degeneracy: on a constant previous image the columns -P and -1 of J_I are collinear, alpha and beta cannot be told apart, the
+ * factorisation fails at beta's pivot and no step is taken in any pass: the call ends and the gate refuses, with or without the depth term.
+ * Callers with such input pass affine = 0.
+ * Per-pixel terms are float32; every sum is formed in double in one fixed order (thread, wave, block, then the per-block partial sums in
+ * block order by the next launch); no float atomics: T, stats and trace are the same bytes on every run. Ranges: affine 0 or 1;
+ * geometric_weight, edge_ratio, max_gain, max_offset >= 0 and the first two finite; sigma_depth_init, sigma_depth_min > 0; the others as in
+ * gsr_odometry_align. workspace: gsr_odometry_align_rgbd_workspace_size bytes, 16-byte aligned; a shorter one is refused. Two launches per
+ * pass and two more on `stream`; no host read anywhere; nothing is enqueued on a bad argument. */
+int gsr_odometry_align_rgbd(int width, int height, int levels, float fx, float fy, float cx, float cy, const void* previous, const void* current,
+                            const float* T_init, const int* iters, int affine, float geometric_weight, float edge_ratio, float nu, float sigma_init,
+                            float sigma_min, float sigma_depth_init, float sigma_depth_min, float min_share, float max_last_step,
+                            float max_translation, float max_rotation, float max_gain, float max_offset, float* T, double* stats, double* trace,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

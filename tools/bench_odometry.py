@@ -2,7 +2,8 @@
 """Device time of one dense odometry call (slam/odometry.py DenseOdometry.align: the current frame's pyramid, then 22 passes of sums and
 solve over three levels, then the gate) at 640 x 480 and 320 x 240, per stage from the library's event timers (gsr_profile_enable: events
 around each stage on the launch stream) and for the whole call from device events over --reps calls after --warmup. The scene is analytic:
-a textured plane seen from two poses 1.4 degrees and 39 mm apart, the previous depth exact. Prints one JSON line and writes it to --out
+a textured plane seen from two poses 1.4 degrees and 39 mm apart, the previous depth exact. The same frames are timed through
+gsr_odometry_align_rgbd (affine brightness and the depth term on, device_ms_per_call_with_terms) in the same process. Prints one JSON line and writes it to --out
 (default profiles/odometry.json)."""
 import argparse
 import json
@@ -58,6 +59,15 @@ def scene(W, H):
     return rgb(prev), torch.tensor(z.astype(np.float32)).cuda(), rgb(cur), (fx, fy, cx, cy), T
 
 
+def current_depth(W, H, K, T):
+    """The current frame's depth [H, W] of the same plane: the step along each of its rays (they have z = 1)."""
+    fx, fy, cx, cy = K
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    ray = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1)
+    origin, direction = -T[:3, :3].T @ T[:3, 3], ray @ T[:3, :3]
+    return torch.tensor(((PLANE_D - PLANE @ origin) / (direction @ PLANE)).astype(np.float32)).cuda()
+
+
 def timed(fn, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -85,10 +95,15 @@ def measure(W, H, reps, warmup):
     _C.profile_enable(False)
     prof = _C.profile_read()
     _C.profile_reset()
+    # the same frames through gsr_odometry_align_rgbd: affine brightness and the depth term, the current pyramid built with its depth
+    terms = odometry.DenseOdometry(W, H, K, affine=True, geometric_weight=1.0)
+    terms.keep(prev, depth, None)
+    depth_cur = current_depth(W, H, K, T_true)
+    terms_ms = timed(lambda: terms.align(cur, depth=depth_cur), reps, warmup)
     T, stats = call()
     T, stats = T.double().cpu().numpy(), stats.cpu().numpy()
     dR = T[:3, :3] @ T_true[:3, :3].T
-    return {"resolution": [W, H], "levels": odo.levels, "iters": odo.iters, "launches_per_call": 2 * sum(odo.iters) + 2 + odo.levels + 1,
+    return {"device_ms_per_call_with_terms": round(terms_ms, 4), "resolution": [W, H], "levels": odo.levels, "iters": odo.iters, "launches_per_call": 2 * sum(odo.iters) + 2 + odo.levels + 1,
             "device_ms_per_call": round(whole, 4), "device_ms_per_keep": round(keep_ms, 4),
             "device_ms_per_stage": {k: round(prof[k][0] / reps, 4) for k in STAGES},
             "accepted": bool(stats[0]), "inlier_share": round(float(stats[1]), 4),

@@ -5,7 +5,8 @@ sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every fr
 --mono-sweep as well, new keyframes are seeded from a plane sweep over the window (Training.mono_sweep, slam/sweep.py) and the result has a
 `sweep` block. With --pose-prior every frame's tracking starts from the dense frame-to-frame alignment (Training.pose_prior,
 slam/odometry.py) and the result has an `odometry` block; --tracking-itr N sets Training.tracking_itr_num (default 60): a prior is worth
-most where the tracker is given few iterations."""
+most where the tracker is given few iterations. --pose-prior-terms (implies --pose-prior) turns on Training.pose_prior_terms with its defaults:
+the alignment's affine brightness and depth term; --pose-prior-against keyframe aligns against the last keyframe, not the previous frame."""
 import json
 import os
 import sys
@@ -26,6 +27,9 @@ profile = "--profile" in sys.argv
 monocular = "--monocular" in sys.argv
 mono_sweep = "--mono-sweep" in sys.argv
 pose_prior = "--pose-prior" in sys.argv
+pose_prior_terms = "--pose-prior-terms" in sys.argv      # implies --pose-prior; --pose-prior-against keyframe aligns against keyframes
+pose_prior = pose_prior or pose_prior_terms
+pose_prior_against = sys.argv[sys.argv.index("--pose-prior-against") + 1] if "--pose-prior-against" in sys.argv else "previous"
 tracking_itr = int(sys.argv[sys.argv.index("--tracking-itr") + 1]) if "--tracking-itr" in sys.argv else 60
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
@@ -52,6 +56,8 @@ for name, dyn, graph, frames, wh in scenarios:
             cfg = merge_config(cfg, {"Training": {"mono_sweep": {"enabled": True}}})
     if pose_prior:
         cfg = merge_config(cfg, {"Training": {"pose_prior": {"enabled": True}}})
+    if pose_prior_terms:
+        cfg = merge_config(cfg, {"Training": {"pose_prior_terms": {"enabled": True, "against": pose_prior_against}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
