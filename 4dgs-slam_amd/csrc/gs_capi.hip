@@ -60,6 +60,8 @@
 #include "gs_odometry.h"
 #include "../../include/relocalisation.h"
 #include "gs_reloc.h"
+#include "../../include/loop_closure.h"
+#include "gs_loop.h"
 
 namespace gsr {
 
@@ -3961,6 +3963,89 @@ int gsr_reloc_score(int width, int height, const float* render, const float* ren
     const unsigned blocks = (unsigned)std::min<size_t>((n + RELOC_BLOCK - 1) / RELOC_BLOCK, RELOC_SCORE_MAX_BLOCKS);
     hipLaunchKernelGGL(reloc_score_kernel, dim3(blocks), dim3(RELOC_BLOCK), 0, stream, n, render, render_depth, opacity, image, depth, mask, tau_colour,
                        tau_depth, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_pose_graph_solve: the old poses, per edge its residual and Jacobian blocks and the two contributions of a product, the
+// vectors of the conjugate gradients, per node the damping and the Cholesky factor of its block, the sorted keys and the node lists
+static bool pose_graph_layout(int nodes, int edges, const void* workspace, PoseGraphWs& l, int& n_keys)
+{
+    if (nodes < 1 || nodes > PG_MAX_NODES || edges < 0 || edges > PG_MAX_EDGES) return false;
+    n_keys = 2;
+    while (n_keys < 2 * edges) n_keys <<= 1;
+    const size_t N = (size_t)nodes, E = (size_t)edges;
+    Carver c(workspace, 16);
+    l.x_old = c.take<double>(N * 12);
+    l.edge_r = c.take<double>(E * 6);
+    l.edge_A = c.take<double>(E * PG_EDGE_DOUBLES);
+    l.con = c.take<double>(E * 12);
+    l.vx = c.take<double>(N * 6);
+    l.vr = c.take<double>(N * 6);
+    l.vz = c.take<double>(N * 6);
+    l.vp = c.take<double>(N * 6);
+    l.vq = c.take<double>(N * 6);
+    l.hd = c.take<double>(N * 6);
+    l.chol = c.take<double>(N * 36);
+    l.keys = c.take<unsigned>((size_t)n_keys);
+    l.start = c.take<int>(N);
+    l.end = c.take<int>(N);
+    l.active = c.take<int>(N);
+    l.valid = c.take<unsigned char>(E);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_pose_graph_workspace_size(int nodes, int edges)
+{
+    PoseGraphWs l;
+    int n_keys;
+    return pose_graph_layout(nodes, edges, nullptr, l, n_keys) ? l.bytes : 0;
+}
+
+int gsr_pose_graph_solve(int nodes, int edges, double* poses, const int* fixed, const int* edge_nodes, const double* edge_Z,
+                         const double* edge_weights, int outer_iters, int cg_iters, double lambda, double step_tol, float* D, double* stats,
+                         void* workspace, size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_pose_graph_solve: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    PoseGraphWs l;
+    int n_keys = 0;
+    if (nodes < 1 || nodes > PG_MAX_NODES) return fail("nodes must be in [1, 4096], got " + std::to_string(nodes));
+    if (edges < 0 || edges > PG_MAX_EDGES) return fail("edges must be in [0, 65536], got " + std::to_string(edges));
+    if (outer_iters < 0 || outer_iters > 1000) return fail("outer_iters must be in [0, 1000], got " + std::to_string(outer_iters));
+    if (cg_iters < 1 || cg_iters > 100000) return fail("cg_iters must be in [1, 100000], got " + std::to_string(cg_iters));
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail("lambda must be finite and not negative");
+    if (!(step_tol >= 0.0) || !std::isfinite(step_tol)) return fail("step_tol must be finite and not negative");
+    if (!poses || !fixed || !D || !stats || !workspace) return fail("poses, fixed, D, stats and workspace must not be NULL");
+    if (edges > 0 && (!edge_nodes || !edge_Z || !edge_weights)) return fail("edge_nodes, edge_Z and edge_weights must not be NULL when edges > 0");
+    pose_graph_layout(nodes, edges, workspace, l, n_keys);
+    if (!workspace_fits("gsr_pose_graph_solve", "gsr_pose_graph_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(pose_graph_kernel, dim3(1), dim3(PG_BLOCK), 0, stream, nodes, edges, n_keys, poses, fixed, edge_nodes, edge_Z, edge_weights,
+                       outer_iters, cg_iters, lambda, step_tol, D, stats, l);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int gsr_map_correct(int P, float* xyz, float* rotation, const int* kf_id, int frames, const int* slot_of_frame, int nodes, const float* D,
+                    float* quat_workspace, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_map_correct: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    if (P < 0) return fail("P must not be negative, got " + std::to_string(P));
+    if (frames < 0) return fail("frames must not be negative, got " + std::to_string(frames));
+    if (nodes < 1 || nodes > PG_MAX_NODES) return fail("nodes must be in [1, 4096], got " + std::to_string(nodes));
+    if (!D || !quat_workspace) return fail("D and quat_workspace must not be NULL");
+    if (frames > 0 && !slot_of_frame) return fail("slot_of_frame must not be NULL when frames > 0");
+    if (P > 0 && (!xyz || !rotation || !kf_id)) return fail("xyz, rotation and kf_id must not be NULL when P > 0");
+    if (((size_t)xyz | (size_t)rotation | (size_t)kf_id | (size_t)quat_workspace) & 15)
+        return fail("xyz, rotation, kf_id and quat_workspace must be 16-byte aligned");
+    if (P == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(map_quat_kernel, dim3((unsigned)((nodes + MAPC_BLOCK - 1) / MAPC_BLOCK)), dim3(MAPC_BLOCK), 0, stream, nodes, D, quat_workspace);
+    GSR_HIP_CHECK(hipGetLastError());
+    const long long groups = ((long long)P + 3) / 4;
+    hipLaunchKernelGGL(map_correct_kernel, dim3((unsigned)((groups + MAPC_BLOCK - 1) / MAPC_BLOCK)), dim3(MAPC_BLOCK), 0, stream, P, xyz, rotation,
+                       kf_id, frames, slot_of_frame, nodes, D, (const float*)quat_workspace);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -276,6 +276,10 @@ FUNCTIONS = {
     "gsr_reloc_encode": (i, [i, i, vp, vp, vp, i, i, i, vp, f, vp, vp, sz, vp]),
     "gsr_reloc_search": (i, [i, i, vp, vp, i, i, vp, vp, vp]),
     "gsr_reloc_score": (i, [i, i] + [vp] * 6 + [i, f, vp, vp]),
+    # loop_closure.h
+    "gsr_pose_graph_workspace_size": (sz, [i, i]),
+    "gsr_pose_graph_solve": (i, [i, i, vp, vp, vp, vp, vp, i, i, d, d, vp, vp, vp, sz, vp]),
+    "gsr_map_correct": (i, [i, vp, vp, vp, i, vp, i, vp, vp, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

@@ -19,8 +19,10 @@ How a frame is processed:
   insert     the window update is computed on the device and read back as two indices; the back-end maps the new keyframe.
 
 What the reference does not have is one object of ``slam/stages.py`` per option, None when its ``Training`` block is absent or off:
-``mono_sweep`` (a monocular keyframe's seed depth), ``pose_prior`` (where tracking starts) and ``relocalisation`` (the judge step). This
-file calls them by name and keeps what couples them: the log, and the prior's kept frame when a frame is lost or relocalised.
+``mono_sweep`` (a monocular keyframe's seed depth), ``pose_prior`` (where tracking starts), ``relocalisation`` (the judge step) and
+``loop_closure`` (a new keyframe is tied to old keyframes that saw the same place; poses and map are corrected before the back-end maps
+it). This file calls them by name and keeps what couples them: the log, and the prior's kept frame when a frame is lost or relocalised or
+a loop is closed.
 """
 import struct
 import time
@@ -34,7 +36,8 @@ from . import keyframes as kf
 from .camera import Camera
 from .eval_utils import eval_ate, save_gaussians
 from .relocalise import relocalisation_options
-from .stages import PosePrior, Relocalisation, SweepSeeding, mono_sweep_options, pose_prior_options, pose_prior_terms_options
+from .stages import (LoopClosure, PosePrior, Relocalisation, SweepSeeding, loop_closure_options, mono_sweep_options, pose_prior_options,
+                     pose_prior_terms_options)
 
 
 def lower_median(x):
@@ -89,6 +92,8 @@ class FrontEnd:
         terms = pose_prior_terms_options(training)                         # refused without pose_prior
         self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model, terms)
         self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model)
+        loops = loop_closure_options(training, self.dynamic_model)          # refused for monocular, dynamic and spherical-harmonics runs
+        self.loop_closure = loops and LoopClosure(loops)
 
     def set_hyperparams(self):
         """:115-126."""
@@ -150,6 +155,10 @@ class FrontEnd:
             # would be freed by the cycle collector alone, whenever it next runs, be that in the middle of a later run's graph capture)
             me = weakref.proxy(self)
             self.relocalisation.restart(frame_idx, viewpoint, self.cameras, lambda c: me._render_at(c), lambda v: me._track_and_render(v))
+        if self.loop_closure is not None:                                 # a map that starts (over) starts its pose graph over; node 0 is this frame
+            me = weakref.proxy(self)
+            self.loop_closure.restart(frame_idx, viewpoint, self.cameras, lambda: me.gaussians,
+                                      self.relocalisation.index if self.relocalisation is not None else None, self.backend.shard.world)
         seed_depth = self.add_new_keyframe(frame_idx, init=True)
         self.sync_backend(self.backend.handle_init(frame_idx, viewpoint, seed_depth))
 
@@ -278,6 +287,12 @@ class FrontEnd:
             return
         if self.relocalisation is not None:
             self.relocalisation.add(cur_frame_idx, viewpoint)
+        if self.loop_closure is not None:                                         # the keyframe is a node before the back-end seeds from its pose
+            closed = self.loop_closure.on_keyframe(cur_frame_idx, viewpoint)
+            if closed is not None and closed["applied"]:
+                self.log.append(("loop_closed", cur_frame_idx, closed["keyframes"], closed["translation"], closed["rotation"]))
+                if self.pose_prior is not None:
+                    self.pose_prior.drop()                                        # as after a relocalised frame: poses moved under the kept frame
         if self.pose_prior is not None:                                           # (aligning against keyframes: this one from now on)
             self.pose_prior.keyframe(viewpoint, render_pkg)
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))

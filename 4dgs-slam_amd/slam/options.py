@@ -1,4 +1,4 @@
-"""Reading an optional ``Training.<key>`` block (mono_sweep, pose_prior, relocalisation) and the checks more than one of them makes. Every
+"""Reading an optional ``Training.<key>`` block (mono_sweep, pose_prior, relocalisation, loop_closure) and the checks more than one of them makes. Every
 refusal names the block and the key. Imports without a GPU or the HIP library."""
 import math
 

@@ -11,8 +11,9 @@ of keyframe codes; gsr_reloc_score: the counts by which a rendering is judged ag
 
 The reference has no counterpart. tests/reloc_reference.py restates the three kernels in integer numpy. No CPU path.
 
-Limits: nothing here has been run on real images. A relocalised frame is only given a pose: the map is not corrected (no loop closure).
-Dynamic saved maps are refused."""
+Limits: nothing here has been run on real images. A relocalised frame is only given a pose; correcting the map when a place is seen again
+is the work of slam/loop_closure.py (``Training.loop_closure``, off by default, static RGB-D and stereo runs only). Dynamic saved maps are
+refused."""
 import math
 
 import numpy as np
@@ -208,12 +209,13 @@ class KeyframeIndex:
         encode(image, depth, mask, self.grid, self.table, self.depth_scale, self.database[row], self._workspace)
         self.ids.append(frame_id)
 
-    def query(self, image, depth=None, mask=None, topk=4, nibble_mask=None):
-        """(best int32 [topk, 2], distance int32 [len(self)]) on the device. nibble_mask None: 0xF with a depth, 0x7 without (a frame that
-        has no depth is compared on its colour bits alone)."""
+    def query(self, image, depth=None, mask=None, topk=4, nibble_mask=None, rows=None):
+        """(best int32 [topk, 2], distance int32 [rows]) on the device. nibble_mask None: 0xF with a depth, 0x7 without (a frame that
+        has no depth is compared on its colour bits alone). rows None: every row; otherwise only the first `rows` rows are searched (loop
+        closure leaves out the newest keyframes)."""
         image, depth, mask = frame_tensors(image, depth, mask, self.device)
         encode(image, depth, mask, self.grid, self.table, self.depth_scale, self._query, self._workspace)
-        rows = len(self.ids)
+        rows = len(self.ids) if rows is None else max(0, min(int(rows), len(self.ids)))
         best = torch.empty((int(topk), 2), dtype=torch.int32, device=self.device)
         distance = torch.empty(rows, dtype=torch.int32, device=self.device)
         if nibble_mask is None:

@@ -1,5 +1,5 @@
 """The optional stages of the front-end, one object each: ``SweepSeeding`` (``Training.mono_sweep``), ``PosePrior`` (``Training.pose_prior``
-with ``Training.pose_prior_terms``) and ``Relocalisation`` (``Training.relocalisation``). Each owns its checked options (``.options``), the device object it builds at its first
+with ``Training.pose_prior_terms``), ``Relocalisation`` (``Training.relocalisation``) and ``LoopClosure`` (``Training.loop_closure``). Each owns its checked options (``.options``), the device object it builds at its first
 use (slam/sweep.py and slam/odometry.py are not imported before that), the device time of its calls and the ``summary()`` a run reports.
 What couples two stages (a lost frame drops the prior's kept frame) is left to ``FrontEnd``. Imports without a GPU."""
 import torch
@@ -7,7 +7,7 @@ import torch
 from .camera import compose_pose, opaque_depth
 from .options import check_gate, check_pass_counts, read_block, to_floats
 from .pretrained import EventLog
-from .relocalise import KeyframeIndex, Relocaliser
+from .relocalise import DEFAULT_ITERS, MAX_TOPK, KeyframeIndex, Relocaliser, relocalisation_options
 
 
 # ---- Training.mono_sweep: a monocular keyframe's seed depth from a plane sweep over the window ---------------------------------------------
@@ -259,3 +259,122 @@ class Relocalisation:
     def summary(self):
         """The `relocalisation` block of the run result: frames scored, lost, relocalised, device ms per score."""
         return {**self.stats, "device_ms_per_score": self.log.summary()["ms_per_item"] or 0.0}
+
+
+# ---- Training.loop_closure: tie a keyframe to the old keyframes that saw the same place, and correct poses and map ------------------------
+# max_code_distance lies between the code distances measured on the synthetic sequence (step 0.02, rot_step 0.012) of frames one or two apart
+# (at most 0.27 of the ferns) and of frames ten or more apart (at least 0.49); consistency between the two-way inconsistency of true pairs
+# (at most 1.7 mm and 0.021 degrees) and of an accepted alignment of two different places (234 mm, 7.6 degrees): DESIGN.md section 8, Loop
+# closure. The weights have not been measured. The fern keys default to those of Training.relocalisation (None here: "as that block, or its
+# defaults")
+FERN_KEYS = ("ferns", "grid", "seed", "depth_scale", "depth_lo", "depth_hi")
+LOOP_CLOSURE_DEFAULTS = {"enabled": False, **{k: None for k in FERN_KEYS}, "min_gap": 10, "topk": 2, "max_code_distance": 0.38,
+                         "consistency": [0.02, 1.0], "min_correction": [0.005, 0.2], "odometry_weights": [1.0, 1.0],
+                         "loop_weights": [10.0, 10.0], "outer_iters": 10, "cg_iters": 200, "lambda": 1e-6, "step_tolerance": 1e-9,
+                         "levels": 4, "iters": None, "max_translation": 1.0, "max_rotation": 30.0, "geometric_weight": 1.0}
+
+
+def _pair(opt, name, key, what):
+    v = opt[key]
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2:
+        raise ValueError(f"{name}.{key} must be [{what}], got {v!r}")
+    opt[key] = [float(v[0]), float(v[1])]
+    if not all(0.0 <= x < float("inf") for x in opt[key]):
+        raise ValueError(f"{name}.{key} must hold two finite numbers that are not negative, got {v!r}")
+
+
+def loop_closure_options(training, dynamic_model=False, ranks=1):
+    """The ``Training.loop_closure`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys, values the
+    kernels or the alignment cannot take, and the runs loop closure cannot serve are refused here, before the run starts. The fern keys
+    (ferns, grid, seed, depth_scale, depth_lo, depth_hi) are those of ``Training.relocalisation`` and, with that stage on, must not differ
+    from it: the two stages share one place index. consistency and min_correction are [metres, degrees]; the weights are [w_t, w_r];
+    max_code_distance is a share of the ferns; iters lists the alignment's passes per level, finest first."""
+    name = "Training.loop_closure"
+    opt = read_block(training, "loop_closure", LOOP_CLOSURE_DEFAULTS)
+    if opt is None:
+        return None
+    if training.get("monocular", False):
+        raise ValueError(f"{name} cannot be used with monocular input: the drift of an RGB-only run includes scale, and correcting that needs "
+                         "Sim(3) constraints; this pose graph is SE(3)")
+    if dynamic_model:
+        raise ValueError(f"{name} cannot be used with model_params.dynamic_model: the deformation field lives in world coordinates and cannot "
+                         "be moved piecewise with the keyframes")
+    if training.get("spherical_harmonics", False):
+        raise ValueError(f"{name} cannot be used with Training.spherical_harmonics: the coefficients of degree 1 and higher would have to be "
+                         "rotated with the Gaussians")
+    if int(ranks) > 1:
+        raise ValueError(f"{name} cannot be used with a sharded back-end of {int(ranks)} ranks: the correction is applied to one copy of the map")
+    reloc = relocalisation_options(training)                               # checked by its own rules; None when that stage is off
+    given = {k: opt[k] for k in FERN_KEYS if opt[k] is not None}
+    ferns = relocalisation_options({"relocalisation": {"enabled": True, **given}}) if reloc is None else reloc
+    norm = lambda key, v: [int(x) for x in v] if key == "grid" else float(v)
+    for key in FERN_KEYS:
+        if reloc is not None and key in given and norm(key, given[key]) != norm(key, reloc[key]):
+            raise ValueError(f"{name}.{key} = {given[key]!r} differs from Training.relocalisation.{key} = {reloc[key]!r}: the two stages share one "
+                             "place index")
+        opt[key] = ferns[key]
+    for key in ("min_gap", "topk", "outer_iters", "cg_iters", "levels"):
+        if isinstance(opt[key], float) and not opt[key].is_integer():
+            raise ValueError(f"{name}.{key} must be an integer, got {opt[key]!r}")
+        opt[key] = int(opt[key])
+    if opt["min_gap"] < 1:
+        raise ValueError(f"{name}.min_gap must be at least 1, got {opt['min_gap']}")
+    if not 1 <= opt["topk"] <= MAX_TOPK:
+        raise ValueError(f"{name}.topk must be 1 to {MAX_TOPK}, got {opt['topk']}")
+    if not 0 <= opt["outer_iters"] <= 1000:
+        raise ValueError(f"{name}.outer_iters must be in [0, 1000], got {opt['outer_iters']}")
+    if not 1 <= opt["cg_iters"] <= 100000:
+        raise ValueError(f"{name}.cg_iters must be in [1, 100000], got {opt['cg_iters']}")
+    to_floats(opt, name, ("max_code_distance", "lambda", "step_tolerance", "max_translation", "max_rotation", "geometric_weight"))
+    if not 0.0 <= opt["max_code_distance"] <= 1.0:
+        raise ValueError(f"{name}.max_code_distance is a share of the ferns and must be in [0, 1], got {opt['max_code_distance']}")
+    for key in ("lambda", "step_tolerance"):
+        if not 0.0 <= opt[key] < float("inf"):
+            raise ValueError(f"{name}.{key} must be finite and not negative, got {opt[key]}")
+    if not 0.0 < opt["geometric_weight"] < float("inf"):
+        raise ValueError(f"{name}.geometric_weight must be positive and finite (verification aligns colour and depth), got {opt['geometric_weight']}")
+    _pair(opt, name, "consistency", "metres, degrees")
+    _pair(opt, name, "min_correction", "metres, degrees")
+    _pair(opt, name, "odometry_weights", "w_t, w_r")
+    _pair(opt, name, "loop_weights", "w_t, w_r")
+    for key in ("odometry_weights", "loop_weights"):
+        if min(opt[key]) <= 0.0:
+            raise ValueError(f"{name}.{key} must be positive, got {opt[key]}")
+    if not 1 <= opt["levels"] <= 6:
+        raise ValueError(f"{name}.levels must be 1 to 6, got {opt['levels']}")
+    if opt["iters"] is None:
+        opt["iters"] = list(DEFAULT_ITERS[:opt["levels"]])
+    check_pass_counts(opt, name)
+    check_gate(opt, name, ("max_translation", "max_rotation"))
+    return opt
+
+
+class LoopClosure:
+    def __init__(self, options):
+        self.options = options
+        self.closer = None                                    # slam.loop_closure.LoopCloser, built with the first map, on the device
+
+    def restart(self, frame_idx, viewpoint, cameras, get_gaussians, index=None, ranks=1):
+        """A map that starts (over) with the keyframe `viewpoint`: the graph (and an owned index) is emptied; the first keyframe is node 0.
+        index: the place index of the relocalisation stage when that is on -- it holds `viewpoint` already -- else None."""
+        if int(ranks) > 1:
+            raise ValueError(f"Training.loop_closure cannot be used with a sharded back-end of {int(ranks)} ranks: the correction is applied to "
+                             "one copy of the map")
+        if self.closer is None:
+            from .loop_closure import LoopCloser
+            self.closer = LoopCloser(self.options, cameras, get_gaussians, (viewpoint.image_width, viewpoint.image_height),
+                                     (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), viewpoint.device, index)
+        self.closer.clear()
+        self.closer.on_keyframe(frame_idx, viewpoint)
+
+    def on_keyframe(self, frame_idx, viewpoint):
+        """LoopCloser.on_keyframe of the new keyframe: None, or the dictionary of a solve (its "applied" says whether map and poses moved)."""
+        return self.closer.on_keyframe(frame_idx, viewpoint)
+
+    def summary(self):
+        """The `loop_closure` block of the run result: keyframes queried, candidates verified, edges accepted, solves, corrections applied,
+        the largest correction, device ms per verify and per solve."""
+        if self.closer is None:
+            return {"keyframes_queried": 0, "candidates_verified": 0, "edges_accepted": 0, "solves": 0, "corrections_applied": 0,
+                    "max_correction_m": 0.0, "max_correction_deg": 0.0, "device_ms_per_verify": 0.0, "device_ms_per_solve": 0.0}
+        return self.closer.summary()

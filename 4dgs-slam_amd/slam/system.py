@@ -98,7 +98,8 @@ class SLAM:
                        "gaussians": int(self.gaussians.get_xyz.shape[0]), "sensor_type": self.config["Dataset"]["sensor_type"]}
         if self.monocular:
             self.result["resets"] = fe.resets
-        for key, stage in (("sweep", fe.mono_sweep if self.monocular else None), ("odometry", fe.pose_prior), ("relocalisation", fe.relocalisation)):
+        for key, stage in (("sweep", fe.mono_sweep if self.monocular else None), ("odometry", fe.pose_prior), ("relocalisation", fe.relocalisation),
+                           ("loop_closure", fe.loop_closure)):
             if stage is not None:
                 self.result[key] = stage.summary()
         if fe.init_done_at is not None and len(fe.cameras) > 1:          # frames per second once the map exists (tracking + keyframe mapping)
@@ -130,6 +131,25 @@ class SLAM:
                 raise ValueError("SLAM.save_map: no directory given and the run has no save_dir")
             directory = os.path.join(self.save_dir, "map")
         return save_map(self, directory)
+
+    def close_loops(self, **overrides):
+        """Loop closure over a finished run (slam/loop_closure.py LoopCloser.close_all): every keyframe in insertion order is searched for
+        earlier keyframes of the same place and verified against them, then ONE pose-graph solve; a correction above min_correction moves
+        the map and every camera. The run's ``Training.loop_closure`` block is read whether or not it is enabled; overrides replace its
+        keys. Returns close_all()'s dictionary; the `loop_closure` block of ``self.result`` is refreshed."""
+        from .loop_closure import LoopCloser
+        from .stages import loop_closure_options
+        fe, training = self.frontend, self.config["Training"]
+        block = {**(training.get("loop_closure") or {}), **overrides, "enabled": True}
+        options = loop_closure_options({**training, "loop_closure": block}, self.config["model_params"]["dynamic_model"], self.backend.shard.world)
+        if not fe.kf_indices:
+            raise ValueError("SLAM.close_loops: the run has no keyframe")
+        first = fe.cameras[fe.kf_indices[0]]
+        closer = LoopCloser(options, fe.cameras, lambda: fe.gaussians, (first.image_width, first.image_height),
+                            (first.fx, first.fy, first.cx, first.cy), first.device)
+        out = closer.close_all(list(fe.kf_indices))
+        self.result["loop_closure"] = closer.summary()
+        return out
 
     def _eval_frames(self):
         """Cameras of the tracked frames; non-keyframes were cleaned (their images dropped) but keep pose, intrinsics and time."""

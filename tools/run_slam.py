@@ -16,6 +16,9 @@ With --lpips-weights ALEXNET.pth LIN.pth (a torchvision AlexNet state_dict and t
 reports `mean_lpips` as well (slam/perceptual.py), and an `lpips` block reports the pairs scored and the device ms per pair.
 `Dataset.sensor_type: monocular` runs on the images alone (a sequence whose Calibration has no depth_scale is read without depth files; the
 ATE is scale-aligned); it cannot be combined with --dynamic.
+A `Training.loop_closure` block in the YAML (`enabled: true` and any key of slam/stages.py LOOP_CLOSURE_DEFAULTS) ties every new keyframe
+to old keyframes of the same place and corrects poses and map (slam/loop_closure.py; static RGB-D and stereo runs only, refused with --dynamic
+and for monocular input), and a `loop_closure` block reports the keyframes queried, the edges accepted and the corrections applied.
 With --save-map [DIR] the finished map is saved after the evaluations (slam/map_io.py) for tools/play_map.py."""
 import argparse
 import json

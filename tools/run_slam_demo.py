@@ -6,7 +6,9 @@ sequence runs with its depth withheld (Dataset.sensor_type 'monocular': every fr
 `sweep` block. With --pose-prior every frame's tracking starts from the dense frame-to-frame alignment (Training.pose_prior,
 slam/odometry.py) and the result has an `odometry` block; --tracking-itr N sets Training.tracking_itr_num (default 60): a prior is worth
 most where the tracker is given few iterations. --pose-prior-terms (implies --pose-prior) turns on Training.pose_prior_terms with its defaults:
-the alignment's affine brightness and depth term; --pose-prior-against keyframe aligns against the last keyframe, not the previous frame."""
+the alignment's affine brightness and depth term; --pose-prior-against keyframe aligns against the last keyframe, not the previous frame.
+--loop-closure turns on Training.loop_closure with its defaults on the static scenarios (a dynamic model is refused) and the result has a
+`loop_closure` block; the demo's arc never returns to a place, so it shows the cost of the stage, not a correction."""
 import json
 import os
 import sys
@@ -30,6 +32,7 @@ pose_prior = "--pose-prior" in sys.argv
 pose_prior_terms = "--pose-prior-terms" in sys.argv      # implies --pose-prior; --pose-prior-against keyframe aligns against keyframes
 pose_prior = pose_prior or pose_prior_terms
 pose_prior_against = sys.argv[sys.argv.index("--pose-prior-against") + 1] if "--pose-prior-against" in sys.argv else "previous"
+loop_closure = "--loop-closure" in sys.argv
 tracking_itr = int(sys.argv[sys.argv.index("--tracking-itr") + 1]) if "--tracking-itr" in sys.argv else 60
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
@@ -38,7 +41,7 @@ scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_64
 if monocular:
     scenarios = (("monocular_sweep_320x240_graph" if mono_sweep else "monocular_320x240_graph", False, True, 40, (320, 240)),)
 for name, dyn, graph, frames, wh in scenarios:
-    if only not in name:
+    if only not in name or (loop_closure and dyn):
         continue
     torch.manual_seed(0)
     ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=0.025 if wh[0] > 320 else 0.03,
@@ -58,6 +61,8 @@ for name, dyn, graph, frames, wh in scenarios:
         cfg = merge_config(cfg, {"Training": {"pose_prior": {"enabled": True}}})
     if pose_prior_terms:
         cfg = merge_config(cfg, {"Training": {"pose_prior_terms": {"enabled": True, "against": pose_prior_against}}})
+    if loop_closure:
+        cfg = merge_config(cfg, {"Training": {"loop_closure": {"enabled": True}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
