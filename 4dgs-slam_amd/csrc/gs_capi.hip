@@ -62,6 +62,8 @@
 #include "gs_reloc.h"
 #include "../../include/loop_closure.h"
 #include "gs_loop.h"
+#include "../../include/feature_matching.h"
+#include "gs_features.h"
 
 namespace gsr {
 
@@ -4046,6 +4048,171 @@ int gsr_map_correct(int P, float* xyz, float* rotation, const int* kf_id, int fr
     const long long groups = ((long long)P + 3) / 4;
     hipLaunchKernelGGL(map_correct_kernel, dim3((unsigned)((groups + MAPC_BLOCK - 1) / MAPC_BLOCK)), dim3(MAPC_BLOCK), 0, stream, P, xyz, rotation,
                        kf_id, frames, slot_of_frame, nodes, D, (const float*)quat_workspace);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_feat_extract: the luma and the corner score of every pixel (bytes) and its 5 x 5 sum (16 bits)
+struct FeatExtractLayout { unsigned char* luma; unsigned char* corner; unsigned short* box; size_t bytes; };
+static bool feat_extract_layout(int width, int height, const void* workspace, FeatExtractLayout& l)
+{
+    if (width < 1 || height < 1 || (long long)width * height >= (1LL << 24)) return false;
+    const size_t n = (size_t)width * height;
+    Carver c(workspace, 16);
+    l.luma = c.take<unsigned char>(n);
+    l.corner = c.take<unsigned char>(n);
+    l.box = c.take<unsigned short>(n);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+static int feat_slot_count(int width, int height, int cell, int per_cell)
+{
+    if (width < 1 || height < 1 || (long long)width * height >= (1LL << 24) || cell < FEAT_MIN_CELL || cell > FEAT_MAX_CELL || per_cell < 1 ||
+        per_cell > FEAT_MAX_PER_CELL)
+        return 0;
+    const long long slots = (long long)((width + cell - 1) / cell) * ((height + cell - 1) / cell) * per_cell;
+    return slots <= FEAT_MAX_SLOTS ? (int)slots : 0;
+}
+
+int gsr_feat_slots(int width, int height, int cell, int per_cell) { return feat_slot_count(width, height, cell, per_cell); }
+
+size_t gsr_feat_extract_workspace_size(int width, int height)
+{
+    FeatExtractLayout l;
+    return feat_extract_layout(width, height, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_feat_extract(int width, int height, const float* image, const unsigned char* mask, int cell, int per_cell, int threshold,
+                     const int* directions, const signed char* pattern, int* keypoints, unsigned int* descriptors, void* workspace,
+                     size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_feat_extract: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    FeatExtractLayout l;
+    if (!feat_extract_layout(width, height, workspace, l))
+        return fail("width and height must be at least 1 and width * height below 2^24, got " + std::to_string(width) + " x " + std::to_string(height));
+    if (cell < FEAT_MIN_CELL || cell > FEAT_MAX_CELL) return fail("cell must be in [8, 64], got " + std::to_string(cell));
+    if (per_cell < 1 || per_cell > FEAT_MAX_PER_CELL) return fail("per_cell must be in [1, 8], got " + std::to_string(per_cell));
+    const int slots = feat_slot_count(width, height, cell, per_cell);
+    if (slots < 1) return fail("the frame must have at most 4096 slots (ceil(width / cell) * ceil(height / cell) * per_cell)");
+    if (threshold < 0 || threshold > 255) return fail("threshold must be in [0, 255], got " + std::to_string(threshold));
+    if (!image || !directions || !pattern || !keypoints || !descriptors || !workspace)
+        return fail("image, directions, pattern, keypoints, descriptors and workspace must not be NULL");
+    if (!workspace_fits("gsr_feat_extract", "gsr_feat_extract_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int cells_x = (width + cell - 1) / cell, cells = slots / per_cell;
+    hipLaunchKernelGGL(feat_score_kernel, dim3((unsigned)((width + FEAT_TILE - 1) / FEAT_TILE), (unsigned)((height + FEAT_TILE - 1) / FEAT_TILE)),
+                       dim3(FEAT_BLOCK), 0, stream, width, height, image, mask, threshold, l.luma, l.corner, l.box);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_select_kernel, dim3((unsigned)cells), dim3(FEAT_BLOCK), 0, stream, width, height, cell, per_cell, cells_x,
+                       (const unsigned char*)l.corner, keypoints);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_describe_kernel, dim3((unsigned)((slots + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream, width, slots,
+                       (const unsigned char*)l.luma, (const unsigned short*)l.box, directions, pattern, keypoints, descriptors);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_feat_match: the best key and the second distance of every slot of A over B, and of every slot of B over A
+struct FeatMatchLayout { unsigned* best_ab; int* second_ab; unsigned* best_ba; int* second_ba; size_t bytes; };
+static bool feat_slots_ok(int slots) { return slots >= 1 && slots <= FEAT_MAX_SLOTS; }
+static bool feat_match_layout(int slots_a, int slots_b, const void* workspace, FeatMatchLayout& l)
+{
+    if (!feat_slots_ok(slots_a) || !feat_slots_ok(slots_b)) return false;
+    Carver c(workspace, 16);
+    l.best_ab = c.take<unsigned>((size_t)slots_a);
+    l.second_ab = c.take<int>((size_t)slots_a);
+    l.best_ba = c.take<unsigned>((size_t)slots_b);
+    l.second_ba = c.take<int>((size_t)slots_b);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_feat_match_workspace_size(int slots_a, int slots_b)
+{
+    FeatMatchLayout l;
+    return feat_match_layout(slots_a, slots_b, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_feat_match(int slots_a, const int* keypoints_a, const unsigned int* descriptors_a, int slots_b, const int* keypoints_b,
+                   const unsigned int* descriptors_b, int max_distance, int ratio_eighths, int* matches, void* workspace,
+                   size_t workspace_bytes, void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_feat_match: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    FeatMatchLayout l;
+    if (!feat_match_layout(slots_a, slots_b, workspace, l))
+        return fail("slots_a and slots_b must be in [1, 4096], got " + std::to_string(slots_a) + " and " + std::to_string(slots_b));
+    if (max_distance < 0 || max_distance > 256) return fail("max_distance must be in [0, 256], got " + std::to_string(max_distance));
+    if (ratio_eighths < 0 || ratio_eighths > 8) return fail("ratio_eighths must be in [0, 8], got " + std::to_string(ratio_eighths));
+    if (!keypoints_a || !descriptors_a || !keypoints_b || !descriptors_b || !matches || !workspace)
+        return fail("keypoints, descriptors, matches and workspace must not be NULL");
+    if (!workspace_fits("gsr_feat_match", "gsr_feat_match_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(feat_nearest_kernel, dim3((unsigned)((slots_a + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream, slots_a, keypoints_a,
+                       descriptors_a, slots_b, keypoints_b, descriptors_b, l.best_ab, l.second_ab);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_nearest_kernel, dim3((unsigned)((slots_b + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream, slots_b, keypoints_b,
+                       descriptors_b, slots_a, keypoints_a, descriptors_a, l.best_ba, l.second_ba);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_mutual_kernel, dim3((unsigned)((slots_a + FEAT_BLOCK - 1) / FEAT_BLOCK)), dim3(FEAT_BLOCK), 0, stream, slots_a, slots_b,
+                       (const unsigned*)l.best_ab, (const int*)l.second_ab, (const unsigned*)l.best_ba, max_distance, ratio_eighths, matches);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_feat_pose: the back-projected points of the pair list in both frames, the pixels of B, M, the count of every hypothesis
+static bool feat_pose_layout(int slots_a, int hypotheses, const void* workspace, FeatPoseWs& l)
+{
+    if (!feat_slots_ok(slots_a) || hypotheses < 1 || hypotheses > FEAT_MAX_HYPOTHESES) return false;
+    Carver c(workspace, 16);
+    l.PA = c.take<float>(3 * (size_t)slots_a);
+    l.PB = c.take<float>(3 * (size_t)slots_a);
+    l.UV = c.take<float>(2 * (size_t)slots_a);
+    l.head = c.take<int>(4);
+    l.hyp = c.take<int>((size_t)hypotheses);
+    l.bytes = c.bytes_padded();
+    return true;
+}
+
+size_t gsr_feat_pose_workspace_size(int slots_a, int hypotheses)
+{
+    FeatPoseWs l;
+    return feat_pose_layout(slots_a, hypotheses, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_feat_pose(int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b, const int* keypoints_b,
+                  const float* depth_b, const int* matches, const float* K_a, const float* K_b, unsigned int seed, int hypotheses,
+                  float min_area, float tau_px, float tau_depth, int refine_iters, int min_matches, int min_inliers, float min_share,
+                  float max_translation, float max_rotation, float* T, int* stats, int* counts, void* workspace, size_t workspace_bytes,
+                  void* stream_)
+{
+    auto fail = [&](const std::string& what) { g_last_error = "gsr_feat_pose: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    FeatPoseWs l;
+    if (width < 1 || height < 1 || (long long)width * height >= 0x80000000LL)
+        return fail("width and height must be at least 1 and width * height below 2^31, got " + std::to_string(width) + " x " + std::to_string(height));
+    if (!feat_slots_ok(slots_a) || !feat_slots_ok(slots_b))
+        return fail("slots_a and slots_b must be in [1, 4096], got " + std::to_string(slots_a) + " and " + std::to_string(slots_b));
+    if (!feat_pose_layout(slots_a, hypotheses, workspace, l)) return fail("hypotheses must be in [1, 1024], got " + std::to_string(hypotheses));
+    if (!(min_area > 0.f) || !std::isfinite(min_area)) return fail("min_area must be positive and finite");
+    if (!(tau_px >= 0.f) || !std::isfinite(tau_px) || !(tau_depth >= 0.f) || !std::isfinite(tau_depth))
+        return fail("tau_px and tau_depth must be finite and not negative");
+    if (refine_iters < 0 || refine_iters > FEAT_MAX_REFINE) return fail("refine_iters must be in [0, 16], got " + std::to_string(refine_iters));
+    if (min_matches < 0) return fail("min_matches must not be negative, got " + std::to_string(min_matches));
+    if (min_inliers < 3) return fail("min_inliers must be at least 3, got " + std::to_string(min_inliers));
+    if (!(min_share >= 0.f && min_share <= 1.f)) return fail("min_share must be in [0, 1]");
+    if (!(max_translation >= 0.f) || !std::isfinite(max_translation) || !(max_rotation >= 0.f) || !std::isfinite(max_rotation))
+        return fail("max_translation and max_rotation must be finite and not negative");
+    if (!keypoints_a || !depth_a || !keypoints_b || !depth_b || !matches || !K_a || !K_b || !T || !stats || !workspace)
+        return fail("keypoints, depths, matches, K_a, K_b, T, stats and workspace must not be NULL");
+    if (!workspace_fits("gsr_feat_pose", "gsr_feat_pose_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(feat_pairs_kernel, dim3(1), dim3(FEAT_BLOCK), 0, stream, width, height, slots_a, keypoints_a, depth_a, slots_b, keypoints_b,
+                       depth_b, matches, K_a, K_b, l, stats);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_hypotheses_kernel, dim3((unsigned)((hypotheses + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream, hypotheses,
+                       seed, min_area, tau_px, tau_depth, K_b, l, counts);
+    GSR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(feat_finish_kernel, dim3(1), dim3(FEAT_BLOCK), 0, stream, hypotheses, seed, min_area, tau_px, tau_depth, refine_iters,
+                       min_matches, min_inliers, min_share, max_translation, max_rotation, K_b, l, T, stats);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -280,6 +280,14 @@ FUNCTIONS = {
     "gsr_pose_graph_workspace_size": (sz, [i, i]),
     "gsr_pose_graph_solve": (i, [i, i, vp, vp, vp, vp, vp, i, i, d, d, vp, vp, vp, sz, vp]),
     "gsr_map_correct": (i, [i, vp, vp, vp, i, vp, i, vp, vp, vp]),
+    # feature_matching.h
+    "gsr_feat_slots": (i, [i, i, i, i]),
+    "gsr_feat_extract_workspace_size": (sz, [i, i]),
+    "gsr_feat_extract": (i, [i, i, vp, vp, i, i, i] + [vp] * 5 + [sz, vp]),
+    "gsr_feat_match_workspace_size": (sz, [i, i]),
+    "gsr_feat_match": (i, [i, vp, vp, i, vp, vp, i, i, vp, vp, sz, vp]),
+    "gsr_feat_pose_workspace_size": (sz, [i, i]),
+    "gsr_feat_pose": (i, [i, i, i, vp, vp, i] + [vp] * 5 + [u, i, f, f, f, i, i, i, f, f, f] + [vp] * 4 + [sz, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

@@ -34,6 +34,27 @@ def _texture(p, rng_phase):
     return np.clip(col, 0.05, 0.95)
 
 
+def _cell_hash(p, size, offset, salt):
+    """An integer hash of the cell of edge `size` a point lies in, mapped to [0, 1]: [P]."""
+    i = np.floor(p / size + offset).astype(np.int64)
+    x = ((i[:, 0] * 73856093) ^ (i[:, 1] * 19349663) ^ (i[:, 2] * 83492791) ^ (int(salt) * 2654435761)) & 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x.astype(np.float64) / 4294967295.0
+
+
+def _blocks_texture(p):
+    """Piecewise-constant colour in [0.15, 0.85] from 3-D position: hashed cells of 16, 37 and 7 cm, per channel. The smooth texture has
+    almost no corners; this one gives the FAST detector of slam/features.py something to find on every surface."""
+    p = np.asarray(p, np.float64)
+    channel = lambda c: 0.15 + 0.7 * (0.5 * _cell_hash(p, 0.16, 0.0, 3 * c + 1) + 0.3 * _cell_hash(p, 0.37, (0.3, 0.1, 0.2), 3 * c + 2) +
+                                      0.2 * _cell_hash(p, 0.07, 0.0, 3 * c + 3))
+    return np.stack([channel(0), channel(1), channel(2)], 1)
+
+
 def _plane(origin, u, v, nu, nv, spacing, rng):
     """Jittered grid of points on the parallelogram origin + s u + t v."""
     s, t = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
@@ -42,8 +63,11 @@ def _plane(origin, u, v, nu, nv, spacing, rng):
     return origin[None] + s[:, None] * u[None] + t[:, None] * v[None]
 
 
-def build_room(spacing=0.03, seed=0):
-    """Static scene points [P,3] (camera looks down +z, y down like the TUM convention) and colours [P,3]."""
+def build_room(spacing=0.03, seed=0, texture="smooth"):
+    """Static scene points [P,3] (camera looks down +z, y down like the TUM convention) and colours [P,3]. texture: "smooth" (_texture) or
+    "blocks" (_blocks_texture); the points are the same."""
+    if texture not in ("smooth", "blocks"):
+        raise ValueError(f"texture must be 'smooth' or 'blocks', got {texture!r}")
     rng = np.random.default_rng(seed)
     ex, ey, ez = np.eye(3)
     parts = []
@@ -59,7 +83,8 @@ def build_room(spacing=0.03, seed=0):
         parts.append(_plane(o, ez, ey, n(sz), n(sy), spacing, rng))                                  # left face
         parts.append(_plane(o + np.array([sx, 0, 0]), ez, ey, n(sz), n(sy), spacing, rng))           # right face
     pts = np.concatenate(parts, 0)
-    return pts.astype(np.float32), _texture(pts, rng.uniform(0, 6.28, 3)).astype(np.float32)
+    smooth = _texture(pts, rng.uniform(0, 6.28, 3))
+    return pts.astype(np.float32), (smooth if texture == "smooth" else _blocks_texture(pts)).astype(np.float32)
 
 
 def build_ball(center, radius=0.22, spacing=0.03, seed=1):
@@ -89,8 +114,12 @@ def trajectory(num_frames, step=0.006, rot_step=0.0035):
 
 
 class SyntheticRGBDDataset:
-    def __init__(self, num_frames=40, width=320, height=240, seed=0, dynamic=False, dystart=None, spacing=0.03, device="cuda:0",
-                 step=0.006, rot_step=0.0035, depth_noise=0.0, sensor_depth=True):
+    def __init__(self, num_frames=40, width=320, height=240, seed=0, dynamic=False, dystart=None, spacing=None, device="cuda:0",
+                 step=0.006, rot_step=0.0035, depth_noise=0.0, sensor_depth=True, texture="smooth"):
+        # spacing None: 3 cm, and 1.5 cm for texture="blocks" -- at 3 cm the splatted points blur the blocks' corners (27 FAST corners in a
+        # 320 x 240 frame against 106 at 1.5 cm, and no feature pose is accepted 8 or more frames apart: DESIGN.md section 8, Feature seed)
+        if spacing is None:
+            spacing = 0.015 if texture == "blocks" else 0.03
         self.device = torch.device(device)
         self.num_imgs, self.width, self.height = num_frames, width, height
         s = width / 640.0
@@ -100,7 +129,7 @@ class SyntheticRGBDDataset:
         self.dystart = (0 if dystart is None else int(dystart)) if dynamic else num_frames + 1     # first frame with the moving object
         self.dynamic_objects = 0
         self.poses = torch.tensor(trajectory(num_frames, step, rot_step), device=self.device)
-        pts, col = build_room(spacing, seed)
+        pts, col = build_room(spacing, seed, texture)
         self.static_xyz, self.static_rgb = torch.tensor(pts, device=self.device), torch.tensor(col, device=self.device)
         self.ball_xyz0, self.ball_rgb = (torch.tensor(a, device=self.device) for a in build_ball((-0.5, 0.2, 1.9), spacing=spacing, seed=seed + 1))
         self.spacing = spacing

@@ -36,7 +36,7 @@ from . import keyframes as kf
 from .camera import Camera
 from .eval_utils import eval_ate, save_gaussians
 from .relocalise import relocalisation_options
-from .stages import (LoopClosure, PosePrior, Relocalisation, SweepSeeding, loop_closure_options, mono_sweep_options, pose_prior_options,
+from .stages import (LoopClosure, PosePrior, Relocalisation, SweepSeeding, feature_seed_options, loop_closure_options, mono_sweep_options, pose_prior_options,
                      pose_prior_terms_options)
 
 
@@ -91,9 +91,10 @@ class FrontEnd:
         self.mono_sweep = sweep and SweepSeeding(sweep)
         terms = pose_prior_terms_options(training)                         # refused without pose_prior
         self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model, terms)
-        self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model)
+        seed = feature_seed_options(training)                               # refused for monocular runs and without a stage to seed
+        self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model, seed)
         loops = loop_closure_options(training, self.dynamic_model)          # refused for monocular, dynamic and spherical-harmonics runs
-        self.loop_closure = loops and LoopClosure(loops)
+        self.loop_closure = loops and LoopClosure(loops, seed)
 
     def set_hyperparams(self):
         """:115-126."""

@@ -165,20 +165,28 @@ class PoseGraph:
 class LoopCloser:
     """options: slam.stages.loop_closure_options(...); cameras: {frame id: Camera} of the run (keyframes keep their image and depth);
     get_gaussians: a callable returning the run's GaussianModel as it is now (the back-end may replace it); size = (width, height), K =
-    (fx, fy, cx, cy); index: a KeyframeIndex another stage fills with every keyframe (relocalisation), or None to own one."""
+    (fx, fy, cx, cy); index: a KeyframeIndex another stage fills with every keyframe (relocalisation), or None to own one; feature_seed:
+    slam.features.feature_seed_options(...) or None -- with it verify() starts at the pose of matched features (slam/features.py) where
+    that is accepted, and the alignment may then move as far as that block's gate allows."""
 
-    def __init__(self, options, cameras, get_gaussians, size, K, device, index=None):
+    def __init__(self, options, cameras, get_gaussians, size, K, device, index=None, feature_seed=None):
         from .odometry import DenseOdometry
         self.options, self.cameras, self.get_gaussians, self.device = options, cameras, get_gaussians, torch.device(device)
         self.shared_index = index is not None
         self.index = index if self.shared_index else KeyframeIndex.from_options(options, self.device)
         self.graph = PoseGraph(self.device)
-        self.odometry = DenseOdometry(size[0], size[1], K, levels=options["levels"], iters=options["iters"],
-                                      max_translation=options["max_translation"], max_rotation=options["max_rotation"], device=self.device,
-                                      affine=True, geometric_weight=options["geometric_weight"])
-        self.verify_log, self.solve_log = EventLog(self.device), EventLog(self.device)
         self.stats = {"keyframes_queried": 0, "candidates_verified": 0, "edges_accepted": 0, "solves": 0, "corrections_applied": 0,
                       "max_correction_m": 0.0, "max_correction_deg": 0.0}
+        self.seeder = None
+        gate = (options["max_translation"], options["max_rotation"])
+        if feature_seed is not None:
+            from .features import FeatureSeeder
+            self.seeder = FeatureSeeder(size, K, feature_seed, self.device)
+            gate = (max(gate[0], feature_seed["max_translation"]), max(gate[1], feature_seed["max_rotation"]))
+            self.stats.update(feature_seeds_tried=0, feature_seeds_accepted=0)
+        self.odometry = DenseOdometry(size[0], size[1], K, levels=options["levels"], iters=options["iters"], max_translation=gate[0],
+                                      max_rotation=gate[1], device=self.device, affine=True, geometric_weight=options["geometric_weight"])
+        self.verify_log, self.solve_log = EventLog(self.device), EventLog(self.device)
         self.last_solve = None
 
     @property
@@ -189,6 +197,8 @@ class LoopCloser:
         self.graph.clear()
         if not self.shared_index:
             self.index.clear()
+        if self.seeder is not None:
+            self.seeder.forget()
 
     # ---- verification ---------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -196,7 +206,9 @@ class LoopCloser:
         """Two-way dense alignment of the real frames of the keyframes a (old) and b (new), frame ids: forward keep(a), align(b) from
         X_b X_a^-1 gives T_ab; backward keep(b), align(a) from T_ab^-1 gives T_ba. Accepted when both gates accept and Log(T_ba T_ab) is
         below `consistency`. ONE host read: the two flags and the size of the inconsistency, together. Returns (accepted, T_ab [4, 4] float32
-        on the device, {"forward", "backward", "translation" in metres, "rotation" in degrees})."""
+        on the device, {"forward", "backward", "translation" in metres, "rotation" in degrees}). With the feature seed on, verify_seeded()."""
+        if self.seeder is not None:
+            return self.verify_seeded(a, b)
         ca, cb = self.cameras[a], self.cameras[b]
         with self.verify_log.timed():
             start = (pose44(cb.R, cb.T) @ inverse44(pose44(ca.R, ca.T))).to(torch.float32)
@@ -211,6 +223,38 @@ class LoopCloser:
         ok = forward > 0.5 and backward > 0.5 and metres <= self.options["consistency"][0] and degrees <= self.options["consistency"][1]
         self.stats["candidates_verified"] += 1
         return ok, T_ab, {"forward": forward > 0.5, "backward": backward > 0.5, "translation": metres, "rotation": degrees}
+
+    @torch.no_grad()
+    def verify_seeded(self, a, b):
+        """verify() with the feature seed: the keypoints of the two real frames (kept per frame id) are matched and posed; an accepted pose
+        replaces X_b X_a^-1 as the start of the forward alignment. The two alignments run with the wider of the two gates; where the seed
+        was refused their own, narrower gate is applied afterwards on the device (features.gated), which is what verify() decides for
+        that pair. The two-way test decides as before. Still ONE host read, the seed's flag packed into it; the dictionary gains "seeded"."""
+        from .features import gated
+        ca, cb = self.cameras[a], self.cameras[b]
+        opt = self.options
+        with self.verify_log.timed():
+            seed, seed_stats = self.seeder.pose(self.seeder.cached(a, ca.original_image), ca.depth_device(),
+                                                self.seeder.cached(b, cb.original_image), cb.depth_device())
+            seeded = seed_stats[6]
+            start = (pose44(cb.R, cb.T) @ inverse44(pose44(ca.R, ca.T))).to(torch.float32)
+            start = torch.where(seeded > 0, seed, start)
+            self.odometry.keep(ca.original_image, ca.depth_device(), None)
+            T_ab, s_ab = self.odometry.align(cb.original_image, start, depth=cb.depth_device())
+            T_ab, f_ab = gated(T_ab, s_ab[0], seeded, opt["max_translation"], opt["max_rotation"])
+            self.odometry.keep(cb.original_image, cb.depth_device(), None)
+            T_ba, s_ba = self.odometry.align(ca.original_image, inverse44(T_ab.to(torch.float64)).to(torch.float32), depth=ca.depth_device())
+            T_ba, f_ba = gated(T_ba, s_ba[0], seeded, opt["max_translation"], opt["max_rotation"])
+            size = motion_size(T_ba.to(torch.float64) @ T_ab.to(torch.float64))
+            packed = torch.cat([torch.stack([f_ab, f_ba]), size, seeded.to(torch.float64).reshape(1)])
+        forward, backward, metres, radians, seeded = packed.tolist()
+        degrees = math.degrees(radians)
+        ok = forward > 0.5 and backward > 0.5 and metres <= opt["consistency"][0] and degrees <= opt["consistency"][1]
+        self.stats["candidates_verified"] += 1
+        self.stats["feature_seeds_tried"] += 1
+        self.stats["feature_seeds_accepted"] += int(seeded > 0.5)
+        return ok, T_ab, {"forward": forward > 0.5, "backward": backward > 0.5, "translation": metres, "rotation": degrees,
+                          "seeded": seeded > 0.5}
 
     def _candidates(self, viewpoint, rows):
         """The rows of the index among its first `rows` whose code is close enough to the frame's: ONE host read, the topk pairs."""

@@ -263,22 +263,41 @@ class Relocaliser:
     keyframes: {id: camera} -- pose (R, T) and time of every id the index holds; render_at(camera) -> render package of the map at that
     camera; track_from(viewpoint) -> render package: refines viewpoint's pose against the map from where it stands and renders there.
     The two callables keep the class ignorant of whether it serves a live run or a loaded map. size = (width, height), K = (fx, fy, cx,
-    cy), opt = relocalisation_options(...); log: an EventLog that times every judge()'s score (default: none is kept)."""
+    cy), opt = relocalisation_options(...); log: an EventLog that times every judge()'s score (default: none is kept). feature_seed:
+    slam.features.feature_seed_options(...) or None -- with it the alignment of _seed starts at the pose of matched features
+    (slam/features.py) and may move as far as that block's gate allows; static_map: the renderings at the keyframes never change (a loaded
+    map), so their features are kept per keyframe id."""
 
-    def __init__(self, index, keyframes, render_at, track_from, size, K, opt, log=None):
+    def __init__(self, index, keyframes, render_at, track_from, size, K, opt, log=None, feature_seed=None, static_map=False):
         from .odometry import DenseOdometry
         self.index, self.keyframes, self.render_at, self.track_from, self.opt = index, keyframes, render_at, track_from, opt
         self.log = EventLog("cpu") if log is None else log
-        self.odometry = DenseOdometry(size[0], size[1], K, levels=opt["levels"], iters=opt["iters"], max_translation=opt["max_translation"],
-                                      max_rotation=opt["max_rotation"], device=index.device)
+        self.seeder, self.static_map = None, bool(static_map)
+        gate = (opt["max_translation"], opt["max_rotation"])
+        if feature_seed is not None:
+            from .features import FeatureSeeder
+            self.seeder = FeatureSeeder(size, K, feature_seed, index.device)
+            gate = (max(gate[0], feature_seed["max_translation"]), max(gate[1], feature_seed["max_rotation"]))
+        self.odometry = DenseOdometry(size[0], size[1], K, levels=opt["levels"], iters=opt["iters"], max_translation=gate[0],
+                                      max_rotation=gate[1], device=index.device)
 
     @torch.no_grad()
-    def _seed(self, viewpoint, keyframe):
+    def _seed(self, viewpoint, keyframe, frame_features=None, key=None):
         """Place `viewpoint` at the keyframe's pose moved by the alignment of its image against the map rendered there; where the
-        alignment's gate refuses, T is the identity and the pose is the keyframe's. Device tensors throughout."""
+        alignment's gate refuses, T is the identity and the pose is the keyframe's. With the feature seed on (frame_features: the frame's
+        keypoints and descriptors) the alignment starts at the feature pose of the rendering and the frame -- the identity where that is
+        refused, and then the alignment's own, narrower gate holds (features.gated). Device tensors throughout; nothing is read."""
         pkg = self.render_at(keyframe)
-        self.odometry.keep(pkg["render"], opaque_depth(pkg["depth"], pkg["opacity"]), None)
-        T, _ = self.odometry.align(viewpoint.original_image)
+        depth = opaque_depth(pkg["depth"], pkg["opacity"])
+        self.odometry.keep(pkg["render"], depth, None)
+        if self.seeder is None:
+            T, _ = self.odometry.align(viewpoint.original_image)
+        else:
+            from .features import gated
+            there = self.seeder.cached(key, pkg["render"]) if self.static_map else self.seeder.features(pkg["render"])
+            start, seed_stats = self.seeder.pose(there, depth, frame_features, viewpoint.depth_device())
+            T, stats = self.odometry.align(viewpoint.original_image, T_init=start)
+            T, _ = gated(T, stats[0], seed_stats[6], self.opt["max_translation"], self.opt["max_rotation"])
         viewpoint.update_RT(*compose_pose(T, keyframe.R, keyframe.T))
 
     def judge(self, viewpoint, render_pkg, fallback, mask=None):
@@ -305,11 +324,12 @@ class Relocaliser:
         exposure0 = [p.detach().clone() for p in (viewpoint.exposure_a, viewpoint.exposure_b)]
         out = {"accepted": False, "keyframe": None, "candidates_tried": 0, "counts": None, "distance": None}
         best, _ = self.index.query(viewpoint.original_image, viewpoint.depth_device(), mask, opt["topk"])
+        frame_features = None if self.seeder is None else self.seeder.features(viewpoint.original_image, mask)
         for row, distance in best.tolist():
             if row < 0:
                 break
             frame_id = self.index.ids[row]
-            self._seed(viewpoint, self.keyframes[frame_id])
+            self._seed(viewpoint, self.keyframes[frame_id], frame_features, frame_id)
             pkg = self.track_from(viewpoint)
             counts = score(pkg, viewpoint, opt["tau_colour"], opt["tau_depth"], mask).tolist()
             out.update(candidates_tried=out["candidates_tried"] + 1, counts=counts, distance=distance)
@@ -343,6 +363,8 @@ class MapLocaliser:
         training = self.config["Training"]
         training.setdefault("monocular", self.config["Dataset"].get("sensor_type") == "monocular")
         self.opt = relocalisation_options({"relocalisation": {**(training.get("relocalisation") or {}), "enabled": True}})
+        from .features import feature_seed_options
+        self.feature_seed = feature_seed_options({**training, "relocalisation": {"enabled": True}})      # None unless its block is on
         self.device = torch.device(loaded_map.device)
         self.keyframes = {k: loaded_map.cameras[k] for k in loaded_map.kf_indices}
         first = self.keyframes[loaded_map.kf_indices[0]]
@@ -354,7 +376,8 @@ class MapLocaliser:
         for i, k in enumerate(loaded_map.kf_indices):
             self.index.add(k, colour[i], opaque_depth(depth[i, 0], opacity[i, 0]), None)
         self._tracker = None
-        self.relocaliser = Relocaliser(self.index, self.keyframes, self._render_at, self._track_from, self.size, self.K, self.opt)
+        self.relocaliser = Relocaliser(self.index, self.keyframes, self._render_at, self._track_from, self.size, self.K, self.opt,
+                                       feature_seed=self.feature_seed, static_map=True)
 
     @torch.no_grad()
     def _render_at(self, camera):
@@ -415,4 +438,7 @@ class MapLocaliser:
         if len(kept) >= 3:
             c2w = lambda m: np.linalg.inv(m.numpy().astype(np.float64))
             ate = ate_rmse([c2w(gts[i]) for i in kept], [c2w(poses[i]) for i in kept])
-        return {"poses": torch.stack(poses) if poses else torch.zeros((0, 4, 4)), "status": status, "frames": list(frames), "ate_rmse": ate}
+        out = {"poses": torch.stack(poses) if poses else torch.zeros((0, 4, 4)), "status": status, "frames": list(frames), "ate_rmse": ate}
+        if self.relocaliser.seeder is not None:
+            out.update(self.relocaliser.seeder.summary())
+        return out

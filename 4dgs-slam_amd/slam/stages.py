@@ -7,6 +7,7 @@ import torch
 from .camera import compose_pose, opaque_depth
 from .options import check_gate, check_pass_counts, read_block, to_floats
 from .pretrained import EventLog
+from .features import feature_seed_options  # noqa: F401  (Training.feature_seed: read here with its neighbours, defined beside its stage object)
 from .relocalise import DEFAULT_ITERS, MAX_TOPK, KeyframeIndex, Relocaliser, relocalisation_options
 
 
@@ -228,8 +229,8 @@ class PosePrior:
 
 # ---- Training.relocalisation: is the tracked frame lost, and if so where is it ------------------------------------------------------------
 class Relocalisation:
-    def __init__(self, options, dynamic_model):
-        self.options, self.dynamic_model = options, dynamic_model
+    def __init__(self, options, dynamic_model, feature_seed=None):
+        self.options, self.dynamic_model, self.feature_seed = options, dynamic_model, feature_seed     # feature_seed_options(...) or None
         self.index = self.relocaliser = None                  # built with the first map, on the device
         self.stats, self.log = {"scored": 0, "lost": 0, "relocalised": 0}, EventLog("cuda")
 
@@ -238,7 +239,8 @@ class Relocalisation:
         if self.index is None:
             self.index = KeyframeIndex.from_options(self.options, viewpoint.device)
             self.relocaliser = Relocaliser(self.index, cameras, render_at, track_from, (viewpoint.image_width, viewpoint.image_height),
-                                           (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), self.options, self.log)
+                                           (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), self.options, self.log,
+                                           **({} if self.feature_seed is None else {"feature_seed": self.feature_seed}))
         self.index.clear()
         self.add(frame_idx, viewpoint)
 
@@ -257,8 +259,13 @@ class Relocalisation:
         return found
 
     def summary(self):
-        """The `relocalisation` block of the run result: frames scored, lost, relocalised, device ms per score."""
-        return {**self.stats, "device_ms_per_score": self.log.summary()["ms_per_item"] or 0.0}
+        """The `relocalisation` block of the run result: frames scored, lost, relocalised, device ms per score; with the feature seed on
+        also feature_seeds_tried and feature_seeds_accepted."""
+        out = {**self.stats, "device_ms_per_score": self.log.summary()["ms_per_item"] or 0.0}
+        if self.feature_seed is not None:
+            seeder = self.relocaliser and self.relocaliser.seeder
+            out.update(seeder.summary() if seeder else {"feature_seeds_tried": 0, "feature_seeds_accepted": 0})
+        return out
 
 
 # ---- Training.loop_closure: tie a keyframe to the old keyframes that saw the same place, and correct poses and map ------------------------
@@ -350,8 +357,8 @@ def loop_closure_options(training, dynamic_model=False, ranks=1):
 
 
 class LoopClosure:
-    def __init__(self, options):
-        self.options = options
+    def __init__(self, options, feature_seed=None):
+        self.options, self.feature_seed = options, feature_seed                                         # feature_seed_options(...) or None
         self.closer = None                                    # slam.loop_closure.LoopCloser, built with the first map, on the device
 
     def restart(self, frame_idx, viewpoint, cameras, get_gaussians, index=None, ranks=1):
@@ -363,7 +370,8 @@ class LoopClosure:
         if self.closer is None:
             from .loop_closure import LoopCloser
             self.closer = LoopCloser(self.options, cameras, get_gaussians, (viewpoint.image_width, viewpoint.image_height),
-                                     (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), viewpoint.device, index)
+                                     (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), viewpoint.device, index,
+                                     **({} if self.feature_seed is None else {"feature_seed": self.feature_seed}))
         self.closer.clear()
         self.closer.on_keyframe(frame_idx, viewpoint)
 
@@ -375,6 +383,7 @@ class LoopClosure:
         """The `loop_closure` block of the run result: keyframes queried, candidates verified, edges accepted, solves, corrections applied,
         the largest correction, device ms per verify and per solve."""
         if self.closer is None:
+            seeds = {} if self.feature_seed is None else {"feature_seeds_tried": 0, "feature_seeds_accepted": 0}
             return {"keyframes_queried": 0, "candidates_verified": 0, "edges_accepted": 0, "solves": 0, "corrections_applied": 0,
-                    "max_correction_m": 0.0, "max_correction_deg": 0.0, "device_ms_per_verify": 0.0, "device_ms_per_solve": 0.0}
+                    "max_correction_m": 0.0, "max_correction_deg": 0.0, **seeds, "device_ms_per_verify": 0.0, "device_ms_per_solve": 0.0}
         return self.closer.summary()

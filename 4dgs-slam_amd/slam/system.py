@@ -138,15 +138,16 @@ class SLAM:
         the map and every camera. The run's ``Training.loop_closure`` block is read whether or not it is enabled; overrides replace its
         keys. Returns close_all()'s dictionary; the `loop_closure` block of ``self.result`` is refreshed."""
         from .loop_closure import LoopCloser
-        from .stages import loop_closure_options
+        from .stages import feature_seed_options, loop_closure_options
         fe, training = self.frontend, self.config["Training"]
         block = {**(training.get("loop_closure") or {}), **overrides, "enabled": True}
         options = loop_closure_options({**training, "loop_closure": block}, self.config["model_params"]["dynamic_model"], self.backend.shard.world)
+        seed = feature_seed_options({**training, "loop_closure": block})               # None unless Training.feature_seed is on
         if not fe.kf_indices:
             raise ValueError("SLAM.close_loops: the run has no keyframe")
         first = fe.cameras[fe.kf_indices[0]]
         closer = LoopCloser(options, fe.cameras, lambda: fe.gaussians, (first.image_width, first.image_height),
-                            (first.fx, first.fy, first.cx, first.cy), first.device)
+                            (first.fx, first.fy, first.cx, first.cy), first.device, feature_seed=seed)
         out = closer.close_all(list(fe.kf_indices))
         self.result["loop_closure"] = closer.summary()
         return out

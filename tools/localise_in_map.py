@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument("--first", type=int, default=0, help="the first of them")
     ap.add_argument("--size", default=None, help="WxH of the synthetic frames (default: the map's)")
     ap.add_argument("--trajectory", default=None, help="write the poses to this file")
+    ap.add_argument("--feature-seed", action="store_true", help="start each candidate's alignment at the pose of matched features "
+                    "(Training.feature_seed); the synthetic frames then carry the blocks texture, as the map must")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     import torch
@@ -39,7 +41,8 @@ def main(argv=None):
     if args.synthetic:
         from slam.dataset import SyntheticRGBDDataset
         W, H = (int(v) for v in args.size.lower().split("x")) if args.size else (int(loaded.meta["width"]), int(loaded.meta["height"]))
-        ds = SyntheticRGBDDataset(num_frames=args.first + args.frames, width=W, height=H, seed=0, spacing=0.025 if W > 320 else 0.03, device=args.device)
+        ds = SyntheticRGBDDataset(num_frames=args.first + args.frames, width=W, height=H, seed=0, spacing=None if args.feature_seed else (0.025 if W > 320 else 0.03), device=args.device,
+                                  texture="blocks" if args.feature_seed else "smooth")
         config = merge_config(default_config(), {"Training": {"tracking_itr_num": 60}})
     else:
         from slam.config import apply_cli_overrides, load_config
@@ -48,6 +51,8 @@ def main(argv=None):
         if args.dataset_path:
             config["Dataset"]["dataset_path"] = args.dataset_path
         ds = load_dataset(config, args.device, max_frames=args.first + args.frames)
+    if args.feature_seed:
+        config = merge_config(config, {"Training": {"feature_seed": {"enabled": True}}})
     frames = list(range(args.first, min(len(ds), args.first + args.frames)))
     out = MapLocaliser(loaded, config).follow(ds, frames)
     if args.trajectory:
@@ -57,7 +62,7 @@ def main(argv=None):
     status = out["status"]
     print(json.dumps({"map": args.map, "frames": out["frames"], "status": status, "counts": {s: status.count(s) for s in sorted(set(status))},
                       "ate_rmse": out["ate_rmse"], "keyframes": len(loaded.kf_indices), "gaussians": int(loaded.gaussians.get_xyz.shape[0]),
-                      "trajectory": args.trajectory}))
+                      "trajectory": args.trajectory, **{k: out[k] for k in ("feature_seeds_tried", "feature_seeds_accepted") if k in out}}))
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@ slam/odometry.py) and the result has an `odometry` block; --tracking-itr N sets 
 most where the tracker is given few iterations. --pose-prior-terms (implies --pose-prior) turns on Training.pose_prior_terms with its defaults:
 the alignment's affine brightness and depth term; --pose-prior-against keyframe aligns against the last keyframe, not the previous frame.
 --loop-closure turns on Training.loop_closure with its defaults on the static scenarios (a dynamic model is refused) and the result has a
-`loop_closure` block; the demo's arc never returns to a place, so it shows the cost of the stage, not a correction."""
+`loop_closure` block; the demo's arc never returns to a place, so it shows the cost of the stage, not a correction. --feature-seed (with
+--loop-closure) turns on Training.feature_seed and gives the room the blocks texture, which has corners to find."""
 import json
 import os
 import sys
@@ -33,6 +34,7 @@ pose_prior_terms = "--pose-prior-terms" in sys.argv      # implies --pose-prior;
 pose_prior = pose_prior or pose_prior_terms
 pose_prior_against = sys.argv[sys.argv.index("--pose-prior-against") + 1] if "--pose-prior-against" in sys.argv else "previous"
 loop_closure = "--loop-closure" in sys.argv
+feature_seed = "--feature-seed" in sys.argv               # needs --loop-closure (or a Training.relocalisation block); the blocks texture
 tracking_itr = int(sys.argv[sys.argv.index("--tracking-itr") + 1]) if "--tracking-itr" in sys.argv else 60
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
@@ -44,8 +46,8 @@ for name, dyn, graph, frames, wh in scenarios:
     if only not in name or (loop_closure and dyn):
         continue
     torch.manual_seed(0)
-    ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=0.025 if wh[0] > 320 else 0.03,
-                              sensor_depth=not monocular)
+    ds = SyntheticRGBDDataset(num_frames=frames, width=wh[0], height=wh[1], seed=0, dynamic=dyn, dystart=6 if dyn else None, spacing=None if feature_seed else (0.025 if wh[0] > 320 else 0.03),
+                              sensor_depth=not monocular, texture="blocks" if feature_seed else "smooth")
     cfg = merge_config(default_config(), {"Training": {"init_itr_num": 400, "init_gaussian_update": 100, "init_gaussian_reset": 200, "tracking_itr_num": tracking_itr,
                                                        "static_map_iters": 30, "dynamic_map_iters": 80, "network_init_iters": 50, "gaussian_update_every": 60,
                                                        "gaussian_update_offset": 20, "tracking_graph": graph,
@@ -63,6 +65,8 @@ for name, dyn, graph, frames, wh in scenarios:
         cfg = merge_config(cfg, {"Training": {"pose_prior_terms": {"enabled": True, "against": pose_prior_against}}})
     if loop_closure:
         cfg = merge_config(cfg, {"Training": {"loop_closure": {"enabled": True}}})
+    if feature_seed:
+        cfg = merge_config(cfg, {"Training": {"feature_seed": {"enabled": True}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
