@@ -13,7 +13,11 @@ Gaussian gradients (the optimizer's flat bucket: the backward kernels already su
 all-reduced; the densification statistics, the visibility union of the opacity reset and the window keyframes' visibility rows are
 reduced only on the iterations that use them; the window cameras' poses / exposures travel owner -> everyone once per iteration (14
 floats each). The view-independent terms (isotropic-scale regulariser, ARAP / elastic node regularisers) are added on rank 0. All ranks
-must be seeded alike: they take the same random draws (extra keyframes, time samples, split noise)."""
+must be seeded alike: they take the same random draws (extra keyframes, time samples, split noise).
+
+Who decides what: WHICH iterations densify or reset opacities is slam/schedule.py's (mapping_rule, init_rule), how long the run of plain
+iterations before the next such one is its plain_run; WHAT they then do to the model is _maintain / _maintain_init here -- for the eager
+bodies below and for the fixed layout of slam/dynamic_graph.py alike. Every attribute an instance carries is declared in __init__."""
 import os
 import random
 
@@ -24,7 +28,8 @@ import mapping_shard
 import slam_losses
 
 from .deform_model import draw_loss_times
-from .schedule import catch_up
+from .keyframe_slots import FlowTargets, KeyframeOperands
+from .schedule import catch_up, init_rule, mapping_rule, plain_run
 
 
 class _IsotropicLoss(torch.autograd.Function):
@@ -77,8 +82,27 @@ class BackEnd:
         self.pose_lr_scale = 0.5
         self.frames_to_optimize = config["Training"]["pose_window"]
         self.log = []
-        self._view_shard = None
-        self._flow_targets = {}          # (keyframe, earlier keyframe) -> masked flow targets of _flow_loss
+        self._view_shard = None          # shard / attach_process_group
+        # ---- set_hyperparams (from config["Training"] / ["Results"]; a test double may assign them directly) ------------------------------
+        self.loss_values = False
+        self.save_results = self.save_dir = None
+        self.init_itr_num = self.init_gaussian_update = self.init_gaussian_reset = self.init_gaussian_th = self.init_gaussian_extent = None
+        self.mapping_itr_num = self.gaussian_update_every = self.gaussian_update_offset = self.gaussian_reset = None
+        self.gaussian_th = self.gaussian_extent = self.size_threshold = self.window_size = self.single_thread = None
+        self.kf_map_iters = self.dynamic_map_iters = self.static_map_iters = self.network_init_iters = None
+        # ---- the mapping loops -----------------------------------------------------------------------------------------------------------
+        self.last_key_opt = []           # map(): the keyframes its last call optimised
+        self._delta_cache = None         # map() / color_refinement(): time -> deltas inside an iteration of the eager bodies, read by _deltas
+        self._reg_weight_cache = {}      # _regulariser_weights
+        self.flow_targets = FlowTargets()    # _flow_losses and dynamic_graph.DynamicMapping: flow targets per keyframe pair, clip rectangles
+        self.flow_clip_checks = []       # dynamic_graph.DynamicMapping._check_flow_clips (Training.flow_clip_check, a test facility)
+        # ---- graph runs (slam/graph_run.py) ------------------------------------------------------------------------------------------------
+        self._kf_operands = None         # keyframe_operands, on first use (the store registers itself with slam_losses)
+        self._graph_streams, self._unit_gradients, self._graph_pools = {}, {}, {}      # graph_streams / unit_gradient / graph_pool, per device
+        self._graph_keepalive = None     # graph_run.capture: the newest graph, which holds the shared pool's blocks
+        self._broken_graphs = set()      # graph_run.replay_run: the kinds of run whose capture failed ("graph", the static kind, stops them all)
+        # graph_run.stats fills a kind's counters in when a run of that kind is first touched: empty until then
+        self.graph_stats, self.init_graph_stats, self.dynamic_graph_stats, self.network_init_graph_stats = {}, {}, {}, {}
 
     @property
     def shard(self):
@@ -92,10 +116,10 @@ class BackEnd:
         return self._view_shard
 
     def set_hyperparams(self):
+        """:81-105."""
         # Training.loss_values (default False): the mapping loops only back-propagate their losses, so the value's two launches per view are
         # skipped and -- in the static loop -- every view is back-propagated on its own (same gradient sum, accumulated in view order)
         self.loss_values = bool(self.config["Training"].get("loss_values", False))
-        """:81-105."""
         t = self.config["Training"]
         self.save_results, self.save_dir = self.config["Results"].get("save_results", False), self.config["Results"].get("save_dir")
         self.init_itr_num, self.init_gaussian_update = t["init_itr_num"], t["init_gaussian_update"]
@@ -121,7 +145,7 @@ class BackEnd:
     def reset(self):
         """:143-157."""
         self.iteration_count, self.occ_aware_visibility, self.viewpoints, self.current_window = 0, {}, {}, []
-        self._flow_targets = {}
+        self.flow_targets.clear()          # (formed again on demand, from the dataset's cached flows)
         self.initialized = not self.monocular
         if self.gaussians.get_xyz.shape[0]:
             self.gaussians.prune_points(self.gaussians.unique_kfIDs >= 0)
@@ -135,7 +159,7 @@ class BackEnd:
         # inside a mapping iteration (ControlNodes.begin_iteration .. end_iteration) neither the nodes nor the Gaussians move: the deltas of
         # a time are blended once and shared by the view's render and the flow terms of the views whose partner it is
         nodes = g.deform.deform
-        cache = getattr(self, "_delta_cache", None) if (train and nodes._batch is not None) else None
+        cache = self._delta_cache if (train and nodes._batch is not None) else None
         key = round(float(viewpoint.time), 7)
         if cache is not None and key in cache:
             return cache[key]
@@ -171,7 +195,8 @@ class BackEnd:
         rm_dynamic = not (self.dystart == cur_frame_idx)
         mapping_iteration = 0
         while mapping_iteration < self.init_itr_num:
-            run = self._plain_init_run(mapping_iteration)
+            run = plain_run(mapping_iteration, self.init_itr_num,
+                            lambda k: any(init_rule(self, k, self.iteration_count + (k - mapping_iteration) + 1)))
             if run >= self.graph_min_run and self._graphs_enabled() and self._graph_ok([viewpoint]):
                 pkg = None         # (lets the last eager iteration's autograd graph go: its AccumulateGrad nodes belong to the default stream)
                 done_pkg = self._initialize_map_graph_run(viewpoint, rm_dynamic, run)
@@ -193,23 +218,18 @@ class BackEnd:
         with torch.no_grad():
             self._view_stats(pkg)
             if mapping_iteration is not None:
-                if mapping_iteration % self.init_gaussian_update == 0:
-                    self.gaussians.densify_and_prune(self.opt_params.densify_grad_threshold, self.init_gaussian_th, self.init_gaussian_extent, None)
-                if self.iteration_count == self.init_gaussian_reset or self.iteration_count == self.opt_params.densify_from_iter:
-                    self.gaussians.reset_opacity()
+                self._maintain_init(*init_rule(self, mapping_iteration, self.iteration_count))
             self.gaussians.optimizer.step()
             self.gaussians.optimizer.zero_grad(set_to_none=True)
         return pkg
 
-    def _plain_init_run(self, mapping_iteration):
-        """How many iterations of initialize_map from `mapping_iteration` on neither densify nor reset opacities."""
-        n = 0
-        while mapping_iteration + n < self.init_itr_num:
-            count = self.iteration_count + n + 1
-            if (mapping_iteration + n) % self.init_gaussian_update == 0 or count == self.init_gaussian_reset or count == self.opt_params.densify_from_iter:
-                break
-            n += 1
-        return n
+    def _maintain_init(self, densify, reset=False):
+        """What schedule.init_rule asks of an initialisation iteration (initialize_map, initialize_network in both its forms): the
+        densification with the initialisation thresholds, then the opacity reset."""
+        if densify:
+            self.gaussians.densify_and_prune(self.opt_params.densify_grad_threshold, self.init_gaussian_th, self.init_gaussian_extent, None)
+        if reset:
+            self.gaussians.reset_opacity()
 
     def _initialize_map_graph_run(self, viewpoint, rm_dynamic, run):
         """`run` plain iterations of initialize_map as warm-up + capture + replays (slam/graph_run.py); returns the last render package, or
@@ -263,8 +283,7 @@ class BackEnd:
             # the node blend's backward and in the regularisers' gathers -- so the replicas stay identical without exchanging anything)
             with torch.no_grad():
                 self._view_stats(pkg)
-                if mapping_iteration % self.init_gaussian_update == 0:           # :209-215 (iteration 0 with the shipped schedule)
-                    g.densify_and_prune(self.opt_params.densify_grad_threshold, self.init_gaussian_th, self.init_gaussian_extent, None)
+                self._maintain_init(init_rule(self, mapping_iteration)[0])       # :209-215 (iteration 0 with the shipped schedule)
                 g.deform.optimizer.step()
                 g.deform.optimizer.zero_grad(set_to_none=True)
                 if update_gaussians:
@@ -292,9 +311,7 @@ class BackEnd:
                 continue
             position = cam_idx if positions is None else positions[cam_idx]
             if viewpoint.uid == 0 or position is None:
-                for p in (viewpoint.cam_rot_delta, viewpoint.cam_trans_delta, viewpoint.exposure_a, viewpoint.exposure_b):
-                    if p is not None:
-                        p.grad = None
+                self._clear_camera_grads([viewpoint])
                 continue
             req = (viewpoint, lr["cam_rot_delta"] * self.pose_lr_scale, lr["cam_trans_delta"] * self.pose_lr_scale, 0.01,
                    position < self.frames_to_optimize, True)
@@ -329,6 +346,18 @@ class BackEnd:
         for p in pkgs:
             seen |= p["visibility_filter"]
         g.reset_opacity_nonvisible([self.shard.union(seen)])
+
+    def _maintain(self, count, pkgs, enabled=True):
+        """What schedule.mapping_rule asks of the mapping iteration whose iteration_count is `count`, after the statistics of its views
+        `pkgs` are in and before the steps: the densification (:722-738,:1185-1199; on the statistics of all ranks) or the opacity reset of
+        what no view saw (:740-745,:1201-1206). `enabled` False (map(): the Gaussians do not take part yet): nothing. Returns gaussian_split."""
+        what = mapping_rule(self, count) if enabled else None
+        if what == "densify":
+            self.shard.reduce_statistics(self.gaussians)
+            self.gaussians.densify_and_prune(self.opt_params.densify_grad_threshold, self.gaussian_th, self.gaussian_extent, self.size_threshold)
+        elif what == "reset":
+            self._reset_opacity_of_unseen(pkgs)
+        return what is not None
 
     def _window_full_bookkeeping(self, current_window):
         """The reference's covisibility step (:663-696 / :1140-1170): once the window is full, the per-Gaussian observation counts are
@@ -366,7 +395,7 @@ class BackEnd:
     def _regulariser_weights(self, n_window, n_random):
         """1e-3 per window view, 1e-4 per random keyframe (:520-524,:649-652) as a device vector, built once per (window size, extras):
         a torch.tensor(..., device=) per iteration is a blocking pageable copy (~0.2 ms behind a busy queue)."""
-        cache = self.__dict__.setdefault("_reg_weight_cache", {})
+        cache = self._reg_weight_cache
         if (n_window, n_random) not in cache:
             cache[(n_window, n_random)] = torch.tensor([1e-3] * n_window + [1e-4] * n_random, dtype=torch.float32, device=self.device)
         return cache[(n_window, n_random)]
@@ -392,7 +421,9 @@ class BackEnd:
         gaussian_split = False
         it = 0
         while it < iters:
-            run = self._plain_run_length(it, iters, prune)
+            run = 0
+            if not prune and self._graphs_enabled():
+                run = plain_run(it, iters, lambda k: mapping_rule(self, self.iteration_count + (k - it) + 1) is not None)
             if run >= self.graph_min_run and self._graph_ok(viewpoint_stack):
                 done = self._map_static_graph_run(current_window, viewpoint_stack, random_viewpoint_stack, run, last=(it + run == iters))
                 if done:
@@ -433,7 +464,6 @@ class BackEnd:
         if torch.is_tensor(loss_mapping) and loss_mapping.requires_grad:
             loss_mapping.backward()
         shard.reduce_gradients(self.gaussians.optimizer)
-        gaussian_split = False
         with torch.no_grad():
             if prune or last:                      # (every iteration overwrites the previous one's rows: only the last ones are ever read)
                 self._publish_visibility(current_window, touched_rows)
@@ -444,14 +474,7 @@ class BackEnd:
                 return False
             for pkg in pkgs:
                 self._view_stats(pkg)
-            update_gaussian = self.iteration_count % self.gaussian_update_every == self.gaussian_update_offset
-            if update_gaussian:
-                shard.reduce_statistics(self.gaussians)
-                self.gaussians.densify_and_prune(self.opt_params.densify_grad_threshold, self.gaussian_th, self.gaussian_extent, self.size_threshold)
-                gaussian_split = True
-            if (self.iteration_count % self.gaussian_reset) == 0 and not update_gaussian:
-                self._reset_opacity_of_unseen(pkgs)
-                gaussian_split = True
+            gaussian_split = self._maintain(self.iteration_count, pkgs)
             self.gaussians.optimizer.step()                 # rebuilt parameters have no gradient yet and are skipped, like in the reference
             self.gaussians.optimizer.zero_grad(set_to_none=True)
             self.gaussians.update_learning_rate(self.iteration_count)
@@ -464,21 +487,9 @@ class BackEnd:
     graph_warmup = 2            # iterations of a run executed directly before the capture (the first may still go view by view, gsr_forward_views)
     dynamic_graph_warmup = 1    # the same for a run of the dynamic call (slam/dynamic_graph.py): its views have capacity estimates from the calls before
 
-    def _plain_run_length(self, it, iters, prune):
-        """How many iterations from `it` on neither densify nor reset opacities (those replace the model's tensors and run eagerly)."""
-        if prune or not self._graphs_enabled():
-            return 0
-        n = 0
-        while it + n < iters:
-            count = self.iteration_count + n + 1
-            if count % self.gaussian_update_every == self.gaussian_update_offset or count % self.gaussian_reset == 0:
-                break
-            n += 1
-        return n
-
     def _graphs_enabled(self):
         cfg = self.config["Training"].get("mapping_graph", True)
-        return bool(cfg) and not self.shard.active and not self.loss_values and str(self.device).startswith("cuda") and not getattr(self, "_graph_broken", False)
+        return bool(cfg) and not self.shard.active and not self.loss_values and str(self.device).startswith("cuda") and "graph" not in self._broken_graphs
 
     def _graph_ok(self, viewpoint_stack):
         from .camera import Camera
@@ -489,28 +500,27 @@ class BackEnd:
 
     def graph_streams(self, dev):
         """(warm-up stream, capture stream) of the mapping graphs, created once per device."""
-        cache = self.__dict__.setdefault("_graph_streams", {})
+        cache = self._graph_streams
         if dev not in cache:
             cache[dev] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
         return cache[dev]
 
     def unit_gradient(self, dev):
         """A scalar 1 on `dev`: the gradient the graph iterations hand every loss term (torch.autograd.backward with several roots)."""
-        cache = self.__dict__.setdefault("_unit_gradients", {})
+        cache = self._unit_gradients
         if dev not in cache:
             cache[dev] = torch.ones((), dtype=torch.float32, device=dev)
         return cache[dev]
 
     def graph_pool(self, dev):
-        cache = self.__dict__.setdefault("_graph_pools", {})
+        cache = self._graph_pools
         if dev not in cache:
             cache[dev] = torch.cuda.graph_pool_handle()
         return cache[dev]
 
     @property
     def keyframe_operands(self):
-        if getattr(self, "_kf_operands", None) is None:
-            from .keyframe_slots import KeyframeOperands
+        if self._kf_operands is None:
             self._kf_operands = KeyframeOperands()
         return self._kf_operands
 
@@ -652,7 +662,6 @@ class BackEnd:
                 self._delta_cache = None
             # (the Gaussians only step after the network's warm-up, :765-770: before that their gradients are dropped unreduced)
             shard.reduce_gradients(g.optimizer if i > warm else None, net_params)
-            gaussian_split = False
             with torch.no_grad():
                 if prune or i == iters - 1:
                     self._publish_visibility(current_window, touched_rows, n_views=len(views))
@@ -665,14 +674,7 @@ class BackEnd:
                     return False
                 for pkg in pkgs:
                     self._view_stats(pkg)
-                update_gaussian = (self.iteration_count % self.gaussian_update_every == self.gaussian_update_offset) and i > warm
-                if update_gaussian:
-                    shard.reduce_statistics(g)
-                    g.densify_and_prune(self.opt_params.densify_grad_threshold, self.gaussian_th, self.gaussian_extent, self.size_threshold)
-                    gaussian_split = True
-                if (self.iteration_count % self.gaussian_reset) == 0 and not update_gaussian and i > warm:
-                    self._reset_opacity_of_unseen(pkgs)
-                    gaussian_split = True
+                gaussian_split = self._maintain(self.iteration_count, pkgs, enabled=i > warm)
                 self._pose_updates(viewpoint_stack, current_window, positions=[window_position.get(v.uid) for v in viewpoint_stack])
                 self._clear_camera_grads(extra)
                 if use_net:
@@ -717,21 +719,11 @@ class BackEnd:
                 continue
             dx1, ds1, dr1 = deltas
             dx2, ds2, dr2 = self._deltas(other)
-            # constants of the keyframe pair: the flow on the moving pixels and their mask in the renderer's [C,H,W] layout (:486-488,
-            # :503-505 mask both sides of the difference by ~motion_mask; with a 0 / 1 mask: the masked target minus the masked rendering)
-            hit = self._flow_targets.get((viewpoint.uid, closest))
-            if hit is None:
-                while len(self._flow_targets) >= 4 * max(1, int(self.config["Training"].get("window_size", 8))):   # ~7 MB per pair at 640x480: keep
-                    self._flow_targets.pop(next(iter(self._flow_targets)))                                            # the window's, drop the oldest
-                def target(flow, mask):
-                    m = (~mask).to(torch.float32)[None]
-                    return (flow.permute(2, 0, 1) * m).contiguous(), m
-                hit = self._flow_targets[(viewpoint.uid, closest)] = \
-                    target(self.dataset.gt_flow(viewpoint.uid, closest)[0], viewpoint.motion_mask) + \
-                    target(self.dataset.gt_flow(closest, viewpoint.uid)[0], other.motion_mask)      # this keyframe -> the earlier one, and back
+            # constants of the keyframe pair: the flow on the moving pixels and their mask in the renderer's [C,H,W] layout, from the store
+            # the fixed layout reads too (this keyframe -> the earlier one, and back)
             requests.append((viewpoint, other, dx1, dx2, dr1, ds1))
             requests.append((other, viewpoint, dx2, dx1, dr2, ds2))
-            pairs.append(hit)
+            pairs.append(FlowTargets.pair_operands(self.flow_targets.get(self.dataset, viewpoint, other)))
         if not requests:
             return 0.0
         rendered = render_flow_views(self.gaussians, requests)

@@ -23,7 +23,8 @@ recorded once and replayed:
     rows by position (ControlNodes.begin_iteration_indexed / regularisers_indexed). Same terms, summed in another order.
 
 ``iteration()`` is ONE code path: executed directly -- every iteration when ``Training.mapping_graph`` is off, the warm-up iterations of a
-run, the iterations that densify or reset opacities (those replace the model's tensors: they end a run) -- or captured once and replayed.
+run, the iterations that densify or reset opacities (those replace the model's tensors: they end a run; WHICH they are is
+slam/schedule.mapping_rule's, how long the run before them its plain_run, WHAT they do BackEnd._maintain) -- or captured once and replayed.
 Direct and replayed iterations are bit-identical (tests/test_hip_slam.py). The call's two halves (:350-355: the loss weights double on the
 moving pixels in the first half; :337-338,:765-770: the Gaussians only step in the second) are different graphs: a run never crosses the
 boundary. Warm-up, capture, replays and undo are slam/graph_run.py's: a replayed forward pass that outgrows its binning buffer is detected
@@ -40,7 +41,8 @@ from . import graph_run, keyframe_slots
 from .camera import Camera
 from .deform_model import draw_loss_times, time_key
 from .mapping_graph import N_INDEX_WORDS
-from .schedule import Schedule, adam_rows, camera_gradients, catch_up, densification_statistics, gaussian_state, network_state, window_state, xyz_lr_rule
+from .schedule import (Schedule, adam_rows, camera_gradients, catch_up, densification_statistics, gaussian_state, init_rule, mapping_rule, network_state,
+                       plain_run, window_state, xyz_lr_rule)
 
 # Head room of the binning buffers a captured iteration lays out (include/gs_rasterizer.h): while the node network trains alone (first half
 # of a call) the moving object's Gaussians can swell and pile up for a few iterations -- measured: instance counts +10 %, the longest tile
@@ -53,8 +55,6 @@ CAPTURE_FLOOR_INSTANCES = int(os.environ.get("GSR_DYN_CAP_FLOOR", "131072"))
 CAPTURE_OPTIONS = {"cap_margin_permille": CAPTURE_MARGIN_PERMILLE, "cap_tile_margin_permille": CAPTURE_TILE_MARGIN_PERMILLE,
                    "cap_floor": CAPTURE_FLOOR_INSTANCES}
 FLOW_CLIPS = os.environ.get("GSR_FLOW_CLIPS", "1") != "0"      # render the flow images only where the flow loss reads them (gsr_view.flow_clip)
-FLOW_TARGET_BUDGET_FRACTION = 0.03  # ... and at most this share of the device memory free when the first target is formed
-FLOW_TARGET_CACHE_MAX = 512       # keyframe pairs whose flow targets are kept (~7 MB each at 640x480); dropped ones are formed again on demand
 WINDOW_SAMPLES, EXTRA_SAMPLES = (4, 8), (2, 8)        # (ARAP, elastic) time samples per window view / per random keyframe (:517-519,:646-648)
 
 
@@ -76,6 +76,19 @@ def eligible(be, views, candidates):
     if g.deform.deform.node_num < 3 or g.dyn_rows().shape[0] == 0 or not getattr(g.optimizer, "_fused_acc", False):
         return False
     return all(isinstance(v, Camera) and v.depth is not None and v.motion_mask is not None for v in list(views) + list(candidates))
+
+
+def phase(i, iters, warm):
+    """Of iteration i of a map(iters) call: (the loss weights double on the moving pixels, :350-355; the Gaussians take part, :337-338,:765-770)"""
+    return (i < iters / 2, i > warm)
+
+
+def plain_rows(be, i, iters, warm):
+    """How many iterations from i on make one run: of i's phase and, while the Gaussians step -- iteration_count advances then only, i's
+    own count is iteration_count + 1 --, none that densifies or resets opacities. 0: iteration i is such a one."""
+    ph = phase(i, iters, warm)
+    count = be.iteration_count + (1 if ph[1] else 0)
+    return plain_run(i, iters, lambda k: phase(k, iters, warm) != ph or (ph[1] and mapping_rule(be, count + (k - i)) is not None))
 
 
 class _Run:
@@ -117,8 +130,7 @@ class DynamicMapping:
 
     # ---- per-call constants --------------------------------------------------------------------------------------------------------------
     def phase(self, i):
-        """(the loss weights double on the moving pixels, :350-355; the Gaussians take part, :337-338,:765-770)"""
-        return (i < self.iters / 2, i > self.warm)
+        return phase(i, self.iters, self.warm)
 
     def with_flow(self, dyn):
         return self.has_flow_data and self.flow_weights[dyn] > 0
@@ -131,48 +143,10 @@ class DynamicMapping:
         other = self.be.viewpoints[closest]
         return other if (v.motion_mask is not None and other.motion_mask is not None) else None
 
-    def flow6(self, v, other):
-        """The constants of a keyframe pair's flow terms as ONE [6, H, W] tensor: planes 0-1 the flow v -> other on v's moving pixels, 2 their
-        mask, 3 the mask of `other`, 4-5 the flow other -> v on other's moving pixels (:486-488,:503-505 mask both sides of the difference by
-        ~motion_mask; with a 0 / 1 mask: the masked target minus the masked rendering). The plane order is the one gsr_slot_gather moves as
-        (gt_image[3], gt_depth, w_rgb, w_depth). One entry per keyframe (its partner never changes), ~7 MB at 640x480, in a bounded store."""
-        cache = self.be.__dict__.setdefault("_flow_targets6", {})
-        hit = cache.get((v.uid, other.uid))
-        if hit is None:
-            ds = self.be.dataset
-            m1 = (~v.motion_mask).to(torch.float32)[None]
-            m2 = (~other.motion_mask).to(torch.float32)[None]
-            back = ds.gt_flow(v.uid, other.uid)[0].permute(2, 0, 1) * m1
-            fwd = ds.gt_flow(other.uid, v.uid)[0].permute(2, 0, 1) * m2
-            hit = torch.cat([back, m1, m2, fwd], 0).to(self.device, torch.float32).contiguous()
-            # bounded by bytes (a share of the memory free at the first use) as well as by count; oldest first; the tables of a running call
-            # hold what they point at
-            budget = self.be.__dict__.get("_flow_targets6_budget")
-            if budget is None:
-                budget = self.be.__dict__["_flow_targets6_budget"] = keyframe_slots.device_store_budget(self.device, FLOW_TARGET_BUDGET_FRACTION)
-            each = hit.numel() * hit.element_size()
-            while cache and (len(cache) >= FLOW_TARGET_CACHE_MAX or (len(cache) + 1) * each > budget):
-                cache.pop(next(iter(cache)))
-            cache[(v.uid, other.uid)] = hit
-        return hit
-
-    def flow_clip(self, v):
-        """The tile rectangle [x0, y0, x1, y1) (16-pixel tiles) around keyframe v's MOVING pixels -- all its flow loss reads of the flow image
-        rendered from v -- as an int32 [4] device tensor (gsr_view.flow_clip); one host read per keyframe, kept."""
-        cache = self.be.__dict__.setdefault("_flow_clips", {})
-        hit = cache.get(v.uid)
-        if hit is None:
-            moving = ~v.motion_mask
-            ys, xs = moving.any(dim=1).nonzero().flatten(), moving.any(dim=0).nonzero().flatten()
-            rect = [0, 0, 0, 0] if ys.numel() == 0 else [int(xs[0]) // 16, int(ys[0]) // 16, int(xs[-1]) // 16 + 1, int(ys[-1]) // 16 + 1]
-            while len(cache) >= 4 * FLOW_TARGET_CACHE_MAX:
-                cache.pop(next(iter(cache)))
-            hit = cache[v.uid] = torch.tensor(rect, dtype=torch.int32).to(self.device)
-        return hit
-
     def layout(self, with_flow):
         hit = self._layouts.get(with_flow)
         if hit is None:
+            store, ds = self.be.flow_targets, self.be.dataset          # (keyframe_slots.FlowTargets: the eager body reads the same tensors)
             partners = [self.partner_of(v) if with_flow else None for v in self.views]
             keys = sorted({time_key(v.time) for v in self.views} | {time_key(p.time) for p in partners if p is not None})
             index = {k: i for i, k in enumerate(keys)}
@@ -182,8 +156,8 @@ class DynamicMapping:
                 "partners": partners, "n_w": n_w, "epf": epf, "n_full": n_w + self.n_slots * epf,
                 "view_idx": [index[time_key(v.time)] for v in self.views] + [n_w + e * epf for e in range(self.n_slots)],
                 "partner_idx": [None if p is None else index[time_key(p.time)] for p in partners],
-                "flow6": [None if p is None else self.flow6(v, p) for v, p in zip(self.views, partners)],
-                "clips": [None if p is None else (self.flow_clip(v), self.flow_clip(p)) for v, p in zip(self.views, partners)],
+                "flow6": [None if p is None else store.get(ds, v, p) for v, p in zip(self.views, partners)],
+                "clips": [None if p is None else (store.clip(v), store.clip(p)) for v, p in zip(self.views, partners)],
                 "wtimes": torch.tensor(keys, dtype=torch.float32).to(self.device)}
         return hit
 
@@ -205,12 +179,12 @@ class DynamicMapping:
                             self._zero6 = torch.zeros((6, self.H, self.W), device=dev)
                         f6 = self._zero6
                     else:
-                        f6 = self.flow6(c, p)
+                        f6 = be.flow_targets.get(be.dataset, c, p)
                     partners.append(p)
                     flows.append(f6)
                     times.append([time_key(c.time), time_key(p.time)])
                     # (rows 2 c and 2 c + 1: the rectangles the two flow images of the pair are read in; the stand-in pair reads nothing)
-                    clip_rows += [self.flow_clip(c), self.flow_clip(p)] if p is not c else [torch.zeros(4, dtype=torch.int32, device=dev)] * 2
+                    clip_rows += [be.flow_targets.clip(c), be.flow_targets.clip(p)] if p is not c else [torch.zeros(4, dtype=torch.int32, device=dev)] * 2
                 else:
                     times.append([time_key(c.time)])
             up = keyframe_slots.upload_rows
@@ -330,7 +304,7 @@ class DynamicMapping:
                 a1, b1, a2, b2 = flow_readers[k]
                 requests += [(v, other, fan[a1["x"]], fan[b1["x"]], fan[a1["r"]], fan[a1["s"]]),      # this keyframe -> the earlier one,
                              (other, v, fan[a2["x"]], fan[b2["x"]], fan[a2["r"]], fan[a2["s"]])]      # and back
-                pairs.append((f6[0:2], f6[2:3], f6[4:6], f6[3:4]))
+                pairs.append(keyframe_slots.FlowTargets.pair_operands(f6))
             if requests:
                 with _region("gsr.flow_render"):
                     flows = render_flow_views(g, requests, clips=clips if FLOW_CLIPS else None)
@@ -345,21 +319,12 @@ class DynamicMapping:
         torch.autograd.backward(terms, [be.unit_gradient(dev)] * len(terms))
         with _region("gsr.end_iteration"):
             nodes.end_iteration()
-        split = False
         with torch.no_grad(), _region("gsr.updates"):
             if special is not None and special.get("last"):           # (before a densification changes the row count, like the eager loop)
                 be._publish_visibility(self.current_window, {k: rendered[k]["n_touched"] for k in range(nv)}, n_views=nv)
             for pkg in rendered:
                 be._view_stats(pkg)
-            if special is not None and r.stepping:
-                count = be.iteration_count
-                update_gaussian = count % be.gaussian_update_every == be.gaussian_update_offset
-                if update_gaussian:
-                    g.densify_and_prune(be.opt_params.densify_grad_threshold, be.gaussian_th, be.gaussian_extent, be.size_threshold)
-                    split = True
-                if count % be.gaussian_reset == 0 and not update_gaussian:
-                    be._reset_opacity_of_unseen(rendered)
-                    split = True
+            split = be._maintain(be.iteration_count, rendered, enabled=special is not None and r.stepping)
             be._pose_updates(self.views, self.current_window, positions=self.positions)
             be._clear_camera_grads(self.slots + self.partner_slots)
             g.deform.optimizer.step()
@@ -402,7 +367,7 @@ class DynamicMapping:
                 for j, m in ((2 * k, m1), (2 * k + 1, m2)):
                     same = same and torch.equal(flows[j]["render"][:2] * m, ref[j]["render"][:2] * m)
             drawn = (sum(int((f["radii"] > 0).sum()) for f in flows), sum(int((f["radii"] > 0).sum()) for f in ref))
-        be.__dict__.setdefault("flow_clip_checks", []).append({"masked_images_equal": same, "gradient_rel_diff": rel, "gaussians_drawn": drawn})
+        be.flow_clip_checks.append({"masked_images_equal": same, "gradient_rel_diff": rel, "gaussians_drawn": drawn})
 
     # ---- executing a run ---------------------------------------------------------------------------------------------------------------
     def direct(self, n):
@@ -423,7 +388,7 @@ class DynamicMapping:
         self.g.deform.optimizer.zero_grad(set_to_none=True)
         self.be._clear_camera_grads(self.views + self.slots + self.partner_slots)
 
-    def plain_run(self, rows):
+    def run_rows(self, rows):
         """A run of plain iterations: replays of one captured iteration when the run is long enough and graphs are on; directly executed,
         what the graph did not do."""
         be, r = self.be, self.run
@@ -444,13 +409,8 @@ class DynamicMapping:
         while i < self.iters:
             ph = self.phase(i)
             stepping = ph[1]
-
-            def special_at(k, count):          # does iteration k (whose iteration_count would be `count`) densify, reset, or lack Adam moments?
-                return stepping and (count % be.gaussian_update_every == be.gaussian_update_offset or count % be.gaussian_reset == 0)
-
-            count = be.iteration_count + (1 if stepping else 0)
-            needs_state = stepping and g.optimizer.scheduled_segments() is None
-            if special_at(i, count) or needs_state:
+            rows = plain_rows(be, i, self.iters, self.warm)
+            if rows == 0 or (stepping and g.optimizer.scheduled_segments() is None):          # special, or no Adam moments yet
                 if stepping:
                     be.iteration_count += 1                                      # :337-338
                 be.last_sent += 1
@@ -459,11 +419,8 @@ class DynamicMapping:
                 self.stats["special"] += 1
                 i += 1
                 continue
-            rows = 0
-            while i + rows < self.iters and self.phase(i + rows) == ph and not special_at(i + rows, count + rows):
-                rows += 1
             self.make_run(i, rows, ph)
-            self.plain_run(rows)
+            self.run_rows(rows)
             split = False
             i += rows
             if i == self.iters:
@@ -507,8 +464,7 @@ class NetworkInit:
         nodes.end_iteration()
         with torch.no_grad():
             be._view_stats(pkg)
-            if densify:                                                            # :209-215 (iteration 0 with the shipped schedule)
-                g.densify_and_prune(be.opt_params.densify_grad_threshold, be.init_gaussian_th, be.init_gaussian_extent, None)
+            be._maintain_init(densify)                                            # :209-215 (iteration 0 with the shipped schedule)
             g.deform.optimizer.step()
             g.deform.optimizer.zero_grad(set_to_none=True)
             g.optimizer.zero_grad(set_to_none=True)
@@ -529,14 +485,12 @@ class NetworkInit:
         be = self.be
         i = 0
         while i < iterations:
-            if i % be.init_gaussian_update == 0:
+            rows = plain_run(i, iterations, lambda k: init_rule(be, k)[0])
+            if rows == 0:
                 self.iteration(densify=True)
                 self.stats["direct"] += 1
                 i += 1
                 continue
-            rows = 0
-            while i + rows < iterations and (i + rows) % be.init_gaussian_update != 0:
-                rows += 1
             done = 0
             if be._graphs_enabled() and rows >= be.graph_min_run and not graph_run.broken(be, "network_init_graph"):
                 done = graph_run.replay_run(be, self, rows, min(be.dynamic_graph_warmup, rows), kind="network_init_graph", options=CAPTURE_OPTIONS)

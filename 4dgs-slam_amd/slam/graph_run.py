@@ -12,9 +12,10 @@ A runner provides:
   * ``state_tensors()`` -- every tensor a replay may write (the snapshot);
   * ``discard()`` -- after an undo: camera matrices from the restored poses, no gradient left over from the capture.
 
-Statistics per kind of run in ``backend.<kind>_stats`` (runs, replays, direct, redone, failed, last_error, capture_ms, overflow_causes); a
-failed capture sets ``backend._<kind>_broken`` and switches that kind's graphs off (a failed static capture also switches off every other
-kind: BackEnd._graphs_enabled reads ``_graph_broken``)."""
+What a run needs of the back-end is declared in BackEnd.__init__: the two streams, the pool and the newest graph; the statistics per kind
+of run, ``backend.<kind>_stats`` (runs, replays, direct, redone, failed, last_error, capture_ms, overflow_causes; empty until a run of
+that kind is first touched); and ``backend._broken_graphs``, the kinds whose capture failed -- that kind's graphs are off from then on (a
+failed static capture, kind "graph", also switches off every other kind: BackEnd._graphs_enabled)."""
 import contextlib
 import gc
 import time
@@ -25,11 +26,14 @@ from diff_gaussian_rasterization import _C
 
 
 def stats(backend, kind):
-    return backend.__dict__.setdefault(f"{kind}_stats", {"runs": 0, "replays": 0, "direct": 0, "redone": 0, "failed": 0})
+    st = getattr(backend, f"{kind}_stats")
+    if not st:
+        st.update(runs=0, replays=0, direct=0, redone=0, failed=0)
+    return st
 
 
 def broken(backend, kind):
-    return getattr(backend, f"_{kind}_broken", False)
+    return kind in backend._broken_graphs
 
 
 def note_failure(backend, kind, error):
@@ -111,7 +115,7 @@ def replay_run(backend, runner, rows, warm, *, kind, options):
         graph = capture(backend, runner, options)
         st["capture_ms"] = st.get("capture_ms", 0.0) + (time.perf_counter() - t0) * 1e3
     except Exception as e:        # a capture that fails leaves the warm-up valid: the caller finishes the run, this kind stops capturing
-        setattr(backend, f"_{kind}_broken", True)
+        backend._broken_graphs.add(kind)
         torch.cuda.synchronize(dev)
         undo()
         note_failure(backend, kind, e)

@@ -85,6 +85,60 @@ class KeyframeOperands:
         return self._bytes
 
 
+class FlowTargets:
+    """Per keyframe pair (a keyframe and the closest earlier one: the partner never changes) the constants of its two flow terms, per
+    keyframe the tile rectangle of its moving pixels: ONE store for both bodies of BackEnd.map (the fixed layout's tables point at the
+    tensors, the eager body reads slices of them). Bounded by count and by bytes, oldest first; what is dropped is formed again on demand
+    from the dataset's cached flows; a running call holds what its tables point at."""
+
+    BUDGET_FRACTION = 0.03      # at most this share of the device memory free when the first target is formed
+    MAX_PAIRS = 512             # ~7 MB each at 640x480
+
+    def __init__(self):
+        self.targets, self.clips, self._budget = {}, {}, None          # (uid, partner's uid) -> [6, H, W]; uid -> int32 [4]
+
+    def clear(self):
+        self.targets, self.clips = {}, {}
+
+    def get(self, dataset, v, other):
+        """ONE [6, H, W] tensor: planes 0-1 the flow v -> other on v's moving pixels, 2 their mask, 3 the mask of `other`, 4-5 the flow
+        other -> v on other's moving pixels (utils/slam_backend.py:486-488,:503-505 mask both sides of the difference by ~motion_mask; with a
+        0 / 1 mask: the masked target minus the masked rendering). The plane order is the one gsr_slot_gather moves as (gt_image[3],
+        gt_depth, w_rgb, w_depth); the operands of slam_losses.masked_l1 are the slices ``pair_operands`` names."""
+        hit = self.targets.get((v.uid, other.uid))
+        if hit is None:
+            m1 = (~v.motion_mask).to(torch.float32)[None]
+            m2 = (~other.motion_mask).to(torch.float32)[None]
+            back = dataset.gt_flow(v.uid, other.uid)[0].permute(2, 0, 1) * m1
+            fwd = dataset.gt_flow(other.uid, v.uid)[0].permute(2, 0, 1) * m2
+            hit = torch.cat([back, m1, m2, fwd], 0).to(torch.float32).contiguous()
+            if self._budget is None:
+                self._budget = device_store_budget(hit.device, self.BUDGET_FRACTION)
+            each = hit.numel() * hit.element_size()
+            while self.targets and (len(self.targets) >= self.MAX_PAIRS or (len(self.targets) + 1) * each > self._budget):
+                self.targets.pop(next(iter(self.targets)))
+            self.targets[(v.uid, other.uid)] = hit
+        return hit
+
+    @staticmethod
+    def pair_operands(f6):
+        """(target, mask) of "this keyframe -> the earlier one", then of the way back."""
+        return f6[0:2], f6[2:3], f6[4:6], f6[3:4]
+
+    def clip(self, v):
+        """The tile rectangle [x0, y0, x1, y1) (16-pixel tiles) around keyframe v's MOVING pixels -- all its flow loss reads of the flow image
+        rendered from v -- as an int32 [4] device tensor (gsr_view.flow_clip); one host read per keyframe, kept."""
+        hit = self.clips.get(v.uid)
+        if hit is None:
+            moving = ~v.motion_mask
+            ys, xs = moving.any(dim=1).nonzero().flatten(), moving.any(dim=0).nonzero().flatten()
+            rect = [0, 0, 0, 0] if ys.numel() == 0 else [int(xs[0]) // 16, int(ys[0]) // 16, int(xs[-1]) // 16 + 1, int(ys[-1]) // 16 + 1]
+            while len(self.clips) >= 4 * self.MAX_PAIRS:
+                self.clips.pop(next(iter(self.clips)))
+            hit = self.clips[v.uid] = torch.tensor(rect, dtype=torch.int32).to(moving.device)
+        return hit
+
+
 def blank_camera(proto, uid, device):
     """A camera with the intrinsics of `proto` and nothing else: pose, matrices and exposure are written on the device."""
     return Camera(uid, None, None, torch.eye(4), proto.projection_matrix, proto.fx, proto.fy, proto.cx, proto.cy, proto.FoVx, proto.FoVy,

@@ -13,8 +13,9 @@ rasterizer's lazy mode, cameras in persistent device buffers, a camera step with
   * everything that depends on the iteration NUMBER -- those indices, Adam's bias corrections, the position learning rate (GM:492-505) -- is a
     row of a device-side schedule written once per run; ``gsr_schedule_advance`` copies row ``counter`` into the "current" block the other
     kernels read and bumps the counter (include/slam_map.h), ``gsr_adam_step_scheduled`` reads its coefficients there (include/slam_losses.h);
-  * the iterations that densify or reset opacities (every ``gaussian_update_every`` / ``gaussian_reset`` iterations) replace the model's
-    tensors: they run eagerly (BackEnd._map_static_iteration) and end a run; the next run captures again.
+  * the iterations that densify or reset opacities (every ``gaussian_update_every`` / ``gaussian_reset`` iterations: slam/schedule.py's
+    mapping_rule, which also measures the runs) replace the model's tensors: they run eagerly (BackEnd._map_static_iteration) and end a
+    run; the next run captures again.
 
 The host draws the random keyframes for the whole run up front -- the same ``torch.randperm`` calls in the same order as the eager loop -- and
 ``iteration()`` is ONE code path: executed directly for the warm-up iterations of a run, captured once, then replayed. Results are

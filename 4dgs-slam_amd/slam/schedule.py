@@ -1,11 +1,39 @@
 """The device-side schedule of a run of graph-replayed mapping iterations (slam/mapping_graph.py, slam/dynamic_graph.py): what depends on
 the iteration NUMBER is a row ``[index words | Adam coefficients | float samples]`` (any block may be empty) of a table written once per run;
 ``gsr_schedule_advance`` (include/slam_map.h) copies row ``counter`` into the ``current`` block the iteration reads and bumps the counter.
-The runners draw and hand the results over. Also here: what the host owes a run afterwards, and the pieces of the runners' snapshots."""
+The runners draw and hand the results over. Also here: what the host owes a run afterwards, and the pieces of the runners' snapshots.
+
+And the HOST rule of what an iteration number does -- densify, reset opacities, or nothing ("plain") -- with the one splitter that measures a
+run of plain iterations by it. Those iterations replace the model's tensors, so they run eagerly and end a run: the eager bodies
+(slam/backend.py) and the runners' splitters (backend.py, slam/dynamic_graph.py) all ask mapping_rule / init_rule / plain_run and nobody
+else writes the expressions out."""
 import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _C
+
+
+def mapping_rule(backend, count):
+    """What the mapping iteration whose iteration_count is `count` does to the model before its step (utils/slam_backend.py:722-745,
+    :1185-1206): "densify", "reset" (the opacities of the Gaussians no view saw) or None; where both hold it densifies. The three periods
+    are read from the back-end when asked."""
+    if count % backend.gaussian_update_every == backend.gaussian_update_offset:
+        return "densify"
+    return "reset" if count % backend.gaussian_reset == 0 else None
+
+
+def init_rule(backend, m, count=None):
+    """(densify, reset opacities) of iteration `m` of an initialisation call (utils/slam_backend.py:217,:277-287); `count`: the
+    iteration_count of that iteration, None for a loop that never resets (initialize_network). Both can hold: densify runs first."""
+    return m % backend.init_gaussian_update == 0, count is not None and (count == backend.init_gaussian_reset or count == backend.opt_params.densify_from_iter)
+
+
+def plain_run(start, stop, is_special):
+    """The number of consecutive k in [start, stop) from `start` on for which is_special(k) is false."""
+    n = 0
+    while start + n < stop and not is_special(start + n):
+        n += 1
+    return n
 
 
 def xyz_lr_rule(gaussians, count0):
