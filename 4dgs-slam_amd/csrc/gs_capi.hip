@@ -4179,13 +4179,16 @@ size_t gsr_feat_pose_workspace_size(int slots_a, int hypotheses)
     return feat_pose_layout(slots_a, hypotheses, nullptr, l) ? l.bytes : 0;
 }
 
-int gsr_feat_pose(int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b, const int* keypoints_b,
-                  const float* depth_b, const int* matches, const float* K_a, const float* K_b, unsigned int seed, int hypotheses,
-                  float min_area, float tau_px, float tau_depth, int refine_iters, int min_matches, int min_inliers, float min_share,
-                  float max_translation, float max_rotation, float* T, int* stats, int* counts, void* workspace, size_t workspace_bytes,
-                  void* stream_)
+// gsr_feat_pose (PNP false) and gsr_feat_pose_pnp (PNP true: depth_b NULL, tau_depth 0): the same checks, workspace and three launches
+extern "C++" {
+template <bool PNP>
+static int feat_pose_run(const char* name, int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b,
+                         const int* keypoints_b, const float* depth_b, const int* matches, const float* K_a, const float* K_b, unsigned int seed,
+                         int hypotheses, float min_area, float tau_px, float tau_depth, int refine_iters, int min_matches, int min_inliers,
+                         float min_share, float max_translation, float max_rotation, float* T, int* stats, int* counts, void* workspace,
+                         size_t workspace_bytes, void* stream_)
 {
-    auto fail = [&](const std::string& what) { g_last_error = "gsr_feat_pose: " + what; return GSR_ERR_INVALID_ARGUMENT; };
+    auto fail = [&](const std::string& what) { g_last_error = std::string(name) + ": " + what; return GSR_ERR_INVALID_ARGUMENT; };
     FeatPoseWs l;
     if (width < 1 || height < 1 || (long long)width * height >= 0x80000000LL)
         return fail("width and height must be at least 1 and width * height below 2^31, got " + std::to_string(width) + " x " + std::to_string(height));
@@ -4194,27 +4197,54 @@ int gsr_feat_pose(int width, int height, int slots_a, const int* keypoints_a, co
     if (!feat_pose_layout(slots_a, hypotheses, workspace, l)) return fail("hypotheses must be in [1, 1024], got " + std::to_string(hypotheses));
     if (!(min_area > 0.f) || !std::isfinite(min_area)) return fail("min_area must be positive and finite");
     if (!(tau_px >= 0.f) || !std::isfinite(tau_px) || !(tau_depth >= 0.f) || !std::isfinite(tau_depth))
-        return fail("tau_px and tau_depth must be finite and not negative");
+        return fail(PNP ? "tau_px must be finite and not negative" : "tau_px and tau_depth must be finite and not negative");
     if (refine_iters < 0 || refine_iters > FEAT_MAX_REFINE) return fail("refine_iters must be in [0, 16], got " + std::to_string(refine_iters));
     if (min_matches < 0) return fail("min_matches must not be negative, got " + std::to_string(min_matches));
     if (min_inliers < 3) return fail("min_inliers must be at least 3, got " + std::to_string(min_inliers));
     if (!(min_share >= 0.f && min_share <= 1.f)) return fail("min_share must be in [0, 1]");
     if (!(max_translation >= 0.f) || !std::isfinite(max_translation) || !(max_rotation >= 0.f) || !std::isfinite(max_rotation))
         return fail("max_translation and max_rotation must be finite and not negative");
-    if (!keypoints_a || !depth_a || !keypoints_b || !depth_b || !matches || !K_a || !K_b || !T || !stats || !workspace)
-        return fail("keypoints, depths, matches, K_a, K_b, T, stats and workspace must not be NULL");
-    if (!workspace_fits("gsr_feat_pose", "gsr_feat_pose_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    if (!keypoints_a || !depth_a || !keypoints_b || (!PNP && !depth_b) || !matches || !K_a || !K_b || !T || !stats || !workspace)
+        return fail(PNP ? "keypoints, depth_a, matches, K_a, K_b, T, stats and workspace must not be NULL"
+                        : "keypoints, depths, matches, K_a, K_b, T, stats and workspace must not be NULL");
+    const std::string size_name = std::string(name) + "_workspace_size";
+    if (!workspace_fits(name, size_name.c_str(), workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
     hipStream_t stream = (hipStream_t)stream_;
-    hipLaunchKernelGGL(feat_pairs_kernel, dim3(1), dim3(FEAT_BLOCK), 0, stream, width, height, slots_a, keypoints_a, depth_a, slots_b, keypoints_b,
-                       depth_b, matches, K_a, K_b, l, stats);
+    hipLaunchKernelGGL((feat_pairs_kernel<PNP>), dim3(1), dim3(FEAT_BLOCK), 0, stream, width, height, slots_a, keypoints_a, depth_a, slots_b,
+                       keypoints_b, depth_b, matches, K_a, K_b, l, stats);
     GSR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(feat_hypotheses_kernel, dim3((unsigned)((hypotheses + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream, hypotheses,
-                       seed, min_area, tau_px, tau_depth, K_b, l, counts);
+    hipLaunchKernelGGL((feat_hypotheses_kernel<PNP>), dim3((unsigned)((hypotheses + FEAT_WAVES - 1) / FEAT_WAVES)), dim3(FEAT_BLOCK), 0, stream,
+                       hypotheses, seed, min_area, tau_px, tau_depth, K_b, l, counts);
     GSR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(feat_finish_kernel, dim3(1), dim3(FEAT_BLOCK), 0, stream, hypotheses, seed, min_area, tau_px, tau_depth, refine_iters,
+    hipLaunchKernelGGL((feat_finish_kernel<PNP>), dim3(1), dim3(FEAT_BLOCK), 0, stream, hypotheses, seed, min_area, tau_px, tau_depth, refine_iters,
                        min_matches, min_inliers, min_share, max_translation, max_rotation, K_b, l, T, stats);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
+}
+}  // extern "C++"
+
+int gsr_feat_pose(int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b, const int* keypoints_b,
+                  const float* depth_b, const int* matches, const float* K_a, const float* K_b, unsigned int seed, int hypotheses,
+                  float min_area, float tau_px, float tau_depth, int refine_iters, int min_matches, int min_inliers, float min_share,
+                  float max_translation, float max_rotation, float* T, int* stats, int* counts, void* workspace, size_t workspace_bytes,
+                  void* stream)
+{
+    return feat_pose_run<false>("gsr_feat_pose", width, height, slots_a, keypoints_a, depth_a, slots_b, keypoints_b, depth_b, matches, K_a, K_b, seed,
+                                hypotheses, min_area, tau_px, tau_depth, refine_iters, min_matches, min_inliers, min_share, max_translation,
+                                max_rotation, T, stats, counts, workspace, workspace_bytes, stream);
+}
+
+// the layout of gsr_feat_pose; PB holds the bearings of B's keypoints
+size_t gsr_feat_pose_pnp_workspace_size(int slots_a, int hypotheses) { return gsr_feat_pose_workspace_size(slots_a, hypotheses); }
+
+int gsr_feat_pose_pnp(int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b, const int* keypoints_b,
+                      const int* matches, const float* K_a, const float* K_b, unsigned int seed, int hypotheses, float min_area, float tau_px,
+                      int refine_iters, int min_matches, int min_inliers, float min_share, float max_translation, float max_rotation, float* T,
+                      int* stats, int* counts, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return feat_pose_run<true>("gsr_feat_pose_pnp", width, height, slots_a, keypoints_a, depth_a, slots_b, keypoints_b, nullptr, matches, K_a, K_b,
+                               seed, hypotheses, min_area, tau_px, 0.f, refine_iters, min_matches, min_inliers, min_share, max_translation,
+                               max_rotation, T, stats, counts, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

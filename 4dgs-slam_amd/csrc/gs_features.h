@@ -1,7 +1,8 @@
 // gs_features.h -- the kernels of include/feature_matching.h: FAST-9 corners with rotated BRIEF descriptors in a fixed slot layout
 // (gsr_feat_extract), the mutual ratio-tested Hamming match of two such sets (gsr_feat_match) and three-point RANSAC with a point-to-point
-// refinement and a gate on the back-projected matches (gsr_feat_pose). gfx950 / wave64; every LDS size is a compile-time constant; no
-// atomics anywhere: every result is formed thread -> wave -> block in one fixed order.
+// refinement and a gate on the back-projected matches (gsr_feat_pose), or the same from the 3D points of A and the pixels of B alone
+// (gsr_feat_pose_pnp). gfx950 / wave64; every LDS size is a compile-time constant; no atomics anywhere: every result is formed thread ->
+// wave -> block in one fixed order.
 //
 // Extract, per call:  feat_score_kernel        a 16 x 16 tile per block with a halo of 3 of luma bytes in LDS: luma, the corner score c(p)
 //                                              and the 5 x 5 sum of every pixel
@@ -14,6 +15,9 @@
 // Pose, per call:     feat_pairs_kernel        (one block) the list of pairs with two valid depths, compacted in ascending a by ballots
 //                     feat_hypotheses_kernel   one wave per hypothesis: the pose of three pairs, the inliers by ballot + popcount
 //                     feat_finish_kernel       (one block) winner, Gauss-Newton in double, recount, gate
+//                     each of the three is a template over PNP: <false> is gsr_feat_pose; <true>, gsr_feat_pose_pnp, reads no depth of B,
+//                     keeps B's bearings where <false> keeps B's points, finds the three ranges along them by Newton in double
+//                     (feat_ranges) before the same triads, tests the reprojection alone and refines the reprojection error
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +38,7 @@ constexpr int FEAT_MAX_HYPOTHESES = 1024;
 constexpr int FEAT_MAX_REFINE = 16;
 constexpr int FEAT_SUMS = 27;                  // 21 of H (upper triangle, row-major) and 6 of g
 constexpr int FEAT_STATS = 8;
+constexpr int FEAT_NEWTON = 8;                 // the steps of feat_ranges
 
 __device__ __forceinline__ int feat_block_sum(int v, int* part)
 {
@@ -308,18 +313,20 @@ __device__ __forceinline__ bool feat_triad(const float* p1, const float* p2, con
     return true;
 }
 
-// R, t of hypothesis h; false for a void one
-__device__ __forceinline__ bool feat_hypothesis(unsigned seed, int h, int M, const float* __restrict__ PA, const float* __restrict__ PB,
-                                                float min_area, FeatRt& rt)
+// the three indices of hypothesis h; false with M < 3 or two equal indices
+__device__ __forceinline__ bool feat_draw(unsigned seed, int h, int M, unsigned* i)
 {
-#pragma clang fp contract(off)
     if (M < 3) return false;
     const unsigned base = seed * 0x9E3779B9u + 3u * (unsigned)h;
-    const unsigned i0 = feat_lowbias32(base) % (unsigned)M, i1 = feat_lowbias32(base + 1u) % (unsigned)M,
-                   i2 = feat_lowbias32(base + 2u) % (unsigned)M;
-    if (i0 == i1 || i0 == i2 || i1 == i2) return false;
-    const float *a1 = PA + 3 * (size_t)i0, *a2 = PA + 3 * (size_t)i1, *a3 = PA + 3 * (size_t)i2;
-    const float *b1 = PB + 3 * (size_t)i0, *b2 = PB + 3 * (size_t)i1, *b3 = PB + 3 * (size_t)i2;
+    i[0] = feat_lowbias32(base) % (unsigned)M, i[1] = feat_lowbias32(base + 1u) % (unsigned)M, i[2] = feat_lowbias32(base + 2u) % (unsigned)M;
+    return !(i[0] == i[1] || i[0] == i[2] || i[1] == i[2]);
+}
+
+// R, t that take the triple a to the triple b; false where either triad is void
+__device__ __forceinline__ bool feat_motion(const float* a1, const float* a2, const float* a3, const float* b1, const float* b2, const float* b3,
+                                            float min_area, FeatRt& rt)
+{
+#pragma clang fp contract(off)
     float ea[9], eb[9];
     const bool ok_a = feat_triad(a1, a2, a3, min_area, ea), ok_b = feat_triad(b1, b2, b3, min_area, eb);
     if (!ok_a || !ok_b) return false;
@@ -338,22 +345,108 @@ __device__ __forceinline__ bool feat_hypothesis(unsigned seed, int h, int M, con
     return true;
 }
 
-// the inlier test of the header; K = (fx, fy, cx, cy) of frame B; uv = (x_b, y_b); a NaN anywhere fails it
-__device__ __forceinline__ bool feat_inlier(const FeatRt& rt, const float* P, const float* Pb, const float* uv, const float* K, float tau_px,
-                                            float tau_depth)
+// the ranges of the header (gsr_feat_pose_pnp): the points pb[3 k + i] = (float)(l_k f_k) of B on the bearings u1, u2, u3 whose mutual
+// distances are those of p1, p2, p3; float64, every operation rounded by itself, in the order written here and in tests/pnp_reference.py.
+// false for a void hypothesis
+__device__ inline bool feat_ranges(const float* p1, const float* p2, const float* p3, const float* u1, const float* u2, const float* u3, float* pb)
+{
+#pragma clang fp contract(off)
+    const float* P[3] = {p1, p2, p3};
+    const float* U[3] = {u1, u2, u3};
+    double f[3][3], l[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double ux = (double)U[k][0], uy = (double)U[k][1], uz = (double)U[k][2];
+        const double n = sqrt(ux * ux + uy * uy + uz * uz);
+        f[k][0] = ux / n, f[k][1] = uy / n, f[k][2] = uz / n;
+        const double px = (double)P[k][0], py = (double)P[k][1], pz = (double)P[k][2];
+        l[k] = sqrt(px * px + py * py + pz * pz);
+    }
+    double c[3], d[3];                                                 // of the pairs (1, 2), (1, 3), (2, 3)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = k == 2 ? 1 : 0, j = k == 0 ? 1 : 2;
+        c[k] = f[i][0] * f[j][0] + f[i][1] * f[j][1] + f[i][2] * f[j][2];
+        const double dx = (double)P[i][0] - (double)P[j][0], dy = (double)P[i][1] - (double)P[j][1], dz = (double)P[i][2] - (double)P[j][2];
+        d[k] = dx * dx + dy * dy + dz * dz;
+    }
+    double l1 = l[0], l2 = l[1], l3 = l[2];
+    for (int it = 0; it < FEAT_NEWTON; ++it) {
+        const double F1 = l1 * l1 + l2 * l2 - 2.0 * l1 * l2 * c[0] - d[0];
+        const double F2 = l1 * l1 + l3 * l3 - 2.0 * l1 * l3 * c[1] - d[1];
+        const double F3 = l2 * l2 + l3 * l3 - 2.0 * l2 * l3 * c[2] - d[2];
+        const double ja = 2.0 * l1 - 2.0 * l2 * c[0], jb = 2.0 * l2 - 2.0 * l1 * c[0];      // the Jacobian [ja jb 0; jc 0 jd; 0 je jg]
+        const double jc = 2.0 * l1 - 2.0 * l3 * c[1], jd = 2.0 * l3 - 2.0 * l1 * c[1];
+        const double je = 2.0 * l2 - 2.0 * l3 * c[2], jg = 2.0 * l3 - 2.0 * l2 * c[2];
+        const double det = -ja * jd * je - jb * jc * jg;
+        if (det == 0.0 || !isfinite(det)) return false;
+        const double w = F2 * jg - jd * F3;
+        const double n1 = -F1 * jd * je - jb * w, n2 = ja * w - F1 * jc * jg, n3 = -ja * F2 * je - jb * jc * F3 + F1 * jc * je;
+        l1 = l1 - n1 / det, l2 = l2 - n2 / det, l3 = l3 - n3 / det;
+    }
+    const double F1 = l1 * l1 + l2 * l2 - 2.0 * l1 * l2 * c[0] - d[0];
+    const double F2 = l1 * l1 + l3 * l3 - 2.0 * l1 * l3 * c[1] - d[1];
+    const double F3 = l2 * l2 + l3 * l3 - 2.0 * l2 * l3 * c[2] - d[2];
+    if (!(isfinite(l1) && l1 > 0.0 && isfinite(l2) && l2 > 0.0 && isfinite(l3) && l3 > 0.0)) return false;
+    if (!(fabs(F1) <= 1e-9 * d[0] && fabs(F2) <= 1e-9 * d[1] && fabs(F3) <= 1e-9 * d[2])) return false;
+    l[0] = l1, l[1] = l2, l[2] = l3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pb[3 * k + i] = (float)(l[k] * f[k][i]);
+    return true;
+}
+
+// R, t of hypothesis h; false for a void one. PNP: PB holds the bearings of B, and the points of B's triple come from feat_ranges
+template <bool PNP>
+__device__ __forceinline__ bool feat_hypothesis(unsigned seed, int h, int M, const float* __restrict__ PA, const float* __restrict__ PB,
+                                                float min_area, FeatRt& rt)
+{
+    unsigned i[3];
+    if (!feat_draw(seed, h, M, i)) return false;
+    const float *a1 = PA + 3 * (size_t)i[0], *a2 = PA + 3 * (size_t)i[1], *a3 = PA + 3 * (size_t)i[2];
+    const float *b1 = PB + 3 * (size_t)i[0], *b2 = PB + 3 * (size_t)i[1], *b3 = PB + 3 * (size_t)i[2];
+    if constexpr (PNP) {
+        float pb[9];
+        return feat_ranges(a1, a2, a3, b1, b2, b3, pb) && feat_motion(a1, a2, a3, pb, pb + 3, pb + 6, min_area, rt);
+    } else {
+        return feat_motion(a1, a2, a3, b1, b2, b3, min_area, rt);
+    }
+}
+
+// Q = R P + t and the squared reprojection error e2 against uv = (x_b, y_b); K = (fx, fy, cx, cy) of frame B; false where Q_z > 0 fails
+__device__ __forceinline__ bool feat_project(const FeatRt& rt, const float* P, const float* uv, const float* K, float& Qz, float& e2)
 {
 #pragma clang fp contract(off)
     const float Qx = rt.R[0] * P[0] + rt.R[1] * P[1] + rt.R[2] * P[2] + rt.t[0];
     const float Qy = rt.R[3] * P[0] + rt.R[4] * P[1] + rt.R[5] * P[2] + rt.t[1];
-    const float Qz = rt.R[6] * P[0] + rt.R[7] * P[1] + rt.R[8] * P[2] + rt.t[2];
+    Qz = rt.R[6] * P[0] + rt.R[7] * P[1] + rt.R[8] * P[2] + rt.t[2];
     if (!(Qz > 0.f)) return false;
     const float ex = K[0] * (Qx / Qz) + K[2] - uv[0], ey = K[1] * (Qy / Qz) + K[3] - uv[1];
-    const float zb = Pb[2];
-    const float e2 = ex * ex + ey * ey, bar2 = tau_px * tau_px, gap = fabsf(Qz - zb), bar = tau_depth * zb;
-    return e2 <= bar2 && gap <= bar;
+    e2 = ex * ex + ey * ey;
+    return true;
 }
 
-// one block. stats[0..2] = valid keypoints of A, of B, M
+// the inlier test of the header for pair m; a NaN anywhere fails it. PNP: the reprojection alone, nothing of PB is read
+template <bool PNP>
+__device__ __forceinline__ bool feat_inlier(const FeatRt& rt, const FeatPoseWs& ws, int m, const float* K, float tau_px, float tau_depth)
+{
+#pragma clang fp contract(off)
+    float Qz, e2;
+    if (!feat_project(rt, ws.PA + 3 * (size_t)m, ws.UV + 2 * (size_t)m, K, Qz, e2)) return false;
+    const float bar2 = tau_px * tau_px;
+    if constexpr (PNP) {
+        return e2 <= bar2;
+    } else {
+        const float zb = ws.PB[3 * (size_t)m + 2];
+        const float gap = fabsf(Qz - zb), bar = tau_depth * zb;
+        return e2 <= bar2 && gap <= bar;
+    }
+}
+
+// one block. stats[0..2] = valid keypoints of A, of B, M. PNP: depth_b is never read (NULL), and PB holds the bearing ((x_b - cx_b) / fx_b,
+// (y_b - cy_b) / fy_b, 1) of B's keypoint
+template <bool PNP>
 __global__ void __launch_bounds__(FEAT_BLOCK) feat_pairs_kernel(int W, int H, int slots_a, const int* __restrict__ kp_a, const float* __restrict__ depth_a,
                                                                 int slots_b, const int* __restrict__ kp_b, const float* __restrict__ depth_b,
                                                                 const int* __restrict__ matches, const float* __restrict__ K_a,
@@ -372,11 +465,14 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_pairs_kernel(int W, int H, in
             if (b >= 0 && b < slots_b && xa >= 0 && xa < W && ya >= 0 && ya < H) {
                 const int xb = kp_b[4 * b], yb = kp_b[4 * b + 1];
                 if (xb >= 0 && xb < W && yb >= 0 && yb < H) {
-                    const float za = depth_a[(size_t)ya * W + xa], zb = depth_b[(size_t)yb * W + xb];
+                    const float za = depth_a[(size_t)ya * W + xa];
+                    float zb = 1.f;
+                    if constexpr (!PNP) zb = depth_b[(size_t)yb * W + xb];
                     if (isfinite(za) && za > 0.f && isfinite(zb) && zb > 0.f) {
                         ok = true;
                         pa[0] = ((float)xa - K_a[2]) * za / K_a[0], pa[1] = ((float)ya - K_a[3]) * za / K_a[1], pa[2] = za;
-                        pb[0] = ((float)xb - K_b[2]) * zb / K_b[0], pb[1] = ((float)yb - K_b[3]) * zb / K_b[1], pb[2] = zb;
+                        if constexpr (PNP) pb[0] = ((float)xb - K_b[2]) / K_b[0], pb[1] = ((float)yb - K_b[3]) / K_b[1], pb[2] = 1.f;
+                        else pb[0] = ((float)xb - K_b[2]) * zb / K_b[0], pb[1] = ((float)yb - K_b[3]) * zb / K_b[1], pb[2] = zb;
                         uv[0] = (float)xb, uv[1] = (float)yb;
                     }
                 }
@@ -408,7 +504,8 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_pairs_kernel(int W, int H, in
     }
 }
 
-// grid: ceil(hypotheses / 4) blocks, one wave per hypothesis
+// grid: ceil(hypotheses / 4) blocks, one wave per hypothesis; PNP: every lane runs the wave-uniform Newton of feat_ranges itself
+template <bool PNP>
 __global__ void __launch_bounds__(FEAT_BLOCK) feat_hypotheses_kernel(int hypotheses, unsigned seed, float min_area, float tau_px, float tau_depth,
                                                                      const float* __restrict__ K_b, FeatPoseWs ws, int* __restrict__ counts)
 {
@@ -418,10 +515,10 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_hypotheses_kernel(int hypothe
     const float K[4] = {K_b[0], K_b[1], K_b[2], K_b[3]};
     FeatRt rt;
     int count = 0;
-    if (feat_hypothesis(seed, h, M, ws.PA, ws.PB, min_area, rt)) {
+    if (feat_hypothesis<PNP>(seed, h, M, ws.PA, ws.PB, min_area, rt)) {
         for (int m0 = 0; m0 < M; m0 += 64) {
             const int m = m0 + lane;
-            const bool in = m < M && feat_inlier(rt, ws.PA + 3 * (size_t)m, ws.PB + 3 * (size_t)m, ws.UV + 2 * (size_t)m, K, tau_px, tau_depth);
+            const bool in = m < M && feat_inlier<PNP>(rt, ws, m, K, tau_px, tau_depth);
             count += __popcll(__ballot(in));
         }
     }
@@ -495,7 +592,24 @@ __device__ inline void feat_exp_apply(const double* xi, double* pose)
     for (int i = 0; i < 3; ++i) pose[9 + i] = t[i];
 }
 
-// one block
+// acc += the 27 sums of ROWS rows of J and their residuals r
+template <int ROWS>
+__device__ __forceinline__ void feat_add_rows(double* acc, const double (*J)[6], const double* r)
+{
+#pragma unroll
+    for (int row = 0; row < ROWS; ++row) {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) acc[k++] += J[row][i] * J[row][j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] += J[row][i] * r[row];
+    }
+}
+
+// one block. PNP: the residual is the reprojection error in pixels (two rows per pair), J = d(proj)/dq [I | -[q]x]
+template <bool PNP>
 __global__ void __launch_bounds__(FEAT_BLOCK) feat_finish_kernel(int hypotheses, unsigned seed, float min_area, float tau_px, float tau_depth,
                                                                  int refine_iters, int min_matches, int min_inliers, float min_share,
                                                                  float max_translation, float max_rotation, const float* __restrict__ K_b,
@@ -516,11 +630,10 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_finish_kernel(int hypotheses,
     key = feat_block_max(key, upart);                                  // a count is at most 4096: count << 10 fits; lowest h on a tie
     const int winner = FEAT_MAX_HYPOTHESES - 1 - (int)(key & 1023u), best = (int)(key >> 10);
     FeatRt rt;
-    const bool have = best >= 3 && feat_hypothesis(seed, winner, M, ws.PA, ws.PB, min_area, rt);
+    const bool have = best >= 3 && feat_hypothesis<PNP>(seed, winner, M, ws.PA, ws.PB, min_area, rt);
     int final_inliers = 0;
     if (have) {                                                        // uniform over the block
-        for (int m = tid; m < M; m += FEAT_BLOCK)
-            flag[m] = feat_inlier(rt, ws.PA + 3 * (size_t)m, ws.PB + 3 * (size_t)m, ws.UV + 2 * (size_t)m, K, tau_px, tau_depth) ? 1 : 0;
+        for (int m = tid; m < M; m += FEAT_BLOCK) flag[m] = feat_inlier<PNP>(rt, ws, m, K, tau_px, tau_depth) ? 1 : 0;
         if (tid == 0) {
             for (int k = 0; k < 9; ++k) pose[k] = (double)rt.R[k];
             for (int i = 0; i < 3; ++i) pose[9 + i] = (double)rt.t[i];
@@ -534,23 +647,23 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_finish_kernel(int hypotheses,
             for (int m = tid; m < M; m += FEAT_BLOCK) {
                 if (!flag[m]) continue;
                 const float* P = ws.PA + 3 * (size_t)m;
-                const float* Pb = ws.PB + 3 * (size_t)m;
-                double q[3], r[3];
+                double q[3];
 #pragma unroll
-                for (int i = 0; i < 3; ++i) {
+                for (int i = 0; i < 3; ++i)
                     q[i] = pose[3 * i] * (double)P[0] + pose[3 * i + 1] * (double)P[1] + pose[3 * i + 2] * (double)P[2] + pose[9 + i];
-                    r[i] = q[i] - (double)Pb[i];
-                }
-                const double J[3][6] = {{1.0, 0.0, 0.0, 0.0, q[2], -q[1]}, {0.0, 1.0, 0.0, -q[2], 0.0, q[0]}, {0.0, 0.0, 1.0, q[1], -q[0], 0.0}};
-#pragma unroll
-                for (int row = 0; row < 3; ++row) {
-                    int k = 0;
-#pragma unroll
-                    for (int i = 0; i < 6; ++i)
-#pragma unroll
-                        for (int j = i; j < 6; ++j) acc[k++] += J[row][i] * J[row][j];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) acc[21 + i] += J[row][i] * r[row];
+                if constexpr (PNP) {
+                    const float* uv = ws.UV + 2 * (size_t)m;
+                    const double fx = (double)K[0], fy = (double)K[1];
+                    const double r[2] = {fx * q[0] / q[2] + (double)K[2] - (double)uv[0], fy * q[1] / q[2] + (double)K[3] - (double)uv[1]};
+                    const double ax = fx / q[2], ay = fy / q[2], bx = -fx * q[0] / (q[2] * q[2]), by = -fy * q[1] / (q[2] * q[2]);
+                    const double J[2][6] = {{ax, 0.0, bx, bx * q[1], ax * q[2] - bx * q[0], -ax * q[1]},
+                                            {0.0, ay, by, by * q[1] - ay * q[2], -by * q[0], ay * q[0]}};
+                    feat_add_rows<2>(acc, J, r);
+                } else {
+                    const float* Pb = ws.PB + 3 * (size_t)m;
+                    const double r[3] = {q[0] - (double)Pb[0], q[1] - (double)Pb[1], q[2] - (double)Pb[2]};
+                    const double J[3][6] = {{1.0, 0.0, 0.0, 0.0, q[2], -q[1]}, {0.0, 1.0, 0.0, -q[2], 0.0, q[0]}, {0.0, 0.0, 1.0, q[1], -q[0], 0.0}};
+                    feat_add_rows<3>(acc, J, r);
                 }
             }
 #pragma unroll
@@ -582,8 +695,7 @@ __global__ void __launch_bounds__(FEAT_BLOCK) feat_finish_kernel(int hypotheses,
 #pragma unroll
         for (int i = 0; i < 3; ++i) fin.t[i] = pose32[9 + i];
         int n = 0;
-        for (int m = tid; m < M; m += FEAT_BLOCK)
-            n += feat_inlier(fin, ws.PA + 3 * (size_t)m, ws.PB + 3 * (size_t)m, ws.UV + 2 * (size_t)m, K, tau_px, tau_depth) ? 1 : 0;
+        for (int m = tid; m < M; m += FEAT_BLOCK) n += feat_inlier<PNP>(fin, ws, m, K, tau_px, tau_depth) ? 1 : 0;
         final_inliers = feat_block_sum(n, ipart);
     }
     if (tid != 0) return;

@@ -288,6 +288,8 @@ FUNCTIONS = {
     "gsr_feat_match": (i, [i, vp, vp, i, vp, vp, i, i, vp, vp, sz, vp]),
     "gsr_feat_pose_workspace_size": (sz, [i, i]),
     "gsr_feat_pose": (i, [i, i, i, vp, vp, i] + [vp] * 5 + [u, i, f, f, f, i, i, i, f, f, f] + [vp] * 4 + [sz, vp]),
+    "gsr_feat_pose_pnp_workspace_size": (sz, [i, i]),
+    "gsr_feat_pose_pnp": (i, [i, i, i, vp, vp, i] + [vp] * 4 + [u, i, f, f, i, i, i, f, f, f] + [vp] * 4 + [sz, vp]),
 }
 
 # Exported by the library (csrc/gs_capi.hip) but not part of include/*.h: the view-slot inspector, and the readers of the

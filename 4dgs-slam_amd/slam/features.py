@@ -1,17 +1,22 @@
-"""The relative pose of two RGB-D frames from matched binary features: the wide-baseline step between place recognition (the ferns of
+"""The relative pose of two frames from matched binary features: the wide-baseline step between place recognition (the ferns of
 slam/relocalise.py) and the dense alignment (slam/odometry.py), whose reach is its basin of convergence. The checked ctypes binding of
 include/feature_matching.h (gsr_feat_extract: FAST-9 corners and rotated BRIEF descriptors in a fixed slot layout; gsr_feat_match: the mutual
-ratio-tested Hamming match; gsr_feat_pose: three-point RANSAC, a point-to-point refinement and a gate; csrc/gs_features.h) and what is
+ratio-tested Hamming match; gsr_feat_pose: three-point RANSAC, a point-to-point refinement and a gate; gsr_feat_pose_pnp: the same from
+the 3D points of the first frame and the pixels of the second alone, for a second frame without depth; csrc/gs_features.h) and what is
 built from them:
 
   pattern_tables        the direction table and the rotated point pairs, built on the host from a seed
   feature_seed_options  the ``Training.feature_seed`` block
-  FeatureSeeder         features(image, mask) and pose(a, depth_a, b, depth_b) for frames of one size, everything on the device
+  FeatureSeeder         features(image, mask) and pose(a, depth_a, b, depth_b) for frames of one size, everything on the device; with
+                        ``solver: pnp`` depth_b is never touched and may be None (a monocular frame)
 
 Relocaliser._seed (slam/relocalise.py) and LoopCloser.verify (slam/loop_closure.py) start the dense alignment at the pose found here when
-the block is on. The reference has no counterpart. tests/features_reference.py restates the three kernels in numpy. No CPU path.
+the block is on. The reference has no counterpart. tests/features_reference.py and tests/pnp_reference.py restate the kernels in numpy.
+No CPU path.
 
-Limits: nothing here has been run on real images. One scale only (no pyramid); frames without depth cannot be used (no PnP)."""
+Limits: nothing here has been run on real images. One scale only (no pyramid). The PnP solver follows one root of the three-point
+problem, the one next to the first frame's ranges (no complete P3P), and its pose is coarser than the 3D-3D one: a start for the dense
+alignment, not a replacement for it (Feature seed)."""
 import math
 
 import numpy as np
@@ -92,6 +97,27 @@ def pose(keypoints_a, depth_a, keypoints_b, depth_b, matches, K_a, K_b, T, stats
                           workspace.data_ptr() or None, int(workspace.numel()), _C.stream_handle(stream, dev))
 
 
+def pose_pnp(keypoints_a, depth_a, keypoints_b, matches, K_a, K_b, T, stats, seed=0, hypotheses=256, min_area=MIN_AREA, tau_px=2.0,
+             refine_iters=3, min_matches=12, min_inliers=8, min_share=0.5, max_translation=1.5, max_rotation=math.radians(45.0), counts=None,
+             workspace=None, stream=None):
+    """One call of gsr_feat_pose_pnp: pose() from the depth of frame A and the pixels of frame B; no depth of B and no tau_depth. The
+    frame size is depth_a's."""
+    _C._require_device(depth_a, "depth_a")
+    H, W = int(depth_a.shape[0]), int(depth_a.shape[1])
+    A, B, dev = int(keypoints_a.shape[0]), int(keypoints_b.shape[0]), depth_a.device
+    args = [W, H, A, _C.dev_ptr(keypoints_a, "keypoints_a", I32, (A, 4)), _C.dev_ptr(depth_a, "depth_a", _C.F32, (H, W)),
+            B, _C.dev_ptr(keypoints_b, "keypoints_b", I32, (B, 4)), _C.dev_ptr(matches, "matches", I32, (A, 2)),
+            _C.dev_ptr(K_a, "K_a", _C.F32, (4,)), _C.dev_ptr(K_b, "K_b", _C.F32, (4,))]
+    outs = [_C.dev_ptr(T, "T", _C.F32, (4, 4)), _C.dev_ptr(stats, "stats", I32, (len(STATS),)),
+            _C.dev_ptr(counts, "counts", I32, (int(hypotheses),))]
+    lib = _C.load_library()
+    workspace = _C.workspace(workspace, int(lib.gsr_feat_pose_pnp_workspace_size(A, int(hypotheses))) if workspace is None else 0, dev)
+    with torch.cuda.device(dev):
+        lib.gsr_feat_pose_pnp(*args, int(seed) & 0xFFFFFFFF, int(hypotheses), float(min_area), float(tau_px), int(refine_iters),
+                              int(min_matches), int(min_inliers), float(min_share), float(max_translation), float(max_rotation), *outs,
+                              workspace.data_ptr() or None, int(workspace.numel()), _C.stream_handle(stream, dev))
+
+
 # ---- the tables ----------------------------------------------------------------------------------------------------------------------
 def pattern_tables(seed):
     """(directions int32 [32, 2], pattern int8 [32, 256, 4]) on the host. directions[k] = round(256 cos, 256 sin) of 2 pi k / 32. The 256
@@ -117,20 +143,25 @@ def pattern_tables(seed):
 # unrelated textures gave (at most 9 pairs and 1 inlier): DESIGN.md section 8, Feature seed
 FEATURE_SEED_DEFAULTS = {"enabled": False, "threshold": 20, "cell": 32, "per_cell": 4, "seed": 0, "max_distance": 64, "ratio_eighths": 6,
                          "hypotheses": 256, "tau_px": 2.0, "tau_depth": 0.05, "min_matches": 12, "min_inliers": 8, "min_share": 0.5,
-                         "refine_iters": 3, "max_translation": 1.5, "max_rotation": 45.0}
+                         "refine_iters": 3, "max_translation": 1.5, "max_rotation": 45.0, "solver": "points"}
+SOLVERS = ("points", "pnp")
 
 
 def feature_seed_options(training):
     """The ``Training.feature_seed`` block with its defaults filled in, or None when it is absent or not enabled. Unknown keys, values the
     kernels cannot take and the runs the stage cannot serve are refused here, before the run starts. max_translation is in metres,
-    max_rotation in degrees: the gate of the feature pose AND of the dense alignment that starts from it."""
+    max_rotation in degrees: the gate of the feature pose AND of the dense alignment that starts from it. solver: "points" (both frames'
+    depths, gsr_feat_pose) or "pnp" (the first frame's depth and the second frame's pixels, gsr_feat_pose_pnp: the one that serves
+    monocular input); "pnp" has no depth test and ignores tau_depth."""
     name = "Training.feature_seed"
     opt = read_block(training, "feature_seed", FEATURE_SEED_DEFAULTS)
     if opt is None:
         return None
-    if training.get("monocular", False):
+    if opt["solver"] not in SOLVERS:
+        raise ValueError(f"{name}.solver must be one of {list(SOLVERS)}, got {opt['solver']!r}")
+    if training.get("monocular", False) and opt["solver"] != "pnp":
         raise ValueError(f"{name} cannot be used with monocular input: a frame has no depth to back-project its keypoints with, and a pose "
-                         "from 2D-3D matches (PnP) is not part of this stage")
+                         "from 2D-3D matches (PnP) is not part of this stage unless solver is 'pnp'")
     if not any((training.get(k) or {}).get("enabled", False) for k in ("relocalisation", "loop_closure")):
         raise ValueError(f"{name} needs Training.relocalisation or Training.loop_closure enabled: it seeds their alignments and would do "
                          "nothing by itself")
@@ -195,7 +226,8 @@ class FeatureSeeder:
         self.K = torch.tensor([float(v) for v in K], dtype=torch.float32, device=self.device)
         lib = _C.load_library()
         sizes = (lib.gsr_feat_extract_workspace_size(self.width, self.height), lib.gsr_feat_match_workspace_size(self.slots, self.slots),
-                 lib.gsr_feat_pose_workspace_size(self.slots, options["hypotheses"]))
+                 lib.gsr_feat_pose_workspace_size(self.slots, options["hypotheses"]),
+                 lib.gsr_feat_pose_pnp_workspace_size(self.slots, options["hypotheses"]))
         self._workspace = torch.empty(max(int(s) for s in sizes), dtype=torch.uint8, device=self.device)
         self._matches = torch.empty((self.slots, 2), dtype=torch.int32, device=self.device)
         self._cache = {}
@@ -218,17 +250,25 @@ class FeatureSeeder:
     def forget(self):
         self._cache = {}
 
-    def pose(self, a, depth_a, b, depth_b, counts=None):
+    def pose(self, a, depth_a, b, depth_b=None, counts=None):
+        """The pose of frame b against frame a. With ``solver: pnp`` depth_b is never touched; with "points" it is required."""
         opt = self.options
+        pnp = opt["solver"] == "pnp"
+        if depth_b is None and not pnp:
+            raise ValueError("FeatureSeeder.pose: the second frame has no depth; Training.feature_seed.solver must be 'pnp' for such a frame")
         plane = lambda d: torch.as_tensor(d).detach().to(device=self.device, dtype=torch.float32).reshape(self.height, self.width).contiguous()
-        depth_a, depth_b = plane(depth_a), plane(depth_b)
+        depth_a, depth_b = plane(depth_a), None if pnp else plane(depth_b)
         match(a[0], a[1], b[0], b[1], opt["max_distance"], opt["ratio_eighths"], self._matches, self._workspace)
         T = torch.empty((4, 4), dtype=torch.float32, device=self.device)
         stats = torch.empty(len(STATS), dtype=torch.int32, device=self.device)
-        pose(a[0], depth_a, b[0], depth_b, self._matches, self.K, self.K, T, stats, seed=opt["seed"], hypotheses=opt["hypotheses"],
-             tau_px=opt["tau_px"], tau_depth=opt["tau_depth"], refine_iters=opt["refine_iters"], min_matches=opt["min_matches"],
-             min_inliers=opt["min_inliers"], min_share=opt["min_share"], max_translation=opt["max_translation"],
-             max_rotation=math.radians(opt["max_rotation"]), counts=counts, workspace=self._workspace)
+        gate = dict(seed=opt["seed"], hypotheses=opt["hypotheses"], tau_px=opt["tau_px"], refine_iters=opt["refine_iters"],
+                    min_matches=opt["min_matches"], min_inliers=opt["min_inliers"], min_share=opt["min_share"],
+                    max_translation=opt["max_translation"], max_rotation=math.radians(opt["max_rotation"]), counts=counts,
+                    workspace=self._workspace)
+        if pnp:
+            pose_pnp(a[0], depth_a, b[0], self._matches, self.K, self.K, T, stats, **gate)
+        else:
+            pose(a[0], depth_a, b[0], depth_b, self._matches, self.K, self.K, T, stats, tau_depth=opt["tau_depth"], **gate)
         self.tried += 1
         self._accepted += stats[6]
         return T, stats

@@ -91,7 +91,7 @@ class FrontEnd:
         self.mono_sweep = sweep and SweepSeeding(sweep)
         terms = pose_prior_terms_options(training)                         # refused without pose_prior
         self.pose_prior = prior and PosePrior(prior, self.monocular, self.dynamic_model, terms)
-        seed = feature_seed_options(training)                               # refused for monocular runs and without a stage to seed
+        seed = feature_seed_options(training)                               # refused without a stage to seed, and for monocular runs unless its solver is pnp
         self.relocalisation = reloc and Relocalisation(reloc, self.dynamic_model, seed)
         loops = loop_closure_options(training, self.dynamic_model)          # refused for monocular, dynamic and spherical-harmonics runs
         self.loop_closure = loops and LoopClosure(loops, seed)

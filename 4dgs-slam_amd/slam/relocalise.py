@@ -286,7 +286,8 @@ class Relocaliser:
         """Place `viewpoint` at the keyframe's pose moved by the alignment of its image against the map rendered there; where the
         alignment's gate refuses, T is the identity and the pose is the keyframe's. With the feature seed on (frame_features: the frame's
         keypoints and descriptors) the alignment starts at the feature pose of the rendering and the frame -- the identity where that is
-        refused, and then the alignment's own, narrower gate holds (features.gated). Device tensors throughout; nothing is read."""
+        refused, and then the alignment's own, narrower gate holds (features.gated). The frame's depth is None for a monocular frame, which
+        the seeder takes with ``solver: pnp`` alone (it then never touches that depth). Device tensors throughout; nothing is read."""
         pkg = self.render_at(keyframe)
         depth = opaque_depth(pkg["depth"], pkg["opacity"])
         self.odometry.keep(pkg["render"], depth, None)

@@ -4,7 +4,9 @@
  * (visual_odometry.h). Three calls: FAST-9 corners with rotated BRIEF descriptors in a fixed slot layout (gsr_feat_extract; Rosten &
  * Drummond, "Machine learning for high-speed corner detection"; Rublee et al., "ORB: an efficient alternative to SIFT or SURF"), the
  * mutual ratio-tested Hamming match of two such sets (gsr_feat_match), and three-point RANSAC with a point-to-point refinement and a gate
- * on the back-projected matches (gsr_feat_pose). slam/features.py builds the stage from them; the reference has no counterpart.
+ * on the back-projected matches (gsr_feat_pose). gsr_feat_pose_pnp is the same pose from the 3D points of A and the PIXELS of B alone, for a
+ * frame B without depth (a minimal three-point solver for the ranges, then the same triads; restated in tests/pnp_reference.py).
+ * slam/features.py builds the stage from them; the reference has no counterpart.
  * Everything is specified HERE, in integers wherever possible, and restated in numpy in tests/features_reference.py: keypoints,
  * descriptors, matches, the count of every hypothesis, the winner and stats equal the restatement bit for bit; T equals it to the last
  * float32 digit or two (below). All pointers are DEVICE pointers. Returns 0 or a negative GSR_ERR_* code (gs_rasterizer.h);
@@ -111,6 +113,51 @@ int gsr_feat_pose(int width, int height, int slots_a, const int* keypoints_a, co
                   float min_area, float tau_px, float tau_depth, int refine_iters, int min_matches, int min_inliers, float min_share,
                   float max_translation, float max_rotation, float* T, int* stats, int* counts, void* workspace, size_t workspace_bytes,
                   void* stream);
+
+/* Bytes of workspace gsr_feat_pose_pnp needs (those of gsr_feat_pose); 0 when slots_a is outside [1, 4096] or hypotheses outside [1, 1024]. */
+size_t gsr_feat_pose_pnp_workspace_size(int slots_a, int hypotheses);
+
+/* gsr_feat_pose_pnp: the motion T with P_b = R P_a + t from the matched keypoints, the depth of frame A and the pixels of frame B: a pose
+ * from 2D-3D matches (PnP) for a frame B without depth. NO DEPTH OF B IS READ ANYWHERE. Arguments, outputs, stats and ranges are those of
+ * gsr_feat_pose without depth_b and tau_depth. What differs from gsr_feat_pose, every float32 AND float64 operation rounded by itself
+ * (nothing fused), in the order written, sums left to right:
+ *   pairs       slot a takes part where matches[a] = (b, .) has 0 <= b < slots_b, both keypoints lie inside the image and z_a is finite and
+ *               positive. P_a as in gsr_feat_pose; (x_b, y_b) are kept as floats; the bearing in float32 is u = (((float)x_b - cx_b) /
+ *               fx_b, ((float)y_b - cy_b) / fy_b, 1).
+ *   draw        as in gsr_feat_pose.
+ *   ranges      in float64, for the three drawn pairs k = 1, 2, 3 (Grunert's equations, solved by Newton from the keyframe's own ranges;
+ *               Haralick et al., "Review and analysis of solutions of the three point perspective pose estimation problem"):
+ *               n_k = sqrt(u_x u_x + u_y u_y + u_z u_z), f_k = u_k / n_k; l_k = sqrt(P_x P_x + P_y P_y + P_z P_z) of A's point; for the
+ *               pairs (i, j) = (1, 2), (1, 3), (2, 3): c_ij = f_ix f_jx + f_iy f_jy + f_iz f_jz; D = P_i - P_j, d_ij = D_x D_x + D_y D_y +
+ *               D_z D_z. Eight times:
+ *                 F_ij = l_i l_i + l_j l_j - 2 l_i l_j c_ij - d_ij     (F1 = F_12, F2 = F_13, F3 = F_23; products left to right)
+ *                 a = 2 l_1 - 2 l_2 c_12, b = 2 l_2 - 2 l_1 c_12, c = 2 l_1 - 2 l_3 c_13, d = 2 l_3 - 2 l_1 c_13, e = 2 l_2 - 2 l_3 c_23,
+ *                 g = 2 l_3 - 2 l_2 c_23                               (the Jacobian [a b 0; c 0 d; 0 e g])
+ *                 det = -a d e - b c g; w = F2 g - d F3
+ *                 n_1 = -F1 d e - b w, n_2 = a w - F1 c g, n_3 = -a F2 e - b c F3 + F1 c e     (Cramer's rule)
+ *                 l_k = l_k - n_k / det
+ *               then F_ij once more at the final ranges. Pb_k = (float)(l_k f_k): each of the nine products is rounded to float32 once.
+ *   void        a hypothesis is void, and counts 0, with M < 3, two equal indices, a det that is zero or not finite in any step, a final
+ *               l_k that is not finite or not positive, |F_ij| <= 1e-9 d_ij false for any pair, or n3 >= min_area false for the triad
+ *               of A's triple or of Pb.
+ *   R, t        as in gsr_feat_pose, from the triads of A's triple and of Pb_1, Pb_2, Pb_3.
+ *   inlier      Q as in gsr_feat_pose; pair m is an inlier where Q_z > 0 and ex ex + ey ey <= tau_px tau_px. There is no depth test.
+ *   winner      as in gsr_feat_pose.
+ *   refinement  refine_iters Gauss-Newton passes in float64 on the REPROJECTION error over the winner's inliers, the set fixed: q = R P_a
+ *               + t, r = (fx_b q_x / q_z + cx_b - x_b, fy_b q_y / q_z + cy_b - y_b), J = d(proj)/dq [I | -[q]x] (two rows per pair)
+ *               against the same left perturbation; H, g, the order of the sums, Cholesky, exp and the stopping rules as in gsr_feat_pose.
+ *   recount, gate   as in gsr_feat_pose, with the inlier rule above.
+ * The device and the restatement differ as those of gsr_feat_pose do (the order of the float64 sums of H and g, the last bits of sin and
+ * cos): counts, winner and stats are equal bit for bit, T agrees within 2.4e-7 max(1, |entry|). The ranges rely on the float64 division
+ * and square root of the device being correctly rounded, which they are under the library's compiler options (no fast-math flag).
+ * One root only: Newton finds the root next to A's ranges, which is the right one while the view of B is not too far from that of A
+ * (tests/test_pnp_host.py measures the reach); a complete P3P solver that returns all four roots is not part of this call.
+ * Ranges: those of gsr_feat_pose. workspace: gsr_feat_pose_pnp_workspace_size bytes, 16-byte aligned. Three launches on `stream` (the pair
+ * list, one block; the hypotheses, one wave each, every lane running the Newton itself; winner, refinement and gate, one block). */
+int gsr_feat_pose_pnp(int width, int height, int slots_a, const int* keypoints_a, const float* depth_a, int slots_b, const int* keypoints_b,
+                      const int* matches, const float* K_a, const float* K_b, unsigned int seed, int hypotheses, float min_area, float tau_px,
+                      int refine_iters, int min_matches, int min_inliers, float min_share, float max_translation, float max_rotation, float* T,
+                      int* stats, int* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument("--first", type=int, default=0, help="the first of them")
     ap.add_argument("--size", default=None, help="WxH of the synthetic frames (default: the map's)")
     ap.add_argument("--trajectory", default=None, help="write the poses to this file")
+    ap.add_argument("--feature-solver", choices=("points", "pnp"), default="points", help="with --feature-seed: the pose from both frames' depths "
+                    "(points) or from the map's depth and the frame's pixels alone (pnp), which needs no depth of the frame")
     ap.add_argument("--feature-seed", action="store_true", help="start each candidate's alignment at the pose of matched features "
                     "(Training.feature_seed); the synthetic frames then carry the blocks texture, as the map must")
     ap.add_argument("--device", default="cuda:0")
@@ -52,7 +54,7 @@ def main(argv=None):
             config["Dataset"]["dataset_path"] = args.dataset_path
         ds = load_dataset(config, args.device, max_frames=args.first + args.frames)
     if args.feature_seed:
-        config = merge_config(config, {"Training": {"feature_seed": {"enabled": True}}})
+        config = merge_config(config, {"Training": {"feature_seed": {"enabled": True, "solver": args.feature_solver}}})
     frames = list(range(args.first, min(len(ds), args.first + args.frames)))
     out = MapLocaliser(loaded, config).follow(ds, frames)
     if args.trajectory:

@@ -9,7 +9,9 @@ most where the tracker is given few iterations. --pose-prior-terms (implies --po
 the alignment's affine brightness and depth term; --pose-prior-against keyframe aligns against the last keyframe, not the previous frame.
 --loop-closure turns on Training.loop_closure with its defaults on the static scenarios (a dynamic model is refused) and the result has a
 `loop_closure` block; the demo's arc never returns to a place, so it shows the cost of the stage, not a correction. --feature-seed (with
---loop-closure) turns on Training.feature_seed and gives the room the blocks texture, which has corners to find."""
+--loop-closure) turns on Training.feature_seed and gives the room the blocks texture, which has corners to find; --feature-solver pnp
+makes it the pose from 2D-3D matches, the one a --monocular run can use (with a Training.relocalisation block: loop closure is refused
+for monocular input)."""
 import json
 import os
 import sys
@@ -35,6 +37,7 @@ pose_prior = pose_prior or pose_prior_terms
 pose_prior_against = sys.argv[sys.argv.index("--pose-prior-against") + 1] if "--pose-prior-against" in sys.argv else "previous"
 loop_closure = "--loop-closure" in sys.argv
 feature_seed = "--feature-seed" in sys.argv               # needs --loop-closure (or a Training.relocalisation block); the blocks texture
+feature_solver = sys.argv[sys.argv.index("--feature-solver") + 1] if "--feature-solver" in sys.argv else "points"      # points | pnp
 tracking_itr = int(sys.argv[sys.argv.index("--tracking-itr") + 1]) if "--tracking-itr" in sys.argv else 60
 out = {}
 scenarios = (("static_640x480_eager", False, False, 40, (640, 480)), ("static_640x480_graph", False, True, 40, (640, 480)),
@@ -66,7 +69,7 @@ for name, dyn, graph, frames, wh in scenarios:
     if loop_closure:
         cfg = merge_config(cfg, {"Training": {"loop_closure": {"enabled": True}}})
     if feature_seed:
-        cfg = merge_config(cfg, {"Training": {"feature_seed": {"enabled": True}}})
+        cfg = merge_config(cfg, {"Training": {"feature_seed": {"enabled": True, "solver": feature_solver}}})
     for i in range(len(ds)):          # the sensor stream is "pre-recorded": rendering the synthetic frames is not part of the SLAM time
         ds[i]
     slam = SLAM(cfg, ds)
