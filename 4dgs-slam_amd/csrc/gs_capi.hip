@@ -42,6 +42,7 @@
 #include "gs_frame.h"
 #include "../../include/video_io.h"
 #include "gs_jpeg.h"
+#include "gs_jpeg_decode.h"
 #include "gs_png.h"
 #include "../../include/stereo_depth.h"
 #include "gs_stereo.h"
@@ -144,11 +145,13 @@ static bool workspace_fits(const char* who, const char* size_fn, const void* wor
 
 // ---- per-kernel timing with events on the launch stream ---------------------------------------------------------
 enum KernelId { K_PREPROCESS = 0, K_SCAN, K_SCATTER, K_SORT, K_RENDER_FWD, K_RENDER_BWD, K_GEOM_BWD, K_KNN, K_FRAME_PREPARE,
-                K_SWEEP_CENSUS, K_SWEEP_COST, K_SWEEP_PATHS, K_SWEEP_SELECT, K_ODO_PYRAMID, K_ODO_SUMS, K_ODO_SOLVE, K_COUNT };
+                K_SWEEP_CENSUS, K_SWEEP_COST, K_SWEEP_PATHS, K_SWEEP_SELECT, K_ODO_PYRAMID, K_ODO_SUMS, K_ODO_SOLVE, K_JPEGD_ENTROPY, K_JPEGD_PIXELS,
+                K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"preprocess_fwd", "scan", "scatter_instances", "sort_tiles",
                                                   "render_fwd", "render_bwd", "geometry_bwd", "knn_total", "frame_prepare",
                                                   "sweep_census", "sweep_cost", "sweep_paths", "sweep_select",
-                                                  "odometry_pyramid", "odometry_sums", "odometry_solve"};
+                                                  "odometry_pyramid", "odometry_sums", "odometry_solve",
+                                                  "jpeg_decode_entropy", "jpeg_decode_pixels"};
 struct Profiler {
     unsigned mask = 0;   // bit i set => kernel id i is timed
     struct Rec { hipEvent_t a, b; int id; };
@@ -3071,6 +3074,87 @@ int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8,
     hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(JPEG_BLOCK), 0, stream, l.shape, coef, lengths, raw);
     GSR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)views), dim3(JPEG_SCAN_BLOCK), 0, stream, l.shape, raw, totals, scan, (long long)scan_stride, sizes);
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// workspace of gsr_jpeg_decode: coefficients [F, mcus, blocks per MCU, 64] int16 (unused when the caller takes them) | restart marker
+// positions [F, max_intervals] i32 | markers found [F] i32 | the intervals' results [F, max_intervals] i32 | the component planes
+// [F, Y | Cb | Cr] bytes; every part starts on a multiple of 16 bytes
+struct JpegDecodeLayout { JpegDecodeShape shape; short* coef; int *marks, *mcount, *ivfail; unsigned char* planes; size_t bytes; };
+static bool jpeg_decode_layout(int frames, int width, int height, int sampling, int max_intervals, const void* workspace, JpegDecodeLayout& l)
+{
+    if (frames <= 0 || frames > 65535 || width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
+    if (sampling < GSR_JPEG_GREY || sampling > GSR_JPEG_420) return false;
+    JpegDecodeShape& s = l.shape;
+    s.frames = frames; s.W = width; s.H = height;
+    s.hs = sampling >= GSR_JPEG_422 ? 2 : 1;
+    s.vs = sampling == GSR_JPEG_420 ? 2 : 1;
+    s.comps = sampling == GSR_JPEG_GREY ? 1 : 3;
+    s.bpm = s.comps == 1 ? 1 : s.hs * s.vs + 2;
+    const long long cols = (width + 8 * s.hs - 1) / (8 * s.hs), rows = (height + 8 * s.vs - 1) / (8 * s.vs), mcus = cols * rows;
+    if (mcus * s.bpm > 1290000) return false;                        // the same ceiling as the encoder
+    if (max_intervals < 1 || max_intervals > mcus) return false;
+    s.mcu_cols = (int)cols; s.mcus = (int)mcus; s.cap = max_intervals;
+    s.yW = (int)cols * 8 * s.hs; s.yH = (int)rows * 8 * s.vs;
+    s.cW = s.comps == 1 ? 0 : (int)cols * 8; s.cH = s.comps == 1 ? 0 : (int)rows * 8;
+    s.cw = (width + s.hs - 1) / s.hs; s.ch = (height + s.vs - 1) / s.vs;
+    s.scan_bytes = 0;
+    Carver c(workspace, 16);
+    l.coef = c.take<short>((size_t)frames * mcus * s.bpm * 64);
+    l.marks = c.take<int>((size_t)frames * max_intervals);
+    l.mcount = c.take<int>((size_t)frames);
+    l.ivfail = c.take<int>((size_t)frames * max_intervals);
+    l.planes = c.take<unsigned char>((size_t)frames * ((size_t)s.yW * s.yH + 2 * (size_t)s.cW * s.cH));
+    l.bytes = c.bytes();
+    return true;
+}
+
+size_t gsr_jpeg_decode_workspace_size(int frames, int width, int height, int sampling, int max_intervals)
+{
+    JpegDecodeLayout l;
+    return jpeg_decode_layout(frames, width, height, sampling, max_intervals, nullptr, l) ? l.bytes : 0;
+}
+
+int gsr_jpeg_decode(int frames, int width, int height, int sampling, int max_intervals, const unsigned char* scans, const int64_t* offsets,
+                    int64_t scan_bytes, const unsigned short* qtables, const int* huffman, const int* descriptors, unsigned char* rgb8,
+                    int* status, short* coefficients, void* workspace, size_t workspace_bytes, void* stream_)
+{
+    JpegDecodeLayout l;
+    if (!jpeg_decode_layout(frames, width, height, sampling, max_intervals, workspace, l)) {
+        g_last_error = "gsr_jpeg_decode: frames, width and height must be in [1, 65535] with at most 1290000 8x8 blocks per frame, sampling one of "
+                       "GSR_JPEG_GREY .. GSR_JPEG_420, max_intervals in [1, MCUs per frame]";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!scans || !offsets || !qtables || !huffman || !descriptors || !rgb8 || !status || !workspace) {
+        g_last_error = "gsr_jpeg_decode: scans, offsets, qtables, huffman, descriptors, rgb8, status and workspace must not be NULL";
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (scan_bytes < 0) { g_last_error = "gsr_jpeg_decode: scan_bytes must not be negative"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (reinterpret_cast<size_t>(coefficients) & 15) { g_last_error = "gsr_jpeg_decode: coefficients must be 16-byte aligned"; return GSR_ERR_INVALID_ARGUMENT; }
+    if (!workspace_fits("gsr_jpeg_decode", "gsr_jpeg_decode_workspace_size", workspace, workspace_bytes, l.bytes)) return GSR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    JpegDecodeShape s = l.shape;
+    s.scan_bytes = scan_bytes;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    short* const coef = coefficients ? coefficients : l.coef;
+    {
+        ScopedKernelTimer tm(K_JPEGD_ENTROPY, stream);                // the serial part: restart markers and entropy decoding
+        hipLaunchKernelGGL(jpegd_markers_kernel, dim3((unsigned)frames), dim3(JPEGD_BLOCK), 0, stream, s, scans, offs, l.marks, l.mcount);
+        GSR_HIP_CHECK(hipGetLastError());
+        const long long lanes = (long long)frames * max_intervals;
+        hipLaunchKernelGGL(jpegd_entropy_kernel, dim3((unsigned)((lanes + JPEGD_ENTROPY_BLOCK - 1) / JPEGD_ENTROPY_BLOCK)), dim3(JPEGD_ENTROPY_BLOCK),
+                           0, stream, s, scans, offs, huffman, descriptors, l.marks, l.mcount, coef, l.ivfail);
+        GSR_HIP_CHECK(hipGetLastError());
+    }
+    ScopedKernelTimer tm(K_JPEGD_PIXELS, stream);                     // the parallel part: inverse DCT, upsampling and colour
+    const int blocks = s.mcus * s.bpm;
+    hipLaunchKernelGGL(jpegd_idct_kernel, dim3((unsigned)((blocks + JPEGD_BLOCK - 1) / JPEGD_BLOCK), (unsigned)frames), dim3(JPEGD_BLOCK), 0, stream,
+                       s, coef, qtables, l.planes);
+    GSR_HIP_CHECK(hipGetLastError());
+    const long long pixels = (long long)width * height;
+    hipLaunchKernelGGL(jpegd_colour_kernel, dim3((unsigned)((pixels + JPEGD_BLOCK - 1) / JPEGD_BLOCK), (unsigned)frames), dim3(JPEGD_BLOCK), 0, stream,
+                       s, l.planes, descriptors, l.mcount, l.ivfail, rgb8, status);
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -346,7 +346,7 @@ def debug_read_state(P, R, W, H, geomBuffer, binningBuffer, imageBuffer):
 
 KERNEL_IDS = {"preprocess_fwd": 0, "scan": 1, "scatter_instances": 2, "sort_tiles": 3, "render_fwd": 4, "render_bwd": 5,
               "geometry_bwd": 6, "frame_prepare": 8, "sweep_census": 9, "sweep_cost": 10, "sweep_paths": 11, "sweep_select": 12,
-              "odometry_pyramid": 13, "odometry_sums": 14, "odometry_solve": 15}
+              "odometry_pyramid": 13, "odometry_sums": 14, "odometry_solve": 15, "jpeg_decode_entropy": 16, "jpeg_decode_pixels": 17}
 
 
 def profile_enable(kernels=True):

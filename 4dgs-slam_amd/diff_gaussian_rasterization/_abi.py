@@ -21,6 +21,8 @@ GSR_NODE_RADIUS_IS_LOG, GSR_NODE_WEIGHT_IS_LOGIT = 1, 2
 GSR_YOLO_MAX_LEVELS, GSR_YOLO_MAX_ANCHORS, GSR_YOLO_REG_MAX, GSR_YOLO_DET_HEAD = 4, 8192, 16, 7  # segmentation.h
 GSR_LPIPS_MAX_LEVELS, GSR_LPIPS_NORM_TORCHMETRICS, GSR_LPIPS_NORM_LPIPS = 8, 0, 1  # perceptual.h
 GSR_PNG_SEGMENT = 16384                                                           # video_io.h
+GSR_JPEG_GREY, GSR_JPEG_444, GSR_JPEG_422, GSR_JPEG_420 = 0, 1, 2, 3
+GSR_JPEG_OK, GSR_JPEG_OUT_OF_BYTES, GSR_JPEG_LONG_CODE, GSR_JPEG_INDEX_PAST_63, GSR_JPEG_BAD_RESTART = 0, 1, 2, 3, 4
 
 # ---- types (field names and order as in the headers; every pointer field is a plain address) -----------------------------------
 gsr_alloc_fn = C.CFUNCTYPE(vp, vp, sz)
@@ -236,6 +238,8 @@ FUNCTIONS = {
     # video_io.h
     "gsr_jpeg_workspace_size": (sz, [i, i, i]),
     "gsr_jpeg_encode": (i, [i, i, i, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "gsr_jpeg_decode_workspace_size": (sz, [i, i, i, i, i]),
+    "gsr_jpeg_decode": (i, [i, i, i, i, i, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "gsr_png_workspace_size": (sz, [i, i, i, i]),
     "gsr_png_stream_bound": (sz, [i, i, i]),
     "gsr_png_encode": (i, [i, i, i, i, i, vp, vp, i64, vp, vp, sz, vp]),

@@ -104,6 +104,21 @@ def eval_ate(frames, kf_ids, save_dir=None, iterations=0, final=False, monocular
     return out["ate_rmse"]
 
 
+def write_trajectory(frames, stamps, path):
+    """The tracked frames' camera-to-world poses as a TUM trajectory file, `stamp tx ty tz qx qy qz qw` per line in frame order (the format
+    of recorded.write_tum_lists' groundtruth.txt, which evo and the TUM tools read). `frames` = {frame id: Camera}; stamps[frame id] is the
+    frame's time in seconds (None: the frame id). Returns the path."""
+    from .recorded import rotation_to_quaternion
+    lines = []
+    for i in sorted(frames.keys()):
+        c2w = _pose_c2w(frames[i].R, frames[i].T)
+        stamp = float(stamps[i]) if stamps is not None else float(i)
+        lines.append(f"{stamp:.6f} " + " ".join(f"{v:.12f}" for v in (*c2w[:3, 3], *rotation_to_quaternion(c2w[:3, :3]))))
+    with open(path, "w") as f:
+        f.write("# estimated trajectory (camera to world; no ground truth)\n# timestamp tx ty tz qx qy qz qw\n" + "\n".join(lines) + "\n")
+    return path
+
+
 def psnr(img1, img2):
     """gaussian_splatting/utils/image_utils.py:19-21."""
     mse = ((img1 - img2) ** 2).view(img1.shape[0], -1).mean(1, keepdim=True)

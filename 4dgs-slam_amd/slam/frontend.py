@@ -148,7 +148,10 @@ class FrontEnd:
         """:189-207."""
         self.kf_indices, self.iteration_count, self.occ_aware_visibility, self.current_window = [], 0, {}, []
         self.initialized, self.reset = not self.monocular, False
-        viewpoint.update_RT(viewpoint.R_gt, viewpoint.T_gt)               # first frame at the ground-truth pose
+        if getattr(self.dataset, "has_ground_truth", True):
+            viewpoint.update_RT(viewpoint.R_gt, viewpoint.T_gt)           # first frame at the ground-truth pose
+        else:                                                             # no ground truth (a plain video): the map's frame is the first camera's
+            viewpoint.update_RT(torch.eye(3, device=viewpoint.R.device), torch.zeros(3, device=viewpoint.R.device))
         if self.pose_prior is not None:                                   # a map that starts (over) drops the kept frame
             self.pose_prior.restart(viewpoint)
         if self.relocalisation is not None:                               # a map that starts (over) forgets the places of the old one
@@ -299,7 +302,7 @@ class FrontEnd:
         self.sync_backend(self.backend.handle_keyframe(cur_frame_idx, viewpoint, self.current_window, depth_map, True, False))
         self.log.append(("keyframe", cur_frame_idx, overlap))
         viewpoint.clean_key()
-        if self.save_results and self.save_trj and len(self.kf_indices) % self.save_trj_kf_intv == 0:
+        if self.save_results and self.save_trj and len(self.kf_indices) % self.save_trj_kf_intv == 0 and getattr(self.dataset, "has_ground_truth", True):
             eval_ate(self.cameras, self.kf_indices, self.save_dir, cur_frame_idx, monocular=self.monocular)
 
     def run(self, max_frames=None):
@@ -334,6 +337,6 @@ class FrontEnd:
             if not wanted or self.reset:                  # (a frame whose insertion ended in a reset is no keyframe: it keeps its pose only)
                 self.cleanup(cur_frame_idx)
             self.dynamic_objects = self.dataset.dynamic_objects
-        if self.save_results and self.save_dir:
+        if self.save_results and self.save_dir and getattr(self.dataset, "has_ground_truth", True):      # (no ATE without ground truth)
             eval_ate(self.cameras, self.kf_indices, self.save_dir, 0, final=True, monocular=self.monocular)
             save_gaussians(self.gaussians, self.save_dir, "final", final=True)

@@ -73,9 +73,10 @@ def save_map(slam, directory):
     n = len(uids)
     eye, zero3 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
     frames = {k: [] for k in FRAME_FIELDS}
+    run_has_gt = bool(getattr(getattr(slam, "dataset", None), "has_ground_truth", True))  # (a plain video's cameras carry the identity where others carry ground truth)
     for uid in uids:
         c = cameras[uid]
-        has_gt = getattr(c, "R_gt", None) is not None and getattr(c, "T_gt", None) is not None
+        has_gt = run_has_gt and getattr(c, "R_gt", None) is not None and getattr(c, "T_gt", None) is not None
         has_exp = getattr(c, "exposure_a", None) is not None and getattr(c, "exposure_b", None) is not None
         frames["frame_uid"].append(int(c.uid))
         frames["frame_time"].append(float(c.time))

@@ -1,7 +1,9 @@
 """Motion-JPEG output: the tables and headers of baseline JPEG (ITU-T T.81: 8 bit, three components, 4:2:0, the Annex K tables), the checked
 ctypes binding of include/video_io.h (gsr_jpeg_encode: colour conversion, DCT, quantisation and Huffman coding on the device, csrc/gs_jpeg.h)
 and a plain RIFF AVI 1.0 container for the frames (AviWriter, read_avi). The host runs no compressor: a file is jfif_header() + the device's
-entropy-coded segment + EOI. tests/jpeg_reference.py restates the encoder's arithmetic in numpy."""
+entropy-coded segment + EOI. tests/jpeg_reference.py restates the encoder's arithmetic in numpy. jpeg_decode is the binding of the inverse
+(gsr_jpeg_decode, csrc/gs_jpeg_decode.h): pictures from entropy-coded segments and the tables slam/jpeg_decode.py parses out of the headers;
+tests/jpeg_decode_reference.py restates its arithmetic."""
 import struct
 
 import numpy as np
@@ -126,6 +128,52 @@ def jpeg_encode(rgb8, qtables, scan, sizes, coefficients=None, workspace=None, s
     workspace = _C.workspace(workspace, need, rgb8.device)
     with torch.cuda.device(rgb8.device):
         lib.gsr_jpeg_encode(V, W, H, *args, workspace.data_ptr(), int(workspace.numel()), _C.stream_handle(stream, rgb8.device))
+
+
+_BLOCKS_PER_MCU, _MCU_SIZE = (1, 3, 4, 6), ((8, 8), (8, 8), (16, 8), (16, 16))     # by GSR_JPEG_GREY, _444, _422, _420; (wide, high)
+_I16 = (torch.int16, getattr(torch, "uint16", torch.int16))
+
+
+def jpeg_decode_workspace_size(frames, width, height, sampling, max_intervals=1):
+    return int(_C.load_library().gsr_jpeg_decode_workspace_size(frames, width, height, sampling, max_intervals))
+
+
+def jpeg_decode(scans, offsets, qtables, huffman, descriptors, rgb8, status, sampling, max_intervals=1, coefficients=None, workspace=None,
+                stream=None):
+    """Baseline JPEG pictures from their entropy-coded segments, on the device (include/video_io.h gsr_jpeg_decode): the inverse of
+    jpeg_encode in libjpeg's arithmetic. The inputs are slam.jpeg_decode.pack()'s arrays as device tensors: scans uint8 [bytes]; offsets
+    int64 [F + 1]; qtables 16-bit [F, 3, 64] (per component, natural order); huffman int32 [F, 4, 96]; descriptors int32 [F, 8]. rgb8 uint8
+    [F, H, W, 3] and status int32 [F] (a GSR_JPEG_* code, 0 = decoded) are written. sampling: GSR_JPEG_GREY / _444 / _422 / _420;
+    max_intervals: the most restart intervals of any frame (pack()["max_intervals"]). coefficients None or int16 [F, mcu rows, mcu columns,
+    blocks per MCU, 64]: the quantised coefficients in scan order, zigzag. workspace None (allocated here) or uint8
+    [>= jpeg_decode_workspace_size(...)]. stream: a torch stream (default: the current stream of rgb8's device)."""
+    _C._require_device(rgb8, "rgb8")
+    if rgb8.dim() != 4 or rgb8.shape[3] != 3:
+        raise RuntimeError(f"rgb8 must be [F, H, W, 3], got {tuple(rgb8.shape)}")
+    F, H, W, _ = (int(v) for v in rgb8.shape)
+    if isinstance(sampling, bool) or not isinstance(sampling, (int, np.integer)) or not 0 <= int(sampling) <= 3:
+        raise RuntimeError(f"sampling must be GSR_JPEG_GREY (0), _444 (1), _422 (2) or _420 (3), got {sampling!r}")
+    sampling = int(sampling)
+    _C._require_device(scans, "scans")
+    if scans.dim() != 1:
+        raise RuntimeError(f"scans must be [bytes], got {tuple(scans.shape)}")
+    mw, mh = _MCU_SIZE[sampling]
+    rows, cols = -(-H // mh), -(-W // mw)
+    _dev = _C.dev_ptr
+    args = [_dev(scans, "scans", (torch.uint8,), (scans.shape[0],)), _dev(offsets, "offsets", (torch.int64,), (F + 1,)), int(scans.shape[0]),
+            _dev(qtables, "qtables", _I16, (F, 3, 64)), _dev(huffman, "huffman", (torch.int32,), (F, 4, 96)),
+            _dev(descriptors, "descriptors", (torch.int32,), (F, 8)), _dev(rgb8, "rgb8", (torch.uint8,), (F, H, W, 3)),
+            _dev(status, "status", (torch.int32,), (F,)),
+            None if coefficients is None else _dev(coefficients, "coefficients", (torch.int16,), (F, rows, cols, _BLOCKS_PER_MCU[sampling], 64))]
+    lib = _C.load_library()
+    need = int(lib.gsr_jpeg_decode_workspace_size(F, W, H, sampling, int(max_intervals)))
+    if need == 0:
+        raise RuntimeError(f"rgb8: {F} frames of {W} x {H} with max_intervals {max_intervals} are outside what gsr_jpeg_decode takes "
+                           f"(max_intervals from 1 to the {rows * cols} MCUs of a frame)")
+    workspace = _C.workspace(workspace, need, rgb8.device)
+    with torch.cuda.device(rgb8.device):
+        lib.gsr_jpeg_decode(F, W, H, sampling, int(max_intervals), *args, workspace.data_ptr(), int(workspace.numel()),
+                            _C.stream_handle(stream, rgb8.device))
 
 
 # ---- container ---------------------------------------------------------------------------------------------------------------------

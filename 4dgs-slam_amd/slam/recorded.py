@@ -18,6 +18,10 @@ Stereo sequences in the EuRoC layout (``parse_euroc`` / ``EurocDataset``, the re
 utils/dataset.py:183-248, 376-487) have no depth files: the two grey images are rectified and matched on the side stream
 (gsr_stereo_depth, include/stereo_depth.h, slam/stereo.py) and the depth handed out is bf / disparity.
 
+A plain video (``VideoDataset``, Dataset.type 'video': a Motion-JPEG AVI file or a folder of .jpg files; no counterpart in the reference) has
+neither depth nor ground truth: its frames are parsed on the read-ahead thread (slam/jpeg_decode.py) and decoded on the side stream
+(gsr_jpeg_decode, include/video_io.h), and ``has_ground_truth`` is False, which the run reads (slam/system.py).
+
 What the reference does and this does not: EXR depth (CoFusion's depth_noise/*.exr raises), and its TUM mask list is not sliced by
 Calibration start / end (:691-696) -- here the masks are sliced with the frames."""
 import collections
@@ -648,11 +652,161 @@ class EurocDataset(RecordedRGBDDataset):
         return image, depth_h, done
 
 
-SUPPORTED_TYPES = ("tum", "CoFusion", "euroc")
+class VideoDataset:
+    """A plain video, with no ground truth beside it: Dataset.type 'video'. ``Dataset.dataset_path`` is a Motion-JPEG AVI file or a folder
+    of .jpg / .jpeg files (slam/jpeg_decode.py AviIndex, JpegFolder); Calibration as for 'tum' (fx fy cx cy width height, distorted and
+    k1 k2 p1 p2 k3, start / end); Dataset.sensor_type must be 'monocular'. The read-ahead thread reads and parses the frames' headers; the
+    pictures are decoded on the device, on the side stream, `prefetch` consecutive frames per call (mjpeg.jpeg_decode, include/video_io.h
+    gsr_jpeg_decode), and kept as bytes in a bounded cache because evaluation reads frames again in any order. Each picture then goes through
+    gsr_frame_prepare like every other dataset's. A frame is (image, None, identity, all-static mask): there is no depth and no ground truth
+    (``has_ground_truth`` is False). ``stamps`` are the frames' times in seconds (frame index / frame rate; the index for a folder)."""
+
+    DECODED_CACHE_FRAMES = 32      # decoded byte pictures kept on the device (0.9 MB each at 640x480)
+    has_ground_truth = False
+
+    def __init__(self, config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None, motion_segmenter=None):
+        import torch
+        from . import jpeg_decode
+        from .camera import getProjectionMatrix2
+        from .pretrained import EventLog
+        d, c = config["Dataset"], config["Dataset"]["Calibration"]
+        if d.get("sensor_type") != "monocular":
+            raise ValueError(f"Dataset.type 'video' needs Dataset.sensor_type 'monocular', got {d.get('sensor_type')!r}: a video file has no depth")
+        for name, given in (("flow estimator", flow), ("segmenter", segmenter), ("motion segmenter", motion_segmenter)):
+            if given is not None:
+                raise ValueError(f"Dataset.type 'video' takes no {name}: the static monocular run is what a plain video feeds")
+        self.device = torch.device(device)
+        self.fx, self.fy, self.cx, self.cy = float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"])
+        self.width, self.height = int(c["width"]), int(c["height"])
+        self.fovx, self.fovy = fov_from_focal(self.fx, self.width), fov_from_focal(self.fy, self.height)
+        self.depth_scale = None
+        self.source = jpeg_decode.open_source(d["dataset_path"])
+        info = self.source.info
+        if "width" in info and (info["width"], info["height"]) != (self.width, self.height):
+            raise ValueError(f"{d['dataset_path']}: the video is {info['width']} x {info['height']}, the calibration says {self.width} x {self.height}")
+        start, end = int(c.get("start", 0)), int(c.get("end", -1))
+        ids = list(range(len(self.source)))[start:len(self.source) if end == -1 else end]
+        if max_frames is not None:
+            ids = ids[:int(max_frames)]
+        if not ids:
+            raise ValueError(f"{d['dataset_path']}: the sequence has no frames (after Calibration start / end)")
+        self._ids = ids
+        self.num_imgs = len(ids)
+        self.stamps = [float(self.source.time(k)) for k in ids]
+        self.dynamic_objects = 0
+        self.projection_matrix = getProjectionMatrix2(0.01, 100.0, self.cx, self.cy, self.fx, self.fy, self.width,
+                                                      self.height).transpose(0, 1).to(self.device)
+        self.poses = torch.eye(4, dtype=torch.float32, device=self.device).repeat(self.num_imgs, 1, 1)
+        self._lut = torch.tensor(byte_lut(), device=self.device)
+        self._map = None
+        if bool(c.get("distorted", False)):
+            m = undistort_map(self.width, self.height, self.fx, self.fy, self.cx, self.cy,
+                              *(float(c.get(k, 0.0)) for k in ("k1", "k2", "p1", "p2", "k3")))
+            self._map = torch.tensor(m, device=self.device)
+        torch.cuda.synchronize(self.device)             # the tables exist before the side stream reads them
+        self._side = torch.cuda.Stream(self.device)
+        self.chunk = max(1, int(prefetch))
+        self._decoded = collections.OrderedDict()       # frame -> (rgb8 [H, W, 3] on the device, its call's host status, position, event)
+        self._decode_log = EventLog(self.device)
+        self._workspace = None
+        tasks = [(self.source, k, self.width, self.height) for k in ids]
+        self._reader = _Reader(tasks, int(prefetch), cache=2 * self.chunk + 4, decode=jpeg_decode.read_frame)
+        self._finalizer = weakref.finalize(self, self._reader.close)
+        self._reader.schedule(0)
+        self._reader.get(0)                             # the reader is up and frame 0 is parsed before the dataset is handed out
+        self._reader.stats.update(wait_ms=0.0, prefetched=0, on_demand=0)
+
+    def __len__(self):
+        return self.num_imgs
+
+    def close(self):
+        """Stop the reader thread (also done when the dataset is dropped and at interpreter exit)."""
+        self._finalizer()
+
+    @property
+    def ingest_stats(self):
+        s = self._reader.stats
+        d = np.asarray(s["decode_ms"], dtype=np.float64)
+        t = self._decode_log.summary()
+        return {"decode_ms_mean": float(d.mean()) if len(d) else None, "decode_ms_p95": float(np.percentile(d, 95)) if len(d) else None,
+                "decoded": int(len(d)), "wait_ms_total": s["wait_ms"], "prefetched": s["prefetched"], "on_demand": s["on_demand"],
+                "cached": s["cached"], "prefetch_depth": self._reader.depth, "device_decode_ms_per_frame": t["ms_per_item"],
+                "device_decode_calls": t["calls"], "device_decoded": t["items"], "device_decode_chunk": self.chunk}
+
+    def _decode_chunk(self, idx):
+        """Decode frame idx and the frames behind it that are not decoded yet, up to `chunk`, of its sampling, in one call on the side stream."""
+        import torch
+        from . import jpeg_decode, mjpeg
+        dev, H, W = self.device, self.height, self.width
+        parsed = [self._reader.get(idx)]
+        for k in range(idx + 1, min(idx + self.chunk, self.num_imgs)):
+            if k in self._decoded:
+                break
+            f = self._reader.get(k)
+            if f.sampling != parsed[0].sampling:
+                break
+            parsed.append(f)
+        p = jpeg_decode.pack(parsed)
+        n = len(parsed)
+        host = {k: torch.from_numpy(p[k].view(np.int16) if k == "qtables" else np.ascontiguousarray(p[k])).pin_memory()
+                for k in ("scans", "offsets", "qtables", "huffman", "descriptors")}
+        status_h = torch.empty(n, dtype=torch.int32).pin_memory()
+        with torch.cuda.stream(self._side):
+            t = {k: v.to(dev, non_blocking=True) for k, v in host.items()}
+            rgb8 = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            need = mjpeg.jpeg_decode_workspace_size(n, W, H, p["sampling"], p["max_intervals"])
+            if self._workspace is None or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)          # (used on the side stream only)
+            with self._decode_log.timed(self._side, count=n):
+                mjpeg.jpeg_decode(t["scans"], t["offsets"], t["qtables"], t["huffman"], t["descriptors"], rgb8, status, p["sampling"],
+                                  p["max_intervals"], None, self._workspace, self._side)
+            status_h.copy_(status, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        for j in range(n):
+            self._decoded[idx + j] = (rgb8[j], status_h, j, done)
+        while len(self._decoded) > max(self.DECODED_CACHE_FRAMES, self.chunk):
+            self._decoded.popitem(last=False)
+
+    def _picture(self, idx):
+        """Frame idx as bytes [H, W, 3] on the device, decoded on the side stream (which the caller must still wait for)."""
+        if idx not in self._decoded:
+            self._decode_chunk(idx)
+        self._decoded.move_to_end(idx)
+        rgb8, status_h, j, done = self._decoded[idx]
+        done.synchronize()                              # the status is read on the host: a damaged frame is refused, not shown
+        if int(status_h[j]) != 0:
+            raise ValueError(f"{self.source.name(self._ids[idx])}: the entropy-coded data cannot be decoded (GSR_JPEG status {int(status_h[j])}, "
+                             "include/video_io.h)")
+        return rgb8
+
+    def __getitem__(self, idx):
+        import torch
+        from . import frame_io
+        if not 0 <= idx < self.num_imgs:
+            raise IndexError(f"frame {idx} of a {self.num_imgs}-frame sequence")
+        H, W, dev = self.height, self.width, self.device
+        rgb8 = self._picture(idx)
+        main = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(self._side):
+            image = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+            motion = torch.empty((H, W), dtype=torch.bool, device=dev)
+            frame_io.frame_prepare(rgb8, self._map, self._lut, None, MASK_THRESHOLD, image, motion, self._side)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        main.wait_event(ready)
+        image.record_stream(main)                       # allocated on the side stream, used (and freed) on the caller's
+        motion.record_stream(main)
+        return image, None, self.poses[idx].clone(), motion
+
+
+SUPPORTED_TYPES = ("tum", "CoFusion", "euroc", "video")
 
 
 def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None, segmenter=None, motion_segmenter=None):
-    """utils/dataset.py:962-976 for the recorded types this project reads: 'tum' (TUM, Bonn), 'CoFusion' and 'euroc' (stereo). flow: an optical-flow
+    """utils/dataset.py:962-976 for the recorded types this project reads: 'tum' (TUM, Bonn), 'CoFusion', 'euroc' (stereo) and 'video' (a
+    Motion-JPEG AVI file or a folder of JPEG files without ground truth, decoded on the device: VideoDataset). flow: an optical-flow
     estimator (slam/optical_flow.py RaftFlow) that gives the dataset gt_flow, or None. segmenter: a YOLO instance segmenter
     (slam/segmentation.py YoloSeg) whose masks of the loader's classes are cleared from the motion masks, or None. motion_segmenter: a
     class-agnostic segmenter from flow and depth (slam/motion_segmentation.py FlowMotionSegmenter; needs flow and an RGB-D type), or None."""
@@ -666,7 +820,10 @@ def load_dataset(config, device="cuda:0", prefetch=4, max_frames=None, flow=None
         if motion_segmenter is not None:
             raise ValueError("Dataset.type 'euroc' takes no motion segmenter: segmenting stereo sequences from flow is not supported")
         return EurocDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter)
-    raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn), 'CoFusion' and 'euroc' (stereo)")
+    if kind == "video":
+        return VideoDataset(config, device, prefetch=prefetch, max_frames=max_frames, flow=flow, segmenter=segmenter, motion_segmenter=motion_segmenter)
+    raise ValueError(f"unknown dataset type {kind!r}: the supported types are 'tum' (TUM RGB-D, Bonn), 'CoFusion', 'euroc' (stereo) and "
+                     "'video' (a Motion-JPEG AVI file or a folder of JPEG files, no ground truth)")
 
 
 # ---- writing a sequence (tests, measurements, exporting the synthetic generator) --------------------------------------------------

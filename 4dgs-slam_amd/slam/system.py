@@ -11,7 +11,7 @@ import torch
 
 from .backend import BackEnd
 from .deform_model import DeformModel
-from .eval_utils import eval_ate, eval_rendering, save_gaussians
+from .eval_utils import eval_ate, eval_rendering, save_gaussians, write_trajectory
 from .frontend import FrontEnd
 from .gaussian_model import GaussianModel
 
@@ -105,8 +105,15 @@ class SLAM:
         if fe.init_done_at is not None and len(fe.cameras) > 1:          # frames per second once the map exists (tracking + keyframe mapping)
             self.result["seconds_init"] = fe.init_done_at - t0
             self.result["fps_after_init"] = (len(fe.cameras) - 1) / max(1e-9, t0 + dt - fe.init_done_at)
+        ground_truth = bool(getattr(self.dataset, "has_ground_truth", True))
+        if not ground_truth:                                              # nothing to compare with: the trajectory itself is the result
+            self.result.update(ate_rmse=None, ground_truth=False)
+            if self.save_dir:
+                self.result["trajectory"] = write_trajectory(fe.cameras, getattr(self.dataset, "stamps", None),
+                                                              os.path.join(self.save_dir, "trajectory.txt"))
         if self.config["Results"].get("eval_rendering", True):
-            self.result["ate_rmse"] = eval_ate(fe.cameras, fe.kf_indices, self.save_dir, 0, final=True, monocular=self.monocular)
+            if ground_truth:
+                self.result["ate_rmse"] = eval_ate(fe.cameras, fe.kf_indices, self.save_dir, 0, final=True, monocular=self.monocular)
             deltas_for = None
             if self.gaussians.deform_init:
                 deltas_for = lambda frame: self.backend._deltas(frame, train=False)

@@ -1,6 +1,6 @@
 /*
- * video_io.h -- C ABI of the on-device picture encoders (libgs_rasterizer_hip.so): JPEG first, the lossless deflate encoder for PNG files
- * (gsr_png_encode) further down. JPEG: baseline sequential JPEG (ITU-T T.81), 8 bit, Y Cb Cr with 4:2:0
+ * video_io.h -- C ABI of the on-device picture coders (libgs_rasterizer_hip.so): the JPEG encoder first, then the JPEG decoder
+ * (gsr_jpeg_decode), the lossless deflate encoder for PNG files (gsr_png_encode) further down. JPEG encoder: baseline sequential JPEG (ITU-T T.81), 8 bit, Y Cb Cr with 4:2:0
  * chroma, the Annex K Huffman tables, no restart markers, of `views` pictures in one call. The call produces each view's entropy-coded segment;
  * a file is the caller's header (SOI .. SOS: slam/mjpeg.py jfif_header) + that segment + EOI. All pointers are DEVICE pointers.
  * Returns 0 or a negative GSR_ERR_* code (gs_rasterizer.h); gsr_last_error() has the text. Nothing is enqueued on a bad argument.
@@ -33,6 +33,76 @@ size_t gsr_jpeg_workspace_size(int views, int width, int height);
  * same input gives the same bytes. */
 int gsr_jpeg_encode(int views, int width, int height, const unsigned char* rgb8, const unsigned short* qtables, unsigned char* scan,
                     int64_t scan_stride, int* sizes, short* coefficients, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The on-device JPEG decoder, the inverse of gsr_jpeg_encode: baseline sequential JPEG (SOF0), 8 bit, ONE scan with all components, of
+ * `frames` pictures of one size and sampling in one call. The host parses SOI .. SOS (slam/jpeg_decode.py) and hands over the
+ * entropy-coded bytes with the tables; everything from the first bit of the scan on runs on the device. The arithmetic is libjpeg's default
+ * one ("slow integer" inverse DCT, "fancy" upsampling, 16-bit fixed-point colour), which PIL and the common viewers use, so a picture an
+ * encoder wrote decodes to libjpeg's bytes (tests/jpeg_decode_reference.py restates it; tests hold both against PIL):
+ *   entropy     T.81 Annex F.2.2. Stuffed 0x00 after 0xFF dropped; DC prediction per component, from 0 at the start of every restart
+ *               interval; AC (run, size) pairs, EOB, ZRL; coefficients in zigzag order, what is not coded is 0
+ *   dequantise  coefficient * table entry, integers
+ *   transform   jidctint.c: constants of 13 bits 2446, 3196, 4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172; columns
+ *               first, (x + 2^10) >> 11; then rows, (x + 2^17) >> 18, plus 128; clamp to 0 .. 255
+ *               32-bit integers. Every intermediate value of a pass is a sum of the pass' eight inputs times integers of magnitude at most
+ *               27431 < 2^15, and a column result is at most 5.56 times the column's sum of magnitudes plus 1. With A the sum of the
+ *               magnitudes of a block's 64 dequantised coefficients, the column pass stays below 2^15 A and the row pass below
+ *               2^15 (5.56 A + 8) + 2^17, so nothing overflows while A <= 11000. An 8 x 8 block of 8-bit samples has a DCT of
+ *               Euclidean norm at most 1024; the bound leaves room for that and for quantisation error, but it is a bound on the block, not
+ *               on a single coefficient: 8-bit tables and coefficients of 11 bits (the format's limits) admit A up to 64 * 2047 * 255,
+ *               which no DCT of a picture produces. The device forms the sums modulo 2^32, so such a block gives defined samples that
+ *               differ from libjpeg's (which computes in `long`). libjpeg also wraps samples more than 384 levels outside 0 .. 255 through
+ *               a 1024-entry table where this clamps; no encoder's output reaches that either. Equality with libjpeg is therefore
+ *               claimed, and tested, for files that encoders wrote, not for arbitrary coefficients.
+ *   chroma      4:2:0, libjpeg's h2v2 triangle filter: per output row s = 3 * (this chroma row) + (the nearer neighbouring chroma row);
+ *               the row above the first is the first, the row below the last REAL row, ceil(H / 2) - 1, is that row (block padding is
+ *               not used). Even columns (3 s[x] + s[x-1] + 8) >> 4, odd columns (3 s[x] + s[x+1] + 7) >> 4; the first column is
+ *               (4 s[0] + 8) >> 4, the last (4 s[last] + 7) >> 4 with last = ceil(W / 2) - 1.
+ *               4:2:2, h2v1: even (3 c[x] + c[x-1] + 1) >> 2, odd (3 c[x] + c[x+1] + 2) >> 2, the first column c[0], the last c[last].
+ *               4:4:4 and grey: none.
+ *   colour      F(v) = int(v * 65536 + 0.5), Cb and Cr minus 128:
+ *               R = Y + ((F(1.402) Cr + 32768) >> 16),  G = Y + ((-F(0.34414) Cb - F(0.71414) Cr + 32768) >> 16),
+ *               B = Y + ((F(1.772) Cb + 32768) >> 16), each clamped to 0 .. 255. Grey: R = G = B = Y.
+ * Blocks per MCU: grey 1; 4:4:4 Y Cb Cr; 4:2:2 Y0 Y1 Cb Cr; 4:2:0 Y00 Y01 Y10 Y11 Cb Cr. MCUs row-major.
+ */
+#define GSR_JPEG_GREY 0
+#define GSR_JPEG_444 1
+#define GSR_JPEG_422 2
+#define GSR_JPEG_420 3
+
+/* status[f] of gsr_jpeg_decode. A restart interval that cannot be decoded ends where it fails: it keeps the coefficients it decoded, the
+ * rest of it is zero, and the frame reports the code of its first such interval (GSR_JPEG_BAD_RESTART first when the scan holds more
+ * restart markers than its intervals need). The other intervals, and the other frames of the call, are complete. */
+#define GSR_JPEG_OK 0
+#define GSR_JPEG_OUT_OF_BYTES 1     /* the interval's bytes ended (or a marker stood) before its last block did */
+#define GSR_JPEG_LONG_CODE 2        /* 16 bits matched no Huffman code, or a DC category above 16 */
+#define GSR_JPEG_INDEX_PAST_63 3    /* a run led past coefficient 63 */
+#define GSR_JPEG_BAD_RESTART 4      /* the restart marker before the interval is missing or is not RST((interval - 1) mod 8) */
+
+/* Bytes of workspace gsr_jpeg_decode needs; 0 when the arguments are outside what it takes: frames, width and height in [1, 65535], at most
+ * 1 290 000 8 x 8 blocks per frame, sampling one of GSR_JPEG_GREY .. GSR_JPEG_420, max_intervals in [1, MCUs per frame]. */
+size_t gsr_jpeg_decode_workspace_size(int frames, int width, int height, int sampling, int max_intervals);
+
+/* gsr_jpeg_decode. All pointers are device pointers.
+ * scans: the entropy-coded bytes of all frames (what follows the SOS header, up to EOI), frame f in [offsets[f], offsets[f + 1]); offsets:
+ * [frames + 1]; scan_bytes: the size of `scans`, to which every range is clamped (of one frame's scan at most 2^30 bytes are looked at).
+ * qtables: [frames, 3, 64] 16-bit, the table of each COMPONENT in natural (row-major) order. huffman: [frames, 4, 96] int32, the tables
+ * DC 0, DC 1, AC 0, AC 1, each as limit[16] (one past the largest code of length l, shifted left to 16 bits; the previous limit where no code
+ * has that length), offset[16] (index of the length's first symbol minus its first code) and the 256 symbols, four to a word, lowest byte
+ * first. descriptors: [frames, 8] int32: the restart interval in MCUs (0: none), the DC table (0 / 1) of the three components, their AC
+ * tables, 0. max_intervals: the largest number of restart intervals of any frame, ceil(MCUs / restart interval); it sizes the launch (one
+ * lane per interval) -- with a smaller value a lane decodes several intervals and those past the marker slots report
+ * GSR_JPEG_BAD_RESTART.
+ * rgb8: [frames, height, width, 3] bytes, the layout gsr_frame_prepare reads. status: [frames] int32, a GSR_JPEG_* code above.
+ * coefficients: NULL, or 16-byte aligned [frames, mcu_rows, mcu_cols, blocks per MCU, 64] int16: the quantised coefficients in scan
+ * order, zigzag, with the DC values (for 4:2:0 the layout of gsr_jpeg_encode's `coefficients`). workspace:
+ * gsr_jpeg_decode_workspace_size bytes, 16-byte aligned. stream: hipStream_t or NULL. Four launches on `stream`, no host read between them,
+ * no atomics; the same bytes in give the same bytes out. Nothing is read outside `scans` and the tables, nothing written outside the
+ * outputs and the workspace, whatever the bytes are. */
+int gsr_jpeg_decode(int frames, int width, int height, int sampling, int max_intervals, const unsigned char* scans, const int64_t* offsets,
+                    int64_t scan_bytes, const unsigned short* qtables, const int* huffman, const int* descriptors, unsigned char* rgb8,
+                    int* status, short* coefficients, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The on-device deflate encoder: lossless zlib streams (RFC 1950 / 1951) of the two picture kinds gsr_frame_export produces, one complete

@@ -19,6 +19,11 @@ ATE is scale-aligned); it cannot be combined with --dynamic.
 A `Training.loop_closure` block in the YAML (`enabled: true` and any key of slam/stages.py LOOP_CLOSURE_DEFAULTS) ties every new keyframe
 to old keyframes of the same place and corrects poses and map (slam/loop_closure.py; static RGB-D and stereo runs only, refused with --dynamic
 and for monocular input), and a `loop_closure` block reports the keyframes queried, the edges accepted and the corrections applied.
+With --video PATH --calibration fx fy cx cy [k1 k2 p1 p2 k3] the input is a plain video with no ground truth: a Motion-JPEG AVI file, or a
+folder of .jpg files with --size W H (`Dataset.type: video`, slam/recorded.py VideoDataset; the pictures are decoded on the device,
+include/video_io.h gsr_jpeg_decode). Without --config a minimal monocular configuration is built in memory; a --config whose Dataset.type is
+`video` works as for any other type. Such a run reports `ate_rmse: null`, writes `trajectory.txt` (TUM format, camera to world) into its
+save directory, and its `ingest` block has the device decode time per frame.
 With --save-map [DIR] the finished map is saved after the evaluations (slam/map_io.py) for tools/play_map.py."""
 import argparse
 import json
@@ -34,12 +39,15 @@ for p in (REPO, os.path.join(REPO, "4dgs-slam_amd")):
     sys.path.insert(0, p)
 from slam.config import apply_cli_overrides, load_config  # noqa: E402
 from slam.recorded import load_dataset  # noqa: E402
-from slam.system import SLAM  # noqa: E402
+from slam.system import SLAM, default_config, merge_config  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--config", required=True)
+    ap.add_argument("--config", default=None, help="YAML configuration (required unless --video is given)")
+    ap.add_argument("--video", default=None, metavar="PATH", help="a Motion-JPEG AVI file or a folder of .jpg files: run on it without ground truth")
+    ap.add_argument("--calibration", type=float, nargs="+", default=None, metavar="V", help="fx fy cx cy [k1 k2 p1 p2 k3] of --video")
+    ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("W", "H"), help="picture size of a --video folder (an AVI file states its own)")
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--dynamic", action="store_true", default=False)
     ap.add_argument("--dataset-path", default=None, help="overrides Dataset.dataset_path")
@@ -58,6 +66,15 @@ def parse_args(argv=None):
     ap.add_argument("--save-map", nargs="?", const="", default=None, metavar="DIR",
                     help="after the evaluations, save the map for tools/play_map.py (default DIR: <save dir>/map)")
     args = ap.parse_args(argv)
+    if args.config is None and args.video is None:
+        ap.error("one of --config and --video is required")
+    if args.video is not None and args.config is None:
+        if args.calibration is None or len(args.calibration) not in (4, 9):
+            ap.error("--video needs --calibration fx fy cx cy [k1 k2 p1 p2 k3]")
+        if args.dynamic:
+            ap.error("--video is monocular input and cannot run with --dynamic: the dynamic model is seeded from sensor depth")
+    elif args.calibration is not None or args.size is not None:
+        ap.error("--calibration and --size belong to --video without --config (a configuration file carries its own Calibration)")
     if args.flow_masks and not (args.dynamic and (args.raft_weights or args.gma_weights)):
         ap.error("--flow-masks needs --dynamic and one of --raft-weights / --gma-weights: the masks are segmented from the estimated flow")
     if args.raft_weights and not args.dynamic:
@@ -74,10 +91,32 @@ def parse_args(argv=None):
     return args
 
 
+def video_config(path, calibration, size=None):
+    """A minimal monocular configuration for a plain video: default_config() with Dataset.type 'video' and the given calibration. The size
+    comes from the AVI header, or from `size` for a folder."""
+    from slam.jpeg_decode import open_source
+    info = open_source(path).info
+    if "width" in info:
+        width, height = info["width"], info["height"]
+    elif size is not None:
+        width, height = size
+    else:
+        raise SystemExit(f"--video {path}: a folder of JPEG files needs --size W H")
+    names = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+    c = dict(zip(names, [float(v) for v in calibration] + [0.0] * (9 - len(calibration))), width=int(width), height=int(height))
+    c["distorted"] = any(c[k] != 0.0 for k in names[4:])
+    return merge_config(default_config(), {"Dataset": {"type": "video", "sensor_type": "monocular", "dataset_path": path, "Calibration": c}})
+
+
 def main(argv=None):
     args = parse_args(argv)
 
-    config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
+    if args.config is None:
+        config = apply_cli_overrides(video_config(args.video, args.calibration, args.size), eval=args.eval, dynamic=False)
+    else:
+        config = apply_cli_overrides(load_config(args.config), eval=args.eval, dynamic=args.dynamic)
+    if args.video and args.config:
+        config["Dataset"]["dataset_path"] = args.video
     if args.dataset_path:
         config["Dataset"]["dataset_path"] = args.dataset_path
     if config["Dataset"].get("sensor_type") == "monocular" and config["model_params"]["dynamic_model"]:
@@ -137,7 +176,7 @@ def main(argv=None):
     if lpips is not None:
         res["lpips"] = lpips.stats
     ds.close()
-    name = os.path.splitext(os.path.basename(args.config))[0] + ("_dynamic" if args.dynamic else "")
+    name = os.path.splitext(os.path.basename(args.config or args.video.rstrip("/")))[0] + ("_dynamic" if args.dynamic else "")
     print(json.dumps({name: res}, indent=1, default=str))
 
 
